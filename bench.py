@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: P2I-GAN train frames/s on synthetic (B,16,1,128,128) events (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N>1 either arrives through `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) or, when WORLD_SIZE is unset, bench.py starts the N ranks
@@ -12,6 +12,9 @@ One "step" = one full G+D training iteration (train.py:240-326: G fwd, rec loss,
 Adam-D, D fwd + adv loss, G bwd through D, Adam-G) on one batch already resident in HBM.
 Per-GPU batch is fixed (weak scaling): configs[1] = B=8 on 1 GPU, configs[2] = 8 per GPU on 8 GPUs.
 Prints ONE JSON line (rank 0) with the driver's fields plus `roofline` and `cpu_baseline`.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (TrainEngine.train_step's dict:
+preds, logits, losses) as DIR/<name>.npy in float32, so that two builds run with the same arguments can be compared output
+for output (the weights and the batch are seeded: the inputs are the same in every run).
 """
 import argparse
 import json
@@ -125,6 +128,29 @@ def collective_evidence(device=None):
     except Exception:
         pass
     return ev
+
+
+DUMP_BYTES = 64 << 20                  # --dump-outputs: at most 64 MB in all
+
+
+def dump_outputs(out, path):
+    """train_step's dict -> path/<name>.npy (float32, host copies).  Smallest arrays first, each gets at most an equal share of
+    what DUMP_BYTES has left; one that does not fit is replaced by a fixed sample: the same seeded, sorted flat indices for
+    the same shape in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float32) for k, v in out.items()}
+    left = DUMP_BYTES
+    sampled = {}
+    for n, (k, a) in enumerate(sorted(arrs.items(), key=lambda kv: (kv[1].nbytes, kv[0]))):
+        share = left // (len(arrs) - n)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(2024).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+            sampled[k] = int(a.size)
+        left -= a.nbytes
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": path, "arrays": sorted(arrs), "sampled": sampled}
 
 
 def stub_main(args, world, rank):
@@ -330,9 +356,13 @@ def main():
                     help="also time the step fed by P2IDataModule from a synthetic train.zarr through device_assemble (step_ms_with_loader)")
     ap.add_argument("--loader-workers", type=int, default=None, help="DataLoader workers of the --with-loader leg (default: the shipped config's)")
     ap.add_argument("--with-infer", action="store_true", help="also time sliding-window inference of one (128,128,40) event (infer)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, <= 64 MB in all)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:                              # no launcher above us: start the N ranks, touch nothing else
@@ -389,10 +419,17 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        eng.train_step(frames, masked, masks)
+        last = eng.train_step(frames, masked, masks)
         marks[i + 1].record()
+        if i + 1 < args.steps:
+            del last                                   # only the last step's outputs outlive their step
     sync()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # host copies now: later passes below step again (and a replayed graph rewrites its output buffers in place)
+        dumped = dump_outputs(last, args.dump_outputs)
+    del last
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     ms_median = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
     if world > 1:
@@ -538,6 +575,8 @@ def main():
                 "roofline": roofline, "cpu_baseline": cpu}
         if rccl is not None:
             line["rccl"] = rccl
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         line.update(extra)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -58,3 +58,35 @@ def test_under_torchrun_contract():
                        env=e, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert _line(r.stdout)["n_gpus"] == 2
+
+
+def test_dump_outputs_caps_and_samples_deterministically(tmp_path):
+    """bench.py --dump-outputs: every entry of the step's dict becomes <name>.npy in float32, at most 64 MB in all; an array
+    over its share is replaced by the same seeded sample in every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    out = {"preds": torch.arange(16 << 20, dtype=torch.float32).reshape(16, 1 << 20), "loss_g": torch.tensor(1.5),
+           "logits_fake": torch.randn(8, 3, dtype=torch.float64)}
+    a = bench.dump_outputs(out, str(tmp_path / "a"))
+    b = bench.dump_outputs(out, str(tmp_path / "b"))
+    assert a["arrays"] == ["logits_fake", "loss_g", "preds"] and list(a["sampled"]) == ["preds"]
+    total = 0
+    for k in a["arrays"]:
+        x, y = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= bench.DUMP_BYTES
+    p = np.load(tmp_path / "a" / "preds.npy")
+    assert p.size == a["sampled"]["preds"] and np.all(np.diff(p) > 0)       # sorted flat indices of arange: a true sample
+    assert np.array_equal(np.load(tmp_path / "a" / "logits_fake.npy"), out["logits_fake"].float().numpy())
+    assert float(np.load(tmp_path / "a" / "loss_g.npy")) == 1.5
+    # arrays that fit are written whole: bench's full-size step output (B=8 preds, 8 MB) is never sampled
+    c = bench.dump_outputs(dict(out, preds=torch.zeros(8, 16, 1, 128, 128)), str(tmp_path / "c"))
+    assert not c["sampled"] and np.load(tmp_path / "c" / "preds.npy").shape == (8, 16, 1, 128, 128)
+
+
+def test_steps_below_one_is_an_error():
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr

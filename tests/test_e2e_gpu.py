@@ -543,6 +543,29 @@ def test_two_rank_rccl_bench_launch(dev):
     assert line["rccl"]["exchange_d_ms_per_step"] > 0 and line["rccl"]["exchange_g_exposed_ms_per_step"] >= 0
 
 
+def test_bench_dump_outputs(dev, tmp_path):
+    """bench.py --steps K --dump-outputs DIR: K timed steps, ms_per_step in the line, and DIR/<name>.npy holding what the last
+    timed step returned (float32, full-size preds at B=2)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--no-roofline", "--no-stack", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    names = line["dump_outputs"]["arrays"]
+    assert {"preds", "loss_g", "loss_d", "logits_fake", "logits_real"} <= set(names) and not line["dump_outputs"]["sampled"]
+    for k in names:
+        a = np.load(tmp_path / "out" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.isfinite(a).all(), k
+    assert np.load(tmp_path / "out" / "preds.npy").shape == (2, 16, 1, 128, 128)
+
+
 def test_autograd_step_matches_direct_step(dev):
     """TrainEngine's direct step (plain forward / backward functions, gradients written in place) and the autograd-driven step
     (the drop-in modules + loss.backward(), what a user of the reference API runs) execute the same kernels: one step from the

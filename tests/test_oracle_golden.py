@@ -22,6 +22,39 @@ def _batch32():
     return torch.cat([f0, f1]), torch.cat([k0, k1]), torch.cat([mk0, mk1])
 
 
+def _fmaf32(a, b, c):
+    """fmaf on float32 arrays, correctly rounded on any host: the float64 product of two floats is exact, and TwoSum's error
+    term decides the one case float64 cannot, a sum that lands exactly on a float32 rounding midpoint."""
+    a, b, c = (np.asarray(v, np.float32).astype(np.float64) for v in (a, b, c))
+    p = a * b
+    s = p + c
+    bp = s - c
+    e = (p - bp) + (c - (s - bp))
+    r = s.astype(np.float32)
+    up = np.nextafter(r, np.float32(np.inf))
+    dn = np.nextafter(r, np.float32(-np.inf))
+    r = np.where(((r.astype(np.float64) + up) * 0.5 == s) & (e > 0), up, r)
+    r = np.where(((r.astype(np.float64) + dn) * 0.5 == s) & (e < 0), dn, r)
+    return r.astype(np.float32)
+
+
+def _pinned_cdist(shape, pts):
+    """(Q, N) float32 voxel-to-gauge distances in the arithmetic of oracle/idw_knn.c, in numpy: no BLAS, so the same on every host."""
+    D, H, W = shape
+    f = np.float32
+    gx, gy, gz = (torch.linspace(0, 1, n).numpy() for n in (W, H, D))
+    qz, qy, qx = (a.reshape(-1, 1) for a in np.meshgrid(gz, gy, gx, indexing="ij"))
+    p = pts.numpy().astype(f)
+    px, py, pz = p[None, :, 0], p[None, :, 1], p[None, :, 2]
+    n1 = (qx * qx + qy * qy) + qz * qz
+    n2 = (px * px + py * py) + pz * pz
+    acc = (f(-2) * qx) * px
+    acc = _fmaf32(f(-2) * qy, py, acc)
+    acc = _fmaf32(f(-2) * qz, pz, acc)
+    acc = (n1 + acc) + n2
+    return np.sqrt(np.maximum(acc, f(0)))
+
+
 def test_idw_matches_reference(golden):
     """N >= 256 (torch.topk -> std::partial_sort, emulated exactly by oracle/idw_knn.c): bit-level
     agreement with the reference.  N < 256 (nth_element path): the order of EXACT rank-4/5 distance
@@ -35,8 +68,11 @@ def test_idw_matches_reference(golden):
         if pts.shape[0] >= 256:
             assert rel_err(out.numpy(), g[name + "_out"]) < 1e-6, name
         else:
-            d = torch.cdist(O.grid_points(16, 32, 32), pts).sort(dim=1)[0]
-            no_tie = (d[:, 3] != d[:, 4]).reshape(16, 32, 32).numpy()
+            # ties judged in the pinned arithmetic (not this host's cdist, whose rounding follows its MKL code path)
+            d = np.sort(_pinned_cdist((16, 32, 32), pts), axis=1)
+            _, seld = O.idw_select_c(pts, (16, 32, 32))
+            assert np.array_equal(d[:, :4], seld.numpy()), name         # _pinned_cdist IS idw_knn.c's arithmetic
+            no_tie = (d[:, 3] != d[:, 4]).reshape(16, 32, 32)
             assert no_tie.mean() > 0.5
             err = np.abs(out.numpy() - g[name + "_out"])
             assert err[no_tie].max() < 1e-6 * np.abs(g[name + "_out"]).max(), name
