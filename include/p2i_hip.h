@@ -369,6 +369,34 @@ int p2i_tape_info(const void* tape, int* counts4);
 int p2i_tape_replay(const void* tape, void* origin_stream);
 int p2i_tape_free(void* tape);
 
+/* ---- STDK baseline (spatio-temporal DeepKriging, reference models/stdk.py).  The reference builds a
+ * [B*T*H*W, K_s + K_t + 79 T] feature tensor and runs nn.Linear x 4 over it (stdk.py:149-186); here layer 1 is split by its input
+ * blocks -- P = phi_s W1s^T [HW][112], Q[b][t] = phi_t[t] W1t^T + z[b] W1z^T + b1 [B*T][112] (columns >= 100 are zero) -- and the
+ * other three layers run fused over the rows (b, t, p) without writing anything but y.  Weights are the reference's nn.Linear
+ * tensors as they are: w1 [100][K_s + K_t + Kz], w2 / w3 [100][100], w4 [1][100].
+ * p2i_stdk_basis: phi[i][k] = Wendland-C2(|pos_i - knot_k| / theta_k) (stdk.py:26-35, 188-276) for the H x W grid pos_i = (i / W, i % W);
+ *   knots [K][2] as (y, x) floats (the temporal basis is H = T, W = 1 with knots (t, 0)).
+ * p2i_stdk_select: per (b, t) frame the first k of [pixels with mask != 0 in raster order, then pixels with mask == 0 in raster
+ *   order] -> idx [BT][k] (int32), z [BT][k] = masked[idx] (replaces topk(mask, k, sorted=False) + gather, stdk.py:143-147, 173-175,
+ *   under the build's tie rule); HW >= k.
+ * p2i_stdk_layer1_fwd: P, zt [T][112], zb [B][112] (scratch), Q.  p2i_stdk_mlp_fwd: y [BT][HW].
+ * p2i_stdk_bwd_workspace: floats needed by p2i_stdk_mlp_bwd's four scratch buffers (rows5, dp_part, dq_part, wpart).
+ * p2i_stdk_mlp_bwd: from dy [BT][HW]: dP [HW][100] (sum over b, t), dQ [BT][100] (sum over p) and the gradients of layers 2..4;
+ *   all cross-workgroup sums are partials added in a fixed order (run-to-run identical).
+ * p2i_stdk_layer1_bwd: dw1 [100][F] and db1 from dP, dQ; dqt [T][100], dqb [B][100] scratch, part [splits][100][F] scratch. */
+int p2i_stdk_basis(const float* knots, const float* theta, int K, int H, int W, float* phi, void* stream);
+int p2i_stdk_select(const float* masked, const float* mask, int BT, int HW, int k, int* idx, float* z, void* stream);
+int p2i_stdk_layer1_fwd(const float* phi_s, const float* phi_t, const float* z, const float* w1, const float* b1, int B, int T, int HW,
+                        int Ks, int Kt, int Kz, float* P, float* zt, float* zb, float* Q, void* stream);
+int p2i_stdk_mlp_fwd(const float* P, const float* Q, const float* w2, const float* b2, const float* w3, const float* b3, const float* w4,
+                     const float* b4, int HW, int BT, float* y, void* stream);
+int p2i_stdk_bwd_workspace(int HW, int BT, int64_t* sizes4);
+int p2i_stdk_mlp_bwd(const float* P, const float* Q, const float* w2, const float* b2, const float* w3, const float* b3, const float* w4,
+                     const float* dy, int HW, int BT, float* rows5, float* dp_part, float* dq_part, float* wpart, float* dP, float* dQ,
+                     float* dw2, float* db2, float* dw3, float* db3, float* dw4, float* db4, void* stream);
+int p2i_stdk_layer1_bwd(const float* phi_s, const float* phi_t, const float* z, const float* dP, const float* dQ, int B, int T, int HW,
+                        int Ks, int Kt, int Kz, float* dqt, float* dqb, float* part, int splits, float* dw1, float* db1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

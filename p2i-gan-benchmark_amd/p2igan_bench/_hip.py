@@ -89,6 +89,13 @@ SIGNATURES = {
     "p2i_tape_info": [_P, C.POINTER(C.c_int)],
     "p2i_tape_replay": [_P, _P],
     "p2i_tape_free": [_P],
+    "p2i_stdk_basis": [_P, _P, _I, _I, _I, _P, _P],
+    "p2i_stdk_select": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "p2i_stdk_layer1_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "p2i_stdk_mlp_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
+    "p2i_stdk_bwd_workspace": [_I, _I, C.POINTER(C.c_int64)],
+    "p2i_stdk_mlp_bwd": [_P] * 8 + [_I, _I] + [_P] * 13,
+    "p2i_stdk_layer1_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P],
 }
 
 

@@ -127,6 +127,9 @@ class TrainEngine:
         memory pool only (every buffer the tape names lives there, at a fixed address); the hipGraph itself is never launched."""
         if self.distributed:
             raise RuntimeError("graph capture is for the single-GPU step")
+        if not self.direct:
+            raise RuntimeError("graph / tape capture replays the direct P2I-GAN step only; this engine runs the autograd step "
+                               f"({type(self.G).__name__}), which stays eager")
         if mode not in ("graph", "tape"):
             raise ValueError(mode)
         for o in (self.opt_g, self.opt_d):

@@ -1,12 +1,13 @@
 """Model registry — the construction API of the reference (models/__init__.py:13-46).
 
-Only the P2I-GAN family is built on the HIP path; the reference's DeepKriging baselines and the
-`simple` fallback are out of this build's scope and raise a clear error."""
+The P2I-GAN family and the STDK (spatio-temporal DeepKriging) baseline are built on the HIP path.  The purely spatial DK
+baseline and the `simple` fallback stub are out of this build's scope and raise a clear error."""
 from typing import Any, Dict
 
 import torch.nn as nn
 
 from .p2igan import P2IDiscriminator, P2IGenerator
+from .stdk import STDKGenerator
 
 
 def _model_name(cfg: Dict[str, Any]) -> str:
@@ -17,7 +18,10 @@ def build_generator(cfg: Dict[str, Any]) -> nn.Module:
     name = _model_name(cfg)
     if name == "p2igan":
         return P2IGenerator(cfg)
-    raise NotImplementedError(f"model '{name}': only 'p2igan' is implemented on the MI355X path")
+    if name == "stdk":
+        data_cfg = cfg.get("data_loader") or cfg.get("data", {}).get("train", {})
+        return STDKGenerator(cfg, length=data_cfg.get("sample_length", 16))
+    raise NotImplementedError(f"model '{name}': only 'p2igan' and 'stdk' are implemented on the MI355X path")
 
 
 def build_discriminator(cfg: Dict[str, Any]) -> nn.Module:
@@ -30,4 +34,4 @@ def build_discriminator(cfg: Dict[str, Any]) -> nn.Module:
     raise NotImplementedError(f"model '{name}': only 'p2igan' is implemented on the MI355X path")
 
 
-__all__ = ["build_generator", "build_discriminator", "P2IGenerator", "P2IDiscriminator"]
+__all__ = ["build_generator", "build_discriminator", "P2IGenerator", "P2IDiscriminator", "STDKGenerator"]

@@ -1141,3 +1141,115 @@ def assemble_batch(frames_u8, mask_u8):
     _hip.check(lib.p2i_assemble_batch(_ptr(frames_u8), _ptr(mask_u8), mask_u8.numel(), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
                                       B, T, H, W, _stream()), "p2i_assemble_batch")
     return out[0], out[1], out[2]
+
+
+# --------------------------------------------------------------------------- STDK baseline (csrc/stdk.hip)
+STDK_K = 79          # visible points per frame (reference models/stdk.py:143-147)
+STDK_HID = 100
+_STDK_HP = 112
+
+
+def stdk_basis(knots, theta, h, w):
+    """Wendland-C2 basis phi [h*w, K] of the grid (i // w, i % w) for knots [K, 2] (y, x) and per-knot theta [K]."""
+    lib = _hip.load()
+    K = theta.numel()
+    if knots.shape != (K, 2):
+        raise RuntimeError("stdk_basis: knots must be [K, 2]")
+    phi = torch.empty(h * w, K, device=theta.device, dtype=torch.float32)
+    _chk(knots, theta)
+    _hip.check(lib.p2i_stdk_basis(_ptr(knots), _ptr(theta), K, h, w, _ptr(phi), _stream()), "p2i_stdk_basis")
+    return phi
+
+
+def stdk_select(masked, mask, k=STDK_K):
+    """masked, mask: (B, T, H*W) fp32.  Returns idx (B, T, k) int32 and z (B, T, k): the observed pixels in raster order, then the
+    unobserved ones, first k."""
+    lib = _hip.load()
+    B, T, HW = masked.shape
+    if mask.shape != masked.shape:
+        raise RuntimeError("stdk_select: mask shape mismatch")
+    if HW < k:
+        raise ValueError(f"STDK needs at least {k} pixels per frame (got {HW})")
+    idx = torch.empty(B, T, k, device=masked.device, dtype=torch.int32)
+    z = torch.empty(B, T, k, device=masked.device, dtype=torch.float32)
+    _chk(masked, mask)
+    _hip.check(lib.p2i_stdk_select(_ptr(masked), _ptr(mask), B * T, HW, k, _ptr(idx), _ptr(z), _stream()), "p2i_stdk_select")
+    return idx, z
+
+
+def stdk_layer1_fwd(phi_s, phi_t, z, w1, b1, B, T):
+    """P [HW, 112] and Q [B*T, 112] of the decomposed first layer (columns >= 100 zero)."""
+    lib = _hip.load()
+    HW, Ks = phi_s.shape
+    Kt, Kz = phi_t.shape[1], z.shape[1]
+    if phi_t.shape[0] != T or z.shape[0] != B or w1.shape != (STDK_HID, Ks + Kt + Kz) or b1.numel() != STDK_HID:
+        raise RuntimeError("stdk_layer1_fwd: shape mismatch")
+    dev = phi_s.device
+    P = torch.empty(HW, _STDK_HP, device=dev, dtype=torch.float32)
+    Q = torch.empty(B * T, _STDK_HP, device=dev, dtype=torch.float32)
+    zt = torch.empty(T, _STDK_HP, device=dev, dtype=torch.float32)
+    zb = torch.empty(B, _STDK_HP, device=dev, dtype=torch.float32)
+    _chk(phi_s, phi_t, z, w1, b1)
+    _hip.check(lib.p2i_stdk_layer1_fwd(_ptr(phi_s), _ptr(phi_t), _ptr(z), _ptr(w1), _ptr(b1), B, T, HW, Ks, Kt, Kz, _ptr(P), _ptr(zt),
+                                       _ptr(zb), _ptr(Q), _stream()), "p2i_stdk_layer1_fwd")
+    return P, Q
+
+
+def _stdk_mlp_check(P, Q, w2, b2, w3, b3, w4):
+    if P.shape[1] != _STDK_HP or Q.shape[1] != _STDK_HP or w2.shape != (STDK_HID, STDK_HID) or w3.shape != (STDK_HID, STDK_HID) \
+            or w4.numel() != STDK_HID or b2.numel() != STDK_HID or b3.numel() != STDK_HID:
+        raise RuntimeError("stdk MLP: shape mismatch")
+
+
+def stdk_mlp_fwd(P, Q, w2, b2, w3, b3, w4, b4):
+    """y [B*T, HW] of the fused layers 2..4 over every row (b, t, p)."""
+    lib = _hip.load()
+    _stdk_mlp_check(P, Q, w2, b2, w3, b3, w4)
+    HW, BT = P.shape[0], Q.shape[0]
+    y = torch.empty(BT, HW, device=P.device, dtype=torch.float32)
+    _chk(P, Q, w2, b2, w3, b3, w4, b4)
+    _hip.check(lib.p2i_stdk_mlp_fwd(_ptr(P), _ptr(Q), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(w4), _ptr(b4), HW, BT, _ptr(y),
+                                    _stream()), "p2i_stdk_mlp_fwd")
+    return y
+
+
+def stdk_mlp_bwd(P, Q, w2, b2, w3, b3, w4, dy, grads=None):
+    """dy [B*T, HW] -> dP [HW, 100], dQ [B*T, 100] and (dw2, db2, dw3, db3, dw4, db4) (written into `grads` when given)."""
+    import ctypes
+    lib = _hip.load()
+    _stdk_mlp_check(P, Q, w2, b2, w3, b3, w4)
+    HW, BT = P.shape[0], Q.shape[0]
+    if dy.shape != (BT, HW):
+        raise RuntimeError("stdk_mlp_bwd: dy shape mismatch")
+    sz = (ctypes.c_int64 * 4)()
+    _hip.check(lib.p2i_stdk_bwd_workspace(HW, BT, sz), "p2i_stdk_bwd_workspace")
+    dev = P.device
+    ws = [torch.empty(int(n), device=dev, dtype=torch.float32) for n in sz]
+    dP = torch.empty(HW, STDK_HID, device=dev, dtype=torch.float32)
+    dQ = torch.empty(BT, STDK_HID, device=dev, dtype=torch.float32)
+    g = list(grads) if grads is not None else [torch.empty_like(t) for t in (w2, b2, w3, b3, w4)] + [torch.empty(1, device=dev)]
+    _chk(P, Q, w2, b2, w3, b3, w4, dy, *g)
+    _hip.check(lib.p2i_stdk_mlp_bwd(_ptr(P), _ptr(Q), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(w4), _ptr(dy), HW, BT,
+                                    *[_ptr(t) for t in ws], _ptr(dP), _ptr(dQ), *[_ptr(t) for t in g], _stream()), "p2i_stdk_mlp_bwd")
+    return dP, dQ, g
+
+
+def stdk_layer1_bwd(phi_s, phi_t, z, dP, dQ, B, T, dw1=None, db1=None):
+    """dw1 [100, F], db1 [100] of the decomposed first layer (fixed-order sums)."""
+    lib = _hip.load()
+    HW, Ks = phi_s.shape
+    Kt, Kz = phi_t.shape[1], z.shape[1]
+    dev = phi_s.device
+    if dP.shape != (HW, STDK_HID) or dQ.shape != (B * T, STDK_HID):
+        raise RuntimeError("stdk_layer1_bwd: shape mismatch")
+    F = Ks + Kt + Kz
+    splits = max(1, min(64, HW // 256))
+    dw1 = torch.empty(STDK_HID, F, device=dev, dtype=torch.float32) if dw1 is None else dw1
+    db1 = torch.empty(STDK_HID, device=dev, dtype=torch.float32) if db1 is None else db1
+    dqt = torch.empty(T, STDK_HID, device=dev, dtype=torch.float32)
+    dqb = torch.empty(B, STDK_HID, device=dev, dtype=torch.float32)
+    part = torch.empty(splits * STDK_HID * F, device=dev, dtype=torch.float32)
+    _chk(phi_s, phi_t, z, dP, dQ, dw1, db1)
+    _hip.check(lib.p2i_stdk_layer1_bwd(_ptr(phi_s), _ptr(phi_t), _ptr(z), _ptr(dP), _ptr(dQ), B, T, HW, Ks, Kt, Kz, _ptr(dqt), _ptr(dqb),
+                                       _ptr(part), splits, _ptr(dw1), _ptr(db1), _stream()), "p2i_stdk_layer1_bwd")
+    return dw1, db1

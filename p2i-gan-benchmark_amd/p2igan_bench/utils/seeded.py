@@ -166,3 +166,17 @@ def metric_fields(seed: int, n: int = 2, t: int = 16, h: int = 32, w: int = 32):
     target = base.clamp(min=0.0)
     preds = (base + noise).clamp(min=0.0)
     return preds.reshape(n, t, 1, h, w), target.reshape(n, t, 1, h, w)
+
+
+def seeded_stdk_state(t: int = 16, seed: int = 2024, k_s: int = 139) -> dict:
+    """Host-independent STDK weights (numpy PCG64): kaiming-normal scale sqrt(2 / fan_in) as BaseNetwork.init_weights draws
+    (modules/layer.py:20-40), small non-zero biases so that the bias paths carry signal.  Keys of the reference's state dict."""
+    rng = _rng(seed, f"stdk{t}")
+    base = max(1, int(round(t / 4)))
+    k_t = sum(min(m, -(-t // max(1, base >> lvl))) for lvl, m in enumerate((10, 19, 37, 73)))    # knots of the temporal basis
+    f = k_s + k_t + 79 * t
+    sd = {}
+    for i, (o, n) in zip((0, 2, 4, 6), ((100, f), (100, 100), (100, 100), (1, 100))):
+        sd[f"_mlp.net.{i}.weight"] = torch.from_numpy((rng.standard_normal((o, n)) * np.sqrt(2.0 / n)).astype(np.float32))
+        sd[f"_mlp.net.{i}.bias"] = torch.from_numpy((rng.standard_normal(o) * 0.01).astype(np.float32))
+    return sd
