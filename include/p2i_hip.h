@@ -397,6 +397,43 @@ int p2i_stdk_mlp_bwd(const float* P, const float* Q, const float* w2, const floa
 int p2i_stdk_layer1_bwd(const float* phi_s, const float* phi_t, const float* z, const float* dP, const float* dQ, int B, int T, int HW,
                         int Ks, int Kt, int Kz, float* dqt, float* dqb, float* part, int splits, float* dw1, float* db1, void* stream);
 
+/* ---- exp1 scoring (reference experiments/exp1.py run_exp1 + experiments/io.py).  Inputs are DEVICE arrays
+ * of dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W]; every statistic is fp64.  transform_mmhr(x) = clip(10^min(max(x,
+ * 0.001) [/3] / 16, 38) * 0.036, 0, 200) (exp1.py:151-159); uint8 values go through lut[256] (computed on the host by numpy).
+ * p2i_exp1_transform: out[i] = transform_mmhr(x[i]) (fp64; the check of the device pow).
+ * p2i_exp1_workspace: doubles of `part` that p2i_exp1_accumulate needs for T frames of an S x S crop.
+ * p2i_exp1_accumulate: one aligned piece of T frames; the crop is [top, top + S) x [left, left + S) of each input; rank[S*S]
+ *   (int32) is the pixel's position in the mode's selection or -1.  part[T][workgroups][P2I_EXP1_NSTAT] gets per workgroup: n,
+ *   sum|d|, sum d^2, the truth's Welford (mean, M2), the count / min / max of the f32 casts that are finite and > 0.5, and per
+ *   threshold (HOST array, <= P2I_EXP1_MAX_THR) hits / misses / false alarms.  Writes the avg_pool2d(pool) f32 frames of the
+ *   whole crop, pool_*[T][S/pool][S/pool] (pool 1 or 8), and the selected f32 casts, sel_*[T][nsel].
+ * p2i_exp1_merge: acc[P2I_EXP1_NSTAT] (+)= part[0 .. nparts) in a fixed order (the partials of a method's pieces, in frame order).
+ * p2i_exp1_hist: per frame t the 50-bin histograms of sel_pred / sel_truth over the range in acc (np.histogram's edges and bin
+ *   rule): flag[t] = both non-empty, score[t] = sum min(p / (sum p + 1e-12), g / (sum g + 1e-12)); edges[52] = the 51 edges + a
+ *   status (1: not strictly increasing).
+ * p2i_exp1_ssim: ssim[t] = SSIM(pred_t, truth_t); d1[t] (t >= 1), d2[t] (t >= 2) = SSIM(p_t, p_t-L) - SSIM(g_t, g_t-L), for the
+ *   method's whole stack of T pooled frames of npix values.
+ * p2i_exp1_finalize: out[P2I_EXP1_NOUT(nthr)] = MAE, RMSE, PSS, SSIM, DTSSIM_L1, DTSSIM_L2, NSE, per threshold POD, FAR, CSI, HSS,
+ *   then a status (1: np.histogram would raise "Too many bins for data range"). */
+#define P2I_EXP1_U8 0
+#define P2I_EXP1_F32 1
+#define P2I_EXP1_F64 2
+#define P2I_EXP1_MAX_THR 8
+#define P2I_EXP1_NSTAT (8 + 3 * P2I_EXP1_MAX_THR)
+#define P2I_EXP1_NOUT(nthr) (8 + 4 * (nthr))
+int p2i_exp1_transform(const void* x, int dtype, int64_t n, int divide_by_3, double* out, void* stream);
+int p2i_exp1_workspace(int T, int S, int pool, int64_t* part_doubles);
+int p2i_exp1_accumulate(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth, int truth_dtype,
+                        int gh, int gw, int gtop, int gleft, int T, int S, int pool, const int* rank, int nsel, const double* lut,
+                        const double* thresholds_host, int nthr, int divide_by_3, float* pool_pred, float* pool_truth, float* sel_pred,
+                        float* sel_truth, double* part, void* stream);
+int p2i_exp1_merge(const double* part, int64_t nparts, double* acc, void* stream);
+int p2i_exp1_hist(const float* sel_pred, const float* sel_truth, int T, int nsel, const double* acc, double* score, int* flag,
+                  float* edges, void* stream);
+int p2i_exp1_ssim(const float* pool_pred, const float* pool_truth, int T, int npix, double* ssim, double* d1, double* d2, void* stream);
+int p2i_exp1_finalize(const double* acc, const double* thresholds_host, int nthr, int T, const double* score, const int* flag,
+                      const float* edges, const double* ssim, const double* d1, const double* d2, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

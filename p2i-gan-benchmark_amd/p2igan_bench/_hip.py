@@ -96,6 +96,14 @@ SIGNATURES = {
     "p2i_stdk_bwd_workspace": [_I, _I, C.POINTER(C.c_int64)],
     "p2i_stdk_mlp_bwd": [_P] * 8 + [_I, _I] + [_P] * 13,
     "p2i_stdk_layer1_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P],
+    "p2i_exp1_transform": [_P, _I, _L, _I, _P, _P],
+    "p2i_exp1_workspace": [_I, _I, _I, C.POINTER(C.c_int64)],
+    "p2i_exp1_accumulate": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P,
+                            C.POINTER(C.c_double), _I, _I, _P, _P, _P, _P, _P, _P],
+    "p2i_exp1_merge": [_P, _L, _P, _P],
+    "p2i_exp1_hist": [_P, _P, _I, _I, _P, _P, _P, _P, _P],
+    "p2i_exp1_ssim": [_P, _P, _I, _I, _P, _P, _P, _P],
+    "p2i_exp1_finalize": [_P, C.POINTER(C.c_double), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 
 

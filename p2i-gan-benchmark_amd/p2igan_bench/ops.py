@@ -6,6 +6,7 @@ raises RuntimeError on failure.  No CPU path exists here by design.
 """
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -1253,3 +1254,90 @@ def stdk_layer1_bwd(phi_s, phi_t, z, dP, dQ, B, T, dw1=None, db1=None):
     _hip.check(lib.p2i_stdk_layer1_bwd(_ptr(phi_s), _ptr(phi_t), _ptr(z), _ptr(dP), _ptr(dQ), B, T, HW, Ks, Kt, Kz, _ptr(dqt), _ptr(dqb),
                                        _ptr(part), splits, _ptr(dw1), _ptr(db1), _stream()), "p2i_stdk_layer1_bwd")
     return dw1, db1
+
+
+# ---- exp1 scoring (csrc/eval_exp1.hip; p2igan_bench/evaluation.py drives these) ----
+EXP1_MAX_THR = 8
+EXP1_NSTAT = 8 + 3 * EXP1_MAX_THR
+EXP1_BINS = 50
+_EXP1_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.float64: 2}
+
+
+def _exp1_code(t: torch.Tensor) -> int:
+    if not (t.is_cuda and t.is_contiguous()):
+        raise RuntimeError("exp1 ops need contiguous CUDA tensors (the HIP path has no CPU fallback)")
+    if t.dtype not in _EXP1_DTYPES:
+        raise RuntimeError(f"exp1: unsupported dtype {t.dtype}")
+    return _EXP1_DTYPES[t.dtype]
+
+
+def _f64s(vals):
+    vals = [float(v) for v in vals]
+    return (C.c_double * max(1, len(vals)))(*vals)
+
+
+def exp1_transform(x: torch.Tensor, divide_by_3: bool = True) -> torch.Tensor:
+    """transform_mmhr of a uint8 / f32 / f64 device tensor, in fp64 on the device."""
+    code = _exp1_code(x)
+    out = torch.empty(x.shape, device=x.device, dtype=torch.float64)
+    if x.numel():
+        _hip.check(_hip.load().p2i_exp1_transform(_ptr(x), code, x.numel(), int(divide_by_3), _ptr(out), _stream()),
+                   "p2i_exp1_transform")
+    return out
+
+
+def exp1_workspace(T: int, S: int, pool: int) -> int:
+    n = C.c_int64(0)
+    _hip.check(_hip.load().p2i_exp1_workspace(T, S, pool, C.byref(n)), "p2i_exp1_workspace")
+    return int(n.value)
+
+
+def exp1_accumulate(pred, truth, ptl, gtl, S, pool, rank, nsel, lut, thresholds, divide_by_3, pool_p, pool_g, sel_p, sel_g, part):
+    """One aligned piece: pred, truth [T, H, W] (their own H, W), crop origins ptl / gtl = (top, left) of the S x S crop.  Writes the
+    piece's per-workgroup statistics to part [exp1_workspace(T, S, pool)] (fp64), pool_* [T, S/pool, S/pool] and sel_* [T, nsel]."""
+    T = pred.shape[0]
+    if truth.shape[0] != T or len(thresholds) > EXP1_MAX_THR:
+        raise RuntimeError("exp1_accumulate: frame count / thresholds")
+    if part.numel() != exp1_workspace(T, S, pool):
+        raise RuntimeError("exp1_accumulate: workspace size")
+    pc, gc = _exp1_code(pred), _exp1_code(truth)
+    for t, dt in ((rank, torch.int32), (lut, torch.float64), (pool_p, torch.float32), (pool_g, torch.float32), (sel_p, torch.float32),
+                  (sel_g, torch.float32), (part, torch.float64)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == dt):
+            raise RuntimeError("exp1_accumulate: bad buffer")
+    _hip.check(_hip.load().p2i_exp1_accumulate(
+        _ptr(pred), pc, pred.shape[1], pred.shape[2], ptl[0], ptl[1], _ptr(truth), gc, truth.shape[1], truth.shape[2], gtl[0], gtl[1],
+        T, S, pool, _ptr(rank), nsel, _ptr(lut), _f64s(thresholds), len(thresholds), int(divide_by_3), _ptr(pool_p), _ptr(pool_g),
+        _ptr(sel_p) if nsel else None, _ptr(sel_g) if nsel else None, _ptr(part), _stream()), "p2i_exp1_accumulate")
+
+
+def exp1_merge(part, acc):
+    """acc [EXP1_NSTAT] (+)= the partial records of part (a multiple of EXP1_NSTAT doubles), folded in a fixed order."""
+    if part.numel() % EXP1_NSTAT or acc.numel() != EXP1_NSTAT or part.dtype != torch.float64 or acc.dtype != torch.float64:
+        raise RuntimeError("exp1_merge: bad buffers")
+    _hip.check(_hip.load().p2i_exp1_merge(_ptr(part), part.numel() // EXP1_NSTAT, _ptr(acc), _stream()), "p2i_exp1_merge")
+
+
+def exp1_hist(sel_p, sel_g, acc, score, flag, edges):
+    """Per-frame PSS histograms of the compacted selections [T, nsel] over acc's range: score [T] f64, flag [T] int32, edges [52]."""
+    T, nsel = sel_p.shape
+    _hip.check(_hip.load().p2i_exp1_hist(_ptr(sel_p) if nsel else None, _ptr(sel_g) if nsel else None, T, nsel, _ptr(acc), _ptr(score),
+                                         _ptr(flag), _ptr(edges), _stream()), "p2i_exp1_hist")
+
+
+def exp1_ssim(pool_p, pool_g):
+    """pool_* [T, npix] f32 -> (SSIM(p_t, g_t), lag-1 and lag-2 dTSSIM terms), each [T] f64."""
+    T, npix = pool_p.shape
+    out = torch.empty(3, T, device=pool_p.device, dtype=torch.float64)
+    _hip.check(_hip.load().p2i_exp1_ssim(_ptr(pool_p), _ptr(pool_g), T, npix, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()),
+               "p2i_exp1_ssim")
+    return out
+
+
+def exp1_finalize(acc, thresholds, score, flag, edges, ssim3):
+    """The table's numbers of one method as a [8 + 4 k] f64 device tensor (see include/p2i_hip.h)."""
+    T = score.shape[0]
+    out = torch.empty(8 + 4 * len(thresholds), device=acc.device, dtype=torch.float64)
+    _hip.check(_hip.load().p2i_exp1_finalize(_ptr(acc), _f64s(thresholds), len(thresholds), T, _ptr(score), _ptr(flag), _ptr(edges),
+                                             _ptr(ssim3[0]), _ptr(ssim3[1]), _ptr(ssim3[2]), _ptr(out), _stream()), "p2i_exp1_finalize")
+    return out

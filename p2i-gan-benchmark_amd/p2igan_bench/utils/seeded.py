@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import math
 import zlib
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -180,3 +180,35 @@ def seeded_stdk_state(t: int = 16, seed: int = 2024, k_s: int = 139) -> dict:
         sd[f"_mlp.net.{i}.weight"] = torch.from_numpy((rng.standard_normal((o, n)) * np.sqrt(2.0 / n)).astype(np.float32))
         sd[f"_mlp.net.{i}.bias"] = torch.from_numpy((rng.standard_normal(o) * 0.01).astype(np.float32))
     return sd
+
+
+def exp1_truth(seed: int, t: int, h: int, w: int, lo: int = 0, hi: int = 255) -> np.ndarray:
+    """(T, 1, H, W) uint8 truth for the exp1 tests (numpy only, portable across hosts): box-blurred noise stretched to
+    [lo, hi], so that the rain-rate transform crosses the 0.5 / 2 / 4 / 8 mm/h thresholds."""
+    raw = _rng(seed, f"exp1truth{t}x{h}x{w}").random((t, h + 6, w + 6))
+    cs = np.cumsum(np.cumsum(np.pad(raw, ((0, 0), (1, 0), (1, 0))), axis=1), axis=2)
+    box = (cs[:, 7:, 7:] - cs[:, :-7, 7:] - cs[:, 7:, :-7] + cs[:, :-7, :-7]) / 49.0
+    box = (box - box.min()) / max(box.max() - box.min(), 1e-12)
+    return np.clip(np.rint(lo + box * (hi - lo)), 0, 255).astype(np.uint8)[:, None]
+
+
+def exp1_pred(seed: int, truth: np.ndarray, noise: float = 12.0, zero_frac: float = 0.0, over_frac: float = 0.0,
+              nan_frac: float = 0.0, t: Optional[int] = None) -> np.ndarray:
+    """(T, 1, H, W) float32 prediction near ``truth`` (its first ``t`` frames, or more: frames past the truth's length repeat it):
+    Gaussian noise, clipped at 0, then a fraction of exact zeros, of values above 255 and of NaN."""
+    t = truth.shape[0] if t is None else t
+    base = truth[np.arange(t) % truth.shape[0]].astype(np.float64)
+    rng = _rng(seed, f"exp1pred{base.shape}")
+    p = np.maximum(base + rng.standard_normal(base.shape) * noise, 0.0)
+    u = rng.random(base.shape)
+    p[u < zero_frac] = 0.0
+    over = (u >= zero_frac) & (u < zero_frac + over_frac)
+    p[over] = 256.0 + rng.random(int(over.sum())) * 200.0
+    p = p.astype(np.float32)
+    p[(u >= zero_frac + over_frac) & (u < zero_frac + over_frac + nan_frac)] = np.nan
+    return p
+
+
+def exp1_mask(seed: int, h: int, w: int, frac: float) -> np.ndarray:
+    """(H, W) bool mask with about ``frac`` of the pixels True."""
+    return _rng(seed, f"exp1mask{h}x{w}").random((h, w)) < frac

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Score inference outputs with the benchmark's exp1 table (the exp1 half of the reference's experiments/main.py) on the GPU.
+
+    python scripts/evaluate.py --truth truth.zarr --method p2igan=pred.zarr --method stdk=stdk.zarr \\
+        --mask mask_train.txt --mode radar --crop-size 128 --output results/exp1
+
+Every zarr is a group of per-event arrays (``event_01``, ``event_02``, ...) as scripts/infer.py writes them.  The truth's keys are
+taken in sorted order, and every method must hold all of them: unlike run_exp1, which skips an event a method lacks and so shifts
+its frames against the truth's, a missing event is refused here.  The mask is read with ``np.loadtxt(...).astype(bool)`` and
+center-cropped to the crop size.  Writes DIR/metrics.json (indent 2, sorted keys) and DIR/metrics.txt in main.py's layout.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from typing import Dict, List
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+from p2igan_bench.data import zarr_lite  # noqa: E402
+from p2igan_bench.evaluation import DEFAULT_THRESHOLDS, crop_mask, run_exp1  # noqa: E402
+
+
+def _method(spec: str):
+    name, sep, path = spec.partition("=")
+    if not sep or not name or not path:
+        raise argparse.ArgumentTypeError(f"expected NAME=ZARR, got {spec!r}")
+    return name, path
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="exp1 scores (MAE, RMSE, PSS, SSIM, dTSSIM, NSE, POD/FAR/CSI/HSS) of inference outputs")
+    p.add_argument("--truth", required=True, help="zarr group of the truth events (uint8 or float, 0-255 scale)")
+    p.add_argument("--method", type=_method, action="append", required=True, metavar="NAME=ZARR",
+                   help="a method's prediction zarr (repeatable)")
+    p.add_argument("--mask", required=True, help="mask .txt of the full domain (np.loadtxt)")
+    p.add_argument("--mode", choices=("radar", "gauge"), default="radar")
+    p.add_argument("--crop-size", type=int, default=128)
+    p.add_argument("--no-pool8", action="store_true", help="SSIM / dTSSIM on the full-resolution crop")
+    p.add_argument("--thresholds", type=float, nargs="+", default=list(DEFAULT_THRESHOLDS))
+    p.add_argument("--output", required=True, help="output directory")
+    p.add_argument("--device", default=None, help="torch device (default: the current GPU)")
+    args = p.parse_args(argv)
+    names = [n for n, _ in args.method]
+    if len(set(names)) != len(names):
+        p.error(f"method names repeat: {names}")
+    return args
+
+
+def load_events(path: str) -> Dict[str, np.ndarray]:
+    g = zarr_lite.Group(path, "r")
+    return {k: np.asarray(g[k][:]) for k in sorted(g.array_keys())}
+
+
+def load_mask(path: str, crop_size: int) -> np.ndarray:
+    return crop_mask(np.loadtxt(path).astype(bool), crop_size)
+
+
+def check_events(truth_keys: List[str], method: str, keys) -> None:
+    missing = [k for k in truth_keys if k not in keys]
+    if missing:
+        raise ValueError(f"method {method!r} lacks truth event {missing[0]!r}" + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+
+
+def format_lines(metrics) -> List[str]:
+    """main.py's metrics.txt layout: [method], `key: value` with 6 decimals, nested `key:` / `  sub: value`, a blank line."""
+    lines = []
+    for name, vals in metrics.items():
+        lines.append(f"[{name}]")
+        for k, v in vals.items():
+            if isinstance(v, dict):
+                lines.append(f"{k}:")
+                for sk, sv in v.items():
+                    lines.append(f"  {sk}: {sv:.6f}")
+            else:
+                lines.append(f"{k}: {v:.6f}")
+        lines.append("")
+    return lines
+
+
+def write_outputs(out_dir: str, metrics) -> None:
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "metrics.json"), "w", encoding="utf-8") as f:
+        json.dump(metrics, f, indent=2, sort_keys=True)
+    with open(os.path.join(out_dir, "metrics.txt"), "w", encoding="utf-8") as f:
+        for line in format_lines(metrics):
+            f.write(line.rstrip() + "\n")
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    truth = load_events(args.truth)
+    if not truth:
+        raise SystemExit(f"{args.truth}: no events")
+    preds = {}
+    for name, path in args.method:
+        g = zarr_lite.Group(path, "r")
+        keys = set(g.array_keys())
+        try:
+            check_events(list(truth), name, keys)
+        except ValueError as e:
+            raise SystemExit(f"{path}: {e}")
+        preds[name] = {k: np.asarray(g[k][:]) for k in truth}
+    mask = load_mask(args.mask, args.crop_size)
+    metrics = run_exp1(preds, truth, mask, args.mode, args.crop_size, thresholds=tuple(args.thresholds),
+                       use_pool8=not args.no_pool8, divide_by_3=True, device=args.device)
+    write_outputs(args.output, metrics)
+    print(f"wrote {os.path.join(args.output, 'metrics.json')} ({len(metrics)} methods)")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""exp1 scoring of a synthetic test set at full size (20 events x 200 frames x 128 x 128, uint8 truth, 3 methods of f32
+predictions, radar mode) on the MI355X, and the numpy restatement (tests/exp1_ref.py) on the host's CPU for comparison.
+Device times: run_exp1 from host (numpy) arrays, upload included, and from arrays already on the device; median of
+--reps runs after one warm-up, wall clock around a call that ends in the evaluator's host sync.  Prints one JSON line.
+
+usage: python tools/exp1_bench.py [--events 20] [--frames 200] [--hw 128] [--reps 5] [--cpu-threads 16] [--no-cpu]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "p2i-gan-benchmark_amd"), os.path.join(ROOT, "tests")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--events", type=int, default=20)
+    ap.add_argument("--frames", type=int, default=200)
+    ap.add_argument("--hw", type=int, default=128)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cpu-threads", type=int, default=16)
+    ap.add_argument("--no-cpu", action="store_true")
+    a = ap.parse_args()
+    for v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
+        os.environ.setdefault(v, str(a.cpu_threads))
+    import numpy as np
+    import torch
+    torch.set_num_threads(a.cpu_threads)
+    from p2igan_bench.evaluation import run_exp1
+    from p2igan_bench.utils import seeded
+
+    keys = [f"event_{i + 1:02d}" for i in range(a.events)]
+    truth = {k: seeded.exp1_truth(700 + i, a.frames, a.hw, a.hw) for i, k in enumerate(keys)}
+    preds = {m: {k: seeded.exp1_pred(7000 + 100 * j + i, truth[k], 8.0 + 10 * j, 0.02, 0.01) for i, k in enumerate(keys)}
+             for j, m in enumerate(("p2igan", "stdk", "idw"))}
+    mask = seeded.exp1_mask(7, a.hw, a.hw, 0.3)
+    dev = torch.device("cuda")
+
+    def run(p, t):
+        t0 = time.perf_counter()
+        res = run_exp1(p, t, mask, "radar", a.hw)
+        return time.perf_counter() - t0, res
+
+    res_host = run(preds, truth)[1]                     # warm-up (library load, allocator)
+    host = [run(preds, truth)[0] for _ in range(a.reps)]
+    truth_d = {k: torch.from_numpy(v).to(dev) for k, v in truth.items()}
+    preds_d = {m: {k: torch.from_numpy(v).to(dev) for k, v in p.items()} for m, p in preds.items()}
+    torch.cuda.synchronize()
+    run(preds_d, truth_d)
+    devt = [run(preds_d, truth_d)[0] for _ in range(a.reps)]
+    out = {"tool": "exp1_bench", "events": a.events, "frames": a.frames, "hw": a.hw, "methods": 3,
+           "gpu_from_host_s": round(statistics.median(host), 4), "gpu_from_device_s": round(statistics.median(devt), 4),
+           "gpu_runs": a.reps, "mae_p2igan": res_host["p2igan"]["MAE"]}
+    if not a.no_cpu:
+        t0 = time.perf_counter()
+        with np.errstate(all="ignore"):
+            import exp1_ref
+            ref = exp1_ref.run_exp1(preds, truth, mask, "radar", a.hw)
+        out["cpu_restatement_s"] = round(time.perf_counter() - t0, 3)
+        out["cpu_threads"] = a.cpu_threads
+        out["max_rel_mae_diff"] = max(abs(res_host[m]["MAE"] - ref[m]["MAE"]) / abs(ref[m]["MAE"]) for m in ref)
+        out["speedup_from_host"] = round(out["cpu_restatement_s"] / out["gpu_from_host_s"], 1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
