@@ -434,6 +434,35 @@ int p2i_exp1_ssim(const float* pool_pred, const float* pool_truth, int T, int np
 int p2i_exp1_finalize(const double* acc, const double* thresholds_host, int nthr, int T, const double* score, const int* flag,
                       const float* edges, const double* ssim, const double* d1, const double* d2, double* out, void* stream);
 
+/* ---- exp3 analysis (reference experiments/exp3.py run_exp3 + experiments/io.py).  Inputs are DEVICE arrays
+ * as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform and uint8 table); statistics are fp64,
+ * counts are integers.
+ * p2i_exp3_accumulate: one aligned piece of T frames, crops [top, top + S) x [left, left + S); rank[S*S] >= 0 marks the mode's
+ *   selection.  Writes rec[T][P2I_EXP3_NREC] = per frame (n, sum (p-g)^2, truth mean, truth M2) over the selection's finite
+ *   pairs; rows[T][S] (int32) = per crop row the scatter pool: pixels of the whole crop with p and g finite and g >= 0.1; and, when
+ *   hist is not NULL, adds the prediction's counts to hist[P2I_EXP3_NHIST]: 64 bins of np.linspace(0, 32, 65) over the finite
+ *   values in [0, 32] (bin min(floor(2 x), 63)), then the count of finite values.
+ * p2i_exp3_truth_hist: adds the same P2I_EXP3_NHIST counts of T truth frames to hist.
+ * p2i_exp3_scan: prefix[i] = rows[0] + ... + rows[i] (int64), i < n: the inclusive prefix of a method's row counts.
+ * p2i_exp3_gather: for i < K, the pool ordinal ords[i] (int64) of a method: when it falls in this piece's rows [row0, row0 + T*S)
+ *   of the method's prefix, out_g[i] / out_p[i] = the transformed truth / prediction of that pool pixel (raster order); other
+ *   entries are left as they are.
+ * p2i_exp3_nse: out[0] = the NSE of the fold of stack_rec[0 .. T) (fixed order; NaN when empty); out[1 + e], e < E = nanmean of
+ *   max(NSE, 0) over the frames event_off[e] .. event_off[e+1] - 1 of event_rec (event_off: DEVICE int32 [E + 1]). */
+#define P2I_EXP3_NREC 4
+#define P2I_EXP3_BINS 64
+#define P2I_EXP3_NHIST (P2I_EXP3_BINS + 1)
+int p2i_exp3_accumulate(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth, int truth_dtype,
+                        int gh, int gw, int gtop, int gleft, int T, int S, const int* rank, const double* lut, int divide_by_3,
+                        double* rec, int* rows, uint64_t* hist, void* stream);
+int p2i_exp3_truth_hist(const void* truth, int truth_dtype, int gh, int gw, int gtop, int gleft, int T, int S, const double* lut,
+                        int divide_by_3, uint64_t* hist, void* stream);
+int p2i_exp3_scan(const int* rows, int64_t n, int64_t* prefix, void* stream);
+int p2i_exp3_gather(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth, int truth_dtype, int gh,
+                    int gw, int gtop, int gleft, int T, int S, const double* lut, int divide_by_3, const int64_t* prefix, int64_t row0,
+                    const int64_t* ords, int K, double* out_g, double* out_p, void* stream);
+int p2i_exp3_nse(const double* event_rec, const int* event_off, int E, const double* stack_rec, int T, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

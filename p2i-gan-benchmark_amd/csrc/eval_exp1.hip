@@ -15,7 +15,7 @@
 //   p2i_exp1_ssim       : per frame the global SSIM of (pred_t, gt_t) and, for lags 1 and 2, SSIM(p_t, p_t-L) - SSIM(g_t, g_t-L)
 //   p2i_exp1_finalize   : the per-frame series reduced in frame order and the table's numbers, out[P2I_EXP1_OUT(k)]
 // Compiled with -ffp-contract=off: the linspace edges and the transform must round as numpy's separate operations do.
-#include "common.h"
+#include "eval_common.h"
 
 namespace p2i {
 
@@ -27,23 +27,6 @@ static_assert(NST == P2I_EXP1_NSTAT, "stats layout");
 constexpr int BINS = 50;
 
 struct Thr { double v[XK]; int k; };
-
-__device__ __forceinline__ double mmhr(double x, int div3) {
-  // np.maximum propagates NaN (fmax would drop it); np.clip(e, None, 38) and np.clip(out, 0, 200) keep NaN as well
-  if (!(x != x) && x < 0.001) x = 0.001;
-  if (div3) x = x / 3.0;
-  double e = x * 0.0625;
-  if (e > 38.0) e = 38.0;
-  double out = pow(10.0, e) * 0.036;
-  if (out < 0.0) out = 0.0;
-  if (out > 200.0) out = 200.0;
-  return out;
-}
-
-template <typename T> __device__ __forceinline__ double tload(const T* p, long long i, const double* lut, int div3);
-template <> __device__ __forceinline__ double tload<uint8_t>(const uint8_t* p, long long i, const double* lut, int) { return lut[p[i]]; }
-template <> __device__ __forceinline__ double tload<float>(const float* p, long long i, const double*, int div3) { return mmhr((double)p[i], div3); }
-template <> __device__ __forceinline__ double tload<double>(const double* p, long long i, const double*, int div3) { return mmhr(p[i], div3); }
 
 struct Stats {
   double n, sabs, ssq, gmean, gm2, npss, vmin, vmax;
@@ -57,13 +40,7 @@ __device__ __forceinline__ void st_zero(Stats& s) {
 }
 // a <- a (+) b, Chan et al.'s pairwise update for (n, mean, M2); sums add; the range is taken over both non-empty sides
 __device__ __forceinline__ void st_merge(Stats& a, const Stats& b) {
-  const double n = a.n + b.n;
-  if (b.n > 0.0) {
-    const double d = b.gmean - a.gmean;
-    a.gmean = a.gmean + d * (b.n / n);
-    a.gm2 = a.gm2 + b.gm2 + d * d * (a.n * b.n / n);
-  }
-  a.n = n;
+  chan_merge(a.n, a.gmean, a.gm2, b.n, b.gmean, b.gm2);
   a.sabs += b.sabs;
   a.ssq += b.ssq;
   if (b.npss > 0.0) {
@@ -135,12 +112,9 @@ __global__ __launch_bounds__(64) void exp1_accumulate_kernel(const PT* __restric
         const int r = rank[y * S + x];
         if (r >= 0 && r < nsel) {
           const double d = p - g;
-          s.n += 1.0;
           s.sabs += fabs(d);
           s.ssq += d * d;
-          const double dg = g - s.gmean;
-          s.gmean += dg / s.n;
-          s.gm2 += dg * (g - s.gmean);
+          welford_push(s.n, s.gmean, s.gm2, g);
 #pragma unroll
           for (int k = 0; k < XK; ++k)
             if (k < thr.k) {

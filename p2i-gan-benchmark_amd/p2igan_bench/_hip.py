@@ -104,6 +104,11 @@ SIGNATURES = {
     "p2i_exp1_hist": [_P, _P, _I, _I, _P, _P, _P, _P, _P],
     "p2i_exp1_ssim": [_P, _P, _I, _I, _P, _P, _P, _P],
     "p2i_exp1_finalize": [_P, C.POINTER(C.c_double), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "p2i_exp3_accumulate": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P],
+    "p2i_exp3_truth_hist": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P],
+    "p2i_exp3_scan": [_P, _L, _P, _P],
+    "p2i_exp3_gather": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _L, _P, _I, _P, _P, _P],
+    "p2i_exp3_nse": [_P, _P, _I, _P, _I, _P, _P],
 }
 
 

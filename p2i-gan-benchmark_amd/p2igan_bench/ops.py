@@ -1341,3 +1341,85 @@ def exp1_finalize(acc, thresholds, score, flag, edges, ssim3):
     _hip.check(_hip.load().p2i_exp1_finalize(_ptr(acc), _f64s(thresholds), len(thresholds), T, _ptr(score), _ptr(flag), _ptr(edges),
                                              _ptr(ssim3[0]), _ptr(ssim3[1]), _ptr(ssim3[2]), _ptr(out), _stream()), "p2i_exp1_finalize")
     return out
+
+
+# ---- exp3 analysis (csrc/eval_exp3.hip; p2igan_bench/evaluation.py drives these) ----
+EXP3_NREC = 4
+EXP3_BINS = 64
+EXP3_NHIST = EXP3_BINS + 1
+
+
+def _exp3_buf(t, dt, n, what):
+    if not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n):
+        raise RuntimeError(f"{what}: bad buffer")
+
+
+def exp3_accumulate(pred, truth, ptl, gtl, S, rank, lut, divide_by_3, rec, rows, hist=None):
+    """One aligned piece: pred, truth [T, H, W] (their own H, W), crop origins ptl / gtl = (top, left) of the S x S crop.  Writes the
+    per-frame records rec [T, EXP3_NREC] (f64) and scatter-pool row counts rows [T, S] (int32); adds the prediction's log-frequency
+    counts to hist [EXP3_NHIST] (int64) when it is given."""
+    T = pred.shape[0]
+    if truth.shape[0] != T:
+        raise RuntimeError("exp3_accumulate: frame count")
+    pc, gc = _exp1_code(pred), _exp1_code(truth)
+    _exp3_buf(rank, torch.int32, S * S, "exp3_accumulate")
+    _exp3_buf(lut, torch.float64, 256, "exp3_accumulate")
+    _exp3_buf(rec, torch.float64, T * EXP3_NREC, "exp3_accumulate")
+    _exp3_buf(rows, torch.int32, T * S, "exp3_accumulate")
+    if hist is not None:
+        _exp3_buf(hist, torch.int64, EXP3_NHIST, "exp3_accumulate")
+    _hip.check(_hip.load().p2i_exp3_accumulate(
+        _ptr(pred), pc, pred.shape[1], pred.shape[2], ptl[0], ptl[1], _ptr(truth), gc, truth.shape[1], truth.shape[2], gtl[0], gtl[1],
+        T, S, _ptr(rank), _ptr(lut), int(divide_by_3), _ptr(rec), _ptr(rows), _ptr(hist), _stream()), "p2i_exp3_accumulate")
+
+
+def exp3_truth_hist(truth, gtl, S, lut, divide_by_3, hist):
+    """Adds the log-frequency counts of every cropped frame of truth [T, H, W] to hist [EXP3_NHIST] (int64)."""
+    gc = _exp1_code(truth)
+    _exp3_buf(lut, torch.float64, 256, "exp3_truth_hist")
+    _exp3_buf(hist, torch.int64, EXP3_NHIST, "exp3_truth_hist")
+    _hip.check(_hip.load().p2i_exp3_truth_hist(_ptr(truth), gc, truth.shape[1], truth.shape[2], gtl[0], gtl[1], truth.shape[0], S,
+                                               _ptr(lut), int(divide_by_3), _ptr(hist), _stream()), "p2i_exp3_truth_hist")
+
+
+def exp3_scan(rows: torch.Tensor) -> torch.Tensor:
+    """The inclusive prefix (int64) of int32 row counts, on the device."""
+    _exp3_buf(rows, torch.int32, rows.numel(), "exp3_scan")
+    out = torch.empty(rows.numel(), device=rows.device, dtype=torch.int64)
+    if rows.numel():
+        _hip.check(_hip.load().p2i_exp3_scan(_ptr(rows), rows.numel(), _ptr(out), _stream()), "p2i_exp3_scan")
+    return out
+
+
+def exp3_gather(pred, truth, ptl, gtl, S, lut, divide_by_3, prefix, row0, ords, out_g, out_p):
+    """For the pool ordinals ords [K] (int64) that fall in this piece's rows [row0, row0 + T * S) of the method's prefix, writes the
+    transformed (truth, prediction) of the pool pixel to out_g / out_p [K] (f64)."""
+    T, K = pred.shape[0], ords.numel()
+    if truth.shape[0] != T or row0 + T * S > prefix.numel():
+        raise RuntimeError("exp3_gather: frame count / rows")
+    pc, gc = _exp1_code(pred), _exp1_code(truth)
+    _exp3_buf(lut, torch.float64, 256, "exp3_gather")
+    _exp3_buf(prefix, torch.int64, prefix.numel(), "exp3_gather")
+    _exp3_buf(ords, torch.int64, K, "exp3_gather")
+    _exp3_buf(out_g, torch.float64, K, "exp3_gather")
+    _exp3_buf(out_p, torch.float64, K, "exp3_gather")
+    if K == 0 or T == 0:
+        return
+    _hip.check(_hip.load().p2i_exp3_gather(
+        _ptr(pred), pc, pred.shape[1], pred.shape[2], ptl[0], ptl[1], _ptr(truth), gc, truth.shape[1], truth.shape[2], gtl[0], gtl[1],
+        T, S, _ptr(lut), int(divide_by_3), _ptr(prefix), int(row0), _ptr(ords), K, _ptr(out_g), _ptr(out_p), _stream()), "p2i_exp3_gather")
+
+
+def exp3_nse(event_rec, event_off, stack_rec) -> torch.Tensor:
+    """[1 + E] f64 on the device: the whole-stack NSE of stack_rec [T, EXP3_NREC], then per event e the nanmean of the clipped
+    per-frame NSEs of event_rec rows event_off[e] .. event_off[e + 1] - 1 (event_off: int32 [E + 1] on the device)."""
+    E = event_off.numel() - 1 if event_off is not None else 0
+    T = stack_rec.shape[0]
+    out = torch.empty(1 + E, device=stack_rec.device, dtype=torch.float64)
+    if E:
+        _exp3_buf(event_off, torch.int32, E + 1, "exp3_nse")
+        _exp3_buf(event_rec, torch.float64, event_rec.numel(), "exp3_nse")
+    _exp3_buf(stack_rec, torch.float64, T * EXP3_NREC, "exp3_nse")
+    _hip.check(_hip.load().p2i_exp3_nse(_ptr(event_rec) if E else None, _ptr(event_off) if E else None, E, _ptr(stack_rec) if T else None,
+                                        T, _ptr(out), _stream()), "p2i_exp3_nse")
+    return out

@@ -8,6 +8,10 @@ Every zarr is a group of per-event arrays (``event_01``, ``event_02``, ...) as s
 taken in sorted order, and every method must hold all of them: unlike run_exp1, which skips an event a method lacks and so shifts
 its frames against the truth's, a missing event is refused here.  The mask is read with ``np.loadtxt(...).astype(bool)`` and
 center-cropped to the crop size.  Writes DIR/metrics.json (indent 2, sorted keys) and DIR/metrics.txt in main.py's layout.
+
+With ``--exp3 DIR3`` it also runs the benchmark's exp3 analysis (run_exp3) on the same inputs and writes DIR3/metrics.json,
+DIR3/metrics.txt (``NSE_<name>: value`` lines, as main.py writes them), DIR3/exp3_data.npz and the figures (scatter_panels.pdf,
+residual_panels.pdf, nse_boxplot.pdf, logfreq.pdf).  exp1's outputs do not depend on it.
 """
 from __future__ import annotations
 
@@ -22,7 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 from p2igan_bench.data import zarr_lite  # noqa: E402
-from p2igan_bench.evaluation import DEFAULT_THRESHOLDS, crop_mask, run_exp1  # noqa: E402
+from p2igan_bench.evaluation import DEFAULT_THRESHOLDS, crop_mask, run_exp1, run_exp3  # noqa: E402
 
 
 def _method(spec: str):
@@ -44,6 +48,8 @@ def parse_args(argv=None):
     p.add_argument("--thresholds", type=float, nargs="+", default=list(DEFAULT_THRESHOLDS))
     p.add_argument("--output", required=True, help="output directory")
     p.add_argument("--device", default=None, help="torch device (default: the current GPU)")
+    p.add_argument("--exp3", default=None, metavar="DIR", help="also run exp3 (NSE, scatter / residual panels, NSE boxplot, "
+                   "log-frequency) and write its outputs into DIR")
     args = p.parse_args(argv)
     names = [n for n, _ in args.method]
     if len(set(names)) != len(names):
@@ -91,6 +97,16 @@ def write_outputs(out_dir: str, metrics) -> None:
             f.write(line.rstrip() + "\n")
 
 
+def write_exp3_outputs(out_dir: str, metrics) -> None:
+    """main.py's exp3 files: metrics.json (indent 2, sorted keys) and metrics.txt (`key: value` with 6 decimals)."""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "metrics.json"), "w", encoding="utf-8") as f:
+        json.dump(metrics, f, indent=2, sort_keys=True)
+    with open(os.path.join(out_dir, "metrics.txt"), "w", encoding="utf-8") as f:
+        for k, v in metrics.items():
+            f.write(f"{k}: {v:.6f}\n")
+
+
 def main(argv=None):
     args = parse_args(argv)
     truth = load_events(args.truth)
@@ -110,6 +126,10 @@ def main(argv=None):
                        use_pool8=not args.no_pool8, divide_by_3=True, device=args.device)
     write_outputs(args.output, metrics)
     print(f"wrote {os.path.join(args.output, 'metrics.json')} ({len(metrics)} methods)")
+    if args.exp3:
+        m3 = run_exp3(preds, truth, mask, args.mode, args.crop_size, args.exp3, device=args.device)
+        write_exp3_outputs(args.exp3, m3)
+        print(f"wrote {os.path.join(args.exp3, 'metrics.json')} and the exp3 figures")
 
 
 if __name__ == "__main__":
