@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "p2i_hip.h"
 #include "tape.h"
 
@@ -26,6 +27,15 @@ static inline int launch_status() {
   }
   return P2I_OK;
 }
+
+// ---- environment switches (every name, default and reader: DESIGN.md section 12).  env_int reads on every call:
+// for switches that a test or an A/B run flips inside one process.  P2I_ENV_ONCE reads when the statement first runs and keeps that
+// value for the process.  A switch that two sites consult has ONE accessor function, next to the code it steers.
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+#define P2I_ENV_ONCE(name, dflt) ([] { static const int v_ = p2i::env_int(name, dflt); return v_; }())
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }

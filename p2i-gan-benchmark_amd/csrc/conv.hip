@@ -264,10 +264,9 @@ static int run_patch_gemm_classes(PatchGeom g, const ClassSpec* css, int ncls, h
     t.eH = (jh - 1) * g.mH + rng[1] + 1;
     t.eW = (jw - 1) * g.mW + rng[2] + 1;
     // 16-B patch DMA: rows and tile origins 16-B aligned
-    static const int v4_off = getenv("P2I_CONV_V4") ? (atoi(getenv("P2I_CONV_V4")) == 0) : 0;   // read once per process
     bool same_lo_w = true;                                  // merged classes may share the aligned origin only if their w windows start alike
     for (int q = 1; q < ncls; ++q) same_lo_w = same_lo_w && lo[q][2] == lo[0][2];
-    t.v4 = (!v4_off && same_lo_w && (g.sW & 3) == 0 && ((jw * g.mW) & 3) == 0) ? 1 : 0;   // any source multiplier: rows are contiguous
+    t.v4 = (conv_v4_on() && same_lo_w && (g.sW & 3) == 0 && ((jw * g.mW) & 3) == 0) ? 1 : 0;   // any source multiplier: rows are contiguous
     t.v4sh = 0;
     if (t.v4) {
       t.v4sh = ((lo[0][2] % 4) + 4) % 4;                    // columns added on the left so that the row starts 16-B aligned
@@ -280,7 +279,7 @@ static int run_patch_gemm_classes(PatchGeom g, const ClassSpec* css, int ncls, h
     t.CSl = t.rpc * t.eW;
     t.CS = t.CSl;
     t.G4 = t.CSl >> 2;
-    static const int force_ck16 = getenv("P2I_CONV_CK16") ? atoi(getenv("P2I_CONV_CK16")) : 0;
+    const int force_ck16 = P2I_ENV_ONCE("P2I_CONV_CK16", 0);
     for (int CKc = ((max_taps <= 4 || ((force_ck16 || g.Ck >= 256) && max_taps == 9 && MBc <= 64)) ? 16 : 8); CKc >= 2; CKc >>= 1) {
       if (g.Ck >= CKc ? (g.Ck % CKc != 0) : (CKc != 2 && g.Ck * 2 <= CKc)) continue;
       if (CKc == 2 && !(MBc == 64 && NP == 128) && !(MBc == 32)) continue;      // instantiated CK=2 tiles
@@ -345,7 +344,7 @@ static int run_patch_gemm_classes(PatchGeom g, const ClassSpec* css, int ncls, h
   const size_t red_bytes = (size_t)4 * acc_regs * 64 * 4;
   // 27-tap (3-D) layers stage 27 * CK weight rows per chunk, so CK stays 4 and one workgroup fills a CU's LDS: give it 8 waves
   // too (two per SIMD: one wave's DMA issue / LDS waits hide under the other's MFMAs), one channel pair per wave group
-  static const int kg27 = getenv("P2I_CONV_KG27") ? atoi(getenv("P2I_CONV_KG27")) : 1;
+  const int kg27 = P2I_ENV_ONCE("P2I_CONV_KG27", 1);
   const bool kg_27 = kg27 && max_taps == 27 && c.CK == 4 && ncls == 1;
   const int KG = ((nb <= 320 || (c.CK == 16 && max_taps == 9) || kg_27) && (c.CK >= 8 || kg_27) && c.MB <= 64 && red_bytes <= best_lds) ? 2 : 1;
   g_last_plan[0] = c.MB; g_last_plan[1] = c.NPIX; g_last_plan[2] = c.WM; g_last_plan[3] = c.CK;

@@ -120,7 +120,7 @@ static bool c1_shape_ok(const p2i_conv_desc* d);
 static int c1_dgrad_fast(const p2i_conv_desc* d, const float* dy, const float* wp_d, const float* add, const float* mask_y, int mask_act,
                          float* dx, hipStream_t s);
 static int c1_wgrad_mfma(const p2i_conv_desc* d, const float* x, const float* dy, float* dwp, float* dbias, hipStream_t s);
-static const int c1_fast_on = getenv("P2I_C1_FAST") ? atoi(getenv("P2I_C1_FAST")) : 1;
+static const int c1_fast_on = env_int("P2I_C1_FAST", 1);      // read when the library is loaded
 
 int c1_dgrad(const p2i_conv_desc* d, const float* dy, const float* wp_d, const float* add, const float* mask_y, int mask_act,
              float* dx, hipStream_t s) {
@@ -619,7 +619,7 @@ __global__ __launch_bounds__(512) void o1_fwd_kernel(const float* __restrict__ x
 
 // 1 = not a case of this kernel
 int o1_fwd(const p2i_conv_desc* d, const float* x, const float* wp, const float* bias, float* y, int act, hipStream_t s) {
-  static const int on = getenv("P2I_O1_FWD") ? atoi(getenv("P2I_O1_FWD")) : 1;
+  const int on = P2I_ENV_ONCE("P2I_O1_FWD", 1);
   if (!on || d->Cout != 1 || d->kt != 1 || d->kh != 3 || d->kw != 3 || d->st != 1 || d->sh != 1 || d->sw != 1 || d->pt != 0 || d->ph != 1 ||
       d->pw != 1 || d->Ti != 1 || d->Cin < 8 || d->Cin > 2048)
     return 1;

@@ -206,6 +206,9 @@ __device__ __forceinline__ void epilogue_pair16(const f32x16& acc0, const f32x16
   }
 }
 
+// 16-byte patch DMA of the f32 engines (conv.hip, conv_fused.hip): P2I_CONV_V4=0 keeps the 4-byte DMA; read once per process
+inline bool conv_v4_on() { return P2I_ENV_ONCE("P2I_CONV_V4", 1) != 0; }
+
 static inline void pick_tile_dims(int NPIX, int B, int nT, int nH, int nW, int& jb, int& jt, int& jh, int& jw) {
   jw = pow2_ceil(nW); if (jw > 32) jw = 32;
   int rem = NPIX / jw;
@@ -304,9 +307,9 @@ struct X6Ctx { const uint16_t* wb; int ntaps_w; };
 X6Ctx& x6_ctx();
 
 // 3x3 stride-1 2-D layers on the bf16 matrix pipe, chunk/tap-row pipeline (conv_x6c.hip); returns 1 when it does not apply
-int run_patch_gemm_x6c(PatchGeom g, const ClassSpec& cs, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry = false);
+int run_patch_gemm_x6c(const PatchGeom& g, const ClassSpec& cs, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry = false);
 // data gradient of a 3x3(x3) stride-(1,2,2) pad-1 convolution: the four input-parity classes in one workgroup, bf16 matrix pipe
-int run_patch_gemm_x6c_fused(PatchGeom g, const ClassSpec* css, int ncls, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry = false);
+int run_patch_gemm_x6c_fused(const PatchGeom& g, const ClassSpec* css, int ncls, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry = false);
 bool x6c_would_take(const p2i_conv_desc* d, bool dgrad, int act_epi);
 
 // strided dgrad with the parity classes fused in one workgroup (conv_fused.hip); returns 1 when it does not apply

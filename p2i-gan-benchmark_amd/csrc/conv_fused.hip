@@ -297,7 +297,7 @@ static int launch_fused(const PatchGeom& g, dim3 grid, size_t lds, hipStream_t s
 
 // returns 1 when the fused kernel does not apply (caller falls back to the per-class launch)
 int run_patch_gemm_fused(PatchGeom g, const ClassSpec* css, int ncls, int* plan6, hipStream_t s) {
-  static const int disabled = getenv("P2I_DGRAD_FUSED") ? (atoi(getenv("P2I_DGRAD_FUSED")) == 0) : 0;
+  const bool disabled = P2I_ENV_ONCE("P2I_DGRAD_FUSED", 1) == 0;
   // (two-class launches, i.e. stride (2,1,1) with 27 taps, were measured slower fused: 61.6 vs 68.6 TF; they stay per class)
   if (disabled || ncls != 4 || g.src_y != nullptr || g.bias != nullptr || g.act_epi != P2I_ACT_NONE) return 1;
   const ClassSpec& c0s = css[0];
@@ -322,7 +322,7 @@ int run_patch_gemm_fused(PatchGeom g, const ClassSpec* css, int ncls, int* plan6
   if (mx[0] <= 0 || mx[1] <= 0 || mx[2] <= 0 || ntt == 0 || ntt > MAX_TAPS) return 1;
   {
     // float2 epilogue: classes (2k, 2k+1) = (.., pW 0), (.., pW 1) over the same grid, even destination row, 8-byte aligned tensors
-    static const int pair_on = getenv("P2I_DGRAD_PAIR") ? atoi(getenv("P2I_DGRAD_PAIR")) : 1;
+    const int pair_on = P2I_ENV_ONCE("P2I_DGRAD_PAIR", 1);
     bool pair = pair_on && c0s.oW == 2 && (g.dW & 1) == 0;
     for (int q = 0; q < ncls && pair; q += 2)
       pair = css[q].pW == 0 && css[q + 1].pW == 1 && css[q].pT == css[q + 1].pT && css[q].pH == css[q + 1].pH &&
@@ -346,8 +346,7 @@ int run_patch_gemm_fused(PatchGeom g, const ClassSpec* css, int ncls, int* plan6
   g.eH = (jh - 1) + hi[1] - lo[1] + 1;
   g.eW = (jw - 1) + hi[2] - lo[2] + 1;
   {
-    static const int v4_off = getenv("P2I_CONV_V4") ? (atoi(getenv("P2I_CONV_V4")) == 0) : 0;
-    g.v4 = (!v4_off && (g.sW & 3) == 0 && jw >= 4) ? 1 : 0;
+    g.v4 = (conv_v4_on() && (g.sW & 3) == 0 && jw >= 4) ? 1 : 0;
     g.v4sh = 0;
     if (g.v4) {
       g.v4sh = ((lo[2] % 4) + 4) % 4;

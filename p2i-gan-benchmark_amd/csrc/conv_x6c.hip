@@ -46,6 +46,19 @@ __device__ __forceinline__ void split8c(const float (&v)[8], u32x4c& hi, u32x4c&
   }
 }
 
+// eight floats `stride` apart -> the three planes' 16-byte units at index i (planes `total` units apart)
+template <class S, class I>
+__device__ __forceinline__ void split8_store(const float* __restrict__ p, S stride, u32x4c* __restrict__ out, I total, I i) {
+  float v[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) v[q] = p[(S)q * stride];
+  u32x4c h, mi, lo;
+  split8c(v, h, mi, lo);
+  out[i] = h;
+  out[total + i] = mi;
+  out[2 * total + i] = lo;
+}
+
 // packed fp32 weights wp[tap][k][CmPad] -> Wb[plane][tap][k/8][CmPad][8] bf16 (planes hi, mid, lo)
 __global__ __launch_bounds__(256) void wsplit_kernel(const float* __restrict__ wp, u32x4c* __restrict__ wb, int ntaps, int Ck, int CmPad) {
   const int KCt = Ck >> 3;
@@ -55,14 +68,7 @@ __global__ __launch_bounds__(256) void wsplit_kernel(const float* __restrict__ w
     const int r = i / CmPad;
     const int kc = r % KCt, tap = r / KCt;
     const float* p = wp + ((size_t)tap * Ck + kc * 8) * CmPad + m;
-    float v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = p[(size_t)q * CmPad];
-    u32x4c h, mi, lo;
-    split8c(v, h, mi, lo);
-    wb[i] = h;
-    wb[total + i] = mi;
-    wb[2 * total + i] = lo;
+    split8_store(p, (size_t)CmPad, wb, total, i);
   }
 }
 
@@ -80,14 +86,7 @@ __global__ __launch_bounds__(256) void wsplit_batched_kernel(const WsplitBatch b
     const int r = i / CmPad;
     const int kc = r % KCt, tap = r / KCt;
     const float* p = wp + ((size_t)tap * Ck + kc * 8) * CmPad + m;
-    float v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = p[(size_t)q * CmPad];
-    u32x4c h, mi, lo;
-    split8c(v, h, mi, lo);
-    wb[i] = h;
-    wb[total + i] = mi;
-    wb[2 * total + i] = lo;
+    split8_store(p, (size_t)CmPad, wb, total, i);
   }
 }
 
@@ -98,14 +97,7 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const long long pix = i % P, r = i / P;          // r = b * KCt + kg
     const float* px = x + (r * 8) * P + pix;
-    float v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = px[(long long)q * P];
-    u32x4c h, mi, lo;
-    split8c(v, h, mi, lo);
-    planes[i] = h;
-    planes[total + i] = mi;
-    planes[2 * total + i] = lo;
+    split8_store(px, P, planes, total, i);
   }
 }
 
@@ -164,261 +156,18 @@ template <int NW> struct X6cTile {
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the immediate must be a constant): a balanced tree of scalar compares, six
 // deep.  (A `switch` over the 61 cases compiled to a LINEAR chain of compare + branch: ~3 n scalar instructions per wait, two or
 // three waits per stage -- a third of a producer wave's instructions, tools: histogram of the loop in the .s.)  n >= 63: vmcnt(0).
+// The tree is spelled by doubling macros so that it expands to the nest of if / else written out by hand before (same code object,
+// instruction for instruction).  A recursive `if constexpr` template says the same in fewer lines, but its 63 nested inlined calls
+// come out with another branch layout in 14 of the 18 kernels (profiles/README.md "Switch reader, one planner, wait tree").
+#define X6C_WAIT1(b) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(b) : "memory")
+#define X6C_WAIT2(b) if (n < (b) + 1) { X6C_WAIT1(b); } else { X6C_WAIT1((b) + 1); }
+#define X6C_WAIT4(b) if (n < (b) + 2) { X6C_WAIT2(b) } else { X6C_WAIT2((b) + 2) }
+#define X6C_WAIT8(b) if (n < (b) + 4) { X6C_WAIT4(b) } else { X6C_WAIT4((b) + 4) }
+#define X6C_WAIT16(b) if (n < (b) + 8) { X6C_WAIT8(b) } else { X6C_WAIT8((b) + 8) }
+#define X6C_WAIT32(b) if (n < (b) + 16) { X6C_WAIT16(b) } else { X6C_WAIT16((b) + 16) }
 __device__ __forceinline__ void x6c_wait_vm(int n) {
   if (n < 0 || n > 62) n = 0;
-  if (n < 32) {
-   if (n < 16) {
-    if (n < 8) {
-     if (n < 4) {
-      if (n < 2) {
-       if (n < 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-       }
-      } else {
-       if (n < 3) {
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-       }
-      }
-     } else {
-      if (n < 6) {
-       if (n < 5) {
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-       }
-      } else {
-       if (n < 7) {
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-       }
-      }
-     }
-    } else {
-     if (n < 12) {
-      if (n < 10) {
-       if (n < 9) {
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-       }
-      } else {
-       if (n < 11) {
-        asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-       }
-      }
-     } else {
-      if (n < 14) {
-       if (n < 13) {
-        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-       }
-      } else {
-       if (n < 15) {
-        asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-       }
-      }
-     }
-    }
-   } else {
-    if (n < 24) {
-     if (n < 20) {
-      if (n < 18) {
-       if (n < 17) {
-        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(17)" ::: "memory");
-       }
-      } else {
-       if (n < 19) {
-        asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(19)" ::: "memory");
-       }
-      }
-     } else {
-      if (n < 22) {
-       if (n < 21) {
-        asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(21)" ::: "memory");
-       }
-      } else {
-       if (n < 23) {
-        asm volatile("s_waitcnt vmcnt(22)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(23)" ::: "memory");
-       }
-      }
-     }
-    } else {
-     if (n < 28) {
-      if (n < 26) {
-       if (n < 25) {
-        asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(25)" ::: "memory");
-       }
-      } else {
-       if (n < 27) {
-        asm volatile("s_waitcnt vmcnt(26)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(27)" ::: "memory");
-       }
-      }
-     } else {
-      if (n < 30) {
-       if (n < 29) {
-        asm volatile("s_waitcnt vmcnt(28)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(29)" ::: "memory");
-       }
-      } else {
-       if (n < 31) {
-        asm volatile("s_waitcnt vmcnt(30)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(31)" ::: "memory");
-       }
-      }
-     }
-    }
-   }
-  } else {
-   if (n < 48) {
-    if (n < 40) {
-     if (n < 36) {
-      if (n < 34) {
-       if (n < 33) {
-        asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(33)" ::: "memory");
-       }
-      } else {
-       if (n < 35) {
-        asm volatile("s_waitcnt vmcnt(34)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(35)" ::: "memory");
-       }
-      }
-     } else {
-      if (n < 38) {
-       if (n < 37) {
-        asm volatile("s_waitcnt vmcnt(36)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(37)" ::: "memory");
-       }
-      } else {
-       if (n < 39) {
-        asm volatile("s_waitcnt vmcnt(38)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(39)" ::: "memory");
-       }
-      }
-     }
-    } else {
-     if (n < 44) {
-      if (n < 42) {
-       if (n < 41) {
-        asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(41)" ::: "memory");
-       }
-      } else {
-       if (n < 43) {
-        asm volatile("s_waitcnt vmcnt(42)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(43)" ::: "memory");
-       }
-      }
-     } else {
-      if (n < 46) {
-       if (n < 45) {
-        asm volatile("s_waitcnt vmcnt(44)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(45)" ::: "memory");
-       }
-      } else {
-       if (n < 47) {
-        asm volatile("s_waitcnt vmcnt(46)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(47)" ::: "memory");
-       }
-      }
-     }
-    }
-   } else {
-    if (n < 56) {
-     if (n < 52) {
-      if (n < 50) {
-       if (n < 49) {
-        asm volatile("s_waitcnt vmcnt(48)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(49)" ::: "memory");
-       }
-      } else {
-       if (n < 51) {
-        asm volatile("s_waitcnt vmcnt(50)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(51)" ::: "memory");
-       }
-      }
-     } else {
-      if (n < 54) {
-       if (n < 53) {
-        asm volatile("s_waitcnt vmcnt(52)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(53)" ::: "memory");
-       }
-      } else {
-       if (n < 55) {
-        asm volatile("s_waitcnt vmcnt(54)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(55)" ::: "memory");
-       }
-      }
-     }
-    } else {
-     if (n < 60) {
-      if (n < 58) {
-       if (n < 57) {
-        asm volatile("s_waitcnt vmcnt(56)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(57)" ::: "memory");
-       }
-      } else {
-       if (n < 59) {
-        asm volatile("s_waitcnt vmcnt(58)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(59)" ::: "memory");
-       }
-      }
-     } else {
-      if (n < 62) {
-       if (n < 61) {
-        asm volatile("s_waitcnt vmcnt(60)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(61)" ::: "memory");
-       }
-      } else {
-       if (n < 63) {
-        asm volatile("s_waitcnt vmcnt(62)" ::: "memory");
-       } else {
-        asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-       }
-      }
-     }
-    }
-   }
-  }
+  if (n < 32) { X6C_WAIT32(0) } else { X6C_WAIT32(32) }
 }
 
 // TPS = taps per pipeline stage (one hand-over barrier per stage): 3 = one kernel row, 9 = the whole 16-channel chunk.  A 32-channel
@@ -1248,26 +997,39 @@ __global__ __launch_bounds__(64 * (4 + NPW)) void patch_gemm_x6p_kernel(const X6
 #endif
 }
 
+// ---- switches of this engine.  Read per call unless noted: tests and A/B runs flip
+// them inside one process.
+static bool x6c_on() { return P2I_ENV_ONCE("P2I_CONV_X6C", 1) != 0; }                  // once per process
+static bool x6c_fused_on() { return P2I_ENV_ONCE("P2I_CONV_X6C_FUSED", 1) != 0; }      // once per process
 // Fewest workgroups for which a tile variant is used (256 CUs; below that the next smaller tile, or the f32 engine).  Read per call
 // (not cached) so that the parity tests can send small layers through these kernels (P2I_X6C_MIN_WG=1).
-static int x6c_min_wg() { const char* e = getenv("P2I_X6C_MIN_WG"); return e ? atoi(e) : 200; }
+static int x6c_min_wg() { return env_int("P2I_X6C_MIN_WG", 200); }
 // When not even the smallest tile reaches that count, the smallest tile is still taken from this many workgroups on: a split-pipe
 // workgroup does its tile ~2x faster than the f32 engine's, which has no more workgroups to offer for the same layer (its smallest tile
 // is 32 x 128 too).  Small per-GPU batches live here: at B = 4 the 512-channel level has 128 tiles of 32 x 128.
-static int x6c_min_wg_low() { const char* e = getenv("P2I_X6C_MIN_WG"); if (e) return atoi(e); e = getenv("P2I_X6C_MIN_WG_LOW"); return e ? atoi(e) : 64; }
-static int x6c_pc();
-static int x6p_tn1() { const char* e = getenv("P2I_X6P_TN1"); return e ? atoi(e) : 1; }      // read per call (A/B runs)
+static int x6c_min_wg_low() { return env_int("P2I_X6C_MIN_WG", env_int("P2I_X6C_MIN_WG_LOW", 64)); }
 // the fused strided data gradient is taken from 128 workgroups on (half the chip, one round: the 128 -> 256 stride-2 layer at B = 8);
-// its f32 alternative is no faster per workgroup.  P2I_X6C_MIN_WG overrides both thresholds (tests).
-static int x6c_fused_min_wg() { const char* e = getenv("P2I_X6C_MIN_WG"); return e ? atoi(e) : 128; }
+// its f32 alternative is no faster per workgroup.  P2I_X6C_MIN_WG overrides all three thresholds (tests).
+static int x6c_fused_min_wg() { return env_int("P2I_X6C_MIN_WG", 128); }
+static int x6p_tn1() { return env_int("P2I_X6P_TN1", 1); }
 // P2I_X6C_TILE=<NW><TM> (82, 81, 41; 41 = the 32 x 128 tile, falling back to 81 where that has no kernel) forces one variant (tests, tuning)
-static int x6c_forced() { const char* e = getenv("P2I_X6C_TILE"); return e ? atoi(e) : 0; }
-
+static int x6c_forced() { return env_int("P2I_X6C_TILE", 0); }
 // P2I_X6C_STAGGER=1: waves 4-7 run their staging work late in the stage (see `staging` in the kernel).  Measured in round 3 at B = 8
 // (gpurun_out/r03d/s0.log vs s1.log): no gain -- 64-channel level 75.0 -> 74.3 / 76.1 -> 81.2 us, every other layer within 1 us -- so
-// the lockstep schedule stays the default; read per call (A/B runs)
-static int x6c_stagger() { const char* e = getenv("P2I_X6C_STAGGER"); return e ? atoi(e) : 0; }
-static int x6c_fused_ksplit() { const char* e = getenv("P2I_X6C_FUSED_KSPLIT"); return e ? atoi(e) : 0; }   // read per call (tests)
+// the lockstep schedule stays the default
+static int x6c_stagger() { return env_int("P2I_X6C_STAGGER", 0); }
+static int x6c_fused_ksplit() { return env_int("P2I_X6C_FUSED_KSPLIT", 0); }
+// P2I_X6P_NPW=4: one producer wave per SIMD for the 32-channel tiles too (default 8)
+static int x6p_npw() { return env_int("P2I_X6P_NPW", 8) == 4 ? 4 : 8; }
+// Producer / consumer wave roles (patch_gemm_x6p_kernel): the default for every layer with more than one 16-channel chunk;
+// P2I_X6C_PC=0 keeps the symmetric kernels.  Measured at B = 8, symmetric -> producer / consumer
+// (gpurun_out/r03f/pc0.log, pc2.log): 64-channel level 75.4 -> 75.8 / 79.0 -> 73.9 us (fwd / dgrad), 128: 62.3 -> 57.4, 256: 64.3 ->
+// 56.3, 512: 75.8 -> 68.6, 3-D 128 -> 128: 86.0 -> 76.5; K = 16 (16 -> 64 forward): 36.8 -> 39.9, hence the exception.
+static int x6c_pc() { return env_int("P2I_X6C_PC", 1); }
+// taps per stage of the 32-channel tiles: 9 (whole chunk) unless P2I_X6C_TPS=3
+static int x6c_tps1() { return env_int("P2I_X6C_TPS", 9) == 3 ? 3 : 9; }
+// x6p: the consumer waves raise their issue priority for the tap loop (X6cGeom::cons_prio)
+static int x6p_prio() { return env_int("P2I_X6P_PRIO", 0); }
 
 struct X6cVariant { int NW, TM; };
 static const X6cVariant kX6cVariants[] = {{8, 2}, {8, 1}, {4, 1}};      // in order of per-CU efficiency ({4, 1}: 32 x 128, x6p only)
@@ -1281,7 +1043,7 @@ static X6cPick x6c_pick(int B, int nH, int nW, int Cm, int Ck, bool linear_epi, 
   const int min_wg = x6c_min_wg();
   const bool tn1_ok = x6c_pc() && Ck_slice >= 32;                // the 32 x 128 tile exists as a producer / consumer kernel only
   if (forced == 41 && !tn1_ok) forced = 81;
-  static const int ksplit_on = getenv("P2I_X6C_KSPLIT") ? atoi(getenv("P2I_X6C_KSPLIT")) : 1;
+  const int ksplit_on = P2I_ENV_ONCE("P2I_X6C_KSPLIT", 1);
   // candidate order: 64x256, 32x256, then split-K 32x256.  (P2I_X6C_KSPLIT=2 tries split-K 64x256 before plain 32x256: measured 70.8 vs
   // 73.5 us on the 256-channel level, inside the noise, not the default.)
   // (round 3: the 32 x 128 tile of the producer / consumer kernel comes before any split-K form; P2I_X6P_TN1=0 removes it)
@@ -1305,23 +1067,35 @@ static X6cPick x6c_pick(int B, int nH, int nW, int Cm, int Ck, bool linear_epi, 
   return low;          // (v = -1 when nothing qualified: f32 engine)
 }
 
-// cheap host-side test used before the weights are split: would run_patch_gemm_x6c take this layer?
+// the fused strided data gradient's plan: always the 32 x 256 tile (kX6cVariants[1]: 256 class-local positions of (b, t) images, 32
+// destination channels, four accumulator classes) over a (jh+1) x (jw+1) patch; v = -1: too few workgroups, or the patch does not fit.
+// Split-K for layers with too few tiles: measured SLOWER than the f32 fused kernel on the one layer of the step it would take
+// (128 -> 256 stride 2 at B = 8: 90.6 vs 72 us, the float2 pairs become two atomics each), so it is off unless asked for.
+// may_split: the launch owns the whole destination and aliases no epilogue operand -- only the runner can see that; x6c_would_take
+// passes true, i.e. it may say yes to a layer the runner then declines.
+static X6cPick x6c_fused_pick(int nimg, int nH, int nW, int Cm, int chunks, bool may_split) {
+  X6cPick pk{-1, 0, 0, 0, 0, 1, 0};
+  int jt;
+  pick_tile_dims(256, nimg, 1, nH, nW, pk.jb, jt, pk.jh, pk.jw);
+  pk.csl = pk.jb * (pk.jh + 1) * (pk.jw + 1);
+  if (jt != 1 || pk.csl > X6cTile<8>::MAXCSL) return pk;
+  const long long tiles = (long long)ceil_div(nimg, pk.jb) * ceil_div(nH, pk.jh) * ceil_div(nW, pk.jw) * ceil_div(Cm, 32);
+  const bool can_split = x6c_fused_ksplit() && may_split && (chunks & 1) == 0;
+  const int min_wg = x6c_fused_min_wg();
+  if (tiles < min_wg && !(can_split && 2 * tiles >= min_wg)) return pk;
+  pk.ksplit = tiles < min_wg ? 2 : 1;
+  pk.wgs = tiles * pk.ksplit;
+  pk.v = 1;
+  return pk;
+}
+
+// cheap host-side test used before the weights are split: would run_patch_gemm_x6c / run_patch_gemm_x6c_fused take this layer?
 bool x6c_would_take(const p2i_conv_desc* d, bool dgrad, int act_epi) {
-  static const int on = getenv("P2I_CONV_X6C") ? atoi(getenv("P2I_CONV_X6C")) : 1;
+  const bool on = x6c_on();
   (void)act_epi;                                       // (an activation is applied by a second pass when the launch is split-K)
   if (on && dgrad && d->sh == 2 && d->sw == 2 && d->st == 1 && d->kh == 3 && d->kw == 3 && d->ph == 1 && d->pw == 1 &&
-      ((d->kt == 1 && d->pt == 0) || (d->kt == 3 && d->pt == 1)) && (d->Cout & 15) == 0 && d->Cout >= 16 && !(d->Hi & 1) && !(d->Wi & 1)) {
-    // fused strided data gradient (run_patch_gemm_x6c_fused): same tile / grid arithmetic as there
-    static const int fused_on = getenv("P2I_CONV_X6C_FUSED") ? atoi(getenv("P2I_CONV_X6C_FUSED")) : 1;
-    if (!fused_on) return false;
-    const int nimg = d->B * d->Ti, nH = d->Hi / 2, nW = d->Wi / 2;
-    int jb, jt, jh, jw;
-    pick_tile_dims(256, nimg, 1, nH, nW, jb, jt, jh, jw);
-    if (jt != 1 || jb * (jh + 1) * (jw + 1) > X6cTile<8>::MAXCSL) return false;
-    const long long tiles = (long long)ceil_div(nimg, jb) * ceil_div(nH, jh) * ceil_div(nW, jw) * ceil_div(d->Cin, 32);
-    const bool can_split = x6c_fused_ksplit() && (((d->kt * (d->Cout >> 4)) & 1) == 0);
-    return tiles >= x6c_fused_min_wg() || (can_split && 2 * tiles >= x6c_fused_min_wg());
-  }
+      ((d->kt == 1 && d->pt == 0) || (d->kt == 3 && d->pt == 1)) && (d->Cout & 15) == 0 && d->Cout >= 16 && !(d->Hi & 1) && !(d->Wi & 1))
+    return x6c_fused_on() && x6c_fused_pick(d->B * d->Ti, d->Hi / 2, d->Wi / 2, d->Cin, d->kt * (d->Cout >> 4), true).v >= 0;
   if (!on || d->kh != 3 || d->kw != 3 || d->sh != 1 || d->sw != 1 || d->ph != 1 || d->pw != 1) return false;
   const bool flat = d->kt == 1 && d->st == 1 && d->pt == 0;           // 2-D layer (or frames convolved independently)
   const bool vol = d->kt == 3 && d->pt == 1 && d->st <= 2;            // 3 x 3 x 3, t stride 1 or 2: tap slices along t
@@ -1354,44 +1128,81 @@ __global__ __launch_bounds__(256) void x6c_post_act_kernel(float* __restrict__ y
   }
 }
 
-template <int NW, int TM, bool FUSED = false, int TPS = 3>
-static void x6c_launch(const X6cGeom& g, dim3 grid, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)patch_gemm_x6c_kernel<NW, TM, FUSED, TPS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  P2I_LAUNCH((patch_gemm_x6c_kernel<NW, TM, FUSED, TPS>), grid, dim3(64 * NW), lds, s, g);
-}
-template <int TM, int TPS, bool FUSED = false, bool EPI4 = false, int NPW = 4, int TN = 2, bool PRE = false>
-static void x6p_launch(const X6cGeom& g, dim3 grid, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)patch_gemm_x6p_kernel<TM, TPS, FUSED, EPI4, NPW, TN, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  P2I_LAUNCH((patch_gemm_x6p_kernel<TM, TPS, FUSED, EPI4, NPW, TN, PRE>), grid, dim3(64 * (4 + NPW)), lds, s, g);
-}
 // experiment (round 4): the source planes of the NEXT split-pipe launch of this thread (tools/presplit_probe.py); consumed by it
 static thread_local const void* g_next_splanes = nullptr;
-// P2I_X6P_NPW=4: one producer wave per SIMD for the 32-channel tiles too (default 8); read per call (A/B runs)
-static int x6p_npw() { const char* e = getenv("P2I_X6P_NPW"); return (e && atoi(e) == 4) ? 4 : 8; }
-// Producer / consumer wave roles (patch_gemm_x6p_kernel): the default for every layer with more than one 16-channel chunk;
-// P2I_X6C_PC=0 keeps the symmetric kernels; read per call (A/B runs).  Measured at B = 8, symmetric -> producer / consumer
-// (gpurun_out/r03f/pc0.log, pc2.log): 64-channel level 75.4 -> 75.8 / 79.0 -> 73.9 us (fwd / dgrad), 128: 62.3 -> 57.4, 256: 64.3 ->
-// 56.3, 512: 75.8 -> 68.6, 3-D 128 -> 128: 86.0 -> 76.5; K = 16 (16 -> 64 forward): 36.8 -> 39.9, hence the exception.
-static int x6c_pc() { const char* e = getenv("P2I_X6C_PC"); return e ? atoi(e) : 1; }
-// taps per stage of the 32-channel tiles: 9 (whole chunk) unless P2I_X6C_TPS=3 (read per call: A/B runs)
-static int x6c_tps1() { const char* e = getenv("P2I_X6C_TPS"); return (e && atoi(e) == 3) ? 3 : 9; }
+
 static size_t x6c_lds_bytes(int csl, int tm, int tps) {
   const int ring = tps == 9 ? 3 : (tm == 2 ? 4 : 6);
   return sizeof(float) * (size_t)((csl + 3) & ~3) + 16 * (size_t)(ring * 6 * tps * 32 * tm + 2 * 6 * csl);
 }
 
+// What both runners fill alike: pointers, extents, the picked tile with a patch of (jh + halo) x (jw + halo) pixels, the weight
+// stack's bounds, the time-axis fields of class css[0] and the per-call switches.  The runners add their tap tables, slice offsets
+// and what only one of them has (bH / bW, fused_atomic, vec4_epi, splanes).
+static X6cGeom x6c_geom(const PatchGeom& g, const ClassSpec* css, int ncls, const X6cPick& pk, int halo, int ns, const uint16_t* wb, int ntaps_w) {
+  const ClassSpec& c0 = css[0];
+  X6cGeom k{};
+  k.src = g.src; k.dst = g.dst; k.wb = wb; k.bias = g.bias; k.res = g.res; k.mask_y = g.mask_y;
+  // planes 0..2 of this layer inside a stack of ntaps_w taps; the layer's own taps reach up to max(tw) + 1
+  int tw_max = 0;
+  for (int q = 0; q < ncls; ++q)
+    for (int i = 0; i < css[q].ntaps; ++i) tw_max = css[q].tw[i] > tw_max ? css[q].tw[i] : tw_max;
+  k.wb_bytes = (2u * (unsigned)ntaps_w + (unsigned)tw_max + 1u) * (unsigned)g.Ck * (unsigned)g.CmPad * 2u;
+  k.act_epi = g.act_epi; k.mask_act = g.mask_act;
+  k.B = g.B; k.Ck = g.Ck; k.Cm = g.Cm; k.CmPad = g.CmPad;
+  k.sH = g.sH; k.sW = g.sW; k.dT = g.dT; k.dH = g.dH; k.dW = g.dW; k.nH = c0.nH; k.nW = c0.nW;
+  k.ljb = ilog2(pk.jb); k.ljh = ilog2(pk.jh); k.ljw = ilog2(pk.jw);
+  k.eH = pk.jh + halo; k.eW = pk.jw + halo; k.CSl = pk.csl;
+  k.nth = ceil_div(c0.nH, pk.jh); k.ntw = ceil_div(c0.nW, pk.jw);
+  k.mg_ew = magic_u16(k.eW); k.mg_eh = magic_u16(k.eH);
+  k.ntaps_w = ntaps_w; k.ksplit = pk.ksplit;
+  k.sT = g.sT; k.nT = c0.nT; k.mT = c0.mT; k.oT = c0.oT; k.pT = c0.pT; k.ns = ns;
+  k.stagger = x6c_stagger(); k.cons_prio = x6p_prio();
+  return k;
+}
+
+template <void (*KERN)(const X6cGeom), int NTHR>
+static void x6c_launch(const X6cGeom& k, dim3 grid, size_t lds, hipStream_t s) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr_set = true;
+  }
+  P2I_LAUNCH(KERN, grid, dim3(NTHR), lds, s, k);
+}
+// The one place that maps (tile, taps per stage, fused, 16-byte epilogue, producer waves, pre-split source) to a kernel, and that
+// fills the plan p2i_conv_last_plan reports.  patch_gemm_x6p_kernel<TM, TPS, FUSED, EPI4, NPW, TN, PRE> has 4 + NPW waves.
+static void x6c_dispatch(const X6cGeom& k, const X6cVariant& tv, int tps, bool fused, int* plan6, hipStream_t s) {
+  const size_t lds = x6c_lds_bytes(k.CSl, tv.TM, tps);
+  const dim3 grid((unsigned)(ceil_div(k.B * k.nT, 1 << k.ljb) * k.nth * k.ntw), (unsigned)ceil_div(k.Cm, 32 * tv.TM), (unsigned)k.ksplit);
+  // (a single 16-channel chunk is all prologue and epilogue: symmetric kernel; the fused producer / consumer kernel has whole-chunk stages only)
+  const bool pc = x6c_pc() && k.Ck >= 32 && (!fused || tps == 9);
+  if (plan6) { plan6[0] = 32 * tv.TM; plan6[1] = 32 * tv.NW; plan6[2] = k.ksplit; plan6[3] = pc ? 4 : 8; plan6[4] = tps; plan6[5] = fused ? 8 : 7; }
+  const bool pre = k.splanes != nullptr;
+  if (!fused && pc) {
+    if (tv.TM == 2) {
+      if (k.vec4_epi) x6c_launch<patch_gemm_x6p_kernel<2, 3, false, true>, 512>(k, grid, lds, s);
+      else x6c_launch<patch_gemm_x6p_kernel<2, 3>, 512>(k, grid, lds, s);
+    } else if (tv.NW == 4) {
+      if (pre) x6c_launch<patch_gemm_x6p_kernel<1, 9, false, false, 8, 1, true>, 768>(k, grid, lds, s);
+      else x6c_launch<patch_gemm_x6p_kernel<1, 9, false, false, 8, 1>, 768>(k, grid, lds, s);
+    } else if (tps == 9) {
+      if (pre && x6p_npw() == 8) x6c_launch<patch_gemm_x6p_kernel<1, 9, false, false, 8, 2, true>, 768>(k, grid, lds, s);
+      else if (x6p_npw() == 8) x6c_launch<patch_gemm_x6p_kernel<1, 9, false, false, 8>, 768>(k, grid, lds, s);
+      else x6c_launch<patch_gemm_x6p_kernel<1, 9>, 512>(k, grid, lds, s);
+    } else x6c_launch<patch_gemm_x6p_kernel<1, 3>, 512>(k, grid, lds, s);
+  } else if (!fused) {
+    if (tv.TM == 2) x6c_launch<patch_gemm_x6c_kernel<8, 2>, 512>(k, grid, lds, s);
+    else if (tps == 9) x6c_launch<patch_gemm_x6c_kernel<8, 1, false, 9>, 512>(k, grid, lds, s);
+    else x6c_launch<patch_gemm_x6c_kernel<8, 1>, 512>(k, grid, lds, s);
+  } else if (pc) x6c_launch<patch_gemm_x6p_kernel<1, 9, true>, 512>(k, grid, lds, s);
+  else if (tps == 9) x6c_launch<patch_gemm_x6c_kernel<8, 1, true, 9>, 512>(k, grid, lds, s);
+  else x6c_launch<patch_gemm_x6c_kernel<8, 1, true>, 512>(k, grid, lds, s);
+}
+
 // returns 1 when the layer is not an x6c case (caller continues with the other engines)
-int run_patch_gemm_x6c(PatchGeom g, const ClassSpec& cs, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry) {
-  static const int on = getenv("P2I_CONV_X6C") ? atoi(getenv("P2I_CONV_X6C")) : 1;
-  if (!on || (!dry && wb == nullptr) || g.src_y != nullptr || (g.Ck & 15) != 0 || g.Ck < 16) return 1;
+int run_patch_gemm_x6c(const PatchGeom& g, const ClassSpec& cs, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry) {
+  if (!x6c_on() || (!dry && wb == nullptr) || g.src_y != nullptr || (g.Ck & 15) != 0 || g.Ck < 16) return 1;
   // spatially a 3x3 stride-1 layer; along t: any source multiplier / destination stride / offset, taps in 1..3 slices of 9
   if (cs.mH != 1 || cs.mW != 1 || cs.oH != 1 || cs.oW != 1 || cs.pH || cs.pW) return 1;
   if (cs.ntaps != 9 && cs.ntaps != 18 && cs.ntaps != 27) return 1;
@@ -1424,85 +1235,42 @@ int run_patch_gemm_x6c(PatchGeom g, const ClassSpec& cs, const uint16_t* wb, int
   if (sbytes >= 0x7FFFFFF0ull || 4ull * (unsigned long long)n_dst >= 0x7FFFFFF0ull) return 1;
   if (dry) return 0;
   const X6cVariant& tv = kX6cVariants[pk.v];
-  const int jb = pk.jb, jh = pk.jh, jw = pk.jw;
-  g.nT = cs.nT; g.nH = cs.nH; g.nW = cs.nW;
-  g.mT = cs.mT; g.mH = g.mW = 1; g.oT = cs.oT; g.oH = g.oW = 1; g.pT = cs.pT; g.pH = g.pW = 0;
-  g.ljb = ilog2(jb); g.ljt = 0; g.ljh = ilog2(jh); g.ljw = ilog2(jw);
-  g.eT = 1; g.eH = jh + 2; g.eW = jw + 2;
-  g.CSl = pk.csl;
-  g.bT = 0; g.bH = lo[1]; g.bW = lo[2];
+  X6cGeom k = x6c_geom(g, &cs, 1, pk, 2, ns, wb, ntaps_w);
+  k.bH = lo[1]; k.bW = lo[2];
   for (int i = 0; i < 9; ++i) {
-    g.tap_w[i] = cs.tw[i];
-    g.tap_off[i] = (cs.dh[i] - lo[1]) * g.eW + (cs.dw[i] - lo[2]);
+    k.tap_w[i] = cs.tw[i];
+    k.tap_off[i] = (cs.dh[i] - lo[1]) * k.eW + (cs.dw[i] - lo[2]);
   }
-  g.ntaps = 9;
-  g.nth = ceil_div(cs.nH, jh); g.ntw = ceil_div(cs.nW, jw); g.ntt = 1;
-  const int ntb = ceil_div((int)nimg, jb);
-  g.ksplit = pk.ksplit;
-  const dim3 grid((unsigned)(ntb * g.nth * g.ntw), (unsigned)ceil_div(g.Cm, 32 * tv.TM), (unsigned)pk.ksplit);
-  g.mg_ew = magic_u16(g.eW); g.mg_eh = magic_u16(g.eH);
-  g.wb = wb; g.ntaps_w = ntaps_w;
-  // planes 0..2 of this layer inside a stack of ntaps_w taps; the layer's own taps reach up to max(tw) + 1
-  int tw_max = 0;
-  for (int i = 0; i < cs.ntaps; ++i) tw_max = cs.tw[i] > tw_max ? cs.tw[i] : tw_max;
-  g.wb_bytes = (2u * (unsigned)ntaps_w + (unsigned)tw_max + 1u) * (unsigned)g.Ck * (unsigned)g.CmPad * 2u;
-  g.nclass = 1;
+  k.sdt0 = cs.dt[0]; k.swt0 = 0;
+  k.sdt1 = ns > 1 ? cs.dt[9] : 0; k.swt1 = ns > 1 ? cs.tw[9] - cs.tw[0] : 0;
+  k.sdt2 = ns > 2 ? cs.dt[18] : 0; k.swt2 = ns > 2 ? cs.tw[18] - cs.tw[0] : 0;
   const int tps = tv.NW == 4 ? 9 : (tv.TM == 1 ? x6c_tps1() : 3);
-  const size_t lds = x6c_lds_bytes(g.CSl, tv.TM, tps);
+  const size_t lds = x6c_lds_bytes(k.CSl, tv.TM, tps);
   const int post_act = (pk.ksplit > 1 && g.act_epi != P2I_ACT_NONE) ? g.act_epi : P2I_ACT_NONE;
-  const float* post_res = nullptr;
   if (pk.ksplit > 1) {       // partial sums are added: start from zero (stream-ordered in front of the kernel)
     if (p2i::memset_async(g.dst, 0, sizeof(float) * (size_t)n_dst, s) != hipSuccess) return P2I_EINVAL;
-    if (post_act != P2I_ACT_NONE) { post_res = g.res; g.res = nullptr; g.act_epi = P2I_ACT_NONE; }   // act(sum + bias) + res: second pass
+    if (post_act != P2I_ACT_NONE) { k.res = nullptr; k.act_epi = P2I_ACT_NONE; }   // act(sum + bias) + res: second pass
   }
-  if (plan6) { plan6[0] = 32 * tv.TM; plan6[1] = 32 * tv.NW; plan6[2] = pk.ksplit; plan6[3] = (x6c_pc() && g.Ck >= 32) ? 4 : 8; plan6[4] = tps; plan6[5] = 7; }
-  X6cGeom k{};
-  k.src = g.src; k.dst = g.dst; k.wb = g.wb; k.bias = g.bias; k.res = g.res; k.mask_y = g.mask_y;
-  k.wb_bytes = g.wb_bytes; k.act_epi = g.act_epi; k.mask_act = g.mask_act;
-  k.B = g.B; k.Ck = g.Ck; k.Cm = g.Cm; k.CmPad = g.CmPad;
-  k.sH = g.sH; k.sW = g.sW; k.dT = g.dT; k.dH = g.dH; k.dW = g.dW; k.nH = g.nH; k.nW = g.nW;
-  k.ljb = g.ljb; k.ljh = g.ljh; k.ljw = g.ljw; k.eH = g.eH; k.eW = g.eW; k.CSl = g.CSl; k.bH = g.bH; k.bW = g.bW;
-  k.nth = g.nth; k.ntw = g.ntw; k.mg_ew = g.mg_ew; k.mg_eh = g.mg_eh; k.ntaps_w = g.ntaps_w; k.ksplit = g.ksplit;
-  for (int i = 0; i < 9; ++i) { k.tap_off[i] = g.tap_off[i]; k.tap_w[i] = g.tap_w[i]; }
-  k.sT = g.sT; k.nT = g.nT; k.mT = g.mT; k.oT = g.oT; k.pT = g.pT; k.ns = ns;
-  k.stagger = x6c_stagger();
-  { const char* e = getenv("P2I_X6P_PRIO"); k.cons_prio = e ? atoi(e) : 0; }      // read per call (A/B runs)
-  const int pc = x6c_pc();
-  k.splanes = nullptr; k.plane_units = 0;
   if (g_next_splanes != nullptr) {                        // pre-split source (32-channel tiles with whole-chunk stages only)
-    if (pc && g.Ck >= 32 && tv.TM == 1 && tps == 9 && pk.ksplit == 1) {
+    if (x6c_pc() && g.Ck >= 32 && tv.TM == 1 && tps == 9 && pk.ksplit == 1) {
       k.splanes = static_cast<const u32x4c*>(g_next_splanes);
       k.plane_units = (unsigned)((long long)g.B * (g.Ck >> 3) * g.sT * g.sH * g.sW);
     }
     g_next_splanes = nullptr;
   }
   {
-    static const int v4_on = getenv("P2I_X6C_EPI4") ? atoi(getenv("P2I_X6C_EPI4")) : 1;
+    const int v4_on = P2I_ENV_ONCE("P2I_X6C_EPI4", 1);
     auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     // 64-channel tiles only (32-channel tiles: 57.9 vs 58.3 us, no gain) and never with split-K (its atomic adds want the plain
     // epilogue's 32 contiguous dwords per instruction: 92 vs 69 us on the 512-channel level)
-    k.vec4_epi = v4_on && tv.TM == 2 && pk.ksplit == 1 && jw >= 4 && (cs.nW & 3) == 0 && (g.dW & 3) == 0 && al16(g.dst) && al16(g.res) && al16(g.mask_y) &&
-                 (32 * 36 * 8 + 4 * tv.TM * 16 * 64) * 4 <= (int)lds - 4 * ((g.CSl + 3) & ~3);
+    k.vec4_epi = v4_on && tv.TM == 2 && pk.ksplit == 1 && pk.jw >= 4 && (cs.nW & 3) == 0 && (g.dW & 3) == 0 && al16(g.dst) && al16(k.res) && al16(g.mask_y) &&
+                 (32 * 36 * 8 + 4 * tv.TM * 16 * 64) * 4 <= (int)lds - 4 * ((k.CSl + 3) & ~3);
   }
-  k.sdt0 = cs.dt[0]; k.swt0 = 0;
-  k.sdt1 = ns > 1 ? cs.dt[9] : 0; k.swt1 = ns > 1 ? cs.tw[9] - cs.tw[0] : 0;
-  k.sdt2 = ns > 2 ? cs.dt[18] : 0; k.swt2 = ns > 2 ? cs.tw[18] - cs.tw[0] : 0;
-  if (pc && g.Ck >= 32) {                                 // (a single 16-channel chunk is all prologue and epilogue: symmetric kernel)
-    if (tv.TM == 2) { if (k.vec4_epi) x6p_launch<2, 3, false, true>(k, grid, lds, s); else x6p_launch<2, 3>(k, grid, lds, s); }
-    else if (tv.NW == 4) { if (k.splanes) x6p_launch<1, 9, false, false, 8, 1, true>(k, grid, lds, s); else x6p_launch<1, 9, false, false, 8, 1>(k, grid, lds, s); }
-    else if (tps == 9) {
-      if (k.splanes && x6p_npw() == 8) x6p_launch<1, 9, false, false, 8, 2, true>(k, grid, lds, s);
-      else if (x6p_npw() == 8) x6p_launch<1, 9, false, false, 8>(k, grid, lds, s);
-      else x6p_launch<1, 9>(k, grid, lds, s);
-    }
-    else x6p_launch<1, 3>(k, grid, lds, s);
-  } else if (tv.TM == 2) x6c_launch<8, 2>(k, grid, lds, s);
-  else if (tps == 9) x6c_launch<8, 1, false, 9>(k, grid, lds, s);
-  else x6c_launch<8, 1>(k, grid, lds, s);
+  x6c_dispatch(k, tv, tps, false, plan6, s);
   if (post_act != P2I_ACT_NONE) {
     const long long n4 = n_dst / 4;
     const long long blocks = (n4 + 255) / 256;
-    P2I_LAUNCH(x6c_post_act_kernel, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, s, g.dst, post_res, n4, post_act);
+    P2I_LAUNCH(x6c_post_act_kernel, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, s, g.dst, g.res, n4, post_act);
   }
   return launch_status();
 }
@@ -1510,9 +1278,8 @@ int run_patch_gemm_x6c(PatchGeom g, const ClassSpec& cs, const uint16_t* wb, int
 // ---- fused strided data gradient (stride (1,2,2), 3x3 or 3x3x3 taps, pad 1 in h and w; t stride 1): classes q = 2 pH + pW in the
 // order p2i_conv_dgrad builds them; class q must hold ns * {1, 2, 2, 4}[q] taps (slice-major), every class the same extents.
 // Returns 1 when the layer is not such a case.
-int run_patch_gemm_x6c_fused(PatchGeom g, const ClassSpec* css, int ncls, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry) {
-  static const int on = getenv("P2I_CONV_X6C_FUSED") ? atoi(getenv("P2I_CONV_X6C_FUSED")) : 1;
-  if (!on || ncls != 4 || (!dry && wb == nullptr) || g.src_y != nullptr || (g.Ck & 15) != 0 || g.Ck < 16) return 1;
+int run_patch_gemm_x6c_fused(const PatchGeom& g, const ClassSpec* css, int ncls, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry) {
+  if (!x6c_fused_on() || ncls != 4 || (!dry && wb == nullptr) || g.src_y != nullptr || (g.Ck & 15) != 0 || g.Ck < 16) return 1;
   static const int per[4] = {1, 2, 2, 4};
   const int ns = css[0].ntaps;                            // class (0,0) has one tap per t slice
   if (ns < 1 || ns > 3) return 1;
@@ -1525,7 +1292,6 @@ int run_patch_gemm_x6c_fused(PatchGeom g, const ClassSpec* css, int ncls, const 
   // slot -> (class, tap within the class's slice): slots 0-3 class 3, 4-5 class 2, 6-7 class 1, 8 class 0 (X6C_CLS)
   static const int slot_cls[9] = {3, 3, 3, 3, 2, 2, 1, 1, 0}, slot_idx[9] = {0, 1, 2, 3, 0, 1, 0, 1, 0};
   int sdt[3] = {0, 0, 0}, swt[3] = {0, 0, 0};
-  X6cGeom k{};
   for (int j = 0; j < ns; ++j)
     for (int sl = 0; sl < 9; ++sl) {
       const ClassSpec& c = css[slot_cls[sl]];
@@ -1535,60 +1301,28 @@ int run_patch_gemm_x6c_fused(PatchGeom g, const ClassSpec* css, int ncls, const 
       if (c.dh[i] != c.dh[i0] || c.dw[i] != c.dw[i0]) return 1;
       if (sl == 0) { sdt[j] = c.dt[i]; swt[j] = c.tw[i] - c.tw[i0]; }
       else if (c.dt[i] != sdt[j] || c.tw[i] - c.tw[i0] != swt[j]) return 1;
-      if (j == 0) { k.tap_w[sl] = c.tw[i]; }
     }
   const ClassSpec& c0 = css[0];
   const long long n_dst = (long long)g.B * g.Cm * g.dT * g.dH * g.dW;
   const long long nimg = (long long)g.B * c0.nT;
   if (nimg >= (1 << 24)) return 1;
-  // tile: 256 class-local positions of (b, t) images, 32 destination channels per workgroup (TM 1: four accumulator classes)
-  int jb, jt, jh, jw;
-  pick_tile_dims(256, (int)nimg, 1, c0.nH, c0.nW, jb, jt, jh, jw);
-  const int csl = jb * (jh + 1) * (jw + 1);
-  if (jt != 1 || csl > X6cTile<8>::MAXCSL) return 1;
   const bool alias = g.dst == g.res || g.dst == g.mask_y;
-  const long long tiles = (long long)ceil_div((int)nimg, jb) * ceil_div(c0.nH, jh) * ceil_div(c0.nW, jw) * ceil_div(g.Cm, 32);
-  const int cps = g.Ck >> 4;
-  // split-K for layers with too few tiles: measured SLOWER than the f32 fused kernel on the one layer of the step it would take
-  // (128 -> 256 stride 2 at B = 8: 90.6 vs 72 us, the float2 pairs become two atomics each), so it is off unless asked for
-  const bool can_split = x6c_fused_ksplit() && !alias && ((ns * cps) & 1) == 0 && c0.oT == 1 && c0.pT == 0 && c0.nT == g.dT;
-  const int min_wg = x6c_fused_min_wg();
-  int ksplit = 1;
-  if (tiles < min_wg) {
-    if (can_split && 2 * tiles >= min_wg) ksplit = 2;
-    else return 1;
-  }
+  const X6cPick pk = x6c_fused_pick((int)nimg, c0.nH, c0.nW, g.Cm, ns * (g.Ck >> 4), !alias && c0.oT == 1 && c0.pT == 0 && c0.nT == g.dT);
+  if (pk.v < 0) return 1;
   const unsigned long long sbytes = 4ull * g.B * g.Ck * g.sT * g.sH * g.sW;
   if (sbytes >= 0x7FFFFFF0ull || 4ull * (unsigned long long)n_dst >= 0x7FFFFFF0ull) return 1;
   if (dry) return 0;
-  k.src = g.src; k.dst = g.dst; k.wb = wb; k.bias = nullptr; k.res = g.res; k.mask_y = g.mask_y;
-  int tw_max = 0;
-  for (int q = 0; q < 4; ++q)
-    for (int i = 0; i < css[q].ntaps; ++i) tw_max = css[q].tw[i] > tw_max ? css[q].tw[i] : tw_max;
-  k.wb_bytes = (2u * (unsigned)ntaps_w + (unsigned)tw_max + 1u) * (unsigned)g.Ck * (unsigned)g.CmPad * 2u;
-  k.act_epi = P2I_ACT_NONE; k.mask_act = g.mask_act;
-  k.B = g.B; k.Ck = g.Ck; k.Cm = g.Cm; k.CmPad = g.CmPad;
-  k.sH = g.sH; k.sW = g.sW; k.dT = g.dT; k.dH = g.dH; k.dW = g.dW; k.nH = c0.nH; k.nW = c0.nW;
-  k.ljb = ilog2(jb); k.ljh = ilog2(jh); k.ljw = ilog2(jw);
-  k.eH = jh + 1; k.eW = jw + 1; k.CSl = csl; k.bH = 0; k.bW = 0;
-  k.nth = ceil_div(c0.nH, jh); k.ntw = ceil_div(c0.nW, jw);
-  k.mg_ew = magic_u16(k.eW); k.mg_eh = magic_u16(k.eH);
-  k.ntaps_w = ntaps_w; k.ksplit = ksplit; k.fused_atomic = ksplit > 1 ? 1 : 0; k.stagger = x6c_stagger();
-  { const char* e = getenv("P2I_X6P_PRIO"); k.cons_prio = e ? atoi(e) : 0; }
-  k.sT = g.sT; k.nT = c0.nT; k.mT = 1; k.oT = c0.oT; k.pT = c0.pT; k.ns = ns;
+  X6cGeom k = x6c_geom(g, css, 4, pk, 1, ns, wb, ntaps_w);
+  k.bias = nullptr; k.act_epi = P2I_ACT_NONE;
+  k.fused_atomic = pk.ksplit > 1 ? 1 : 0;
   k.sdt0 = sdt[0]; k.sdt1 = sdt[1]; k.sdt2 = sdt[2]; k.swt0 = swt[0]; k.swt1 = swt[1]; k.swt2 = swt[2];
   for (int sl = 0; sl < 9; ++sl) {
     const ClassSpec& c = css[slot_cls[sl]];
+    k.tap_w[sl] = c.tw[slot_idx[sl]];
     k.tap_off[sl] = c.dh[slot_idx[sl]] * k.eW + c.dw[slot_idx[sl]];
   }
-  if (ksplit > 1 && p2i::memset_async(g.dst, 0, sizeof(float) * (size_t)n_dst, s) != hipSuccess) return P2I_EINVAL;
-  const dim3 grid((unsigned)(ceil_div((int)nimg, jb) * k.nth * k.ntw), (unsigned)ceil_div(g.Cm, 32), (unsigned)ksplit);
-  const int tps = x6c_tps1();
-  const size_t lds = x6c_lds_bytes(k.CSl, 1, tps);
-  if (plan6) { plan6[0] = 32; plan6[1] = 256; plan6[2] = ksplit; plan6[3] = (x6c_pc() && tps == 9 && g.Ck >= 32) ? 4 : 8; plan6[4] = tps; plan6[5] = 8; }
-  if (x6c_pc() && tps == 9 && g.Ck >= 32) x6p_launch<1, 9, true>(k, grid, lds, s);
-  else if (tps == 9) x6c_launch<8, 1, true, 9>(k, grid, lds, s);
-  else x6c_launch<8, 1, true>(k, grid, lds, s);
+  if (pk.ksplit > 1 && p2i::memset_async(g.dst, 0, sizeof(float) * (size_t)n_dst, s) != hipSuccess) return P2I_EINVAL;
+  x6c_dispatch(k, kX6cVariants[pk.v], x6c_tps1(), true, plan6, s);
   return launch_status();
 }
 

@@ -757,8 +757,7 @@ static int idw_fwd_impl(const float* vals_src, const float* mask, const float* g
   const float4* pts = reinterpret_cast<const float4*>(pt_xyzn);
   // P2I_IDW_REPLAY_ALL=1: MODE 2 replays the reference's scan for every listed voxel (round 3's pass) instead of deciding from the
   // points within the 4th distance first (read per call: A/B runs, tests)
-  const char* rae = getenv("P2I_IDW_REPLAY_ALL");
-  const int replay_all = (rae && atoi(rae) != 0) ? 1 : 0;
+  const int replay_all = env_int("P2I_IDW_REPLAY_ALL", 0) != 0 ? 1 : 0;
   if (amb && nblk1 <= IDW_MAX_BLK) {
     P2I_LAUNCH((idw_knn_kernel<1, 256>), grid, dim3(256), 0, s, vals_src, grid_x, grid_y, grid_z, pt_pos, pt_count, row_start, pts, out,
                        sel_idx, sel_w, amb, nblk1, T, H, W, tau, 0);
@@ -770,8 +769,7 @@ static int idw_fwd_impl(const float* vals_src, const float* mask, const float* g
     P2I_LAUNCH((idw_knn_kernel<2, 256>), grid, dim3(256), 0, s, vals_src, grid_x, grid_y, grid_z, pt_pos, pt_count,
                        row_start, pts, out, sel_idx, sel_w, amb, nblk1, T, H, W, tau, replay_all);
     if (!replay_all) {   // what the fixed bound could not decide (~5 % of the listed voxels): the exact replay, a lane per voxel
-      const char* we = getenv("P2I_IDW_LANE_REPLAY");               // 0: the cooperative replay over the second list (A/B; read per call)
-      if (we && atoi(we) == 0)
+      if (env_int("P2I_IDW_LANE_REPLAY", 1) == 0)                    // 0: the cooperative replay over the second list (A/B; read per call)
         P2I_LAUNCH((idw_knn_kernel<2, 256>), grid, dim3(256), 0, s, vals_src, grid_x, grid_y, grid_z, pt_pos, pt_count,
                            row_start, pts, out, sel_idx, sel_w, amb, nblk1, T, H, W, tau, 3);
       else {

@@ -673,7 +673,7 @@ static int launch_wgrad_reduce(const float* ws, int ns, long long slice, int Co,
                                long long pstride = 0) {
   if (pstride == 0) pstride = slice;
 #ifdef P2I_STAMP
-  { const char* e = getenv("P2I_DEBUG_SKIP_REDUCE"); if (e && atoi(e)) return P2I_OK; }      // diagnostic build only: what the slice reduces cost a step (wrong gradients)
+  if (env_int("P2I_DEBUG_SKIP_REDUCE", 0)) return P2I_OK;     // diagnostic build only: what the slice reduces cost a step (wrong gradients)
 #endif
   const int nmain4 = (int)(slice / 4);
   const int n4 = nmain4 + (dbias ? CoPad / 4 : 0);
@@ -780,7 +780,7 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
     const int PPh = y4 ? NPIX + 4 : NPIX + 1;
     g.eWq = g.eW | 1;
     {
-      static const int x4_off = getenv("P2I_WGRAD_X4") ? (atoi(getenv("P2I_WGRAD_X4")) == 0) : 0;
+      const bool x4_off = P2I_ENV_ONCE("P2I_WGRAD_X4", 1) == 0;
       g.x4 = (!x4_off && (d->Wi & 3) == 0 && ((jw * d->sw) & 3) == 0) ? 1 : 0;
       g.x4sh = 0;
       if (g.x4) {
@@ -806,11 +806,11 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
     else {
       g.mg_ewq = magic_u16(g.eWq); g.mg_pp = magic_u16(PPh);
       g.x_bytes = (unsigned)xb; g.dy_bytes = (unsigned)yb;
-      { static const int dbg_env = getenv("P2I_WGRAD_DBG") ? atoi(getenv("P2I_WGRAD_DBG")) : 0; g.dbg = dbg_env; }
+      g.dbg = P2I_ENV_ONCE("P2I_WGRAD_DBG", 0);
       typedef void (*wk_t)(const WgradGeom);
       wk_t kern;
       // window inner loop (3x3, stride 1 in h and w, pad 1 in w, 16-B x image): P2I_WGRAD_WINDOW=0 keeps the per-tap reads
-      static const int window_on = getenv("P2I_WGRAD_WINDOW") ? atoi(getenv("P2I_WGRAD_WINDOW")) : 1;
+      const int window_on = P2I_ENV_ONCE("P2I_WGRAD_WINDOW", 1);
       const int lju = ilog2(jw) - 2;
       const bool win_shape = window_on && g.tpg == 9 && y4 && g.x4 && d->pw == 1 && d->kw == 3 && d->kh == 3 && lju >= 1 && lju <= 3 && g.rowblk <= 4096;
       const bool window = win_shape && d->sh == 1 && d->sw == 1;                    // stride 1: CB 64 or 32

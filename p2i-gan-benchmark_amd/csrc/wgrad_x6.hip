@@ -555,7 +555,7 @@ __global__ __launch_bounds__(512) void wgrad_x6p_kernel(const Wx6Geom g) {
 // 0 = launched (plan filled), 1 = not a case of this kernel (caller continues with the f32 kernels)
 int run_wgrad_x6(const p2i_conv_desc* d, const float* x, const float* dy, float* dwp, float* dbias, float* ws, long long ws_floats,
                  int* ns_out, long long* slice_out, hipStream_t s) {
-  { const char* e = getenv("P2I_WGRAD_X6"); if (e && atoi(e) == 0) return 1; }     // read per call: tests run both engines in one process
+  if (env_int("P2I_WGRAD_X6", 1) == 0) return 1;    // read per call: tests run both engines in one process
   if (d->kh != 3 || d->kw != 3 || d->sh != 1 || d->sw != 1 || d->ph != 1 || d->pw != 1) return 1;
   const bool flat = d->kt == 1 && d->st == 1 && d->pt == 0;             // 2-D layer (or frames convolved independently)
   const bool vol = d->kt == 3 && d->pt == 1 && d->st <= 2;              // 3 x 3 x 3: three t slices of nine taps
@@ -593,14 +593,12 @@ int run_wgrad_x6(const p2i_conv_desc* d, const float* x, const float* dy, float*
   // level 73.5 vs 66.2 us, 256: 68.8 vs 64.5, 3-D 128 -> 128: 93.8 vs 87.5): a consumer issues 1.1 transposed 8-byte reads per MFMA
   // (the convolution consumers 0.6-0.75 16-byte reads) and has no partner wave on its SIMD to cover the 2-way conflicted ones.  Kept as
   // an option (same results, tested); read per call.
-  const char* pce = getenv("P2I_WGRAD_X6_PC");
-  if (pce != nullptr && atoi(pce) != 0) P2I_LAUNCH(wgrad_x6p_kernel, dim3(ns, ncb, nco * d->kt), dim3(512), 2 * WX_BUF + 1024, s, g);
+  if (env_int("P2I_WGRAD_X6_PC", 0) != 0) P2I_LAUNCH(wgrad_x6p_kernel, dim3(ns, ncb, nco * d->kt), dim3(512), 2 * WX_BUF + 1024, s, g);
   // conflict-free row assignment of the transposed reads (wx_read_tr_s4): the default; P2I_WGRAD_X6_S4=0 keeps round 2's rows (A/B, read
   // per call).  Measured in one box (gpurun_out/r03x/wg_s0.log, wg_s4.log, wg_s0b.log; PMC: gpurun_out/r03x/pmc): conflict cycles 43 % ->
   // 0.5 % of the LDS cycles, launch time within 1 % (66.5-71.5 us either way): the transposed reads were never what the kernel waits for.
 #ifdef P2I_STAMP
-  else if (getenv("P2I_WGRAD_DIAG") && atoi(getenv("P2I_WGRAD_DIAG")) != 0) {
-    const int dg = atoi(getenv("P2I_WGRAD_DIAG"));
+  else if (const int dg = env_int("P2I_WGRAD_DIAG", 0)) {
     const dim3 gr(ns, ncb, nco * d->kt);
 #define WX_DIAG_CASE(n) case n: { static bool a_ = false; if (!a_) { (void)hipFuncSetAttribute((const void*)wgrad_x6_kernel<true, n>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); a_ = true; } \
       P2I_LAUNCH((wgrad_x6_kernel<true, n>), gr, dim3(512), 2 * WX_BUF + 1024, s, g); break; }
@@ -609,7 +607,7 @@ int run_wgrad_x6(const p2i_conv_desc* d, const float* x, const float* dy, float*
 #undef WX_DIAG_CASE
   }
 #endif
-  else if (!(getenv("P2I_WGRAD_X6_S4") && atoi(getenv("P2I_WGRAD_X6_S4")) == 0))
+  else if (env_int("P2I_WGRAD_X6_S4", 1) != 0)
     P2I_LAUNCH(wgrad_x6_kernel<true>, dim3(ns, ncb, nco * d->kt), dim3(512), 2 * WX_BUF + 1024, s, g);
   else P2I_LAUNCH(wgrad_x6_kernel<false>, dim3(ns, ncb, nco * d->kt), dim3(512), 2 * WX_BUF + 1024, s, g);
   *ns_out = sliced ? ns : 0;

@@ -72,3 +72,22 @@ def test_integration_doc_lists_every_entry_point():
                         seen.add(cand)
     missing = sorted(declared - seen)
     assert not missing, f"INTEGRATION.md does not mention {missing}"
+
+
+def test_switches_read_in_one_place_and_listed():
+    """The native library reads its environment switches through csrc/common.h only (env_int / P2I_ENV_ONCE), and every switch
+    name it passes to them is in DESIGN.md's table (section "Switches")."""
+    import glob
+    csrc = os.path.join(ROOT, "p2i-gan-benchmark_amd", "csrc")
+    doc = open(os.path.join(ROOT, "DESIGN.md")).read()
+    table = set(re.findall(r"^\| `(P2I_[A-Z0-9_]+)`", doc, flags=re.M))
+    names = set()
+    for path in sorted(glob.glob(os.path.join(csrc, "*"))):
+        src = open(path).read()
+        if os.path.basename(path) != "common.h":
+            assert "getenv(" not in src, f"{os.path.basename(path)} calls getenv: use env_int / P2I_ENV_ONCE (csrc/common.h)"
+        names |= set(re.findall(r"\b(?:env_int|P2I_ENV_ONCE)\(\s*\"(P2I_[A-Z0-9_]+)\"", src))
+    assert len(names) >= 30, sorted(names)
+    assert "getenv(" in open(os.path.join(csrc, "common.h")).read()
+    missing = sorted(names - table)
+    assert not missing, f"DESIGN.md's switch table does not list {missing}"
