@@ -63,6 +63,10 @@ const char* p2i_last_error(void);
  *                 caller zeroes dWp), db[cout] += sum dy*act'(y) when db != NULL.
  * dims: x (B,Cin,Ti,Hi,Wi), y (B,Cout,To,Ho,Wo); kernel (kt,kh,kw); stride (st,sh,sw);
  * padding (pt,ph,pw).  bias / residual / y_act may be NULL.
+ * Limits (refused with P2I_EINVAL / P2I_ELDS and a p2i_last_error message, never answered wrongly): kt*kh*kw <= 27;
+ * p2i_conv_wgrad: kh*kw <= 9, and the x patch of its smallest pixel tile (16 output positions, 64 channels) has to fit 160 KB
+ * of LDS ("wgrad tile does not fit LDS": strides far above 3).  Extents of 1 on any axis, any padding and strides 1..3 are
+ * covered by tests/test_conv_sweep_gpu.py.
  */
 typedef struct {
   int B, Cin, Cout;
@@ -131,9 +135,15 @@ int p2i_conv_dgrad_x6s(const p2i_conv_desc* d, const float* dy, const float* wp_
  * patch_gemm_kernel<MB,NPIX,WAVES_M,CK>; KG = 7: patch_gemm_x6c_kernel<8, MB/32, false, TPS>, fields {MB = 32 or 64, 256, ksplit,
  * 16, TPS = taps per pipeline stage (3 or 9), 7}; KG = 8: the fused strided data gradient patch_gemm_x6c_kernel<8, 1, true, TPS>,
  * fields {32, 256, ksplit, 16, TPS, 8}; KG = 3: o1_fwd_kernel (single output channel), fields {1, 64, 8, 1, 9, 3}; KG > 10: the f32
- * fused strided data gradient patch_gemm_fused_kernel with KG - 10 parity classes per workgroup)
+ * fused strided data gradient patch_gemm_fused_kernel with KG - 10 parity classes per workgroup; KG = 4: the single-input-channel
+ * data gradient c1_dgrad_kernel / c1_dgrad_fast_kernel, fields {1, 256, 1, 1, taps, 4})
  * so that bench.py's roofline can be matched to rocprofv3 rows */
 int p2i_conv_last_plan(int* out6);
+/* Host only, no device work: the multiplier the planners hand the kernels for an index division, floor(n / d) ==
+ * (uint64_t(n) * *magic) >> 32 for every 0 <= n < 65536.  It exists for 2 <= d < 65536 only; any other d (d = 1 in particular:
+ * 2^32 + 1 does not fit 32 bits) is refused with P2I_EINVAL.  The planners stage a patch axis of extent 1 with extent 2, so no
+ * convolution geometry that the descriptor check accepts asks for d = 1. */
+int p2i_fast_div_magic(int d, uint32_t* magic);
 /* same for the most recent p2i_conv_wgrad: {kind (0 wgrad_kernel<64>, 1 wgrad_dma_kernel<64,NTAP,Y4,CB>, 2 c1_wgrad_kernel,
  * 3 wgrad_x6_kernel), NTAP (wgrad_x6: 9 * kt taps in one launch), Y4, CB} */
 int p2i_wgrad_last_plan(int* out4);

@@ -49,8 +49,13 @@ static inline int ilog2(int v) {
   while ((1 << l) < v) ++l;
   return l;
 }
-// exact floor(n/d) for 0 <= n < 65536, 1 <= d < 65536 via one mul_hi
+// exact floor(n/d) for 0 <= n < 65536, 2 <= d < 65536 via one mul_hi.  NOT for d = 1: 2^32 + 1 does not fit the 32-bit multiplier
+// (it wraps to 1, and umulhi(n, 1) is 0 for every n).  The planners never hand a kernel a divisor of 1: a patch axis of extent 1
+// (one tap, one output row / column per tile) is staged with extent 2 (patch_extent_div; the extra row or column is loaded and never
+// addressed), and every planner checks its divisors with magic_u16_ok before it computes their multipliers.
+static inline bool magic_u16_ok(int d) { return d >= 2 && d < 65536; }
 static inline unsigned magic_u16(int d) { return (unsigned)(0x100000000ull / (unsigned)d) + 1u; }
+static inline int patch_extent_div(int e) { return e < 2 ? 2 : e; }
 __device__ __forceinline__ int fast_div(int n, unsigned magic) { return (int)__umulhi((unsigned)n, magic); }
 
 __device__ __forceinline__ float act_apply(float v, int act) {

@@ -261,7 +261,7 @@ static int run_patch_gemm_classes(PatchGeom g, const ClassSpec* css, int ncls, h
     PatchGeom t = g;
     t.ljb = ilog2(jb); t.ljt = ilog2(jt); t.ljh = ilog2(jh); t.ljw = ilog2(jw);
     t.eT = (jt - 1) * g.mT + rng[0] + 1;
-    t.eH = (jh - 1) * g.mH + rng[1] + 1;
+    t.eH = patch_extent_div((jh - 1) * g.mH + rng[1] + 1);    // (never 1: the offset tables divide by it, common.h)
     t.eW = (jw - 1) * g.mW + rng[2] + 1;
     // 16-B patch DMA: rows and tile origins 16-B aligned
     bool same_lo_w = true;                                  // merged classes may share the aligned origin only if their w windows start alike
@@ -273,6 +273,7 @@ static int run_patch_gemm_classes(PatchGeom g, const ClassSpec* css, int ncls, h
       t.eW = (t.eW + t.v4sh + 3) & ~3;
       t.eW4 = t.eW >> 2;
     }
+    if (!t.v4) t.eW = patch_extent_div(t.eW);               // (4-byte DMA: the table divides by eW; 16-byte: eW4 == 1 is branched round)
     t.eWp = t.eW;
     t.eth = t.eT * t.eH;
     t.rpc = jb * t.eth;
@@ -306,6 +307,9 @@ static int run_patch_gemm_classes(PatchGeom g, const ClassSpec* css, int ncls, h
   const unsigned long long sbytes = 4ull * g.B * g.Ck * g.sT * g.sH * g.sW;
   if (best < 0 || sbytes >= 0xF0000000ull) return 1;
   TileCfg c{cand[best][0], cand[best][1], cand[best][2], best_ck};
+  P2I_REQUIRE(magic_u16_ok(bg.CSl) && magic_u16_ok(bg.eW) && magic_u16_ok(bg.rpc) && magic_u16_ok(bg.eth) && magic_u16_ok(bg.eH) &&
+              (!bg.v4 || (magic_u16_ok(bg.G4) && (bg.eW4 == 1 || magic_u16_ok(bg.eW4)))),
+              "conv planner: offset-table divisor outside [2, 65535] (%d %d %d %d %d)", bg.CSl, bg.eW, bg.rpc, bg.eth, bg.eH);
   bg.mg_csl = magic_u16(bg.CSl); bg.mg_ew = magic_u16(bg.eW);
   bg.mg_rpc = magic_u16(bg.rpc); bg.mg_eth = magic_u16(bg.eth); bg.mg_eh = magic_u16(bg.eH);
   if (bg.v4) { bg.mg_g4 = magic_u16(bg.G4); bg.mg_ew4 = magic_u16(bg.eW4); }
@@ -399,12 +403,13 @@ static int run_patch_gemm(PatchGeom g, const ClassSpec& cs, hipStream_t s) {
     pick_tile_dims(c.NPIX, g.B, cs.nT, cs.nH, cs.nW, jb, jt, jh, jw);
     g.ljb = ilog2(jb); g.ljt = ilog2(jt); g.ljh = ilog2(jh); g.ljw = ilog2(jw);
     g.eT = (jt - 1) * cs.mT + (hi[0] - lo[0]) + 1;
-    g.eH = (jh - 1) * cs.mH + (hi[1] - lo[1]) + 1;
+    g.eH = patch_extent_div((jh - 1) * cs.mH + (hi[1] - lo[1]) + 1);   // (never 1: the staging loop divides by it, common.h)
     g.eW = (jw - 1) * cs.mW + (hi[2] - lo[2]) + 1;
     g.eWp = g.eW | 1;
     g.eth = g.eT * g.eH;
     g.rpc = jb * g.eth;
     g.CS = g.rpc * g.eWp;
+    P2I_REQUIRE(magic_u16_ok(g.eH) && magic_u16_ok(g.eth) && g.rpc >= 2, "conv planner: staging divisor below 2 (%d %d %d)", g.rpc, g.eth, g.eH);
     g.mg_rpc = magic_u16(g.rpc); g.mg_eth = magic_u16(g.eth); g.mg_eh = magic_u16(g.eH);
     const size_t lds = sizeof(float) * ((size_t)cs.ntaps * c.CK * c.MB + (size_t)c.CK * g.CS);
     if (lds > 160 * 1024 || c.CK * g.rpc >= 65536) {
@@ -441,6 +446,13 @@ extern "C" int p2i_debug_set_stamp(unsigned long long* buf) {
 extern "C" int p2i_conv_last_plan(int* out6) {
   if (!out6) return P2I_EINVAL;
   for (int i = 0; i < 6; ++i) out6[i] = g_last_plan[i];
+  return P2I_OK;
+}
+
+extern "C" int p2i_fast_div_magic(int d, uint32_t* magic) {
+  P2I_REQUIRE(magic != nullptr, "null pointer");
+  P2I_REQUIRE(magic_u16_ok(d), "fast_div: no 32-bit multiplier for divisor %d (2 <= d < 65536)", d);
+  *magic = magic_u16(d);
   return P2I_OK;
 }
 
@@ -484,8 +496,10 @@ extern "C" int p2i_conv_dgrad(const p2i_conv_desc* d, const float* dy, const flo
   g.src = dy; g.src_y = y_act; g.wp = wp_d; g.bias = nullptr; g.res = dx_add; g.dst = dx; g.act_epi = P2I_ACT_NONE; g.act_pro = y_act ? act : P2I_ACT_NONE;
   g.mask_y = mask_y; g.mask_act = mask_y ? mask_act : P2I_ACT_NONE;
   P2I_REQUIRE(!(mask_y && y_act), "dgrad: use either the act'(y) prologue or the epilogue mask");
-  if (d->Cin == 1 && !y_act && d->kt * d->kh * d->kw * d->Cout * 4 <= 64 * 1024)
+  if (d->Cin == 1 && !y_act && d->kt * d->kh * d->kw * d->Cout * 4 <= 64 * 1024) {   // single-channel input: VALU kernels (conv_c1.hip)
+    g_last_plan[0] = 1; g_last_plan[1] = 256; g_last_plan[2] = 1; g_last_plan[3] = 1; g_last_plan[4] = d->kt * d->kh * d->kw; g_last_plan[5] = 4;
     return c1_dgrad(d, dy, wp_d, dx_add, mask_y, mask_act, dx, (hipStream_t)stream);
+  }
   g.B = d->B; g.Ck = d->Cout; g.Cm = d->Cin; g.CmPad = (d->Cin + 31) / 32 * 32;
   g.wp_bytes = 4u * (unsigned)(d->kt * d->kh * d->kw) * g.Ck * g.CmPad;
   g.sT = d->To; g.sH = d->Ho; g.sW = d->Wo; g.dT = d->Ti; g.dH = d->Hi; g.dW = d->Wi;

@@ -343,7 +343,7 @@ int run_patch_gemm_fused(PatchGeom g, const ClassSpec* css, int ncls, int* plan6
   pick_tile_dims(NP, g.B, mx[0], mx[1], mx[2], jb, jt, jh, jw);
   g.ljb = ilog2(jb); g.ljt = ilog2(jt); g.ljh = ilog2(jh); g.ljw = ilog2(jw);
   g.eT = (jt - 1) + hi[0] - lo[0] + 1;
-  g.eH = (jh - 1) + hi[1] - lo[1] + 1;
+  g.eH = patch_extent_div((jh - 1) + hi[1] - lo[1] + 1);      // (never 1: the offset tables divide by it, common.h)
   g.eW = (jw - 1) + hi[2] - lo[2] + 1;
   {
     g.v4 = (conv_v4_on() && (g.sW & 3) == 0 && jw >= 4) ? 1 : 0;
@@ -354,6 +354,7 @@ int run_patch_gemm_fused(PatchGeom g, const ClassSpec* css, int ncls, int* plan6
       g.eW4 = g.eW >> 2;
     }
   }
+  if (!g.v4) g.eW = patch_extent_div(g.eW);
   g.eWp = g.eW;
   g.eth = g.eT * g.eH;
   g.rpc = jb * g.eth;
@@ -368,6 +369,9 @@ int run_patch_gemm_fused(PatchGeom g, const ClassSpec* css, int ncls, int* plan6
   const size_t lds = sizeof(float) * (((nwrows + 63) & ~63) + (size_t)PTp + 2 * (WSZ + PTp));
   const unsigned long long sbytes = 4ull * g.B * g.Ck * g.sT * g.sH * g.sW;
   if (lds > 160 * 1024 || sbytes >= 0xF0000000ull) return 1;
+  P2I_REQUIRE(magic_u16_ok(g.CSl) && magic_u16_ok(g.eW) && magic_u16_ok(g.rpc) && magic_u16_ok(g.eth) && magic_u16_ok(g.eH) &&
+              (!g.v4 || (magic_u16_ok(g.G4) && (g.eW4 == 1 || magic_u16_ok(g.eW4)))),
+              "fused dgrad planner: offset-table divisor outside [2, 65535] (%d %d %d %d %d)", g.CSl, g.eW, g.rpc, g.eth, g.eH);
   g.mg_csl = magic_u16(g.CSl); g.mg_ew = magic_u16(g.eW);
   if (g.v4) { g.mg_g4 = magic_u16(g.G4); g.mg_ew4 = magic_u16(g.eW4); }
   g.mg_rpc = magic_u16(g.rpc); g.mg_eth = magic_u16(g.eth); g.mg_eh = magic_u16(g.eH);

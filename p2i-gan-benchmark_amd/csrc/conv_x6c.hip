@@ -1154,7 +1154,7 @@ static X6cGeom x6c_geom(const PatchGeom& g, const ClassSpec* css, int ncls, cons
   k.ljb = ilog2(pk.jb); k.ljh = ilog2(pk.jh); k.ljw = ilog2(pk.jw);
   k.eH = pk.jh + halo; k.eW = pk.jw + halo; k.CSl = pk.csl;
   k.nth = ceil_div(c0.nH, pk.jh); k.ntw = ceil_div(c0.nW, pk.jw);
-  k.mg_ew = magic_u16(k.eW); k.mg_eh = magic_u16(k.eH);
+  k.mg_ew = magic_u16(k.eW); k.mg_eh = magic_u16(k.eH);      // (3 .. 34 by construction: jh, jw in 1 .. 32, halo 1 or 2)
   k.ntaps_w = ntaps_w; k.ksplit = pk.ksplit;
   k.sT = g.sT; k.nT = c0.nT; k.mT = c0.mT; k.oT = c0.oT; k.pT = c0.pT; k.ns = ns;
   k.stagger = x6c_stagger(); k.cons_prio = x6p_prio();

@@ -735,23 +735,33 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
   g.tpg = d->kh * d->kw;                      // one kt slice per group
   P2I_REQUIRE(g.tpg <= 9, "wgrad supports kh*kw <= 9");
   const int ngroups = d->kt;
-  constexpr int NPIX = 64;
-  // the staged patch covers ONE kt slice: group z uses t offset (a - pt) => separate patch per group
+  constexpr int NPIXD = 64;                   // pixel tile of the DMA-pipelined kernels
+  // Pixel tile of the plain kernel (wgrad_kernel<NPIX>): 64 positions, or 32 / 16 where the x patch of 64 positions does not fit
+  // LDS (strided layers: 64 positions of a 3x3 stride-3 layer span 24 x 24 pixels per batch slot and channel).
+  // The staged patch covers ONE kt slice: group z uses t offset (a - pt) => separate patch per group.
+  // A tile is at least two positions wide: the MFMA's two k slots are the positions (s, s + 1) of a tile row, so a one-column
+  // tile would pair each position with its neighbour in the next row (Wo == 1: the second column is masked like any tile border).
+  int NPIX = 64;
   int jb, jt, jh, jw;
-  pick_tile_dims(NPIX, d->B, 1, d->Ho, d->Wo, jb, jt, jh, jw);   // jt = 1: one output frame per tile row group
-  // allow several frames/batches in a tile when the frame is small
-  g.ljb = ilog2(jb); g.ljt = 0; g.ljh = ilog2(jh); g.ljw = ilog2(jw);
-  // tile covers jb "batch*time" slots: fold T into the batch-like dim by treating (b,t) pairs
-  // -> keep it simple: jt = 1 and jb spans batches only; tiles iterate over t explicitly.
-  g.eT = 1;
-  g.eH = (jh - 1) * d->sh + d->kh;
-  g.eW = (jw - 1) * d->sw + d->kw;
-  g.eWp = g.eW | 1;
-  g.eth = g.eT * g.eH;
-  g.rpc = jb * g.eth;
-  g.CS = (g.rpc * g.eWp) | 1;
-  g.PP = NPIX | 1;
+  size_t lds = 0;
+  for (;; NPIX >>= 1) {
+    const int nWp = d->Wo < 2 ? 2 : (d->Wo > NPIX ? NPIX : d->Wo);
+    pick_tile_dims(NPIX, d->B, 1, d->Ho, nWp, jb, jt, jh, jw);   // jt = 1: one output frame per tile; jb spans batches only
+    g.ljb = ilog2(jb); g.ljt = 0; g.ljh = ilog2(jh); g.ljw = ilog2(jw);
+    g.eT = 1;
+    g.eH = patch_extent_div((jh - 1) * d->sh + d->kh);     // (never 1: wgrad_kernel's staging loop divides by it, common.h)
+    g.eW = (jw - 1) * d->sw + d->kw;
+    g.eWp = g.eW | 1;
+    g.eth = g.eT * g.eH;
+    g.rpc = jb * g.eth;
+    g.CS = (g.rpc * g.eWp) | 1;
+    g.PP = NPIX | 1;
+    lds = sizeof(float) * (64 * (size_t)g.CS + 64 * (size_t)g.PP);
+    if ((lds <= 160 * 1024 && 64 * g.rpc < 65536) || NPIX == 16) break;
+  }
   P2I_REQUIRE(64 * g.rpc < 65536, "wgrad patch too large");
+  P2I_REQUIRE(lds <= 160 * 1024, "wgrad tile does not fit LDS (%zu)", lds);
+  P2I_REQUIRE(magic_u16_ok(g.rpc) && magic_u16_ok(g.eth) && magic_u16_ok(g.eH), "wgrad planner: staging divisor below 2 (%d %d %d)", g.rpc, g.eth, g.eH);
   g.mg_rpc = magic_u16(g.rpc); g.mg_eth = magic_u16(g.eth); g.mg_eh = magic_u16(g.eH);
   g.bH = -d->ph; g.bW = -d->pw;
   g.ntb = ceil_div(d->B, jb); g.ntt = d->To; g.nth = ceil_div(d->Ho, jh); g.ntw = ceil_div(d->Wo, jw);
@@ -760,24 +770,24 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
     for (int c = 0; c < d->kw; ++c)
       for (int a = 0; a < d->kt; ++a) g.tap_off[(a * d->kh + b) * d->kw + c] = b * g.eWp + c;
   const int ncx = ceil_div(d->Cin, 64), nco = ceil_div(d->Cout, 64);
-  const size_t lds = sizeof(float) * (64 * (size_t)g.CS + 64 * (size_t)g.PP);
-  P2I_REQUIRE(lds <= 160 * 1024, "wgrad tile does not fit LDS (%zu)", lds);
+  typedef void (*plain_t)(const WgradGeom);
+  const plain_t plain = NPIX == 64 ? (plain_t)wgrad_kernel<64> : (NPIX == 32 ? (plain_t)wgrad_kernel<32> : (plain_t)wgrad_kernel<16>);
   int nsplit = 768 / (ncx * nco * ngroups);
   if (nsplit < 1) nsplit = 1;
   if (nsplit > g.ntiles) nsplit = g.ntiles;
   g.nsplit = nsplit;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)wgrad_kernel<NPIX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
+  static bool attr_set[3] = {false, false, false};
+  if (!attr_set[NPIX == 64 ? 0 : (NPIX == 32 ? 1 : 2)]) {
+    (void)hipFuncSetAttribute((const void*)plain, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr_set[NPIX == 64 ? 0 : (NPIX == 32 ? 1 : 2)] = true;
   }
   // ---- DMA-pipelined variant (no act'(y) prologue): [row][c][eWq] / [o][PP] images, double buffered.
   // CB = x channels per block: 64, or 32 when the patch is large (strided convs) or Cin is small.
   bool bias_fused = false;
-  bool use_dma = (y_act == nullptr) && (g.tpg == 9 || g.tpg == 1) && jw >= 8;
+  bool use_dma = (y_act == nullptr) && (g.tpg == 9 || g.tpg == 1) && jw >= 8 && NPIX == NPIXD;
   if (use_dma) {
     const bool y4 = (d->Wo % 4 == 0);
-    const int PPh = y4 ? NPIX + 4 : NPIX + 1;
+    const int PPh = y4 ? NPIXD + 4 : NPIXD + 1;
     g.eWq = g.eW | 1;
     {
       const bool x4_off = P2I_ENV_ONCE("P2I_WGRAD_X4", 1) == 0;
@@ -804,6 +814,7 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
     g.YSZ = 64 * PPh;
     if (lds2 > 160 * 1024 || g.XSZ >= 65536 || xb >= 0xF0000000ull || yb >= 0xF0000000ull) use_dma = false;
     else {
+      P2I_REQUIRE(magic_u16_ok(g.eWq) && magic_u16_ok(PPh), "wgrad planner: image divisor outside [2, 65535] (%d %d)", g.eWq, PPh);
       g.mg_ewq = magic_u16(g.eWq); g.mg_pp = magic_u16(PPh);
       g.x_bytes = (unsigned)xb; g.dy_bytes = (unsigned)yb;
       g.dbg = P2I_ENV_ONCE("P2I_WGRAD_DBG", 0);
@@ -816,15 +827,15 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
       const bool window = win_shape && d->sh == 1 && d->sw == 1;                    // stride 1: CB 64 or 32
       const bool window2 = win_shape && d->sh == 2 && d->sw == 2 && CBh == 32;      // stride 2 (its x image only fits with CB = 32)
       if (window && CBh == 64)
-        kern = lju == 3 ? (wk_t)wgrad_dma_kernel<NPIX, 9, true, 64, 3> : (lju == 2 ? (wk_t)wgrad_dma_kernel<NPIX, 9, true, 64, 2> : (wk_t)wgrad_dma_kernel<NPIX, 9, true, 64, 1>);
+        kern = lju == 3 ? (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 64, 3> : (lju == 2 ? (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 64, 2> : (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 64, 1>);
       else if (window)
-        kern = lju == 3 ? (wk_t)wgrad_dma_kernel<NPIX, 9, true, 32, 3> : (lju == 2 ? (wk_t)wgrad_dma_kernel<NPIX, 9, true, 32, 2> : (wk_t)wgrad_dma_kernel<NPIX, 9, true, 32, 1>);
+        kern = lju == 3 ? (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 32, 3> : (lju == 2 ? (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 32, 2> : (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 32, 1>);
       else if (window2)
-        kern = lju == 3 ? (wk_t)wgrad_dma_kernel<NPIX, 9, true, 32, 3, 2> : (lju == 2 ? (wk_t)wgrad_dma_kernel<NPIX, 9, true, 32, 2, 2> : (wk_t)wgrad_dma_kernel<NPIX, 9, true, 32, 1, 2>);
-      else if (CBh == 64) kern = g.tpg == 9 ? (y4 ? (wk_t)wgrad_dma_kernel<NPIX, 9, true, 64> : (wk_t)wgrad_dma_kernel<NPIX, 9, false, 64>)
-                                       : (y4 ? (wk_t)wgrad_dma_kernel<NPIX, 1, true, 64> : (wk_t)wgrad_dma_kernel<NPIX, 1, false, 64>);
-      else kern = g.tpg == 9 ? (y4 ? (wk_t)wgrad_dma_kernel<NPIX, 9, true, 32> : (wk_t)wgrad_dma_kernel<NPIX, 9, false, 32>)
-                             : (y4 ? (wk_t)wgrad_dma_kernel<NPIX, 1, true, 32> : (wk_t)wgrad_dma_kernel<NPIX, 1, false, 32>);
+        kern = lju == 3 ? (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 32, 3, 2> : (lju == 2 ? (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 32, 2, 2> : (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 32, 1, 2>);
+      else if (CBh == 64) kern = g.tpg == 9 ? (y4 ? (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 64> : (wk_t)wgrad_dma_kernel<NPIXD, 9, false, 64>)
+                                       : (y4 ? (wk_t)wgrad_dma_kernel<NPIXD, 1, true, 64> : (wk_t)wgrad_dma_kernel<NPIXD, 1, false, 64>);
+      else kern = g.tpg == 9 ? (y4 ? (wk_t)wgrad_dma_kernel<NPIXD, 9, true, 32> : (wk_t)wgrad_dma_kernel<NPIXD, 9, false, 32>)
+                             : (y4 ? (wk_t)wgrad_dma_kernel<NPIXD, 1, true, 32> : (wk_t)wgrad_dma_kernel<NPIXD, 1, false, 32>);
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       g_wgrad_plan[0] = 1; g_wgrad_plan[1] = g.tpg; g_wgrad_plan[2] = y4 ? 1 : 0; g_wgrad_plan[3] = CBh;
       const int ncb = ceil_div(d->Cin, CBh);
@@ -875,7 +886,7 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
       ga.partial = sliced ? g_wgrad_ws : nullptr;
       ga.pstride = slice;
       for (int i = 0; i < g.tpg; ++i) ga.tap_off[i] = g.tap_off[a * g.tpg + i];
-      P2I_LAUNCH(wgrad_kernel<NPIX>, dim3(nsplit, ncx, nco), dim3(256), lds, s, ga);
+      P2I_LAUNCH(plain, dim3(nsplit, ncx, nco), dim3(256), lds, s, ga);
       if (int e = launch_status()) return e;
       if (sliced)
         if (int e = launch_wgrad_reduce(g_wgrad_ws, nsplit, slice, d->Cout, g.CoPad, ga.dwp, s)) return e;

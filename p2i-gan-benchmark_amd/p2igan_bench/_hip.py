@@ -41,6 +41,7 @@ SIGNATURES = {
     "p2i_conv_dgrad_x6s": [_D, _P, _P, _P, _I, _P, _P, _I, _P, _P],
     "p2i_conv_last_plan": [C.POINTER(C.c_int)],
     "p2i_wgrad_last_plan": [C.POINTER(C.c_int)],
+    "p2i_fast_div_magic": [_I, C.POINTER(C.c_uint32)],
     "p2i_doconv_fold_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
     "p2i_doconv_fold_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "p2i_doconv_fold_fwd_batched": [_P, _P, _P, _I, _I, _I, _P, _P, _P],

@@ -110,6 +110,8 @@ def _prof_end(e0, kind, spec, desc, stride1):
                 plan[1] // 32, plan[0] // 32, plan[4], plan[0], plan[1], plan[4])
         elif plan[5] == 3:
             key = "o1_fwd_kernel (single output channel, bandwidth-bound)"
+        elif plan[5] == 4:
+            key = "c1_dgrad_kernel (single input channel, %d taps)" % plan[4]
         elif plan[5] == 8 and plan[3] == 4:
             key = "patch_gemm_x6p_kernel<1, %d, true> (strided dgrad, 4 parity classes per workgroup, producer / consumer waves, bf16-split x6)" % plan[4]
         elif plan[5] == 8:
