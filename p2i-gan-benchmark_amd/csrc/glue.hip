@@ -386,9 +386,12 @@ __global__ void dtail_bwd3_kernel(const float* __restrict__ df, float* do3, int 
   if (idx >= B * H3 * W3) return;
   const int xi = idx % W3, yi = (idx / W3) % H3, b = idx / (W3 * H3);
   const float sh = (float)H3 / (float)H2, sw = (float)W3 / (float)W2;
-  const int ry = H2 / H3 > 0 ? H2 / H3 : 1, rx = W2 / W3 > 0 ? W2 / W3 : 1;
-  const int ylo = max(0, (yi - 1) * ry - 1), yhi = min(H2 - 1, (yi + 2) * ry);
-  const int xlo = max(0, (xi - 1) * rx - 1), xhi = min(W2 - 1, (xi + 2) * rx);
+  // outputs that sample yi: hp_src's inverse, yi - 1 < (y + 0.5) sh - 0.5 < yi + 1, one pixel wider on each side for the rounding
+  // (a superset is safe: the weight test below drops the rest).  An integer ratio H2 / H3 is not assumed: H2 = 2 H3 - 1 for any
+  // input height = 4 mod 8.
+  const float ih = (float)H2 / (float)H3, iw = (float)W2 / (float)W3;
+  const int ylo = max(0, (int)floorf(((float)yi - 0.5f) * ih - 0.5f) - 1), yhi = min(H2 - 1, (int)ceilf(((float)yi + 1.5f) * ih - 0.5f) + 1);
+  const int xlo = max(0, (int)floorf(((float)xi - 0.5f) * iw - 0.5f) - 1), xhi = min(W2 - 1, (int)ceilf(((float)xi + 1.5f) * iw - 0.5f) + 1);
   float acc = 0.f;
   const bool same = (H3 == H2 && W3 == W2);
   for (int y = ylo; y <= yhi; ++y) {

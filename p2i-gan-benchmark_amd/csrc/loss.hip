@@ -90,9 +90,8 @@ __device__ __forceinline__ float bce_term(float x, float y, bool& bad) {
   if (!(x >= 0.f && x <= 1.f)) { bad = true; return 0.f; }
   return -(y * fmaxf(logf(x), -100.f) + (1.f - y) * fmaxf(logf(1.f - x), -100.f));
 }
-__device__ __forceinline__ float bce_grad(float x, float y) {     // d/dx with the same clamps (grad 0 where the log is clamped)
-  const float gl = (logf(x) > -100.f) ? 1.f / x : 0.f, g1 = (logf(1.f - x) > -100.f) ? 1.f / (1.f - x) : 0.f;
-  return -(y * gl - (1.f - y) * g1);
+__device__ __forceinline__ float bce_grad(float x, float y) {     // torch's binary_cross_entropy backward, x = 0 and x = 1 included
+  return (x - y) / fmaxf(x * (1.f - x), 1e-12f);
 }
 // adversarial losses, single block.  loss_type 0 hinge, 1 lsgan, 2 nsgan.
 __global__ __launch_bounds__(1024) void gan_loss_kernel(const float* __restrict__ la, const float* __restrict__ lb, int n, int loss_type,
