@@ -473,6 +473,25 @@ int p2i_exp3_gather(const void* pred, int pred_dtype, int ph, int pw, int ptop, 
                     const int64_t* ords, int K, double* out_g, double* out_p, void* stream);
 int p2i_exp3_nse(const double* event_rec, const int* event_off, int E, const double* stack_rec, int T, double* out, void* stream);
 
+/* ---- exp2 comparison renders (reference experiments/exp2.py run_exp2 / _save_combo_gif / run_exp2_paper_zarr; DESIGN.md section
+ * 12).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform and uint8
+ * table).
+ * p2i_exp2_index: out[n][S][S] (uint8, any alignment) = the colour index of the first n frames' crop [top, top + S) x [left,
+ *   left + S): clip(searchsorted_right(bounds, transform_mmhr(x)) - 1, 0, 140) over the P2I_EXP2_NBOUNDS fp64 bounds (DEVICE,
+ *   ascending), decided by fp64 >= compares; NaN -> P2I_EXP2_BAD.
+ * p2i_exp2_compose: out[n][Hc][pitch] (uint8; pitch a multiple of 16, out and chrome 16-byte aligned) = chrome[Hc][pitch] with
+ *   panel p of panels[P][n][S][S] magnified zoom x zoom (nearest) at rows [oy, oy + S zoom), columns [ox + p step, ox + p step +
+ *   S zoom).  Panel p with bit p of gauge_bits set is instead the index bg plus one disc per point of points[K][2] (DEVICE int32
+ *   (row, column), each inside [0, S)), in the order given, the later point on top: in doubled coordinates d2 = (2 y + 1 - (2 row
+ *   + 1) zoom)^2 + (2 x + 1 - (2 column + 1) zoom)^2 of panel pixel (y, x); with R = 3 zoom, d2 <= (R - 2)^2 takes the panel's
+ *   own index at the point (bg where that is P2I_EXP2_BAD), (R - 2)^2 < d2 <= R^2 takes the index edge. */
+#define P2I_EXP2_NBOUNDS 142
+#define P2I_EXP2_BAD 141
+int p2i_exp2_index(const void* x, int dtype, int T, int H, int W, int top, int left, int S, int n, const double* bounds,
+                   const double* lut, int divide_by_3, uint8_t* out, void* stream);
+int p2i_exp2_compose(const uint8_t* panels, int P, int n, int S, int zoom, unsigned gauge_bits, const int* points, int K,
+                     const uint8_t* chrome, int Hc, int pitch, int oy, int ox, int step, int bg, int edge, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ static inline int launch_status() {
   return P2I_OK;
 }
 
-// ---- environment switches (every name, default and reader: DESIGN.md section 12).  env_int reads on every call:
+// ---- environment switches (every name, default and reader: DESIGN.md section 13).  env_int reads on every call:
 // for switches that a test or an A/B run flips inside one process.  P2I_ENV_ONCE reads when the statement first runs and keeps that
 // value for the process.  A switch that two sites consult has ONE accessor function, next to the code it steers.
 static inline int env_int(const char* name, int dflt) {

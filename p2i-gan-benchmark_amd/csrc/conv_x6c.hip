@@ -997,7 +997,7 @@ __global__ __launch_bounds__(64 * (4 + NPW)) void patch_gemm_x6p_kernel(const X6
 #endif
 }
 
-// ---- switches of this engine (DESIGN.md section 12).  Read per call unless noted: tests and A/B runs flip
+// ---- switches of this engine (DESIGN.md section 13).  Read per call unless noted: tests and A/B runs flip
 // them inside one process.
 static bool x6c_on() { return P2I_ENV_ONCE("P2I_CONV_X6C", 1) != 0; }                  // once per process
 static bool x6c_fused_on() { return P2I_ENV_ONCE("P2I_CONV_X6C_FUSED", 1) != 0; }      // once per process

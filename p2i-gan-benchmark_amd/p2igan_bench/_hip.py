@@ -110,6 +110,8 @@ SIGNATURES = {
     "p2i_exp3_scan": [_P, _L, _P, _P],
     "p2i_exp3_gather": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _L, _P, _I, _P, _P, _P],
     "p2i_exp3_nse": [_P, _P, _I, _P, _I, _P, _P],
+    "p2i_exp2_index": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P],
+    "p2i_exp2_compose": [_P, _I, _I, _I, _I, C.c_uint, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
 }
 
 

@@ -1425,3 +1425,44 @@ def exp3_nse(event_rec, event_off, stack_rec) -> torch.Tensor:
     _hip.check(_hip.load().p2i_exp3_nse(_ptr(event_rec) if E else None, _ptr(event_off) if E else None, E, _ptr(stack_rec) if T else None,
                                         T, _ptr(out), _stream()), "p2i_exp3_nse")
     return out
+
+
+# ---- exp2 comparison renders (csrc/eval_exp2.hip; p2igan_bench/evaluation.py drives these) ----
+EXP2_NBOUNDS = 142
+EXP2_BAD = 141
+
+
+def exp2_index(x, tl, S, n, bounds, lut, divide_by_3, out):
+    """The colour indices of the first n frames of x [T, H, W] (uint8 / f32 / f64), cropped to S x S at tl = (top, left), into out
+    [n, S, S] (uint8): see include/p2i_hip.h.  bounds [EXP2_NBOUNDS] and lut [256] are f64 on the device."""
+    dc = _exp1_code(x)
+    _exp3_buf(bounds, torch.float64, EXP2_NBOUNDS, "exp2_index")
+    _exp3_buf(lut, torch.float64, 256, "exp2_index")
+    _exp3_buf(out, torch.uint8, n * S * S, "exp2_index")
+    if n == 0:
+        return
+    _hip.check(_hip.load().p2i_exp2_index(_ptr(x), dc, x.shape[0], x.shape[1], x.shape[2], tl[0], tl[1], S, n, _ptr(bounds), _ptr(lut),
+                                          int(divide_by_3), _ptr(out), _stream()), "p2i_exp2_index")
+
+
+def exp2_pitch(width: int) -> int:
+    """The canvas row pitch: the width rounded up to 16 bytes."""
+    return (int(width) + 15) // 16 * 16
+
+
+def exp2_compose(panels, zoom, gauge_bits, points, chrome, oy, ox, step, bg, edge, out):
+    """Index panels [P, n, S, S] (uint8) over the chrome [Hc, pitch] (uint8) into out [n, Hc, pitch] (uint8): see include/p2i_hip.h.
+    points: int32 [K, 2] (row, column) on the device, each inside the panel (the caller checks that on the host)."""
+    P, n, S, _ = panels.shape
+    Hc, pitch = chrome.shape
+    K = 0 if points is None else points.shape[0]
+    _exp3_buf(panels, torch.uint8, P * n * S * S, "exp2_compose")
+    _exp3_buf(chrome, torch.uint8, Hc * pitch, "exp2_compose")
+    _exp3_buf(out, torch.uint8, n * Hc * pitch, "exp2_compose")
+    if K:
+        _exp3_buf(points, torch.int32, K * 2, "exp2_compose")
+    if n == 0:
+        return
+    _hip.check(_hip.load().p2i_exp2_compose(_ptr(panels), P, n, S, int(zoom), int(gauge_bits), _ptr(points) if K else None, K, _ptr(chrome),
+                                            Hc, pitch, int(oy), int(ox), int(step), int(bg), int(edge), _ptr(out), _stream()),
+               "p2i_exp2_compose")

@@ -12,6 +12,11 @@ center-cropped to the crop size.  Writes DIR/metrics.json (indent 2, sorted keys
 With ``--exp3 DIR3`` it also runs the benchmark's exp3 analysis (run_exp3) on the same inputs and writes DIR3/metrics.json,
 DIR3/metrics.txt (``NSE_<name>: value`` lines, as main.py writes them), DIR3/exp3_data.npz and the figures (scatter_panels.pdf,
 residual_panels.pdf, nse_boxplot.pdf, logfreq.pdf).  exp1's outputs do not depend on it.
+
+With ``--exp2 DIR2 --observation OBS.zarr`` it also writes the benchmark's exp2 comparison animations (run_exp2 on the zarr paths:
+the first 20 events in lexicographic key order, 30 frames each): DIR2/comparison_<event>.gif, DIR2/event_ranges.txt and
+DIR2/exp2_data.npz.  ``--exp2-pdf FILE --exp2-events EVENTS.json`` writes the paper's frame grid (run_exp2_paper_zarr); the JSON is
+a list of ``{"event_id": 3, "select_idx": [0, 2, 4], "title": "..."}``.  Neither changes exp1's or exp3's outputs.
 """
 from __future__ import annotations
 
@@ -26,7 +31,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 from p2igan_bench.data import zarr_lite  # noqa: E402
-from p2igan_bench.evaluation import DEFAULT_THRESHOLDS, crop_mask, run_exp1, run_exp3  # noqa: E402
+from p2igan_bench.evaluation import DEFAULT_THRESHOLDS, crop_mask, run_exp1, run_exp2, run_exp2_paper_zarr, run_exp3  # noqa: E402
 
 
 def _method(spec: str):
@@ -50,7 +55,21 @@ def parse_args(argv=None):
     p.add_argument("--device", default=None, help="torch device (default: the current GPU)")
     p.add_argument("--exp3", default=None, metavar="DIR", help="also run exp3 (NSE, scatter / residual panels, NSE boxplot, "
                    "log-frequency) and write its outputs into DIR")
+    p.add_argument("--exp2", default=None, metavar="DIR", help="also write exp2's comparison GIFs, event_ranges.txt and exp2_data.npz "
+                   "into DIR (needs --observation)")
+    p.add_argument("--observation", default=None, metavar="OBS.zarr", help="zarr group of the observed events (exp2's Input / Gauge "
+                   "panel and the paper grid's first two columns)")
+    p.add_argument("--gif-fps", type=int, default=4, help="frames per second of exp2's GIFs")
+    p.add_argument("--exp2-zoom", type=int, default=None, help="magnification of exp2's panels (default: at least 256 pixels wide)")
+    p.add_argument("--exp2-pdf", default=None, metavar="FILE", help="also write exp2's paper frame grid to FILE (needs --observation "
+                   "and --exp2-events)")
+    p.add_argument("--exp2-events", default=None, metavar="JSON", help="the paper grid's events: a JSON list of "
+                   "{event_id, select_idx, title}")
     args = p.parse_args(argv)
+    if (args.exp2 or args.exp2_pdf) and not args.observation:
+        p.error("--exp2 / --exp2-pdf need --observation")
+    if args.exp2_pdf and not args.exp2_events:
+        p.error("--exp2-pdf needs --exp2-events")
     names = [n for n, _ in args.method]
     if len(set(names)) != len(names):
         p.error(f"method names repeat: {names}")
@@ -130,6 +149,17 @@ def main(argv=None):
         m3 = run_exp3(preds, truth, mask, args.mode, args.crop_size, args.exp3, device=args.device)
         write_exp3_outputs(args.exp3, m3)
         print(f"wrote {os.path.join(args.exp3, 'metrics.json')} and the exp3 figures")
+    paths = {name: path for name, path in args.method}
+    if args.exp2:
+        run_exp2(paths, args.truth, args.observation, mask, args.exp2, args.crop_size, None, 0.0, 0.0, args.gif_fps, divide_by_3=True,
+                 mode=args.mode, device=args.device, zoom=args.exp2_zoom)
+        print(f"wrote {os.path.join(args.exp2, 'event_ranges.txt')} and the exp2 GIFs")
+    if args.exp2_pdf:
+        with open(args.exp2_events, encoding="utf-8") as f:
+            events = json.load(f)
+        out_dir, name = os.path.split(os.path.abspath(args.exp2_pdf))
+        run_exp2_paper_zarr(args.observation, paths, events, args.mask, args.crop_size, out_dir, name, device=args.device)
+        print(f"wrote {args.exp2_pdf}")
 
 
 if __name__ == "__main__":
