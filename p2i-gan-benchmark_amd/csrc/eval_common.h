@@ -1,6 +1,8 @@
-// Device helpers shared by the benchmark's scoring units (eval_exp1.hip, eval_exp3.hip): the reference's rain-rate transform
-// (experiments/exp1.py transform_mmhr) in fp64 and the Welford / Chan updates of (n, mean, M2).  Both units compile with
-// -ffp-contract=off, so every helper rounds as numpy's separate operations do.
+// Shared by the benchmark's evaluation units (eval_exp1.hip, eval_exp3.hip, eval_exp2.hip).  Device side: the reference's rain-rate
+// transform (experiments/exp1.py transform_mmhr) in fp64, the cropped-input view Crop<T> every kernel reads its inputs through, the
+// Welford / Chan updates of (n, mean, M2) and the fixed-order workgroup tree that folds per-thread records.  Host side: the crop
+// check and the dtype dispatch of the entry points.  The units compile with -ffp-contract=off, so every helper rounds as numpy's
+// separate operations do.
 #pragma once
 #include "common.h"
 
@@ -24,6 +26,19 @@ template <> __device__ __forceinline__ double tload<uint8_t>(const uint8_t* p, l
 template <> __device__ __forceinline__ double tload<float>(const float* p, long long i, const double*, int div3) { return mmhr((double)p[i], div3); }
 template <> __device__ __forceinline__ double tload<double>(const double* p, long long i, const double*, int div3) { return mmhr(p[i], div3); }
 
+// An input [T][h][w] of uint8 / f32 / f64 seen through its crop at (top, left): at(t, y, x) is the transformed value of crop pixel
+// (y, x) of frame t.  row(t, y) is the element offset of a crop row's first pixel and at(row, x) reads along it, for a kernel that
+// walks one row.  Offsets are 64-bit.  A pointer inside a by-value kernel argument carries no noalias.  The kernels that only load
+// in their loops take the view as their argument at no cost; exp1_accumulate_kernel, which stores in the loop that loads its
+// inputs, measured 5 % slower in run_exp1 with it and keeps loose `const T* __restrict__` arguments (see there).
+template <typename T> struct Crop {
+  const T* p;
+  int h, w, top, left;
+  __device__ __forceinline__ long long row(long long t, int y) const { return t * h * w + (long long)(top + y) * w + left; }
+  __device__ __forceinline__ double at(long long row, int x, const double* lut, int div3) const { return tload<T>(p, row + x, lut, div3); }
+  __device__ __forceinline__ double at(long long t, int y, int x, const double* lut, int div3) const { return at(row(t, y), x, lut, div3); }
+};
+
 // Welford: (n, mean, M2) <- (n, mean, M2) + one value g
 __device__ __forceinline__ void welford_push(double& n, double& mean, double& m2, double g) {
   n += 1.0;
@@ -43,6 +58,32 @@ __device__ __forceinline__ void chan_merge(double& n, double& mean, double& m2, 
   n = nn;
 }
 
+// The workgroup's N per-thread records folded in a fixed order: thread i takes thread i + o for o = N/2, ..., 1, through
+// red[N * R::WORDS] doubles of LDS; thread 0 ends with the whole.  R has store(double*), a static load(const double*) and
+// merge(const R&).  Every thread of the workgroup calls it (it has barriers).
+template <int N, typename R> __device__ __forceinline__ void block_tree(R& r, double* red) {
+  r.store(red + threadIdx.x * R::WORDS);
+  __syncthreads();
+  for (int o = N / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      r.merge(R::load(red + (threadIdx.x + o) * R::WORDS));
+      r.store(red + threadIdx.x * R::WORDS);
+    }
+    __syncthreads();
+  }
+}
+
 static inline bool eval_dtype_ok(int d) { return d == P2I_EXP1_U8 || d == P2I_EXP1_F32 || d == P2I_EXP1_F64; }
+static inline bool crop_ok(int h, int w, int top, int left, int S) { return top >= 0 && left >= 0 && top + S <= h && left + S <= w; }
+
+// dtype dispatch of the entry points (after eval_dtype_ok): f(T{}) for an input's dtype, f(PT{}, GT{}) for a pair's
+template <typename F> static void dispatch1(int dt, F&& f) {
+  if (dt == P2I_EXP1_U8) f(uint8_t{});
+  else if (dt == P2I_EXP1_F32) f(float{});
+  else f(double{});
+}
+template <typename F> static void dispatch2(int pdt, int gdt, F&& f) {
+  dispatch1(pdt, [&](auto pz) { dispatch1(gdt, [&](auto gz) { f(pz, gz); }); });
+}
 
 }  // namespace p2i

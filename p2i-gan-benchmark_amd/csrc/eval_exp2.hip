@@ -39,8 +39,7 @@ __device__ __forceinline__ int bound_index(const double* b, double v) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void exp2_index_kernel(const T* __restrict__ x, int H, int W, int top, int left, int S,
-                                                         long long total, const double* __restrict__ bounds,
+__global__ __launch_bounds__(256) void exp2_index_kernel(Crop<T> x, int S, long long total, const double* __restrict__ bounds,
                                                          const double* __restrict__ lut, int div3, uint8_t* __restrict__ out) {
   __shared__ double b[NB];
   if ((int)threadIdx.x < NB) b[threadIdx.x] = bounds[threadIdx.x];
@@ -61,7 +60,7 @@ __global__ __launch_bounds__(256) void exp2_index_kernel(const T* __restrict__ x
     const long long t = o / ss;
     const int r = (int)(o - t * ss);
     const int y = r / S, xx = r - y * S;
-    const double v = tload<T>(x, (t * H + top + y) * W + left + xx, lut, div3);
+    const double v = x.at(t, y, xx, lut, div3);
     pack |= (uint32_t)bound_index(b, v) << (8 * j);
   }
   if (cnt == 4) {
@@ -171,20 +170,16 @@ extern "C" int p2i_exp2_index(const void* x, int dtype, int T, int H, int W, int
                               const double* lut, int divide_by_3, uint8_t* out, void* stream) {
   P2I_REQUIRE(x && bounds && lut && out && eval_dtype_ok(dtype), "bad arguments");
   P2I_REQUIRE(S > 0 && n > 0 && n <= T, "bad frame count / crop");
-  P2I_REQUIRE(top >= 0 && left >= 0 && top + S <= H && left + S <= W, "crop outside the input");
+  P2I_REQUIRE(crop_ok(H, W, top, left, S), "crop outside the input");
   const long long total = (long long)n * S * S;
   const long long blocks = (total + (long long)((uintptr_t)out & 3u) + 1023) / 1024;
   P2I_REQUIRE(blocks <= 0x7fffffffLL, "too many pixels for one launch");
   const hipStream_t s = (hipStream_t)stream;
-  if (dtype == P2I_EXP1_U8)
-    P2I_LAUNCH(exp2_index_kernel<uint8_t>, dim3((unsigned)blocks), dim3(256), 0, s, (const uint8_t*)x, H, W, top, left, S, total, bounds,
+  dispatch1(dtype, [&](auto z) {
+    using XT = decltype(z);
+    P2I_LAUNCH(exp2_index_kernel<XT>, dim3((unsigned)blocks), dim3(256), 0, s, Crop<XT>{(const XT*)x, H, W, top, left}, S, total, bounds,
                lut, divide_by_3, out);
-  else if (dtype == P2I_EXP1_F32)
-    P2I_LAUNCH(exp2_index_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)x, H, W, top, left, S, total, bounds, lut,
-               divide_by_3, out);
-  else
-    P2I_LAUNCH(exp2_index_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, s, (const double*)x, H, W, top, left, S, total, bounds,
-               lut, divide_by_3, out);
+  });
   return launch_status();
 }
 

@@ -24,14 +24,16 @@ constexpr int LBINS = P2I_EXP3_BINS;
 constexpr int NHIST = P2I_EXP3_NHIST;
 static_assert(NREC == 4 && NHIST == LBINS + 1, "exp3 layout");
 
-struct Rec { double n, sq, mean, m2; };
-
-__device__ __forceinline__ void rec_merge(Rec& a, const Rec& b) {
-  chan_merge(a.n, a.mean, a.m2, b.n, b.mean, b.m2);
-  a.sq += b.sq;
-}
-__device__ __forceinline__ void rec_store(double* p, const Rec& r) { p[0] = r.n; p[1] = r.sq; p[2] = r.mean; p[3] = r.m2; }
-__device__ __forceinline__ Rec rec_load(const double* p) { return Rec{p[0], p[1], p[2], p[3]}; }
+struct Rec {
+  static constexpr int WORDS = NREC;
+  double n, sq, mean, m2;
+  __device__ __forceinline__ void merge(const Rec& b) {
+    chan_merge(n, mean, m2, b.n, b.mean, b.m2);
+    sq += b.sq;
+  }
+  __device__ __forceinline__ void store(double* p) const { p[0] = n; p[1] = sq; p[2] = mean; p[3] = m2; }
+  static __device__ __forceinline__ Rec load(const double* p) { return Rec{p[0], p[1], p[2], p[3]}; }
+};
 
 // 1 - sum d^2 / (M2 + 1e-10) (experiments/exp3.py nse), NaN without a finite pair
 __device__ __forceinline__ double rec_nse(const Rec& r) { return r.n > 0.0 ? 1.0 - r.sq / (r.m2 + 1e-10) : __builtin_nan(""); }
@@ -49,18 +51,15 @@ __device__ __forceinline__ void hist_flush(const int* h, unsigned long long* his
 
 // One workgroup (4 waves) per frame; wave w takes crop rows w, w + 4, ...; lane l takes columns l, l + 64, ... of the row.
 template <typename PT, typename GT>
-__global__ __launch_bounds__(256) void exp3_accumulate_kernel(const PT* __restrict__ pred, int ph, int pw, int ptop, int pleft,
-                                                              const GT* __restrict__ gt, int gh, int gw, int gtop, int gleft, int S,
-                                                              const int* __restrict__ rank, const double* __restrict__ lut, int div3,
-                                                              double* __restrict__ rec, int* __restrict__ rows,
-                                                              unsigned long long* __restrict__ hist) {
+__global__ __launch_bounds__(256) void exp3_accumulate_kernel(Crop<PT> pred, Crop<GT> gt, int S, const int* __restrict__ rank,
+                                                              const double* __restrict__ lut, int div3, double* __restrict__ rec,
+                                                              int* __restrict__ rows, unsigned long long* __restrict__ hist) {
   __shared__ int h[NHIST];
   __shared__ double red[256 * NREC];
   const long long t = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if ((int)threadIdx.x < NHIST) h[threadIdx.x] = 0;
   __syncthreads();
-  const long long pbase = t * ph * pw, gbase = t * gh * gw;
   Rec r{0.0, 0.0, 0.0, 0.0};
   for (int y = wave; y < S; y += 4) {
     int cnt = 0;
@@ -68,8 +67,8 @@ __global__ __launch_bounds__(256) void exp3_accumulate_kernel(const PT* __restri
       const int x = x0 + lane;
       bool keep = false;
       if (x < S) {
-        const double p = tload<PT>(pred, pbase + (long long)(ptop + y) * pw + pleft + x, lut, div3);
-        const double g = tload<GT>(gt, gbase + (long long)(gtop + y) * gw + gleft + x, lut, div3);
+        const double p = pred.at(t, y, x, lut, div3);
+        const double g = gt.at(t, y, x, lut, div3);
         const bool fp = isfinite(p), fg = isfinite(g);
         keep = fp && fg && g >= 0.1;
         if (fp && fg && rank[y * S + x] >= 0) {
@@ -87,32 +86,21 @@ __global__ __launch_bounds__(256) void exp3_accumulate_kernel(const PT* __restri
     }
     if (lane == 0) rows[t * S + y] = cnt;
   }
-  // tree over the workgroup: thread i takes thread i + o for o = 128, 64, ..., 1 (fixed order)
-  rec_store(red + threadIdx.x * NREC, r);
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      rec_merge(r, rec_load(red + (threadIdx.x + o) * NREC));
-      rec_store(red + threadIdx.x * NREC, r);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) rec_store(rec + t * NREC, r);
+  block_tree<256>(r, red);
+  if (threadIdx.x == 0) r.store(rec + t * NREC);
   if (hist) hist_flush(h, hist);
 }
 
 template <typename GT>
-__global__ __launch_bounds__(256) void exp3_truth_hist_kernel(const GT* __restrict__ gt, int gh, int gw, int gtop, int gleft, int S,
-                                                              const double* __restrict__ lut, int div3,
+__global__ __launch_bounds__(256) void exp3_truth_hist_kernel(Crop<GT> gt, int S, const double* __restrict__ lut, int div3,
                                                               unsigned long long* __restrict__ hist) {
   __shared__ int h[NHIST];
   const long long t = blockIdx.x;
   if ((int)threadIdx.x < NHIST) h[threadIdx.x] = 0;
   __syncthreads();
-  const long long gbase = t * gh * gw;
   for (int i = threadIdx.x; i < S * S; i += 256) {
     const int y = i / S, x = i - y * S;
-    const double g = tload<GT>(gt, gbase + (long long)(gtop + y) * gw + gleft + x, lut, div3);
+    const double g = gt.at(t, y, x, lut, div3);
     const int b = lf_bin(g);
     if (b >= 0) atomicAdd(&h[b], 1);
     if (isfinite(g)) atomicAdd(&h[LBINS], 1);
@@ -146,11 +134,10 @@ __global__ __launch_bounds__(1024) void exp3_scan_kernel(const int* __restrict__
 }
 
 template <typename PT, typename GT>
-__global__ __launch_bounds__(256) void exp3_gather_kernel(const PT* __restrict__ pred, int ph, int pw, int ptop, int pleft,
-                                                          const GT* __restrict__ gt, int gh, int gw, int gtop, int gleft, int T, int S,
-                                                          const double* __restrict__ lut, int div3, const long long* __restrict__ prefix,
-                                                          long long row0, const long long* __restrict__ ords, int K,
-                                                          double* __restrict__ out_g, double* __restrict__ out_p) {
+__global__ __launch_bounds__(256) void exp3_gather_kernel(Crop<PT> pred, Crop<GT> gt, int T, int S, const double* __restrict__ lut,
+                                                          int div3, const long long* __restrict__ prefix, long long row0,
+                                                          const long long* __restrict__ ords, int K, double* __restrict__ out_g,
+                                                          double* __restrict__ out_p) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= K) return;
   const long long nrows = (long long)T * S;
@@ -167,10 +154,10 @@ __global__ __launch_bounds__(256) void exp3_gather_kernel(const PT* __restrict__
   const long long lr = a - row0;
   const long long t = lr / S;
   const int y = (int)(lr - t * S);
-  const long long pbase = t * ph * pw + (long long)(ptop + y) * pw + pleft, gbase = t * gh * gw + (long long)(gtop + y) * gw + gleft;
+  const long long prow = pred.row(t, y), grow = gt.row(t, y);
   for (int x = 0; x < S; ++x) {
-    const double p = tload<PT>(pred, pbase + x, lut, div3);
-    const double g = tload<GT>(gt, gbase + x, lut, div3);
+    const double p = pred.at(prow, x, lut, div3);
+    const double g = gt.at(grow, x, lut, div3);
     if (isfinite(p) && isfinite(g) && g >= 0.1) {
       if (j == 0) {
         out_g[i] = g;
@@ -188,21 +175,13 @@ __global__ __launch_bounds__(256) void exp3_nse_kernel(const double* __restrict_
                                                        const double* __restrict__ srec, int T, double* __restrict__ out) {
   __shared__ double red[256 * NREC];
   Rec r{0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < T; i += 256) rec_merge(r, rec_load(srec + (long long)i * NREC));
-  rec_store(red + threadIdx.x * NREC, r);
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      rec_merge(r, rec_load(red + (threadIdx.x + o) * NREC));
-      rec_store(red + threadIdx.x * NREC, r);
-    }
-    __syncthreads();
-  }
+  for (int i = threadIdx.x; i < T; i += 256) r.merge(Rec::load(srec + (long long)i * NREC));
+  block_tree<256>(r, red);
   if (threadIdx.x == 0) out[0] = rec_nse(r);
   for (int e = threadIdx.x; e < E; e += 256) {
     double s = 0.0, c = 0.0;
     for (int f = off[e]; f < off[e + 1]; ++f) {
-      const double v = rec_nse(rec_load(erec + (long long)f * NREC));
+      const double v = rec_nse(Rec::load(erec + (long long)f * NREC));
       if (isfinite(v)) {
         s += v > 0.0 ? v : 0.0;
         c += 1.0;
@@ -210,19 +189,6 @@ __global__ __launch_bounds__(256) void exp3_nse_kernel(const double* __restrict_
     }
     out[1 + e] = c > 0.0 ? s / c : __builtin_nan("");
   }
-}
-
-// dtype dispatch: f(PT*, GT*) over the three input dtypes of each side
-template <typename F> static void dispatch2(int pdt, int gdt, F&& f) {
-  auto inner = [&](auto pz) {
-    using PT = decltype(pz);
-    if (gdt == P2I_EXP1_U8) f(PT{}, uint8_t{});
-    else if (gdt == P2I_EXP1_F32) f(PT{}, float{});
-    else f(PT{}, double{});
-  };
-  if (pdt == P2I_EXP1_U8) inner(uint8_t{});
-  else if (pdt == P2I_EXP1_F32) inner(float{});
-  else inner(double{});
 }
 
 }  // namespace p2i
@@ -235,14 +201,14 @@ extern "C" int p2i_exp3_accumulate(const void* pred, int pred_dtype, int ph, int
   P2I_REQUIRE(pred && truth && rank && lut && rec && rows, "bad arguments");
   P2I_REQUIRE(eval_dtype_ok(pred_dtype) && eval_dtype_ok(truth_dtype), "unsupported dtype");
   P2I_REQUIRE(T > 0 && S > 0, "bad frame count / crop");
-  P2I_REQUIRE(ptop >= 0 && pleft >= 0 && ptop + S <= ph && pleft + S <= pw, "crop outside the prediction");
-  P2I_REQUIRE(gtop >= 0 && gleft >= 0 && gtop + S <= gh && gleft + S <= gw, "crop outside the truth");
+  P2I_REQUIRE(crop_ok(ph, pw, ptop, pleft, S), "crop outside the prediction");
+  P2I_REQUIRE(crop_ok(gh, gw, gtop, gleft, S), "crop outside the truth");
   const hipStream_t s = (hipStream_t)stream;
   dispatch2(pred_dtype, truth_dtype, [&](auto pz, auto gz) {
     using PT = decltype(pz);
     using GT = decltype(gz);
-    P2I_LAUNCH((exp3_accumulate_kernel<PT, GT>), dim3((unsigned)T), dim3(256), 0, s, (const PT*)pred, ph, pw, ptop, pleft,
-               (const GT*)truth, gh, gw, gtop, gleft, S, rank, lut, divide_by_3, rec, rows, (unsigned long long*)hist);
+    P2I_LAUNCH((exp3_accumulate_kernel<PT, GT>), dim3((unsigned)T), dim3(256), 0, s, Crop<PT>{(const PT*)pred, ph, pw, ptop, pleft},
+               Crop<GT>{(const GT*)truth, gh, gw, gtop, gleft}, S, rank, lut, divide_by_3, rec, rows, (unsigned long long*)hist);
   });
   return launch_status();
 }
@@ -250,18 +216,13 @@ extern "C" int p2i_exp3_accumulate(const void* pred, int pred_dtype, int ph, int
 extern "C" int p2i_exp3_truth_hist(const void* truth, int truth_dtype, int gh, int gw, int gtop, int gleft, int T, int S,
                                    const double* lut, int divide_by_3, uint64_t* hist, void* stream) {
   P2I_REQUIRE(truth && lut && hist && eval_dtype_ok(truth_dtype) && T > 0 && S > 0, "bad arguments");
-  P2I_REQUIRE(gtop >= 0 && gleft >= 0 && gtop + S <= gh && gleft + S <= gw, "crop outside the truth");
+  P2I_REQUIRE(crop_ok(gh, gw, gtop, gleft, S), "crop outside the truth");
   const hipStream_t s = (hipStream_t)stream;
-  unsigned long long* hh = (unsigned long long*)hist;
-  if (truth_dtype == P2I_EXP1_U8)
-    P2I_LAUNCH(exp3_truth_hist_kernel<uint8_t>, dim3((unsigned)T), dim3(256), 0, s, (const uint8_t*)truth, gh, gw, gtop, gleft, S, lut,
-               divide_by_3, hh);
-  else if (truth_dtype == P2I_EXP1_F32)
-    P2I_LAUNCH(exp3_truth_hist_kernel<float>, dim3((unsigned)T), dim3(256), 0, s, (const float*)truth, gh, gw, gtop, gleft, S, lut,
-               divide_by_3, hh);
-  else
-    P2I_LAUNCH(exp3_truth_hist_kernel<double>, dim3((unsigned)T), dim3(256), 0, s, (const double*)truth, gh, gw, gtop, gleft, S, lut,
-               divide_by_3, hh);
+  dispatch1(truth_dtype, [&](auto gz) {
+    using GT = decltype(gz);
+    P2I_LAUNCH(exp3_truth_hist_kernel<GT>, dim3((unsigned)T), dim3(256), 0, s, Crop<GT>{(const GT*)truth, gh, gw, gtop, gleft}, S, lut,
+               divide_by_3, (unsigned long long*)hist);
+  });
   return launch_status();
 }
 
@@ -278,15 +239,15 @@ extern "C" int p2i_exp3_gather(const void* pred, int pred_dtype, int ph, int pw,
   P2I_REQUIRE(pred && truth && lut && prefix && ords && out_g && out_p && K > 0 && row0 >= 0, "bad arguments");
   P2I_REQUIRE(eval_dtype_ok(pred_dtype) && eval_dtype_ok(truth_dtype), "unsupported dtype");
   P2I_REQUIRE(T > 0 && S > 0, "bad frame count / crop");
-  P2I_REQUIRE(ptop >= 0 && pleft >= 0 && ptop + S <= ph && pleft + S <= pw, "crop outside the prediction");
-  P2I_REQUIRE(gtop >= 0 && gleft >= 0 && gtop + S <= gh && gleft + S <= gw, "crop outside the truth");
+  P2I_REQUIRE(crop_ok(ph, pw, ptop, pleft, S), "crop outside the prediction");
+  P2I_REQUIRE(crop_ok(gh, gw, gtop, gleft, S), "crop outside the truth");
   const hipStream_t s = (hipStream_t)stream;
   dispatch2(pred_dtype, truth_dtype, [&](auto pz, auto gz) {
     using PT = decltype(pz);
     using GT = decltype(gz);
-    P2I_LAUNCH((exp3_gather_kernel<PT, GT>), dim3((unsigned)ceil_div(K, 256)), dim3(256), 0, s, (const PT*)pred, ph, pw, ptop, pleft,
-               (const GT*)truth, gh, gw, gtop, gleft, T, S, lut, divide_by_3, (const long long*)prefix, (long long)row0,
-               (const long long*)ords, K, out_g, out_p);
+    P2I_LAUNCH((exp3_gather_kernel<PT, GT>), dim3((unsigned)ceil_div(K, 256)), dim3(256), 0, s,
+               Crop<PT>{(const PT*)pred, ph, pw, ptop, pleft}, Crop<GT>{(const GT*)truth, gh, gw, gtop, gleft}, T, S, lut, divide_by_3,
+               (const long long*)prefix, (long long)row0, (const long long*)ords, K, out_g, out_p);
   });
   return launch_status();
 }

@@ -1,0 +1,26 @@
+"""The benchmark's evaluation of inference outputs (reference experiments/exp1.py, exp2.py, exp3.py with experiments/io.py), with the
+arithmetic on the device (csrc/eval_exp1.hip, eval_exp2.hip, eval_exp3.hip over eval_common.h).  There is no CPU path: without a GPU
+every evaluator raises RuntimeError.  The package imports without a GPU, matplotlib or PIL.
+
+exp1 (``exp1.py``): ``run_exp1`` takes the reference's arguments and returns its table: per method MAE, RMSE,
+PSS, SSIM, DTSSIM_L1, DTSSIM_L2, NSE and ``CAT_<thr:g>`` = {POD, FAR, CSI, HSS}.  Inputs may be numpy arrays, torch tensors (CPU or
+device) or dicts of per-event arrays (``[T, H, W]``, ``[T, 1, H, W]``, ``[T, H, W, 1]`` or ``[1, T, H, W]``, on the 0-255 scale).
+``Exp1Evaluator`` is the streaming form it is built on: one ``update`` per aligned piece, one host sync in ``compute``.
+
+exp2 (``exp2.py``, ``exp2_chrome.py``, section 12): ``run_exp2`` takes the reference's arguments and writes its
+comparison GIFs and ``event_ranges.txt`` plus ``exp2_data.npz``; the frames are canvases of palette indices (``compute_exp2``,
+``exp2_canvases``).  ``run_exp2_paper_zarr`` writes the paper's frame grid.
+
+exp3 (``exp3.py``, section 11): ``run_exp3`` takes the reference's arguments, returns ``{"NSE_<name>": float}`` and writes the
+reference's four figures plus ``exp3_data.npz`` (the numbers behind them).  ``Exp3Evaluator`` is its streaming form (one
+``add_event`` per truth event, two host syncs in ``compute``).
+
+``_common.py`` holds what the three share."""
+from ._common import crop_mask, crop_origin, ensure_thw_shape, selection, transform_mmhr, truth_lut  # noqa: F401
+from .exp1 import DEFAULT_THRESHOLDS, PSS_BINS, PSS_MIN_VALUE, Exp1Evaluator, pss_bin, pss_edges, run_exp1  # noqa: F401
+from .exp2 import (EXP2_MAX_EVENTS, EXP2_MAX_FRAMES, Exp2Event, Exp2Result, compute_exp2, default_zoom, exp2_canvases,  # noqa: F401
+                   iter_exp2, paper_panels, run_exp2, run_exp2_paper_zarr)
+from .exp2_chrome import (EXP2_GREYS, EXP2_IDX_BAD, EXP2_IDX_BG, EXP2_IDX_EDGE, EXP2_IDX_GREY, PAPER_BOUNDS, PAPER_COLORS,  # noqa: F401
+                          PAPER_SUB, exp2_chrome, exp2_layout, exp2_palette, paper_cmap, write_exp2_gif)
+from .exp3 import (EXP3_MAX_POINTS, EXP3_MIN_VALUE, EXP3_SEED, LOGFREQ_EDGES, SCATTER_COLORS, Exp3Evaluator, Exp3Result,  # noqa: F401
+                   compute_exp3, linregress, run_exp3, write_exp3_figures)

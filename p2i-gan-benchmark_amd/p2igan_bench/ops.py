@@ -1258,19 +1258,38 @@ def stdk_layer1_bwd(phi_s, phi_t, z, dP, dQ, B, T, dw1=None, db1=None):
     return dw1, db1
 
 
-# ---- exp1 scoring (csrc/eval_exp1.hip; p2igan_bench/evaluation.py drives these) ----
+# ---- evaluation: exp1 scoring, exp3 analysis, exp2 renders (csrc/eval_exp{1,3,2}.hip; p2igan_bench/evaluation/ drives these) ----
 EXP1_MAX_THR = 8
 EXP1_NSTAT = 8 + 3 * EXP1_MAX_THR
 EXP1_BINS = 50
-_EXP1_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.float64: 2}
+EXP3_NREC = 4
+EXP3_BINS = 64
+EXP3_NHIST = EXP3_BINS + 1
+EXP2_NBOUNDS = 142
+EXP2_BAD = 141
+_EVAL_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.float64: 2}
 
 
-def _exp1_code(t: torch.Tensor) -> int:
+def _eval_code(t: torch.Tensor) -> int:
     if not (t.is_cuda and t.is_contiguous()):
-        raise RuntimeError("exp1 ops need contiguous CUDA tensors (the HIP path has no CPU fallback)")
-    if t.dtype not in _EXP1_DTYPES:
-        raise RuntimeError(f"exp1: unsupported dtype {t.dtype}")
-    return _EXP1_DTYPES[t.dtype]
+        raise RuntimeError("evaluation ops need contiguous CUDA tensors (the HIP path has no CPU fallback)")
+    if t.dtype not in _EVAL_DTYPES:
+        raise RuntimeError(f"evaluation ops: unsupported dtype {t.dtype}")
+    return _EVAL_DTYPES[t.dtype]
+
+
+def _eval_input(t: torch.Tensor, tl):
+    """An input [T, H, W] (uint8 / f32 / f64) and its crop origin (top, left) as the ABI's group ptr, dtype, H, W, top, left."""
+    if t.dim() != 3:
+        raise RuntimeError(f"evaluation ops: expected [T, H, W], got {tuple(t.shape)}")
+    return _ptr(t), _eval_code(t), t.shape[1], t.shape[2], int(tl[0]), int(tl[1])
+
+
+def _eval_bufs(what, *bufs):
+    """Every (tensor, dtype, numel) is a contiguous device tensor of that dtype and size."""
+    for t, dt, n in bufs:
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n):
+            raise RuntimeError(f"{what}: bad buffer")
 
 
 def _f64s(vals):
@@ -1280,7 +1299,7 @@ def _f64s(vals):
 
 def exp1_transform(x: torch.Tensor, divide_by_3: bool = True) -> torch.Tensor:
     """transform_mmhr of a uint8 / f32 / f64 device tensor, in fp64 on the device."""
-    code = _exp1_code(x)
+    code = _eval_code(x)
     out = torch.empty(x.shape, device=x.device, dtype=torch.float64)
     if x.numel():
         _hip.check(_hip.load().p2i_exp1_transform(_ptr(x), code, x.numel(), int(divide_by_3), _ptr(out), _stream()),
@@ -1300,29 +1319,31 @@ def exp1_accumulate(pred, truth, ptl, gtl, S, pool, rank, nsel, lut, thresholds,
     T = pred.shape[0]
     if truth.shape[0] != T or len(thresholds) > EXP1_MAX_THR:
         raise RuntimeError("exp1_accumulate: frame count / thresholds")
+    pin, gin = _eval_input(pred, ptl), _eval_input(truth, gtl)
     if part.numel() != exp1_workspace(T, S, pool):
         raise RuntimeError("exp1_accumulate: workspace size")
-    pc, gc = _exp1_code(pred), _exp1_code(truth)
-    for t, dt in ((rank, torch.int32), (lut, torch.float64), (pool_p, torch.float32), (pool_g, torch.float32), (sel_p, torch.float32),
-                  (sel_g, torch.float32), (part, torch.float64)):
-        if not (t.is_cuda and t.is_contiguous() and t.dtype == dt):
-            raise RuntimeError("exp1_accumulate: bad buffer")
+    npool = T * (S // pool) ** 2
+    _eval_bufs("exp1_accumulate", (rank, torch.int32, S * S), (lut, torch.float64, 256), (pool_p, torch.float32, npool),
+               (pool_g, torch.float32, npool), (sel_p, torch.float32, T * nsel), (sel_g, torch.float32, T * nsel),
+               (part, torch.float64, part.numel()))
     _hip.check(_hip.load().p2i_exp1_accumulate(
-        _ptr(pred), pc, pred.shape[1], pred.shape[2], ptl[0], ptl[1], _ptr(truth), gc, truth.shape[1], truth.shape[2], gtl[0], gtl[1],
-        T, S, pool, _ptr(rank), nsel, _ptr(lut), _f64s(thresholds), len(thresholds), int(divide_by_3), _ptr(pool_p), _ptr(pool_g),
-        _ptr(sel_p) if nsel else None, _ptr(sel_g) if nsel else None, _ptr(part), _stream()), "p2i_exp1_accumulate")
+        *pin, *gin, T, S, pool, _ptr(rank), nsel, _ptr(lut), _f64s(thresholds), len(thresholds), int(divide_by_3), _ptr(pool_p),
+        _ptr(pool_g), _ptr(sel_p) if nsel else None, _ptr(sel_g) if nsel else None, _ptr(part), _stream()), "p2i_exp1_accumulate")
 
 
 def exp1_merge(part, acc):
     """acc [EXP1_NSTAT] (+)= the partial records of part (a multiple of EXP1_NSTAT doubles), folded in a fixed order."""
-    if part.numel() % EXP1_NSTAT or acc.numel() != EXP1_NSTAT or part.dtype != torch.float64 or acc.dtype != torch.float64:
-        raise RuntimeError("exp1_merge: bad buffers")
+    if part.numel() % EXP1_NSTAT:
+        raise RuntimeError("exp1_merge: bad buffer")
+    _eval_bufs("exp1_merge", (part, torch.float64, part.numel()), (acc, torch.float64, EXP1_NSTAT))
     _hip.check(_hip.load().p2i_exp1_merge(_ptr(part), part.numel() // EXP1_NSTAT, _ptr(acc), _stream()), "p2i_exp1_merge")
 
 
 def exp1_hist(sel_p, sel_g, acc, score, flag, edges):
     """Per-frame PSS histograms of the compacted selections [T, nsel] over acc's range: score [T] f64, flag [T] int32, edges [52]."""
     T, nsel = sel_p.shape
+    _eval_bufs("exp1_hist", (sel_p, torch.float32, T * nsel), (sel_g, torch.float32, T * nsel), (acc, torch.float64, EXP1_NSTAT),
+               (score, torch.float64, T), (flag, torch.int32, T), (edges, torch.float32, EXP1_BINS + 2))
     _hip.check(_hip.load().p2i_exp1_hist(_ptr(sel_p) if nsel else None, _ptr(sel_g) if nsel else None, T, nsel, _ptr(acc), _ptr(score),
                                          _ptr(flag), _ptr(edges), _stream()), "p2i_exp1_hist")
 
@@ -1330,6 +1351,7 @@ def exp1_hist(sel_p, sel_g, acc, score, flag, edges):
 def exp1_ssim(pool_p, pool_g):
     """pool_* [T, npix] f32 -> (SSIM(p_t, g_t), lag-1 and lag-2 dTSSIM terms), each [T] f64."""
     T, npix = pool_p.shape
+    _eval_bufs("exp1_ssim", (pool_p, torch.float32, T * npix), (pool_g, torch.float32, T * npix))
     out = torch.empty(3, T, device=pool_p.device, dtype=torch.float64)
     _hip.check(_hip.load().p2i_exp1_ssim(_ptr(pool_p), _ptr(pool_g), T, npix, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()),
                "p2i_exp1_ssim")
@@ -1339,21 +1361,12 @@ def exp1_ssim(pool_p, pool_g):
 def exp1_finalize(acc, thresholds, score, flag, edges, ssim3):
     """The table's numbers of one method as a [8 + 4 k] f64 device tensor (see include/p2i_hip.h)."""
     T = score.shape[0]
+    _eval_bufs("exp1_finalize", (acc, torch.float64, EXP1_NSTAT), (score, torch.float64, T), (flag, torch.int32, T),
+               (edges, torch.float32, EXP1_BINS + 2), (ssim3, torch.float64, 3 * T))
     out = torch.empty(8 + 4 * len(thresholds), device=acc.device, dtype=torch.float64)
     _hip.check(_hip.load().p2i_exp1_finalize(_ptr(acc), _f64s(thresholds), len(thresholds), T, _ptr(score), _ptr(flag), _ptr(edges),
                                              _ptr(ssim3[0]), _ptr(ssim3[1]), _ptr(ssim3[2]), _ptr(out), _stream()), "p2i_exp1_finalize")
     return out
-
-
-# ---- exp3 analysis (csrc/eval_exp3.hip; p2igan_bench/evaluation.py drives these) ----
-EXP3_NREC = 4
-EXP3_BINS = 64
-EXP3_NHIST = EXP3_BINS + 1
-
-
-def _exp3_buf(t, dt, n, what):
-    if not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n):
-        raise RuntimeError(f"{what}: bad buffer")
 
 
 def exp3_accumulate(pred, truth, ptl, gtl, S, rank, lut, divide_by_3, rec, rows, hist=None):
@@ -1363,30 +1376,24 @@ def exp3_accumulate(pred, truth, ptl, gtl, S, rank, lut, divide_by_3, rec, rows,
     T = pred.shape[0]
     if truth.shape[0] != T:
         raise RuntimeError("exp3_accumulate: frame count")
-    pc, gc = _exp1_code(pred), _exp1_code(truth)
-    _exp3_buf(rank, torch.int32, S * S, "exp3_accumulate")
-    _exp3_buf(lut, torch.float64, 256, "exp3_accumulate")
-    _exp3_buf(rec, torch.float64, T * EXP3_NREC, "exp3_accumulate")
-    _exp3_buf(rows, torch.int32, T * S, "exp3_accumulate")
-    if hist is not None:
-        _exp3_buf(hist, torch.int64, EXP3_NHIST, "exp3_accumulate")
-    _hip.check(_hip.load().p2i_exp3_accumulate(
-        _ptr(pred), pc, pred.shape[1], pred.shape[2], ptl[0], ptl[1], _ptr(truth), gc, truth.shape[1], truth.shape[2], gtl[0], gtl[1],
-        T, S, _ptr(rank), _ptr(lut), int(divide_by_3), _ptr(rec), _ptr(rows), _ptr(hist), _stream()), "p2i_exp3_accumulate")
+    pin, gin = _eval_input(pred, ptl), _eval_input(truth, gtl)
+    _eval_bufs("exp3_accumulate", (rank, torch.int32, S * S), (lut, torch.float64, 256), (rec, torch.float64, T * EXP3_NREC),
+               (rows, torch.int32, T * S), *([(hist, torch.int64, EXP3_NHIST)] if hist is not None else []))
+    _hip.check(_hip.load().p2i_exp3_accumulate(*pin, *gin, T, S, _ptr(rank), _ptr(lut), int(divide_by_3), _ptr(rec), _ptr(rows),
+                                               _ptr(hist), _stream()), "p2i_exp3_accumulate")
 
 
 def exp3_truth_hist(truth, gtl, S, lut, divide_by_3, hist):
     """Adds the log-frequency counts of every cropped frame of truth [T, H, W] to hist [EXP3_NHIST] (int64)."""
-    gc = _exp1_code(truth)
-    _exp3_buf(lut, torch.float64, 256, "exp3_truth_hist")
-    _exp3_buf(hist, torch.int64, EXP3_NHIST, "exp3_truth_hist")
-    _hip.check(_hip.load().p2i_exp3_truth_hist(_ptr(truth), gc, truth.shape[1], truth.shape[2], gtl[0], gtl[1], truth.shape[0], S,
-                                               _ptr(lut), int(divide_by_3), _ptr(hist), _stream()), "p2i_exp3_truth_hist")
+    gin = _eval_input(truth, gtl)
+    _eval_bufs("exp3_truth_hist", (lut, torch.float64, 256), (hist, torch.int64, EXP3_NHIST))
+    _hip.check(_hip.load().p2i_exp3_truth_hist(*gin, truth.shape[0], S, _ptr(lut), int(divide_by_3), _ptr(hist), _stream()),
+               "p2i_exp3_truth_hist")
 
 
 def exp3_scan(rows: torch.Tensor) -> torch.Tensor:
     """The inclusive prefix (int64) of int32 row counts, on the device."""
-    _exp3_buf(rows, torch.int32, rows.numel(), "exp3_scan")
+    _eval_bufs("exp3_scan", (rows, torch.int32, rows.numel()))
     out = torch.empty(rows.numel(), device=rows.device, dtype=torch.int64)
     if rows.numel():
         _hip.check(_hip.load().p2i_exp3_scan(_ptr(rows), rows.numel(), _ptr(out), _stream()), "p2i_exp3_scan")
@@ -1399,17 +1406,13 @@ def exp3_gather(pred, truth, ptl, gtl, S, lut, divide_by_3, prefix, row0, ords, 
     T, K = pred.shape[0], ords.numel()
     if truth.shape[0] != T or row0 + T * S > prefix.numel():
         raise RuntimeError("exp3_gather: frame count / rows")
-    pc, gc = _exp1_code(pred), _exp1_code(truth)
-    _exp3_buf(lut, torch.float64, 256, "exp3_gather")
-    _exp3_buf(prefix, torch.int64, prefix.numel(), "exp3_gather")
-    _exp3_buf(ords, torch.int64, K, "exp3_gather")
-    _exp3_buf(out_g, torch.float64, K, "exp3_gather")
-    _exp3_buf(out_p, torch.float64, K, "exp3_gather")
+    pin, gin = _eval_input(pred, ptl), _eval_input(truth, gtl)
+    _eval_bufs("exp3_gather", (lut, torch.float64, 256), (prefix, torch.int64, prefix.numel()), (ords, torch.int64, K),
+               (out_g, torch.float64, K), (out_p, torch.float64, K))
     if K == 0 or T == 0:
         return
-    _hip.check(_hip.load().p2i_exp3_gather(
-        _ptr(pred), pc, pred.shape[1], pred.shape[2], ptl[0], ptl[1], _ptr(truth), gc, truth.shape[1], truth.shape[2], gtl[0], gtl[1],
-        T, S, _ptr(lut), int(divide_by_3), _ptr(prefix), int(row0), _ptr(ords), K, _ptr(out_g), _ptr(out_p), _stream()), "p2i_exp3_gather")
+    _hip.check(_hip.load().p2i_exp3_gather(*pin, *gin, T, S, _ptr(lut), int(divide_by_3), _ptr(prefix), int(row0), _ptr(ords), K,
+                                           _ptr(out_g), _ptr(out_p), _stream()), "p2i_exp3_gather")
 
 
 def exp3_nse(event_rec, event_off, stack_rec) -> torch.Tensor:
@@ -1419,30 +1422,22 @@ def exp3_nse(event_rec, event_off, stack_rec) -> torch.Tensor:
     T = stack_rec.shape[0]
     out = torch.empty(1 + E, device=stack_rec.device, dtype=torch.float64)
     if E:
-        _exp3_buf(event_off, torch.int32, E + 1, "exp3_nse")
-        _exp3_buf(event_rec, torch.float64, event_rec.numel(), "exp3_nse")
-    _exp3_buf(stack_rec, torch.float64, T * EXP3_NREC, "exp3_nse")
+        _eval_bufs("exp3_nse", (event_off, torch.int32, E + 1), (event_rec, torch.float64, event_rec.numel()))
+    _eval_bufs("exp3_nse", (stack_rec, torch.float64, T * EXP3_NREC))
     _hip.check(_hip.load().p2i_exp3_nse(_ptr(event_rec) if E else None, _ptr(event_off) if E else None, E, _ptr(stack_rec) if T else None,
                                         T, _ptr(out), _stream()), "p2i_exp3_nse")
     return out
 
 
-# ---- exp2 comparison renders (csrc/eval_exp2.hip; p2igan_bench/evaluation.py drives these) ----
-EXP2_NBOUNDS = 142
-EXP2_BAD = 141
-
-
 def exp2_index(x, tl, S, n, bounds, lut, divide_by_3, out):
     """The colour indices of the first n frames of x [T, H, W] (uint8 / f32 / f64), cropped to S x S at tl = (top, left), into out
     [n, S, S] (uint8): see include/p2i_hip.h.  bounds [EXP2_NBOUNDS] and lut [256] are f64 on the device."""
-    dc = _exp1_code(x)
-    _exp3_buf(bounds, torch.float64, EXP2_NBOUNDS, "exp2_index")
-    _exp3_buf(lut, torch.float64, 256, "exp2_index")
-    _exp3_buf(out, torch.uint8, n * S * S, "exp2_index")
+    ptr, code, *crop = _eval_input(x, tl)
+    _eval_bufs("exp2_index", (bounds, torch.float64, EXP2_NBOUNDS), (lut, torch.float64, 256), (out, torch.uint8, n * S * S))
     if n == 0:
         return
-    _hip.check(_hip.load().p2i_exp2_index(_ptr(x), dc, x.shape[0], x.shape[1], x.shape[2], tl[0], tl[1], S, n, _ptr(bounds), _ptr(lut),
-                                          int(divide_by_3), _ptr(out), _stream()), "p2i_exp2_index")
+    _hip.check(_hip.load().p2i_exp2_index(ptr, code, x.shape[0], *crop, S, n, _ptr(bounds), _ptr(lut), int(divide_by_3), _ptr(out),
+                                          _stream()), "p2i_exp2_index")
 
 
 def exp2_pitch(width: int) -> int:
@@ -1456,11 +1451,8 @@ def exp2_compose(panels, zoom, gauge_bits, points, chrome, oy, ox, step, bg, edg
     P, n, S, _ = panels.shape
     Hc, pitch = chrome.shape
     K = 0 if points is None else points.shape[0]
-    _exp3_buf(panels, torch.uint8, P * n * S * S, "exp2_compose")
-    _exp3_buf(chrome, torch.uint8, Hc * pitch, "exp2_compose")
-    _exp3_buf(out, torch.uint8, n * Hc * pitch, "exp2_compose")
-    if K:
-        _exp3_buf(points, torch.int32, K * 2, "exp2_compose")
+    _eval_bufs("exp2_compose", (panels, torch.uint8, P * n * S * S), (chrome, torch.uint8, Hc * pitch), (out, torch.uint8, n * Hc * pitch),
+               *([(points, torch.int32, K * 2)] if K else []))
     if n == 0:
         return
     _hip.check(_hip.load().p2i_exp2_compose(_ptr(panels), P, n, S, int(zoom), int(gauge_bits), _ptr(points) if K else None, K, _ptr(chrome),
