@@ -287,6 +287,50 @@ int p2i_gan_loss(const float* logits_a, const float* logits_b, int n, int loss_t
                  float weight, float real_label, float fake_label, float* loss, float* dlogits_a,
                  float* dlogits_b, void* stream);
 
+/* ---- the reference's other objectives (losses.py:51-162).  fp32, contiguous.  Scalar results (out1) are sums of
+ * workgroup partials added in a fixed order: they need the scratch of p2i_det_workspace.  gout: DEVICE pointer to the upstream
+ * gradient of a scalar result.  Every backward pass is a gather (no atomics); max-pool ties go to the first maximal element of
+ * the window in raster order (torch's rule).
+ * p2i_loss_transform_fwd / _bwd: y = 0.036 * 10^((x*255/3)*0.0625) (losses.py:51-53; NOT metric.py's transform); dx = dy * dy/dx.
+ * p2i_fdiff_fwd / _bwd: out[b][t] = x[b][t+1] - x[b][t] over dim 1 of [B][T][inner] (losses.py:83-85); T >= 2.
+ * p2i_wl1_fwd / _bwd: mean(w(target) * |pred - target|), w = 0.5 exp(5.14 min(target, 0.7)) + 0.12 (losses.py:56-65); sign(0) = 0.
+ * p2i_softmax_t_fwd / _bwd: y = softmax(x / temperature) over each of `rows` rows of L elements, the row maximum subtracted
+ *   (losses.py:68-73); dx from y and dy.
+ * p2i_kl_fwd / _bwd: out1 = sum(xlogy(q, q) - q log p) / B = F.kl_div(p.log(), q, 'batchmean') (losses.py:76-80); dp = -gout q / (p B).
+ * p2i_spool_fwd / _bwd: MaxPool2d(5, stride 4, padding 2) on N planes of H x W (losses.py:88-91; padding is -inf), output
+ *   ((H-1)/4+1) x ((W-1)/4+1); idx (may be NULL) = plane index h*W + w of each window's argmax.  _bwd: dx = scale[0] (DEVICE, may
+ *   be NULL: 1) * the sum of dout over the up to four windows whose argmax the pixel is.
+ * p2i_tdm_fwd: out1 = mean((P(pred_diff) - P(true_diff))^2 / (1 + beta P(true[:, :-1]) + eps)), P = the pool above
+ *   (losses.py:94-109); pred_diff / true_diff [B][Tm1][H][W], truth [B][Tm1 + 1][H][W].  coef, idx (both or neither): d out1 / d
+ *   P(pred_diff) and P(pred_diff)'s argmax; the backward pass is p2i_spool_bwd(idx, coef, gout).
+ * p2i_shock_map_fwd / _bwd: s = tanh(beta lap) sqrt(gx^2 + gy^2 + eps) on N planes, gx / gy / lap = Sobel / 8 and the 5-point
+ *   Laplacian under reflect padding of 1 (losses.py:112-137); H, W >= 2.  scratch: 3 N H W floats.
+ * p2i_shock_loss_fwd / _bwd: out [N][Hp - 2 border][Wp - 2 border] = relu(|s(P truth)| - |s(P pred)|) cropped by border, P =
+ *   max_pool2d(pool, pool), Hp = H / pool (floor) (losses.py:140-162); one kernel, no map is written.  _bwd: dpred from dout in two
+ *   kernels (map-gradient coefficients, then the transposed-stencil gather routed through the pool argmax); relu'(0) = 0,
+ *   sign(0) = 0; scratch: 3 N Hp Wp floats. */
+int p2i_loss_transform_fwd(const float* x, float* y, int64_t n, void* stream);
+int p2i_loss_transform_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream);
+int p2i_fdiff_fwd(const float* x, float* out, int B, int T, int64_t inner, void* stream);
+int p2i_fdiff_bwd(const float* dy, float* dx, int B, int T, int64_t inner, void* stream);
+int p2i_wl1_fwd(const float* pred, const float* target, float* out1, int64_t n, void* stream);
+int p2i_wl1_bwd(const float* pred, const float* target, const float* gout, float* dpred, int64_t n, void* stream);
+int p2i_softmax_t_fwd(const float* x, float* y, int rows, int L, float temperature, void* stream);
+int p2i_softmax_t_bwd(const float* y, const float* dy, float* dx, int rows, int L, float temperature, void* stream);
+int p2i_kl_fwd(const float* p, const float* q, float* out1, int64_t n, int B, void* stream);
+int p2i_kl_bwd(const float* p, const float* q, const float* gout, float* dp, int64_t n, int B, void* stream);
+int p2i_spool_fwd(const float* x, float* out, int* idx, int N, int H, int W, void* stream);
+int p2i_spool_bwd(const int* idx, const float* dout, const float* scale, float* dx, int N, int H, int W, void* stream);
+int p2i_tdm_fwd(const float* pred_diff, const float* true_diff, const float* truth, float beta, float eps, float* out1,
+                float* coef, int* idx, int B, int Tm1, int H, int W, void* stream);
+int p2i_shock_map_fwd(const float* x, float* out, int N, int H, int W, float beta, float eps, void* stream);
+int p2i_shock_map_bwd(const float* x, const float* dout, float* dx, float* scratch, int N, int H, int W, float beta, float eps,
+                      void* stream);
+int p2i_shock_loss_fwd(const float* pred, const float* truth, float* out, int N, int H, int W, int pool, int border, float beta,
+                       float eps, void* stream);
+int p2i_shock_loss_bwd(const float* pred, const float* truth, const float* dout, float* dpred, float* scratch, int N, int H,
+                       int W, int pool, int border, float beta, float eps, void* stream);
+
 /* ------------------------------------------------------------------ optimiser
  * torch.optim.Adam step on flat fp32 buffers (train.py:125-136): no weight decay, no amsgrad. */
 int p2i_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,

@@ -69,6 +69,23 @@ SIGNATURES = {
     "p2i_dtail_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "p2i_recloss": [_P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
     "p2i_gan_loss": [_P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P],
+    "p2i_loss_transform_fwd": [_P, _P, _L, _P],
+    "p2i_loss_transform_bwd": [_P, _P, _P, _L, _P],
+    "p2i_fdiff_fwd": [_P, _P, _I, _I, _L, _P],
+    "p2i_fdiff_bwd": [_P, _P, _I, _I, _L, _P],
+    "p2i_wl1_fwd": [_P, _P, _P, _L, _P],
+    "p2i_wl1_bwd": [_P, _P, _P, _P, _L, _P],
+    "p2i_softmax_t_fwd": [_P, _P, _I, _I, _F, _P],
+    "p2i_softmax_t_bwd": [_P, _P, _P, _I, _I, _F, _P],
+    "p2i_kl_fwd": [_P, _P, _P, _L, _I, _P],
+    "p2i_kl_bwd": [_P, _P, _P, _P, _L, _I, _P],
+    "p2i_spool_fwd": [_P, _P, _P, _I, _I, _I, _P],
+    "p2i_spool_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "p2i_tdm_fwd": [_P, _P, _P, _F, _F, _P, _P, _P, _I, _I, _I, _I, _P],
+    "p2i_shock_map_fwd": [_P, _P, _I, _I, _I, _F, _F, _P],
+    "p2i_shock_map_bwd": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
+    "p2i_shock_loss_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P],
+    "p2i_shock_loss_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P],
     "p2i_adam": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _P],
     "p2i_adam_dev": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _P, _P],
     "p2i_metrics_pointwise": [_P, _P, _L, C.POINTER(C.c_float), _I, _I, _P, _P, _P, _P],

@@ -1016,6 +1016,238 @@ def gan_loss_g(logits, weight, loss_type="hinge", real_label=1.0):
     return loss, da
 
 
+# --------------------------------------------------------------------------- the reference's other objectives (csrc/loss_ext.hip)
+def _chk_f32(*ts):
+    _chk(*ts)
+    for t in ts:
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"the loss kernels are fp32 only (got {t.dtype})")
+
+
+def _same(a, b, what):
+    if a.shape != b.shape:
+        raise RuntimeError(f"{what}: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+
+
+def loss_transform_fwd(x):
+    _chk_f32(x)
+    y = torch.empty_like(x)
+    if x.numel():
+        _hip.check(_hip.load().p2i_loss_transform_fwd(_ptr(x), _ptr(y), x.numel(), _stream()), "p2i_loss_transform_fwd")
+    return y
+
+
+def loss_transform_bwd(x, dy):
+    _chk_f32(x, dy)
+    _same(x, dy, "loss_transform_bwd")
+    dx = torch.empty_like(x)
+    if x.numel():
+        _hip.check(_hip.load().p2i_loss_transform_bwd(_ptr(x), _ptr(dy), _ptr(dx), x.numel(), _stream()), "p2i_loss_transform_bwd")
+    return dx
+
+
+def _btinner(shape, what):
+    if len(shape) < 2 or shape[1] < 2:
+        raise RuntimeError(f"{what}: needs [B, T >= 2, ...], got {tuple(shape)}")
+    inner = 1
+    for s in shape[2:]:
+        inner *= s
+    return shape[0], shape[1], inner
+
+
+def fdiff_fwd(x):
+    """x[:, 1:] - x[:, :-1]."""
+    _chk_f32(x)
+    B, T, inner = _btinner(x.shape, "fdiff_fwd")
+    out = torch.empty((B, T - 1) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
+    if out.numel():
+        _hip.check(_hip.load().p2i_fdiff_fwd(_ptr(x), _ptr(out), B, T, inner, _stream()), "p2i_fdiff_fwd")
+    return out
+
+
+def fdiff_bwd(dy, T):
+    _chk_f32(dy)
+    if dy.dim() < 2 or dy.shape[1] != T - 1:
+        raise RuntimeError(f"fdiff_bwd: gradient {tuple(dy.shape)} is not that of {T} frames")
+    dx = torch.empty((dy.shape[0], T) + tuple(dy.shape[2:]), device=dy.device, dtype=torch.float32)
+    if dx.numel():
+        _hip.check(_hip.load().p2i_fdiff_bwd(_ptr(dy), _ptr(dx), dy.shape[0], T, dx[0, 0].numel(), _stream()), "p2i_fdiff_bwd")
+    return dx
+
+
+def wl1_fwd(pred, target):
+    """mean(w(target) * |pred - target|) as a 0-dim device tensor."""
+    _chk_f32(pred, target)
+    _same(pred, target, "wl1_fwd")
+    det_ready(pred.device)
+    out = torch.empty((), device=pred.device, dtype=torch.float32)
+    _hip.check(_hip.load().p2i_wl1_fwd(_ptr(pred), _ptr(target), _ptr(out), pred.numel(), _stream()), "p2i_wl1_fwd")
+    return out
+
+
+def wl1_bwd(pred, target, gout):
+    _chk_f32(pred, target, gout)
+    dpred = torch.empty_like(pred)
+    _hip.check(_hip.load().p2i_wl1_bwd(_ptr(pred), _ptr(target), _ptr(gout), _ptr(dpred), pred.numel(), _stream()), "p2i_wl1_bwd")
+    return dpred
+
+
+def _rows(shape, what):
+    if len(shape) < 2:
+        raise RuntimeError(f"{what}: needs at least 2 dims, got {tuple(shape)}")
+    L = 1
+    for s in shape[2:]:
+        L *= s
+    if shape[0] * shape[1] == 0 or L == 0:
+        raise RuntimeError(f"{what}: empty tensor {tuple(shape)}")
+    return shape[0] * shape[1], L
+
+
+def softmax_t_fwd(x, temperature):
+    _chk_f32(x)
+    rows, L = _rows(x.shape, "softmax_t_fwd")
+    y = torch.empty_like(x)
+    _hip.check(_hip.load().p2i_softmax_t_fwd(_ptr(x), _ptr(y), rows, L, float(temperature), _stream()), "p2i_softmax_t_fwd")
+    return y
+
+
+def softmax_t_bwd(y, dy, temperature):
+    _chk_f32(y, dy)
+    _same(y, dy, "softmax_t_bwd")
+    rows, L = _rows(y.shape, "softmax_t_bwd")
+    dx = torch.empty_like(y)
+    _hip.check(_hip.load().p2i_softmax_t_bwd(_ptr(y), _ptr(dy), _ptr(dx), rows, L, float(temperature), _stream()), "p2i_softmax_t_bwd")
+    return dx
+
+
+def kl_fwd(p, q):
+    _chk_f32(p, q)
+    _same(p, q, "kl_fwd")
+    _rows(p.shape, "kl_fwd")
+    det_ready(p.device)
+    out = torch.empty((), device=p.device, dtype=torch.float32)
+    _hip.check(_hip.load().p2i_kl_fwd(_ptr(p), _ptr(q), _ptr(out), p.numel(), p.shape[0], _stream()), "p2i_kl_fwd")
+    return out
+
+
+def kl_bwd(p, q, gout):
+    _chk_f32(p, q, gout)
+    dp = torch.empty_like(p)
+    _hip.check(_hip.load().p2i_kl_bwd(_ptr(p), _ptr(q), _ptr(gout), _ptr(dp), p.numel(), p.shape[0], _stream()), "p2i_kl_bwd")
+    return dp
+
+
+def _planes(x, what, dims=(3, 4)):
+    if x.dim() not in dims or x.numel() == 0:
+        raise RuntimeError(f"{what}: needs a non-empty {' or '.join(str(d) + '-D' for d in dims)} tensor, got {tuple(x.shape)}")
+    H, W = x.shape[-2], x.shape[-1]
+    return x.numel() // (H * W), H, W
+
+
+def spool_out(n):
+    return (n - 1) // 4 + 1
+
+
+def spool_fwd(x, want_idx=True):
+    """MaxPool2d(5, 4, 2) on the last two dims; returns (out, argmax plane indices or None)."""
+    _chk_f32(x)
+    N, H, W = _planes(x, "spool_fwd")
+    oshape = tuple(x.shape[:-2]) + (spool_out(H), spool_out(W))
+    out = torch.empty(oshape, device=x.device, dtype=torch.float32)
+    idx = torch.empty(oshape, device=x.device, dtype=torch.int32) if want_idx else None
+    _hip.check(_hip.load().p2i_spool_fwd(_ptr(x), _ptr(out), _ptr(idx), N, H, W, _stream()), "p2i_spool_fwd")
+    return out, idx
+
+
+def spool_bwd(idx, dout, in_shape, scale=None):
+    _chk(idx)
+    _chk_f32(dout, *([] if scale is None else [scale]))
+    _same(idx, dout, "spool_bwd")
+    dx = torch.empty(tuple(in_shape), device=dout.device, dtype=torch.float32)
+    N, H, W = _planes(dx, "spool_bwd")
+    if tuple(dout.shape) != tuple(in_shape[:-2]) + (spool_out(H), spool_out(W)):
+        raise RuntimeError(f"spool_bwd: gradient {tuple(dout.shape)} is not the pool of {tuple(in_shape)}")
+    _hip.check(_hip.load().p2i_spool_bwd(_ptr(idx), _ptr(dout), _ptr(scale), _ptr(dx), N, H, W, _stream()), "p2i_spool_bwd")
+    return dx
+
+
+def tdm_fwd(pred_diff, true_diff, true, beta, eps, save=True):
+    """Temporal-difference matching loss; returns (0-dim loss, coef, idx) -- the backward pass is spool_bwd(idx, coef, ., gout)."""
+    _chk_f32(pred_diff, true_diff, true)
+    _same(pred_diff, true_diff, "tdm_fwd")
+    if pred_diff.dim() != 4 or pred_diff.numel() == 0:
+        raise RuntimeError(f"tdm_fwd: needs non-empty [B, T-1, H, W] differences, got {tuple(pred_diff.shape)}")
+    B, Tm1, H, W = pred_diff.shape
+    if tuple(true.shape) != (B, Tm1 + 1, H, W):
+        raise RuntimeError(f"tdm_fwd: true {tuple(true.shape)} is not [B, T, H, W] for differences {tuple(pred_diff.shape)}")
+    det_ready(pred_diff.device)
+    out = torch.empty((), device=pred_diff.device, dtype=torch.float32)
+    oshape = (B, Tm1, spool_out(H), spool_out(W))
+    coef = torch.empty(oshape, device=out.device, dtype=torch.float32) if save else None
+    idx = torch.empty(oshape, device=out.device, dtype=torch.int32) if save else None
+    _hip.check(_hip.load().p2i_tdm_fwd(_ptr(pred_diff), _ptr(true_diff), _ptr(true), float(beta), float(eps), _ptr(out), _ptr(coef),
+                                       _ptr(idx), B, Tm1, H, W, _stream()), "p2i_tdm_fwd")
+    return out, coef, idx
+
+
+def _shock_dims(x, pool, border, what):
+    if x.dim() != 4 or x.numel() == 0:
+        raise RuntimeError(f"{what}: needs a non-empty [B, T, H, W] tensor, got {tuple(x.shape)}")
+    B, T, H, W = x.shape
+    if pool < 1 or border < 0:
+        raise ValueError(f"{what}: pool >= 1 and border_ignore >= 0")
+    Hp, Wp = (H // pool, W // pool) if pool > 1 else (H, W)
+    if Hp < 2 or Wp < 2:
+        raise RuntimeError(f"{what}: the reflect padding of 1 needs a (pooled) height and width of at least 2, got {Hp} x {Wp}")
+    if Hp - 2 * border < 1 or Wp - 2 * border < 1:
+        raise ValueError(f"{what}: border_ignore={border} leaves nothing of a {Hp} x {Wp} map")
+    if B * T > 65535:
+        raise RuntimeError(f"{what}: at most 65535 planes")
+    return B, T, H, W, Hp, Wp
+
+
+def shock_map_fwd(x, beta, eps):
+    _chk_f32(x)
+    B, T, H, W, _, _ = _shock_dims(x, 1, 0, "shock_map")
+    out = torch.empty_like(x)
+    _hip.check(_hip.load().p2i_shock_map_fwd(_ptr(x), _ptr(out), B * T, H, W, float(beta), float(eps), _stream()), "p2i_shock_map_fwd")
+    return out
+
+
+def shock_map_bwd(x, dout, beta, eps):
+    _chk_f32(x, dout)
+    _same(x, dout, "shock_map_bwd")
+    B, T, H, W, _, _ = _shock_dims(x, 1, 0, "shock_map")
+    dx = torch.empty_like(x)
+    scratch = torch.empty(3 * x.numel(), device=x.device, dtype=torch.float32)
+    _hip.check(_hip.load().p2i_shock_map_bwd(_ptr(x), _ptr(dout), _ptr(dx), _ptr(scratch), B * T, H, W, float(beta), float(eps),
+                                             _stream()), "p2i_shock_map_bwd")
+    return dx
+
+
+def shock_loss_fwd(pred, true, beta, pool, border, eps):
+    """relu(|shock(P true)| - |shock(P pred)|) cropped by `border`: [B, T, Hp - 2 border, Wp - 2 border]."""
+    _chk_f32(pred, true)
+    _same(pred, true, "shock_loss_fwd")
+    B, T, H, W, Hp, Wp = _shock_dims(pred, pool, border, "shock_map_loss")
+    out = torch.empty((B, T, Hp - 2 * border, Wp - 2 * border), device=pred.device, dtype=torch.float32)
+    _hip.check(_hip.load().p2i_shock_loss_fwd(_ptr(pred), _ptr(true), _ptr(out), B * T, H, W, int(pool), int(border), float(beta),
+                                              float(eps), _stream()), "p2i_shock_loss_fwd")
+    return out
+
+
+def shock_loss_bwd(pred, true, dout, beta, pool, border, eps):
+    _chk_f32(pred, true, dout)
+    B, T, H, W, Hp, Wp = _shock_dims(pred, pool, border, "shock_map_loss")
+    if tuple(dout.shape) != (B, T, Hp - 2 * border, Wp - 2 * border):
+        raise RuntimeError(f"shock_loss_bwd: gradient {tuple(dout.shape)} does not match the loss tensor")
+    dpred = torch.empty_like(pred)
+    scratch = torch.empty(3 * B * T * Hp * Wp, device=pred.device, dtype=torch.float32)
+    _hip.check(_hip.load().p2i_shock_loss_bwd(_ptr(pred), _ptr(true), _ptr(dout), _ptr(dpred), _ptr(scratch), B * T, H, W, int(pool),
+                                              int(border), float(beta), float(eps), _stream()), "p2i_shock_loss_bwd")
+    return dpred
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step):
     lib = _hip.load()
     n = p.numel()
