@@ -536,6 +536,44 @@ int p2i_exp2_index(const void* x, int dtype, int T, int H, int W, int top, int l
 int p2i_exp2_compose(const uint8_t* panels, int P, int n, int S, int zoom, unsigned gauge_bits, const int* points, int K,
                      const uint8_t* chrome, int Hc, int pitch, int oy, int ox, int step, int bg, int edge, uint8_t* out, void* stream);
 
+/* ---- classical baselines: ordinary kriging (dual form, global neighbourhood) and all-gauge IDW per (b, t) frame (DESIGN.md
+ * section 14; no counterpart in the reference).  F = B T frames of H x W (both <= 16384, F <= 65535).  The gauges of a frame are its
+ * pixels with mask != 0 in raster order; cap (a multiple of 32, <= 4096) is the row length of every per-gauge array.  Covariance
+ * C(h) = psill (1 - g(h / a)), model 0: g(r) = 1 - exp(-r), model 1: g(r) = 1.5 r - 0.5 r^3 (r < 1), 1 beyond; params [B][4] fp32 =
+ * (nugget, psill, range a, unused) per sample.  A "system" s of a call is the gauge set of frame f0 + s R, with R = 1 (one system
+ * per frame) or R = T and f0 a multiple of T (one system per sample whose frames share their mask, R + 1 right-hand sides); systems
+ * are padded to np (a multiple of 32, <= cap) with identity rows and zero right-hand sides.  All sums run in a fixed order.
+ * p2i_krig_compact: pix [F][cap] (int32 (y << 16) | x), z [F][cap] = masked there (both zero past the count), info [2 F]: info[f] =
+ *   the frame's gauge count (it may exceed cap: only the first cap gauges are stored, the caller refuses), info[F + f] = 1 if the
+ *   frame's mask pattern differs from that of its sample's first frame.
+ * p2i_krig_bins: fp64 partial variogram bins part [F][chunks][n_lags][3] = (pairs, sum (z_i - z_j)^2 / 2, sum h) over the pairs
+ *   i < j of a frame with h < n_lags lag_width, bin min(floor(h / lag_width), n_lags - 1); n_lags <= 32.
+ * p2i_krig_fit: per sample (nparts = T chunks partials each, added in order): bins [B][n_lags][3] (the sums), then for the 25 range
+ *   candidates a_c = lag_width 2^((c - 6) / 3) the count-weighted least squares (nugget, psill) of gamma(h) = nugget + psill g(h / a)
+ *   over the non-empty bins' means (nugget < 0: nugget = 0 and psill alone; psill not > 0: invalid); fit [B][4] fp64 = (nugget, psill,
+ *   range, weighted SSE) of the smallest SSE (lowest c on a tie), cand [B] its index or -1 (degenerate sample: no valid candidate),
+ *   params [B][4] the fp32 copy for the calls below.
+ * p2i_krig_factor: L [nsys][np][np] fp32 (lower triangle) = the Cholesky factor of K = [C(|x_i - x_j|)] + nugget I; status[s] is set
+ *   to 1 where a pivot is not > 0 (the caller zeroes it beforehand).
+ * p2i_krig_solve: K u = 1 and K v = z_f for the R frames of each system (sol [nsys][R + 1][np] fp64 scratch), then mean[f] = 1^T v /
+ *   1^T u and alpha [F][cap] = v - mean u (zero past the count).  A frame without gauges gets (0, 0); a frame of a degenerate sample
+ *   (cand[b] < 0; cand may be NULL) or of a system with status != 0 gets its gauge mean and alpha = 0.
+ * p2i_krig_predict: out [F][H W] = mean[f] + sum_i alpha[f][i] (C(|p - x_i|) + nugget [p = x_i]) for the frames f0 .. f0 + nsets R.
+ * p2i_idw_all: out [F][H W] = sum_i w_i z_i / sum_i w_i, w_i = |p - x_i|^-power; z_i on a gauge pixel; 0 for a frame without gauges. */
+int p2i_krig_compact(const float* masked, const float* mask, int B, int T, int H, int W, int cap, int* pix, float* z, int* info,
+                     void* stream);
+int p2i_krig_bins(const int* pix, const float* z, const int* counts, int F, int cap, int chunks, int n_lags, double lag_width,
+                  double* part, void* stream);
+int p2i_krig_fit(const double* part, int B, int nparts, int n_lags, double lag_width, int model, double* bins, double* fit, int* cand,
+                 float* params, void* stream);
+int p2i_krig_factor(const int* pix, const int* counts, const float* params, int model, int f0, int R, int T, int nsys, int np, int cap,
+                    float* L, int* status, void* stream);
+int p2i_krig_solve(const float* L, const float* z, const int* counts, const int* status, const int* cand, int f0, int R, int T, int nsys,
+                   int np, int cap, double* sol, float* alpha, float* mean, void* stream);
+int p2i_krig_predict(const int* pix, const float* alpha, const float* mean, const int* counts, const float* params, int model, int f0,
+                     int R, int T, int nsets, int H, int W, int cap, float* out, void* stream);
+int p2i_idw_all(const int* pix, const float* z, const int* counts, int F, int H, int W, int cap, float power, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

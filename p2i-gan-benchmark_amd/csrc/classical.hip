@@ -1,0 +1,610 @@
+// Classical (parameter-free) baselines: ordinary kriging in its dual form and all-gauge inverse-distance weighting, per (b, t) frame
+// (DESIGN.md section 14).  Stages: point compaction -> [empirical variogram bins -> fit] -> covariance build + Cholesky factor ->
+// triangular solves + dual coefficients -> pairwise-sum predictor; IDW shares the compaction and the predictor's shape.
+//
+// Gauges of a frame are its pixels with mask != 0 in raster order, packed as (y << 16) | x.  Systems are padded to a multiple of
+// TS = 32 with identity rows / columns and zero right-hand sides, so a padded unknown is exactly 0 and never touches a result.
+// Number formats: the covariance matrix and its factor are fp32 (fmaf); every long sum that feeds a result (substitutions, 1^T u,
+// 1^T v, the predictor's sum over gauges, IDW's numerator and denominator) is accumulated in fp64 from fp32 terms; the variogram
+// (bins and fit) is fp64 throughout.  Every sum has a fixed order (no atomics): results are identical from run to run.
+#include "common.h"
+
+namespace p2i {
+namespace {
+
+constexpr int TS = 32;            // tile of the factorisation; systems are padded to a multiple of it
+constexpr int MAX_LAGS = 32;
+constexpr int N_CAND = 25;        // range candidates a_c = w 2^((c - 6) / 3)
+constexpr int BIN_THREADS = 64;
+constexpr int PCHUNK = 128;       // gauges staged in LDS per predictor pass
+constexpr int RC = 8;             // right-hand sides fed from one covariance evaluation
+
+__device__ __forceinline__ double block_sum_d(double v, double* red) {   // red: 256 doubles of LDS; fixed tree, 256 threads
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// C(h) = psill (1 - g(h / a)): exponential g(r) = 1 - exp(-r); spherical g(r) = 1.5 r - 0.5 r^3 below 1, 1 beyond
+__device__ __forceinline__ float cov_f(float h, float psill, float a, int model) {
+  const float r = h / a;
+  if (model == 0) return psill * expf(-r);
+  return r < 1.f ? psill * (1.f - (1.5f * r - 0.5f * r * r * r)) : 0.f;
+}
+
+// ---- compaction: one workgroup per frame.  pix / z [F][cap] (entries past the count are zero), info[f] = count (may exceed cap:
+// the host refuses), info[F + f] = 1 if the frame's mask pattern differs from that of frame 0 of its sample
+__global__ __launch_bounds__(256) void krig_compact_kernel(const float* __restrict__ masked, const float* __restrict__ mask, int F, int T,
+                                                           int HW, int W, int cap, int* __restrict__ pix, float* __restrict__ z,
+                                                           int* __restrict__ info) {
+  __shared__ int wave_cnt[4];
+  __shared__ int wave_diff[4];
+  const int f = blockIdx.x;
+  const float* m = mask + (size_t)f * HW;
+  const float* m0 = mask + (size_t)(f / T) * T * HW;
+  const float* xv = masked + (size_t)f * HW;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int found = 0;
+  bool diff = false;
+  for (int base = 0; base < HW; base += 256) {
+    const int p = base + threadIdx.x;
+    const bool hit = p < HW && m[p] != 0.f;
+    if (p < HW) diff |= (m0[p] != 0.f) != hit;
+    const unsigned long long bal = __ballot(hit);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    int off = found;
+    for (int w = 0; w < wave; ++w) off += wave_cnt[w];
+    const int slot = off + before;
+    if (hit && slot < cap) {
+      pix[(size_t)f * cap + slot] = ((p / W) << 16) | (p % W);
+      z[(size_t)f * cap + slot] = xv[p];
+    }
+    found += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    __syncthreads();
+  }
+  for (int i = min(found, cap) + threadIdx.x; i < cap; i += 256) {
+    pix[(size_t)f * cap + i] = 0;
+    z[(size_t)f * cap + i] = 0.f;
+  }
+  const int any = __any(diff) ? 1 : 0;
+  if (lane == 0) wave_diff[wave] = any;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    info[f] = found;
+    info[F + f] = wave_diff[0] | wave_diff[1] | wave_diff[2] | wave_diff[3];
+  }
+}
+
+// ---- empirical variogram.  Workgroup (chunk, frame) takes the rows i = chunk (mod chunks) of the frame's pairs i < j; every thread
+// keeps its own bins in LDS ([bin][thread]: no conflicts, no dynamic register indexing) and the threads are added in thread order.
+// part [F][chunks][n_lags][3] = (pairs, sum of (z_i - z_j)^2 / 2, sum of h)
+__global__ __launch_bounds__(BIN_THREADS) void krig_bins_kernel(const int* __restrict__ pix, const float* __restrict__ z,
+                                                                const int* __restrict__ counts, int cap, int n_lags, double lagw,
+                                                                double* __restrict__ part) {
+  __shared__ double sg[MAX_LAGS][BIN_THREADS];
+  __shared__ double sh[MAX_LAGS][BIN_THREADS];
+  __shared__ unsigned sc[MAX_LAGS][BIN_THREADS];
+  const int f = blockIdx.y, ch = blockIdx.x, nch = gridDim.x, tid = threadIdx.x;
+  for (int k = 0; k < n_lags; ++k) {
+    sg[k][tid] = 0.0;
+    sh[k][tid] = 0.0;
+    sc[k][tid] = 0u;
+  }
+  const int n = min(counts[f], cap);
+  const int* px = pix + (size_t)f * cap;
+  const float* zf = z + (size_t)f * cap;
+  const double hmax = (double)n_lags * lagw;
+  for (int i = ch; i < n; i += nch) {
+    const int pi = px[i];
+    const double zi = (double)zf[i];
+    for (int j = i + 1 + tid; j < n; j += BIN_THREADS) {
+      const int pj = px[j];
+      const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
+      const double h = sqrt((double)(dy * dy + dx * dx));
+      if (h < hmax) {
+        const int k = min((int)floor(h / lagw), n_lags - 1);
+        const double d = zi - (double)zf[j];
+        sg[k][tid] += 0.5 * (d * d);
+        sh[k][tid] += h;
+        sc[k][tid] += 1u;
+      }
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < n_lags; k += BIN_THREADS) {
+    double g = 0.0, h = 0.0, c = 0.0;
+    for (int t = 0; t < BIN_THREADS; ++t) {
+      g += sg[k][t];
+      h += sh[k][t];
+      c += (double)sc[k][t];
+    }
+    double* o = part + (((size_t)f * nch + ch) * n_lags + k) * 3;
+    o[0] = c;
+    o[1] = g;
+    o[2] = h;
+  }
+}
+
+// ---- fit: one workgroup per sample.  Adds the sample's partial bins in order, then thread c < 25 fits (nugget, psill) for the range
+// candidate a_c by count-weighted least squares; thread 0 keeps the smallest SSE (lowest c on a tie).
+// bins [B][n_lags][3] (raw sums), fit [B][4] = (nugget, psill, range, sse), cand [B] (-1: degenerate), params [B][4] fp32 for the
+// kriging kernels (a harmless (0, 1, w) when degenerate)
+__global__ __launch_bounds__(64) void krig_fit_kernel(const double* __restrict__ part, int nparts, int n_lags, double lagw, int model,
+                                                      double* __restrict__ bins, double* __restrict__ fit, int* __restrict__ cand,
+                                                      float* __restrict__ params) {
+  __shared__ double sn[MAX_LAGS], sgam[MAX_LAGS], shb[MAX_LAGS];
+  __shared__ double c_sse[N_CAND], c_nug[N_CAND], c_ps[N_CAND];
+  __shared__ int c_ok[N_CAND];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  for (int k = tid; k < n_lags; k += 64) {
+    double c = 0.0, g = 0.0, h = 0.0;
+    for (int p = 0; p < nparts; ++p) {
+      const double* q = part + (((size_t)b * nparts + p) * n_lags + k) * 3;
+      c += q[0];
+      g += q[1];
+      h += q[2];
+    }
+    double* o = bins + ((size_t)b * n_lags + k) * 3;
+    o[0] = c;
+    o[1] = g;
+    o[2] = h;
+    sn[k] = c;
+    sgam[k] = c > 0.0 ? g / c : 0.0;
+    shb[k] = c > 0.0 ? h / c : 0.0;
+  }
+  __syncthreads();
+  if (tid < N_CAND) {
+    const double a = lagw * exp2((double)(tid - 6) / 3.0);
+    double S0 = 0.0, S1 = 0.0, S2 = 0.0, T0 = 0.0, T1 = 0.0;
+    for (int k = 0; k < n_lags; ++k) {
+      if (!(sn[k] > 0.0)) continue;
+      const double r = shb[k] / a;
+      const double g = model == 0 ? 1.0 - exp(-r) : (r < 1.0 ? 1.5 * r - 0.5 * r * r * r : 1.0);
+      S0 += sn[k];
+      S1 += sn[k] * g;
+      S2 += sn[k] * g * g;
+      T0 += sn[k] * sgam[k];
+      T1 += sn[k] * g * sgam[k];
+    }
+    const double det = S0 * S2 - S1 * S1;
+    double nug = -1.0, ps = 0.0;
+    if (det > 1e-12 * S0 * S2) {
+      ps = (S0 * T1 - S1 * T0) / det;
+      nug = (T0 - ps * S1) / S0;
+    }
+    if (nug < 0.0) {
+      nug = 0.0;
+      ps = S2 > 0.0 ? T1 / S2 : 0.0;
+    }
+    double sse = 0.0;
+    for (int k = 0; k < n_lags; ++k) {
+      if (!(sn[k] > 0.0)) continue;
+      const double r = shb[k] / a;
+      const double g = model == 0 ? 1.0 - exp(-r) : (r < 1.0 ? 1.5 * r - 0.5 * r * r * r : 1.0);
+      const double e = sgam[k] - nug - ps * g;
+      sse += sn[k] * e * e;
+    }
+    c_ok[tid] = (S0 > 0.0 && ps > 0.0) ? 1 : 0;
+    c_sse[tid] = sse;
+    c_nug[tid] = nug;
+    c_ps[tid] = ps;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int best = -1;
+    for (int c = 0; c < N_CAND; ++c)
+      if (c_ok[c] && (best < 0 || c_sse[c] < c_sse[best])) best = c;
+    double* o = fit + (size_t)b * 4;
+    float* pf = params + (size_t)b * 4;
+    cand[b] = best;
+    if (best >= 0) {
+      const double a = lagw * exp2((double)(best - 6) / 3.0);
+      o[0] = c_nug[best];
+      o[1] = c_ps[best];
+      o[2] = a;
+      o[3] = c_sse[best];
+      pf[0] = (float)c_nug[best];
+      pf[1] = (float)c_ps[best];
+      pf[2] = (float)a;
+      pf[3] = 0.f;
+    } else {
+      o[0] = o[1] = o[2] = o[3] = 0.0;
+      pf[0] = 0.f;
+      pf[1] = 1.f;
+      pf[2] = (float)lagw;
+      pf[3] = 0.f;
+    }
+  }
+}
+
+// ---- covariance matrix of system s (gauges of frame f0 + s R), lower tiles only; identity on the padding
+__global__ __launch_bounds__(256) void krig_build_kernel(const int* __restrict__ pix, const int* __restrict__ counts,
+                                                         const float* __restrict__ params, int model, int f0, int R, int T, int cap, int np,
+                                                         float* __restrict__ A) {
+  if (blockIdx.x > blockIdx.y) return;
+  const int s = blockIdx.z, f = f0 + s * R, b = f / T;
+  const int n = min(counts[f], np);
+  const float nug = params[b * 4], psill = params[b * 4 + 1], a = params[b * 4 + 2];
+  const int* px = pix + (size_t)f * cap;
+  float* As = A + (size_t)s * np * np;
+  const int j = blockIdx.x * TS + (threadIdx.x & 31);
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    const int i = blockIdx.y * TS + (threadIdx.x >> 5) + 8 * rr;
+    float v = i == j ? 1.f : 0.f;
+    if (i < n && j < n) {
+      const int pi = px[i], pj = px[j];
+      const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
+      v = cov_f(sqrtf((float)(dy * dy + dx * dx)), psill, a, model) + (i == j ? nug : 0.f);
+    }
+    As[(size_t)i * np + j] = v;
+  }
+}
+
+// ---- one panel of the right-looking Cholesky: factor the diagonal tile at k0 in LDS, then solve the rows below it against it (one
+// row per thread, the row's 32 entries in registers).  A pivot that is not > 0 marks the system and is replaced by 1: the system's
+// frames fall back to their gauge mean, and nothing non-finite is divided by.
+__global__ __launch_bounds__(256) void krig_panel_kernel(float* __restrict__ A, int np, int k0, int* __restrict__ status) {
+  __shared__ float D[TS][TS + 1];
+  __shared__ int bad;
+  float* As = A + (size_t)blockIdx.x * np * np;
+  const int tid = threadIdx.x, c = tid & 31, r0 = tid >> 5;
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) D[r0 + 8 * rr][c] = As[(size_t)(k0 + r0 + 8 * rr) * np + k0 + c];
+  if (tid == 0) bad = 0;
+  __syncthreads();
+  for (int j = 0; j < TS; ++j) {
+    const float p = D[j][j];
+    const bool ok = p > 0.f;
+    const float d = ok ? sqrtf(p) : 1.f;
+    __syncthreads();                                   // every thread has read the pivot
+    if (tid < TS) {
+      if (tid == j) {
+        D[j][j] = d;
+        if (!ok) bad = 1;
+      } else if (tid > j) {
+        D[tid][j] = D[tid][j] / d;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int i = r0 + 8 * rr;
+      if (c > j && i >= c) D[i][c] = fmaf(-D[i][j], D[c][j], D[i][c]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    const int i = r0 + 8 * rr;
+    if (c <= i) As[(size_t)(k0 + i) * np + k0 + c] = D[i][c];
+  }
+  for (int i = k0 + TS + tid; i < np; i += 256) {
+    float4* row = reinterpret_cast<float4*>(As + (size_t)i * np + k0);
+    float x[TS];
+#pragma unroll
+    for (int q = 0; q < TS / 4; ++q) {
+      const float4 v = row[q];
+      x[4 * q] = v.x;
+      x[4 * q + 1] = v.y;
+      x[4 * q + 2] = v.z;
+      x[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int cc = 0; cc < TS; ++cc) {
+      float acc = x[cc];
+#pragma unroll
+      for (int m = 0; m < cc; ++m) acc = fmaf(-x[m], D[cc][m], acc);
+      x[cc] = acc / D[cc][cc];
+    }
+#pragma unroll
+    for (int q = 0; q < TS / 4; ++q) row[q] = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+  }
+  if (tid == 0 && bad) status[blockIdx.x] = 1;
+}
+
+// ---- trailing update after the panel at k0: tile (I, J), J <= I, of the rows / columns past the panel loses L[I][k] L[J][k]^T
+__global__ __launch_bounds__(256) void krig_update_kernel(float* __restrict__ A, int np, int k0) {
+  if (blockIdx.x > blockIdx.y) return;
+  __shared__ float Li[TS][TS + 1], Lj[TS][TS + 1];
+  float* As = A + (size_t)blockIdx.z * np * np;
+  const int i0 = k0 + TS + blockIdx.y * TS, j0 = k0 + TS + blockIdx.x * TS;
+  const int tid = threadIdx.x, c = tid & 31, r0 = tid >> 5;
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    const int r = r0 + 8 * rr;
+    Li[r][c] = As[(size_t)(i0 + r) * np + k0 + c];
+    Lj[r][c] = As[(size_t)(j0 + r) * np + k0 + c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    const int r = r0 + 8 * rr;
+    float* o = As + (size_t)(i0 + r) * np + j0 + c;
+    float acc = *o;
+#pragma unroll
+    for (int m = 0; m < TS; ++m) acc = fmaf(-Li[r][m], Lj[c][m], acc);
+    *o = acc;
+  }
+}
+
+// ---- L L^T x = rhs for right-hand side q of system s: q = 0 is the ones vector, q >= 1 the values of frame f0 + s R + q - 1.
+// The vector lives in LDS as fp64; per tile, wave 0 substitutes through the diagonal tile (lane = row, the solved entry handed on by
+// a shuffle) and all threads then take the tile's contribution off the remaining rows.  sol [nsys][R + 1][np] fp64
+__global__ __launch_bounds__(256) void krig_solve_kernel(const float* __restrict__ A, const float* __restrict__ z,
+                                                         const int* __restrict__ counts, int f0, int R, int cap, int np,
+                                                         double* __restrict__ sol) {
+  extern __shared__ double y[];
+  __shared__ float D[TS][TS + 1];
+  const int s = blockIdx.y, q = blockIdx.x, f = f0 + s * R;
+  const int n = min(counts[f], np);
+  const float* As = A + (size_t)s * np * np;
+  const int tid = threadIdx.x, c = tid & 31, r0 = tid >> 5;
+  for (int i = tid; i < np; i += 256) y[i] = i < n ? (q == 0 ? 1.0 : (double)z[(size_t)(f + q - 1) * cap + i]) : 0.0;
+  __syncthreads();
+  for (int k0 = 0; k0 < np; k0 += TS) {                     // forward: L w = rhs
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) D[r0 + 8 * rr][c] = As[(size_t)(k0 + r0 + 8 * rr) * np + k0 + c];
+    __syncthreads();
+    if (tid < 64) {
+      double val = y[k0 + c];
+      for (int cc = 0; cc < TS; ++cc) {
+        if (c == cc) val = val / (double)D[cc][cc];
+        const double yc = __shfl(val, cc, 64);
+        if (c > cc) val -= (double)D[c][cc] * yc;
+      }
+      if (tid < TS) y[k0 + c] = val;
+    }
+    __syncthreads();
+    for (int i = k0 + TS + tid; i < np; i += 256) {
+      const float4* row = reinterpret_cast<const float4*>(As + (size_t)i * np + k0);
+      double acc = 0.0;
+#pragma unroll
+      for (int m = 0; m < TS / 4; ++m) {
+        const float4 v = row[m];
+        acc += (double)v.x * y[k0 + 4 * m];
+        acc += (double)v.y * y[k0 + 4 * m + 1];
+        acc += (double)v.z * y[k0 + 4 * m + 2];
+        acc += (double)v.w * y[k0 + 4 * m + 3];
+      }
+      y[i] -= acc;
+    }
+    __syncthreads();
+  }
+  for (int k0 = np - TS; k0 >= 0; k0 -= TS) {               // backward: L^T x = w
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) D[r0 + 8 * rr][c] = As[(size_t)(k0 + r0 + 8 * rr) * np + k0 + c];
+    __syncthreads();
+    if (tid < 64) {
+      double val = y[k0 + c];
+      for (int cc = TS - 1; cc >= 0; --cc) {
+        if (c == cc) val = val / (double)D[cc][cc];
+        const double xc = __shfl(val, cc, 64);
+        if (c < cc) val -= (double)D[cc][c] * xc;
+      }
+      if (tid < TS) y[k0 + c] = val;
+    }
+    __syncthreads();
+    for (int i = tid; i < k0; i += 256) {
+      double acc = 0.0;
+#pragma unroll 8
+      for (int m = 0; m < TS; ++m) acc += (double)As[(size_t)(k0 + m) * np + i] * y[k0 + m];
+      y[i] -= acc;
+    }
+    __syncthreads();
+  }
+  double* o = sol + ((size_t)s * (R + 1) + q) * np;
+  for (int i = tid; i < np; i += 256) o[i] = y[i];
+}
+
+// ---- dual coefficients of frame f = f0 + s R + t: m = 1^T v / 1^T u, alpha = v - m u.  A frame without gauges gives (0, 0); a
+// degenerate sample (cand < 0) or a failed factorisation gives the gauge mean and alpha = 0.
+__global__ __launch_bounds__(256) void krig_dual_kernel(const double* __restrict__ sol, const float* __restrict__ z,
+                                                        const int* __restrict__ counts, const int* __restrict__ status,
+                                                        const int* __restrict__ cand, int f0, int R, int T, int cap, int np,
+                                                        float* __restrict__ alpha, float* __restrict__ mean) {
+  __shared__ double red[256];
+  const int s = blockIdx.y, t = blockIdx.x, fs = f0 + s * R, f = fs + t;
+  const int n = min(counts[fs], np);
+  const double* u = sol + (size_t)s * (R + 1) * np;
+  const double* v = u + (size_t)(t + 1) * np;
+  const float* zf = z + (size_t)f * cap;
+  float* af = alpha + (size_t)f * cap;
+  const bool fallback = n == 0 || status[s] != 0 || (cand != nullptr && cand[f / T] < 0);
+  double su = 0.0, sv = 0.0, sz = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    su += u[i];
+    sv += v[i];
+    sz += (double)zf[i];
+  }
+  su = block_sum_d(su, red);
+  sv = block_sum_d(sv, red);
+  sz = block_sum_d(sz, red);
+  const double m = fallback ? (n > 0 ? sz / (double)n : 0.0) : sv / su;
+  for (int i = threadIdx.x; i < cap; i += 256) af[i] = (!fallback && i < n) ? (float)(v[i] - m * u[i]) : 0.f;
+  if (threadIdx.x == 0) mean[f] = (float)m;
+}
+
+// ---- predictor: out[f][p] = mean[f] + sum_i alpha[f][i] c0(p, i) for the frames f of set s (gauges of frame f0 + s R), one pixel per
+// thread.  c0 is evaluated once per (pixel, gauge) and feeds up to RC frames of the set; blockIdx.z walks the set in groups of RC.
+__global__ __launch_bounds__(256) void krig_predict_kernel(const int* __restrict__ pix, const float* __restrict__ alpha,
+                                                           const float* __restrict__ mean, const int* __restrict__ counts,
+                                                           const float* __restrict__ params, int model, int f0, int R, int T, int W, int HW,
+                                                           int cap, float* __restrict__ out) {
+  __shared__ int spix[PCHUNK];
+  __shared__ float sa[RC][PCHUNK];
+  const int s = blockIdx.y, fs = f0 + s * R, fg = fs + blockIdx.z * RC;
+  const int nr = min(RC, R - (int)blockIdx.z * RC);
+  const int n = min(counts[fs], cap);
+  const int b = fs / T;
+  const float nug = params[b * 4], psill = params[b * 4 + 1], a = params[b * 4 + 2];
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int py = p / W, px = p % W;
+  double acc[RC];
+#pragma unroll
+  for (int q = 0; q < RC; ++q) acc[q] = 0.0;
+  for (int i0 = 0; i0 < n; i0 += PCHUNK) {
+    __syncthreads();
+    if (threadIdx.x < PCHUNK) spix[threadIdx.x] = i0 + (int)threadIdx.x < n ? pix[(size_t)fs * cap + i0 + threadIdx.x] : 0;
+    for (int e = threadIdx.x; e < RC * PCHUNK; e += 256) {
+      const int q = e / PCHUNK, i = e % PCHUNK;
+      sa[q][i] = (q < nr && i0 + i < n) ? alpha[(size_t)(fg + q) * cap + i0 + i] : 0.f;
+    }
+    __syncthreads();
+    const int cnt = min(PCHUNK, n - i0);
+    for (int i = 0; i < cnt; ++i) {
+      const int g = spix[i];
+      const int dy = py - (g >> 16), dx = px - (g & 0xffff);
+      const int d2 = dy * dy + dx * dx;
+      const double c0 = (double)(cov_f(sqrtf((float)d2), psill, a, model) + (d2 == 0 ? nug : 0.f));
+#pragma unroll
+      for (int q = 0; q < RC; ++q) acc[q] = fma((double)sa[q][i], c0, acc[q]);
+    }
+  }
+  if (p < HW) {
+#pragma unroll
+    for (int q = 0; q < RC; ++q)
+      if (q < nr) out[(size_t)(fg + q) * HW + p] = (float)((double)mean[fg + q] + acc[q]);
+  }
+}
+
+// ---- all-gauge IDW of frame f: sum_i w_i z_i / sum_i w_i, w_i = h^-power; the gauge's own value on a gauge pixel; 0 without gauges
+__global__ __launch_bounds__(256) void idw_all_kernel(const int* __restrict__ pix, const float* __restrict__ z, const int* __restrict__ counts,
+                                                      int W, int HW, int cap, float power, float* __restrict__ out) {
+  __shared__ int spix[PCHUNK];
+  __shared__ float sz[PCHUNK];
+  const int f = blockIdx.y;
+  const int n = min(counts[f], cap);
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int py = p / W, px = p % W;
+  const float e = -0.5f * power;
+  const bool square = power == 2.f;
+  double num = 0.0, den = 0.0;
+  float hitv = 0.f;
+  bool hit = false;
+  for (int i0 = 0; i0 < n; i0 += PCHUNK) {
+    __syncthreads();
+    if (threadIdx.x < PCHUNK) {
+      const bool in = i0 + (int)threadIdx.x < n;
+      spix[threadIdx.x] = in ? pix[(size_t)f * cap + i0 + threadIdx.x] : 0;
+      sz[threadIdx.x] = in ? z[(size_t)f * cap + i0 + threadIdx.x] : 0.f;
+    }
+    __syncthreads();
+    const int cnt = min(PCHUNK, n - i0);
+    for (int i = 0; i < cnt; ++i) {
+      const int g = spix[i];
+      const int dy = py - (g >> 16), dx = px - (g & 0xffff);
+      const int d2 = dy * dy + dx * dx;
+      if (d2 == 0) {
+        hit = true;
+        hitv = sz[i];
+      } else {
+        const float w = square ? 1.f / (float)d2 : powf((float)d2, e);
+        num = fma((double)w, (double)sz[i], num);
+        den += (double)w;
+      }
+    }
+  }
+  if (p < HW) out[(size_t)f * HW + p] = n == 0 ? 0.f : (hit ? hitv : (float)(num / den));
+}
+
+constexpr int MAX_NP = 4096;       // fp64 vector of the solve in LDS: 32 KiB
+constexpr int MAX_SIDE = 16384;    // squared pixel distances stay in int32
+
+}  // namespace
+}  // namespace p2i
+
+using namespace p2i;
+
+extern "C" int p2i_krig_compact(const float* masked, const float* mask, int B, int T, int H, int W, int cap, int* pix, float* z, int* info,
+                                void* stream) {
+  P2I_REQUIRE(masked && mask && pix && z && info, "null pointer");
+  P2I_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE, "bad frame shape %d x %d x %d x %d", B, T, H, W);
+  P2I_REQUIRE((long long)B * T <= 65535, "at most 65535 frames per call (got %lld)", (long long)B * T);
+  P2I_REQUIRE(cap > 0 && cap % TS == 0 && cap <= MAX_NP, "cap must be a multiple of %d, at most %d (got %d)", TS, MAX_NP, cap);
+  P2I_LAUNCH(krig_compact_kernel, dim3(B * T), dim3(256), 0, (hipStream_t)stream, masked, mask, B * T, T, H * W, W, cap, pix, z, info);
+  return launch_status();
+}
+
+extern "C" int p2i_krig_bins(const int* pix, const float* z, const int* counts, int F, int cap, int chunks, int n_lags, double lag_width,
+                             double* part, void* stream) {
+  P2I_REQUIRE(pix && z && counts && part, "null pointer");
+  P2I_REQUIRE(F > 0 && F <= 65535 && cap > 0 && chunks > 0 && chunks <= 1024, "bad variogram shape");
+  P2I_REQUIRE(n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "n_lags must be 1..%d with a positive lag width", MAX_LAGS);
+  P2I_LAUNCH(krig_bins_kernel, dim3(chunks, F), dim3(BIN_THREADS), 0, (hipStream_t)stream, pix, z, counts, cap, n_lags, lag_width, part);
+  return launch_status();
+}
+
+extern "C" int p2i_krig_fit(const double* part, int B, int nparts, int n_lags, double lag_width, int model, double* bins, double* fit,
+                            int* cand, float* params, void* stream) {
+  P2I_REQUIRE(part && bins && fit && cand && params, "null pointer");
+  P2I_REQUIRE(B > 0 && nparts > 0 && n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "bad fit shape");
+  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
+  P2I_LAUNCH(krig_fit_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, part, nparts, n_lags, lag_width, model, bins, fit, cand, params);
+  return launch_status();
+}
+
+static int krig_sys_check(int f0, int R, int T, int nsys, int np, int cap) {
+  P2I_REQUIRE(R > 0 && T > 0 && f0 >= 0 && nsys > 0 && nsys <= 65535, "bad system range");
+  P2I_REQUIRE(R == 1 || (R == T && f0 % T == 0), "a system spans one frame or one whole sample");
+  P2I_REQUIRE(np > 0 && np % TS == 0 && np <= cap && cap <= MAX_NP, "padded size %d must be a multiple of %d within cap %d", np, TS, cap);
+  return P2I_OK;
+}
+
+extern "C" int p2i_krig_factor(const int* pix, const int* counts, const float* params, int model, int f0, int R, int T, int nsys, int np,
+                               int cap, float* L, int* status, void* stream) {
+  P2I_REQUIRE(pix && counts && params && L && status, "null pointer");
+  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
+  if (int rc = krig_sys_check(f0, R, T, nsys, np, cap)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int nt = np / TS;
+  P2I_LAUNCH(krig_build_kernel, dim3(nt, nt, nsys), dim3(256), 0, s, pix, counts, params, model, f0, R, T, cap, np, L);
+  for (int k = 0; k < nt; ++k) {
+    P2I_LAUNCH(krig_panel_kernel, dim3(nsys), dim3(256), 0, s, L, np, k * TS, status);
+    const int rem = nt - k - 1;
+    if (rem > 0) P2I_LAUNCH(krig_update_kernel, dim3(rem, rem, nsys), dim3(256), 0, s, L, np, k * TS);
+  }
+  return launch_status();
+}
+
+extern "C" int p2i_krig_solve(const float* L, const float* z, const int* counts, const int* status, const int* cand, int f0, int R, int T,
+                              int nsys, int np, int cap, double* sol, float* alpha, float* mean, void* stream) {
+  P2I_REQUIRE(L && z && counts && status && sol && alpha && mean, "null pointer");
+  if (int rc = krig_sys_check(f0, R, T, nsys, np, cap)) return rc;
+  P2I_REQUIRE(R + 1 <= 65535, "too many right-hand sides");
+  hipStream_t s = (hipStream_t)stream;
+  P2I_LAUNCH(krig_solve_kernel, dim3(R + 1, nsys), dim3(256), (size_t)np * sizeof(double), s, L, z, counts, f0, R, cap, np, sol);
+  P2I_LAUNCH(krig_dual_kernel, dim3(R, nsys), dim3(256), 0, s, sol, z, counts, status, cand, f0, R, T, cap, np, alpha, mean);
+  return launch_status();
+}
+
+extern "C" int p2i_krig_predict(const int* pix, const float* alpha, const float* mean, const int* counts, const float* params, int model,
+                                int f0, int R, int T, int nsets, int H, int W, int cap, float* out, void* stream) {
+  P2I_REQUIRE(pix && alpha && mean && counts && params && out, "null pointer");
+  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
+  P2I_REQUIRE(H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE, "bad frame shape");
+  if (int rc = krig_sys_check(f0, R, T, nsets, TS, cap)) return rc;
+  const int HW = H * W;
+  P2I_REQUIRE(ceil_div(R, RC) <= 65535, "too many frames per set");
+  P2I_LAUNCH(krig_predict_kernel, dim3(ceil_div(HW, 256), nsets, ceil_div(R, RC)), dim3(256), 0, (hipStream_t)stream, pix, alpha, mean,
+             counts, params, model, f0, R, T, W, HW, cap, out);
+  return launch_status();
+}
+
+extern "C" int p2i_idw_all(const int* pix, const float* z, const int* counts, int F, int H, int W, int cap, float power, float* out,
+                           void* stream) {
+  P2I_REQUIRE(pix && z && counts && out, "null pointer");
+  P2I_REQUIRE(F > 0 && F <= 65535 && H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE && cap > 0, "bad IDW shape");
+  P2I_REQUIRE(power > 0.f, "IDW power must be positive");
+  const int HW = H * W;
+  P2I_LAUNCH(idw_all_kernel, dim3(ceil_div(HW, 256), F), dim3(256), 0, (hipStream_t)stream, pix, z, counts, W, HW, cap, power, out);
+  return launch_status();
+}

@@ -24,6 +24,7 @@ _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
 _L = C.c_int64
+_F64 = C.c_double
 _D = C.POINTER(ConvDesc)
 
 # name -> argtypes (every entry point returns int); must list EVERY symbol of include/p2i_hip.h
@@ -129,6 +130,13 @@ SIGNATURES = {
     "p2i_exp3_nse": [_P, _P, _I, _P, _I, _P, _P],
     "p2i_exp2_index": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P],
     "p2i_exp2_compose": [_P, _I, _I, _I, _I, C.c_uint, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "p2i_krig_compact": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "p2i_krig_bins": [_P, _P, _P, _I, _I, _I, _I, _F64, _P, _P],
+    "p2i_krig_fit": [_P, _I, _I, _I, _F64, _I, _P, _P, _P, _P, _P],
+    "p2i_krig_factor": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "p2i_krig_solve": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "p2i_krig_predict": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "p2i_idw_all": [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P],
 }
 
 

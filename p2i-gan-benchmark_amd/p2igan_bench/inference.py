@@ -41,3 +41,13 @@ def infer_event(generator, masked: torch.Tensor, masks: torch.Tensor, stride: in
         cnt.index_add_(0, ii[vv], torch.ones_like(ii[vv], dtype=torch.float32))
     comp = acc / cnt.clamp(min=1e-5).view(L, 1, 1, 1) * float(output_scale)
     return comp.clamp(min=0.0)
+
+
+@torch.no_grad()
+def infer_event_chunks(generator, masked: torch.Tensor, masks: torch.Tensor, stride: int = 16, output_scale: float = 255.0) -> torch.Tensor:
+    """The parameter-free baselines' event pass: masked, masks (1, L, 1, H, W) -> (L, 1, H, W) float32.  The event runs in consecutive
+    chunks of `stride` frames without overlap (the last one shorter); each chunk is one sample to the generator, so a fitted variogram
+    pools the chunk's frames.  Scaled and clipped at 0 as infer_event does."""
+    L = masked.shape[1]
+    parts = [generator(masked[:, s:s + stride].contiguous(), masks[:, s:s + stride].contiguous())[0] for s in range(0, L, stride)]
+    return (torch.cat(parts, dim=0) * float(output_scale)).clamp(min=0.0)

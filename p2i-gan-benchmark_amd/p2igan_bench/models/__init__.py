@@ -1,11 +1,14 @@
 """Model registry — the construction API of the reference (models/__init__.py:13-46).
 
-The P2I-GAN family and the STDK (spatio-temporal DeepKriging) baseline are built on the HIP path.  The purely spatial DK
-baseline and the `simple` fallback stub are out of this build's scope and raise a clear error."""
+The P2I-GAN family and the STDK (spatio-temporal DeepKriging) baseline are built on the HIP path, and so are two parameter-free
+classical baselines the reference does not have: ordinary kriging and all-gauge IDW (models/classical.py).
+The purely spatial DK baseline and the `simple` fallback stub are out of this build's scope and raise a clear
+error."""
 from typing import Any, Dict
 
 import torch.nn as nn
 
+from .classical import CLASSICAL, IDWGenerator, KrigingGenerator
 from .p2igan import P2IDiscriminator, P2IGenerator
 from .stdk import STDKGenerator
 
@@ -21,7 +24,9 @@ def build_generator(cfg: Dict[str, Any]) -> nn.Module:
     if name == "stdk":
         data_cfg = cfg.get("data_loader") or cfg.get("data", {}).get("train", {})
         return STDKGenerator(cfg, length=data_cfg.get("sample_length", 16))
-    raise NotImplementedError(f"model '{name}': only 'p2igan' and 'stdk' are implemented on the MI355X path")
+    if name in CLASSICAL:
+        return CLASSICAL[name](cfg)
+    raise NotImplementedError(f"model '{name}': only 'p2igan', 'stdk', 'kriging' and 'idw' are implemented on the MI355X path")
 
 
 def build_discriminator(cfg: Dict[str, Any]) -> nn.Module:
@@ -34,4 +39,5 @@ def build_discriminator(cfg: Dict[str, Any]) -> nn.Module:
     raise NotImplementedError(f"model '{name}': only 'p2igan' is implemented on the MI355X path")
 
 
-__all__ = ["build_generator", "build_discriminator", "P2IGenerator", "P2IDiscriminator", "STDKGenerator"]
+__all__ = ["build_generator", "build_discriminator", "P2IGenerator", "P2IDiscriminator", "STDKGenerator",
+           "KrigingGenerator", "IDWGenerator"]

@@ -1,0 +1,133 @@
+"""Classical, parameter-free baselines on the HIP path: ordinary kriging and all-gauge IDW of every frame's own gauges
+(csrc/classical.hip).  The reference has no such method; they give the comparison table its non-learnt rows.
+
+Both take the generators' (masked_frames, masks) pair, (B, T, 1, H, W) fp32 on the device, and return (B, T, 1, H, W).  The gauges
+of frame (b, t) are its pixels with mask != 0 in raster order, their values masked_frames there, their coordinates pixel indices.
+Neither has parameters (state_dict() is empty) and both are deterministic from run to run."""
+from __future__ import annotations
+
+import logging
+from typing import Any, Dict
+
+import torch
+import torch.nn as nn
+
+from .. import ops
+
+_FACTOR_BYTES = 1 << 30          # the factor workspace of one chunk of systems stays under this
+
+
+def _round_up(v: int, m: int) -> int:
+    return (v + m - 1) // m * m
+
+
+def _frames(masked_frames, masks, who):
+    if masked_frames.dim() != 5 or masked_frames.shape[2] != 1:
+        raise RuntimeError(f"{who} takes (B, T, 1, H, W) frames")
+    if masks.shape != masked_frames.shape:
+        raise RuntimeError(f"{who}: masks shape {tuple(masks.shape)} differs from the frames' {tuple(masked_frames.shape)}")
+    if not (masked_frames.is_cuda and masks.is_cuda):
+        raise RuntimeError(f"{who} runs on the HIP path only (CUDA tensors)")
+    b, t, _, h, w = masked_frames.shape
+    return masked_frames.reshape(b, t, h, w).contiguous().float(), masks.reshape(b, t, h, w).contiguous().float()
+
+
+class _ClassicalBase(nn.Module):
+    def __init__(self, config: Dict[str, Any]):
+        super().__init__()
+        self.config = config
+        mc = config.get("model", {})
+        self.max_points = int(mc.get("max_points", 1024))
+        if not 1 <= self.max_points <= ops.KRIG_MAX_CAP:
+            raise ValueError(f"model.max_points must be in [1, {ops.KRIG_MAX_CAP}] (got {self.max_points})")
+
+    def _compact(self, masked_frames, masks):
+        """(pix, z, info, counts on the host, 'every sample's frames share their mask') -- the call's one host read."""
+        x, m = _frames(masked_frames, masks, type(self).__name__)
+        f = x.shape[0] * x.shape[1]
+        pix, z, info = ops.krig_compact(x, m, _round_up(self.max_points, ops.KRIG_TILE))
+        host = info.cpu()
+        counts, differs = host[:f], host[f:]
+        if int(counts.max()) > self.max_points:
+            raise ValueError(f"{type(self).__name__}: a frame has {int(counts.max())} gauges, more than model.max_points = {self.max_points}")
+        return pix, z, info, counts, not bool(differs.any())
+
+
+class KrigingGenerator(_ClassicalBase):
+    """Ordinary kriging with a global neighbourhood in its dual form, one system per frame (or per sample when its frames share
+    their mask).  model.variogram = {"model": "exponential" | "spherical", "fit": true, "n_lags": 16} fits (nugget, psill, range)
+    per sample on the device; {"model", "fit": false, "nugget", "psill", "range"} takes them as given."""
+
+    def __init__(self, config: Dict[str, Any]):
+        super().__init__(config)
+        mc = config.get("model", {})
+        vg = dict(mc.get("variogram") or {})
+        name = str(vg.get("model", "exponential")).lower()
+        if name not in ops.KRIG_MODELS:
+            raise ValueError(f"model.variogram.model must be one of {sorted(ops.KRIG_MODELS)} (got '{name}')")
+        self.variogram_model = ops.KRIG_MODELS[name]
+        self.fit = bool(vg.get("fit", True))
+        self.n_lags = int(vg.get("n_lags", 16))
+        if self.fit:
+            if not 1 <= self.n_lags <= ops.KRIG_MAX_LAGS:
+                raise ValueError(f"model.variogram.n_lags must be in [1, {ops.KRIG_MAX_LAGS}] (got {self.n_lags})")
+        else:
+            try:
+                self.fixed = (float(vg["nugget"]), float(vg["psill"]), float(vg["range"]))
+            except KeyError as e:
+                raise ValueError(f"model.variogram with fit=false needs nugget, psill and range (missing {e})") from None
+            if not (self.fixed[0] >= 0 and self.fixed[1] > 0 and self.fixed[2] > 0):
+                raise ValueError("model.variogram: nugget >= 0, psill > 0 and range > 0 are required")
+        self.share_sets = bool(mc.get("share_sets", True))   # false: one factorisation per frame even where a sample shares its mask
+        self.last_fit = None         # {"bins", "fit", "cand"} device tensors of the last call (fit=true)
+        self.last_status = None      # per-system int32 of the last call: 1 where the factorisation met a non-positive pivot
+
+    @torch.no_grad()
+    def forward(self, masked_frames, masks):
+        b, t, _, h, w = masked_frames.shape
+        pix, z, info, counts, shared = self._compact(masked_frames, masks)
+        f, dev = b * t, masked_frames.device
+        cand = None
+        if self.fit:
+            lag_width = (min(h, w) / 2.0) / self.n_lags
+            bins, fit, cand, params = ops.krig_variogram(pix, z, info, b, t, self.n_lags, lag_width, self.variogram_model)
+            self.last_fit = {"bins": bins, "fit": fit, "cand": cand}
+        else:
+            params = torch.tensor(self.fixed + (0.0,), dtype=torch.float32).repeat(b, 1).to(dev)
+        r = t if (shared and self.share_sets) else 1
+        nsys = f // r
+        np_ = max(ops.KRIG_TILE, _round_up(int(counts.max()), ops.KRIG_TILE))
+        per = max(1, min(nsys, _FACTOR_BYTES // (np_ * np_ * 4)))
+        work = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
+        status = torch.zeros(nsys, device=dev, dtype=torch.int32)
+        alpha = torch.empty(f, pix.shape[1], device=dev, dtype=torch.float32)
+        mean = torch.empty(f, device=dev, dtype=torch.float32)
+        for s0 in range(0, nsys, per):
+            ns = min(per, nsys - s0)
+            ops.krig_factor(pix, info, params, self.variogram_model, s0 * r, r, t, ns, np_, work, status[s0:s0 + ns])
+            ops.krig_solve(work, z, info, status[s0:s0 + ns], cand, s0 * r, r, t, ns, np_, alpha, mean)
+        out = ops.krig_predict(pix, alpha, mean, info, params, self.variogram_model, r, t, h, w)
+        self.last_status = status
+        failed = int(status.sum()) * r
+        if failed:
+            logging.warning("kriging: %d frame(s) met a non-positive pivot and predict their gauge mean", failed)
+        return out.view(b, t, 1, h, w)
+
+
+class IDWGenerator(_ClassicalBase):
+    """Inverse-distance weighting over all gauges of the frame, weights h^-power (model.power, default 2)."""
+
+    def __init__(self, config: Dict[str, Any]):
+        super().__init__(config)
+        self.power = float(config.get("model", {}).get("power", 2.0))
+        if not self.power > 0:
+            raise ValueError(f"model.power must be positive (got {self.power})")
+
+    @torch.no_grad()
+    def forward(self, masked_frames, masks):
+        b, t, _, h, w = masked_frames.shape
+        pix, z, info, _, _ = self._compact(masked_frames, masks)
+        return ops.idw_all(pix, z, info, h, w, self.power).view(b, t, 1, h, w)
+
+
+CLASSICAL = {"kriging": KrigingGenerator, "idw": IDWGenerator}

@@ -1490,6 +1490,145 @@ def stdk_layer1_bwd(phi_s, phi_t, z, dP, dQ, B, T, dw1=None, db1=None):
     return dw1, db1
 
 
+# --------------------------------------------------------------------------- classical baselines (csrc/classical.hip)
+KRIG_TILE = 32           # systems and per-gauge rows are padded to a multiple of this
+KRIG_MAX_CAP = 4096
+KRIG_MAX_LAGS = 32
+KRIG_CANDIDATES = 25
+KRIG_BIN_CHUNKS = 8      # workgroups per frame of the variogram pass (a fixed number: the partials are added in order)
+KRIG_MODELS = {"exponential": 0, "spherical": 1}
+
+
+def _krig_t(what, t, dtype, shape=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()):
+        raise RuntimeError(f"{what}: contiguous CUDA tensors only (the HIP path has no CPU fallback)")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{what}: expected {dtype}, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _krig_sys(what, f0, R, T, nsys, F, np_, cap):
+    if not (R == 1 or (R == T and f0 % T == 0)) or f0 < 0 or nsys < 1 or f0 + nsys * R > F:
+        raise RuntimeError(f"{what}: systems {f0} + {nsys} x {R} do not fit {F} frames of {T}-frame samples")
+    if np_ < KRIG_TILE or np_ % KRIG_TILE or np_ > cap:
+        raise RuntimeError(f"{what}: padded size {np_} must be a multiple of {KRIG_TILE} within cap {cap}")
+
+
+def krig_compact(masked, mask, cap):
+    """masked, mask: (B, T, H, W) fp32.  Returns pix (B*T, cap) int32 ((y << 16) | x of the frame's mask != 0 pixels in raster order),
+    z (B*T, cap) (masked there; both zero past the count) and info (2*B*T,) int32: counts, then 'mask differs from the sample's
+    first frame' flags."""
+    lib = _hip.load()
+    _krig_t("krig_compact", masked, torch.float32)
+    _krig_t("krig_compact", mask, torch.float32, masked.shape)
+    if masked.dim() != 4:
+        raise RuntimeError("krig_compact: (B, T, H, W) expected")
+    if cap < KRIG_TILE or cap % KRIG_TILE or cap > KRIG_MAX_CAP:
+        raise ValueError(f"krig_compact: cap must be a multiple of {KRIG_TILE} in [{KRIG_TILE}, {KRIG_MAX_CAP}] (got {cap})")
+    B, T, H, W = masked.shape
+    F = B * T
+    pix = torch.empty(F, cap, device=masked.device, dtype=torch.int32)
+    z = torch.empty(F, cap, device=masked.device, dtype=torch.float32)
+    info = torch.empty(2 * F, device=masked.device, dtype=torch.int32)
+    _hip.check(lib.p2i_krig_compact(_ptr(masked), _ptr(mask), B, T, H, W, cap, _ptr(pix), _ptr(z), _ptr(info), _stream()),
+               "p2i_krig_compact")
+    return pix, z, info
+
+
+def krig_variogram(pix, z, info, B, T, n_lags, lag_width, model):
+    """Empirical variogram pooled per sample and its fit, fp64 on the device.  Returns bins (B, n_lags, 3) fp64 (pairs, sum of
+    semivariances, sum of distances), fit (B, 4) fp64 (nugget, psill, range, weighted SSE), cand (B,) int32 (-1: degenerate sample)
+    and params (B, 4) fp32 for the kriging calls."""
+    lib = _hip.load()
+    F = B * T
+    cap = pix.shape[1]
+    _krig_t("krig_variogram", pix, torch.int32, (F, cap))
+    _krig_t("krig_variogram", z, torch.float32, (F, cap))
+    _krig_t("krig_variogram", info, torch.int32, (2 * F,))
+    if not (1 <= n_lags <= KRIG_MAX_LAGS) or not lag_width > 0:
+        raise ValueError(f"krig_variogram: n_lags must be 1..{KRIG_MAX_LAGS} and the lag width positive")
+    dev = pix.device
+    part = torch.empty(F, KRIG_BIN_CHUNKS, n_lags, 3, device=dev, dtype=torch.float64)
+    bins = torch.empty(B, n_lags, 3, device=dev, dtype=torch.float64)
+    fit = torch.empty(B, 4, device=dev, dtype=torch.float64)
+    cand = torch.empty(B, device=dev, dtype=torch.int32)
+    params = torch.empty(B, 4, device=dev, dtype=torch.float32)
+    _hip.check(lib.p2i_krig_bins(_ptr(pix), _ptr(z), _ptr(info), F, cap, KRIG_BIN_CHUNKS, n_lags, float(lag_width), _ptr(part), _stream()),
+               "p2i_krig_bins")
+    _hip.check(lib.p2i_krig_fit(_ptr(part), B, T * KRIG_BIN_CHUNKS, n_lags, float(lag_width), int(model), _ptr(bins), _ptr(fit), _ptr(cand),
+                                _ptr(params), _stream()), "p2i_krig_fit")
+    return bins, fit, cand, params
+
+
+def krig_factor(pix, info, params, model, f0, R, T, nsys, np_, L, status):
+    """Cholesky factors of the nsys covariance systems of frames f0, f0 + R, ... into L (>= nsys * np_ * np_ fp32); status (nsys,) int32
+    (zeroed by the caller) is set where a pivot was not positive."""
+    lib = _hip.load()
+    F, cap = pix.shape
+    _krig_t("krig_factor", pix, torch.int32)
+    _krig_t("krig_factor", info, torch.int32, (2 * F,))
+    _krig_t("krig_factor", params, torch.float32, (F // T, 4))
+    _krig_t("krig_factor", L, torch.float32)
+    _krig_t("krig_factor", status, torch.int32, (nsys,))
+    _krig_sys("krig_factor", f0, R, T, nsys, F, np_, cap)
+    if L.numel() < nsys * np_ * np_:
+        raise RuntimeError("krig_factor: factor workspace too small")
+    _hip.check(lib.p2i_krig_factor(_ptr(pix), _ptr(info), _ptr(params), int(model), f0, R, T, nsys, np_, cap, _ptr(L), _ptr(status),
+                                   _stream()), "p2i_krig_factor")
+
+
+def krig_solve(L, z, info, status, cand, f0, R, T, nsys, np_, alpha, mean):
+    """Dual coefficients alpha (F, cap) and mean (F,) of the frames of the nsys factored systems (written in place)."""
+    lib = _hip.load()
+    F, cap = z.shape
+    _krig_t("krig_solve", L, torch.float32)
+    _krig_t("krig_solve", z, torch.float32)
+    _krig_t("krig_solve", info, torch.int32, (2 * F,))
+    _krig_t("krig_solve", status, torch.int32, (nsys,))
+    if cand is not None:
+        _krig_t("krig_solve", cand, torch.int32, (F // T,))
+    _krig_t("krig_solve", alpha, torch.float32, (F, cap))
+    _krig_t("krig_solve", mean, torch.float32, (F,))
+    _krig_sys("krig_solve", f0, R, T, nsys, F, np_, cap)
+    if L.numel() < nsys * np_ * np_:
+        raise RuntimeError("krig_solve: factor workspace too small")
+    sol = torch.empty(nsys, R + 1, np_, device=z.device, dtype=torch.float64)
+    _hip.check(lib.p2i_krig_solve(_ptr(L), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), f0, R, T, nsys, np_, cap, _ptr(sol), _ptr(alpha),
+                                  _ptr(mean), _stream()), "p2i_krig_solve")
+
+
+def krig_predict(pix, alpha, mean, info, params, model, R, T, H, W):
+    """out (F, H*W) = mean + sum_i alpha_i c0(p, x_i) for every frame; R = T: the frames of a sample share frame 0's gauges."""
+    lib = _hip.load()
+    F, cap = pix.shape
+    _krig_t("krig_predict", pix, torch.int32)
+    _krig_t("krig_predict", alpha, torch.float32, (F, cap))
+    _krig_t("krig_predict", mean, torch.float32, (F,))
+    _krig_t("krig_predict", info, torch.int32, (2 * F,))
+    _krig_t("krig_predict", params, torch.float32, (F // T, 4))
+    _krig_sys("krig_predict", 0, R, T, F // R, F, KRIG_TILE, cap)
+    out = torch.empty(F, H * W, device=pix.device, dtype=torch.float32)
+    _hip.check(lib.p2i_krig_predict(_ptr(pix), _ptr(alpha), _ptr(mean), _ptr(info), _ptr(params), int(model), 0, R, T, F // R, H, W, cap,
+                                    _ptr(out), _stream()), "p2i_krig_predict")
+    return out
+
+
+def idw_all(pix, z, info, H, W, power=2.0):
+    """out (F, H*W): inverse-distance weighting over ALL gauges of each frame (the gauge's value on a gauge pixel, 0 without gauges)."""
+    lib = _hip.load()
+    F, cap = pix.shape
+    _krig_t("idw_all", pix, torch.int32)
+    _krig_t("idw_all", z, torch.float32, (F, cap))
+    _krig_t("idw_all", info, torch.int32, (2 * F,))
+    if not power > 0:
+        raise ValueError("idw_all: power must be positive")
+    out = torch.empty(F, H * W, device=pix.device, dtype=torch.float32)
+    _hip.check(lib.p2i_idw_all(_ptr(pix), _ptr(z), _ptr(info), F, H, W, cap, float(power), _ptr(out), _stream()), "p2i_idw_all")
+    return out
+
+
 # ---- evaluation: exp1 scoring, exp3 analysis, exp2 renders (csrc/eval_exp{1,3,2}.hip; p2igan_bench/evaluation/ drives these) ----
 EXP1_MAX_THR = 8
 EXP1_NSTAT = 8 + 3 * EXP1_MAX_THR

@@ -19,8 +19,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 from p2igan_bench.data import zarr_lite  # noqa: E402
 from p2igan_bench.data.dataloader import P2IDataModule  # noqa: E402
-from p2igan_bench.inference import infer_event  # noqa: E402
-from p2igan_bench.models import build_generator  # noqa: E402
+from p2igan_bench.inference import infer_event, infer_event_chunks  # noqa: E402
+from p2igan_bench.models import CLASSICAL, build_generator  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -69,30 +69,35 @@ def main(argv=None):
     dev = torch.device(args.device or cfg.get("device", "cuda:0"))
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise RuntimeError("the MI355X path needs a GPU: there is no CPU fallback")
-    ckpt = resolve_checkpoint(cfg, args)
+    name = cfg.get("model", {}).get("name", "model")
+    classical = str(name).lower() in CLASSICAL         # parameter-free: no checkpoint to resolve or load
+    ckpt = None if classical else resolve_checkpoint(cfg, args)
     loader = P2IDataModule(cfg).test_dataloader()
     if loader is None or len(loader.dataset) == 0:
         raise RuntimeError("Test dataloader is not configured or empty.")
-    name = cfg.get("model", {}).get("name", "model")
     out = Path(args.output or Path(args.model_dir or cfg.get("save_dir", "weights")) / f"test{name}.zarr")
     if out.exists():
         if not args.overwrite:
             raise FileExistsError(f"Output already exists: {out}")
         shutil.rmtree(out)
     group = zarr_lite.Group(str(out), "w")
-    group.attrs.update({"config_path": str(args.config), "checkpoint": str(ckpt), "model_name": name,
+    group.attrs.update({"config_path": str(args.config), "checkpoint": None if ckpt is None else str(ckpt), "model_name": name,
                         "data_root": cfg.get("data", {}).get("test", {}).get("data_root"), "passes": int(args.passes),
                         "output_scale": float(args.output_scale)})
     G = build_generator(cfg).to(dev)
-    state = torch.load(ckpt, map_location=dev, weights_only=True)
-    G.load_state_dict(state["generator"] if isinstance(state, dict) and "generator" in state else state)
+    if not classical:
+        state = torch.load(ckpt, map_location=dev, weights_only=True)
+        G.load_state_dict(state["generator"] if isinstance(state, dict) and "generator" in state else state)
     G.eval()
     results = {}
     for p in range(max(1, args.passes)):
         t0 = time.time()
         for i, batch in enumerate(loader):
             _, masked, masks = [t.permute(0, 1, 4, 2, 3).contiguous().to(dev) for t in batch]
-            comp = infer_event(G, masked, masks, max(1, args.stride), max(0, args.overlap), args.output_scale).cpu().numpy()
+            if classical:       # consecutive chunks of --stride frames, no overlap: each chunk is one sample of the variogram fit
+                comp = infer_event_chunks(G, masked, masks, max(1, args.stride), args.output_scale).cpu().numpy()
+            else:
+                comp = infer_event(G, masked, masks, max(1, args.stride), max(0, args.overlap), args.output_scale).cpu().numpy()
             key = f"event_{i + 1:02d}"
             results[key] = comp if p == 0 else results[key] + (comp - results[key]) / float(p + 1)
             if (i + 1) % max(1, args.log_every) == 0:

@@ -22,7 +22,7 @@ from p2igan_bench import ops, parallel  # noqa: E402
 from p2igan_bench.data.dataloader import P2IDataModule  # noqa: E402
 from p2igan_bench.data.prefetch import DevicePrefetcher  # noqa: E402
 from p2igan_bench.engine import TrainEngine  # noqa: E402
-from p2igan_bench.models import build_discriminator, build_generator  # noqa: E402
+from p2igan_bench.models import CLASSICAL, build_discriminator, build_generator  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -213,6 +213,9 @@ def main(argv=None):
     args = parse_args(argv)
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO), format="%(asctime)s | %(levelname)s | %(message)s")
     cfg = load_config(args.config)
+    name = str(cfg.get("model", {}).get("name", "")).lower()
+    if name in CLASSICAL:          # before any loader, engine or process group exists
+        raise RuntimeError(f"model '{name}' has no parameters: there is nothing to train (run scripts/infer.py with this config)")
     tr = cfg.setdefault("train", {})
     if args.experiment_name:
         cfg["experiment_name"] = args.experiment_name
