@@ -574,6 +574,37 @@ int p2i_krig_predict(const int* pix, const float* alpha, const float* mean, cons
                      int R, int T, int nsets, int H, int W, int cap, float* out, void* stream);
 int p2i_idw_all(const int* pix, const float* z, const int* counts, int F, int H, int W, int cap, float power, float* out, void* stream);
 
+/* ---- scale-aware verification: fractions skill score and radially averaged power spectra (no counterpart in
+ * the reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform
+ * and uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <= P2I_SCALE_MAX_CROP.
+ * p2i_scale_fss: one aligned piece of T frames.  For threshold q (HOST array, <= P2I_EXP1_MAX_THR) and window size n >= 1 (HOST
+ *   array, <= P2I_SCALE_MAX_SCALES), with I_p = (pred >= q), I_g = (truth >= q) (NaN compares false) and c(y, x) = the number of set
+ *   pixels in rows y - n/2 .. y - n/2 + n - 1 and the same range of columns (outside the crop: 0): part[T][nthr][3 nscales + 1]
+ *   (int64) = per scale sum c_p^2, sum c_g^2, sum c_p c_g over the frame, then sum I_g.  workspace NULL: 16-bit tables in LDS, S <=
+ *   P2I_SCALE_LDS_CROP; otherwise uint32 [T][nthr][2][S][S] of table workspace, any S.  The integers are the same on both paths.
+ * p2i_scale_fss_merge: acc[i] += sum_t part[t][i], i < n (int64).
+ * p2i_scale_dft_rows: G[t][field][y][kx][2] (fp64 re, im) = sum_x f[y][x] exp(-2 pi i x kx / S), kx <= S/2, of the transformed crop
+ *   f of T frames of ONE input (field 0: prediction, 1: truth; G holds both); twiddle [2][S] = cos, sin(2 pi m / S) (DEVICE, computed
+ *   on the host); nanflag[t][2] (int32, zeroed by the caller) is set to 1 where the crop holds a NaN.
+ * p2i_scale_dft_cols: psd[t][field][ky][kx] = |sum_y G[..][y][kx] exp(-2 pi i y ky / S)|^2 / S^2 for both fields.
+ * p2i_scale_rings: P[t][field][r] = (sum_{i in [offsets[r], offsets[r+1])} weight[i] psd[..][order[i]]) / count[r], r < R = S/2 + 1,
+ *   summed in list order (order: int32 indices ky (S/2 + 1) + kx; weight, count: fp64; all DEVICE).
+ * p2i_scale_spectrum_merge: out[field][r] = the mean of P[t][field][r] in frame order over the frames t < T with nanflag[t][0] ==
+ *   nanflag[t][1] == 0 (NaN when there is none); out[2 R] = the number of frames left out. */
+#define P2I_SCALE_MAX_SCALES 16
+#define P2I_SCALE_LDS_CROP 128
+#define P2I_SCALE_MAX_CROP 1024
+int p2i_scale_fss(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth, int truth_dtype, int gh,
+                  int gw, int gtop, int gleft, int T, int S, const double* lut, const double* thresholds_host, int nthr,
+                  const int* scales_host, int nscales, int divide_by_3, void* workspace, int64_t* part, void* stream);
+int p2i_scale_fss_merge(const int64_t* part, int64_t T, int n, int64_t* acc, void* stream);
+int p2i_scale_dft_rows(const void* x, int dtype, int h, int w, int top, int left, int T, int S, int field, const double* lut,
+                       int divide_by_3, const double* twiddle, double* G, int* nanflag, void* stream);
+int p2i_scale_dft_cols(const double* G, int T, int S, const double* twiddle, double* psd, void* stream);
+int p2i_scale_rings(const double* psd, int T, int S, const int* order, const double* weight, const int* offsets, const double* count,
+                    int R, double* P, void* stream);
+int p2i_scale_spectrum_merge(const double* P, const int* nanflag, int64_t T, int R, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

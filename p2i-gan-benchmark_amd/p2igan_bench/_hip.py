@@ -137,6 +137,13 @@ SIGNATURES = {
     "p2i_krig_solve": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "p2i_krig_predict": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "p2i_idw_all": [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P],
+    "p2i_scale_fss": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(C.c_double), _I, C.POINTER(C.c_int), _I, _I,
+                      _P, _P, _P],
+    "p2i_scale_fss_merge": [_P, _L, _I, _P, _P],
+    "p2i_scale_dft_rows": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
+    "p2i_scale_dft_cols": [_P, _I, _I, _P, _P, _P],
+    "p2i_scale_rings": [_P, _I, _I, _P, _P, _P, _P, _I, _P, _P],
+    "p2i_scale_spectrum_merge": [_P, _P, _L, _I, _P, _P],
 }
 
 

@@ -1829,3 +1829,65 @@ def exp2_compose(panels, zoom, gauge_bits, points, chrome, oy, ox, step, bg, edg
     _hip.check(_hip.load().p2i_exp2_compose(_ptr(panels), P, n, S, int(zoom), int(gauge_bits), _ptr(points) if K else None, K, _ptr(chrome),
                                             Hc, pitch, int(oy), int(ox), int(step), int(bg), int(edge), _ptr(out), _stream()),
                "p2i_exp2_compose")
+
+
+# ---- scale-aware verification: FSS and radial spectra (csrc/eval_scale.hip; p2igan_bench/evaluation/scale.py drives these) ----
+SCALE_MAX_SCALES = 16
+SCALE_LDS_CROP = 128
+SCALE_MAX_CROP = 1024
+
+
+def scale_fss(pred, truth, ptl, gtl, S, lut, thresholds, scales, divide_by_3, part, workspace=None):
+    """One aligned piece: pred, truth [T, H, W] (their own H, W), crop origins ptl / gtl.  Writes part [T, nthr, 3 * nscales + 1]
+    (int64): per scale sum c_p^2, sum c_g^2, sum c_p c_g, then the truth's hits.  Without ``workspace`` the tables live in LDS
+    (S <= SCALE_LDS_CROP); with it (uint32 [T * nthr * 2 * S * S]) in global memory."""
+    T, K, N = pred.shape[0], len(thresholds), len(scales)
+    if truth.shape[0] != T or not 0 < K <= EXP1_MAX_THR or not 0 < N <= SCALE_MAX_SCALES:
+        raise RuntimeError("scale_fss: frame count / thresholds / scales")
+    pin, gin = _eval_input(pred, ptl), _eval_input(truth, gtl)
+    _eval_bufs("scale_fss", (lut, torch.float64, 256), (part, torch.int64, T * K * (3 * N + 1)),
+               *([(workspace, torch.int32, T * K * 2 * S * S)] if workspace is not None else []))
+    sc = (C.c_int * N)(*[min(int(n), 2 ** 31 - 1) for n in scales])
+    _hip.check(_hip.load().p2i_scale_fss(*pin, *gin, T, S, _ptr(lut), _f64s(thresholds), K, sc, N, int(divide_by_3),
+                                         _ptr(workspace) if workspace is not None else None, _ptr(part), _stream()), "p2i_scale_fss")
+
+
+def scale_fss_merge(part, acc):
+    """acc [n] (int64) += the sums over the frames of part [T, ...] (n values per frame)."""
+    n = acc.numel()
+    _eval_bufs("scale_fss_merge", (part, torch.int64, part.shape[0] * n), (acc, torch.int64, n))
+    _hip.check(_hip.load().p2i_scale_fss_merge(_ptr(part), part.shape[0], n, _ptr(acc), _stream()), "p2i_scale_fss_merge")
+
+
+def scale_spectra(pred, truth, ptl, gtl, S, lut, divide_by_3, tw, rings, G, psd, P, nanflag):
+    """One aligned piece of T frames: P [T, 2, R] (fp64) = the ring means of the power spectra of the transformed S x S crops of pred
+    (field 0) and truth (field 1), nanflag [T, 2] (int32, zeroed here) = 1 where a crop holds a NaN.  tw [2, S] = cos, sin(2 pi m /
+    S); rings = (order, weight, offsets, count) as p2i_scale_rings takes them; G [T, 2, S, R, 2] and psd [T, 2, S, R] are workspace."""
+    T, R = pred.shape[0], S // 2 + 1
+    if truth.shape[0] != T or not 0 < S <= SCALE_MAX_CROP:
+        raise RuntimeError("scale_spectra: frame count / crop")
+    order, weight, offsets, count = rings
+    _eval_bufs("scale_spectra", (lut, torch.float64, 256), (tw, torch.float64, 2 * S), (order, torch.int32, order.numel()),
+               (weight, torch.float64, order.numel()), (offsets, torch.int32, R + 1), (count, torch.float64, R),
+               (G, torch.float64, T * 4 * S * R), (psd, torch.float64, T * 2 * S * R), (P, torch.float64, T * 2 * R),
+               (nanflag, torch.int32, T * 2))
+    if not 0 < order.numel() <= S * R:
+        raise RuntimeError("scale_spectra: ring list")
+    nanflag.zero_()
+    lib = _hip.load()
+    for field, (x, tl) in enumerate(((pred, ptl), (truth, gtl))):
+        _hip.check(lib.p2i_scale_dft_rows(*_eval_input(x, tl), T, S, field, _ptr(lut), int(divide_by_3), _ptr(tw), _ptr(G), _ptr(nanflag),
+                                          _stream()), "p2i_scale_dft_rows")
+    _hip.check(lib.p2i_scale_dft_cols(_ptr(G), T, S, _ptr(tw), _ptr(psd), _stream()), "p2i_scale_dft_cols")
+    _hip.check(lib.p2i_scale_rings(_ptr(psd), T, S, _ptr(order), _ptr(weight), _ptr(offsets), _ptr(count), R, _ptr(P), _stream()),
+               "p2i_scale_rings")
+
+
+def scale_spectrum_merge(P, nanflag):
+    """P [T, 2, R], nanflag [T, 2] -> [2 * R + 1] fp64: the two mean spectra over the frames without a NaN (frame order), then the
+    number of frames left out."""
+    T, _, R = P.shape
+    _eval_bufs("scale_spectrum_merge", (P, torch.float64, T * 2 * R), (nanflag, torch.int32, T * 2))
+    out = torch.empty(2 * R + 1, device=P.device, dtype=torch.float64)
+    _hip.check(_hip.load().p2i_scale_spectrum_merge(_ptr(P), _ptr(nanflag), T, R, _ptr(out), _stream()), "p2i_scale_spectrum_merge")
+    return out

@@ -17,6 +17,11 @@ With ``--exp2 DIR2 --observation OBS.zarr`` it also writes the benchmark's exp2 
 the first 20 events in lexicographic key order, 30 frames each): DIR2/comparison_<event>.gif, DIR2/event_ranges.txt and
 DIR2/exp2_data.npz.  ``--exp2-pdf FILE --exp2-events EVENTS.json`` writes the paper's frame grid (run_exp2_paper_zarr); the JSON is
 a list of ``{"event_id": 3, "select_idx": [0, 2, 4], "title": "..."}``.  Neither changes exp1's or exp3's outputs.
+
+With ``--scale DIRS [--scales N ...]`` it also runs the scale-aware verification (run_scale: the fractions skill score over
+``--thresholds`` x the neighbourhood sizes, and the radially averaged power spectra) on the whole crop and writes DIRS/metrics.json,
+DIRS/metrics.txt (``FSS_<name>_thr<q>_n<n>: value`` and ``LSD_<name>: value`` lines), DIRS/scale_data.npz and DIRS/scale_panels.pdf.
+It needs ``--mode radar``; the other outputs do not depend on it.
 """
 from __future__ import annotations
 
@@ -31,7 +36,8 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 from p2igan_bench.data import zarr_lite  # noqa: E402
-from p2igan_bench.evaluation import DEFAULT_THRESHOLDS, crop_mask, run_exp1, run_exp2, run_exp2_paper_zarr, run_exp3  # noqa: E402
+from p2igan_bench.evaluation import (DEFAULT_SCALES, DEFAULT_THRESHOLDS, crop_mask, run_exp1, run_exp2, run_exp2_paper_zarr,  # noqa: E402
+                                     run_exp3, run_scale, write_scale_outputs)
 
 
 def _method(spec: str):
@@ -65,7 +71,15 @@ def parse_args(argv=None):
                    "and --exp2-events)")
     p.add_argument("--exp2-events", default=None, metavar="JSON", help="the paper grid's events: a JSON list of "
                    "{event_id, select_idx, title}")
+    p.add_argument("--scale", default=None, metavar="DIR", help="also run the scale-aware verification (FSS over thresholds x "
+                   "neighbourhood sizes, radial power spectra) and write its outputs into DIR")
+    p.add_argument("--scales", type=int, nargs="+", default=list(DEFAULT_SCALES), metavar="N", help="FSS neighbourhood sizes in pixels "
+                   "(at most 16)")
     args = p.parse_args(argv)
+    if args.scale and args.mode != "radar":
+        p.error("--scale scores the whole crop: it needs --mode radar")
+    if args.scale and not 0 < len(args.scales) <= 16:
+        p.error("--scales takes 1 to 16 sizes")
     if (args.exp2 or args.exp2_pdf) and not args.observation:
         p.error("--exp2 / --exp2-pdf need --observation")
     if args.exp2_pdf and not args.exp2_events:
@@ -149,6 +163,11 @@ def main(argv=None):
         m3 = run_exp3(preds, truth, mask, args.mode, args.crop_size, args.exp3, device=args.device)
         write_exp3_outputs(args.exp3, m3)
         print(f"wrote {os.path.join(args.exp3, 'metrics.json')} and the exp3 figures")
+    if args.scale:
+        ms = run_scale(preds, truth, args.crop_size, thresholds=tuple(args.thresholds), scales=tuple(args.scales), divide_by_3=True,
+                       device=args.device, mode=args.mode)
+        write_scale_outputs(args.scale, ms)
+        print(f"wrote {os.path.join(args.scale, 'metrics.json')} and the scale figure")
     paths = {name: path for name, path in args.method}
     if args.exp2:
         run_exp2(paths, args.truth, args.observation, mask, args.exp2, args.crop_size, None, 0.0, 0.0, args.gif_fps, divide_by_3=True,
