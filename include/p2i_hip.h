@@ -119,7 +119,10 @@ int p2i_conv_dgrad_x6(const p2i_conv_desc* d, const float* dy, const float* wp_d
  * plane 0 of that layer) and ntaps_w = the stack's total tap count.  p2i_x6c_would_take tells (1 / 0) whether a call with this
  * geometry (and, for a forward call, this epilogue activation) would use the split at all, so that callers can skip splitting
  * stacks no layer needs.  Layers with too few output tiles for 256 CUs whose epilogue is linear (no activation) run with the channel
- * chunks split over two workgroups per tile that add their partial sums into the zeroed destination (P2I_X6C_KSPLIT=0 disables). */
+ * chunks split over two workgroups per tile that add their partial sums into the zeroed destination (P2I_X6C_KSPLIT=0 disables).
+ * The split is exact -- hi + mid + lo == w, each term w's remainder truncated to its upper 16 bits -- for +-0 and every normal
+ * float32 whose remainders stay normal (pinned bit for bit for binary exponents -60 .. 60 by tests/test_weightprep_gpu.py); a
+ * subnormal w loses its last bits (1e-40: the remainder's significant bits fall in the lower half-word). */
 int p2i_x6_split(const float* wp, uint16_t* wb, int ntaps, int K, int Mpad, void* stream);
 /* the same for n <= 24 packed tensors of different shapes in one launch (wb[i]: 3 * ntaps[i] * K[i] * Mpad[i] uint16 each): the
  * discriminators' layers after p2i_weight_pack_batched */
@@ -153,8 +156,12 @@ int p2i_wgrad_last_plan(int* out4);
  *   reference's memory reinterpretation to (O, I/g, 3, 3) (deconv_pytorch.py:111-127), written
  *   densely (zeros outside the group) in both packed layouts: wp_f[9][I][Opad] for p2i_conv_fwd
  *   and wp_d[9][O][Ipad] for p2i_conv_dgrad.  ksz==1: DoW = W.reshape (no D).  `identity_rep`>0
- *   adds the `+ x.repeat_interleave(rep, dim=1)` skip of p2igan.py:79 as a centre-tap identity.
+ *   adds the `+ x.repeat_interleave(rep, dim=1)` skip of p2igan.py:79 as a centre-tap identity; that skip exists for a 3x3
+ *   layer with I * rep == O only, anything else is refused with P2I_EINVAL.
  * p2i_doconv_fold_bwd: dW, dD from the packed weight gradient produced by p2i_conv_wgrad.
+ * Every fold, pack, unpack and spectral-norm entry point of this and the next section, and the weight split p2i_x6_split /
+ * p2i_x6_split_batched, are swept over their shapes -- exactly, on integer-valued inputs, wherever the operation allows it -- by
+ * tests/test_weightprep_gpu.py (cases: tests/weightprep_cases.py).
  */
 int p2i_doconv_fold_fwd(const float* W, const float* D, const float* D_diag, int O, int I, int groups,
                         int ksz, int identity_rep, float* wp_f, float* wp_d, void* stream);
@@ -359,7 +366,10 @@ int p2i_window_mean(const float* pred_windows, float* out, int L, int64_t HW, in
  * thresholds[k] (CategoricalMetrics.update :92-111; always transformed); bits (may be NULL): byte plane, bit k =
  * T(pred)>=thr[k], bit 4+k = T(target)>=thr[k], the input of p2i_metrics_fss.  thresholds/scales are HOST arrays (<= 4).
  * p2i_metrics_fss (FractionalSkillScoreMetric.update :152-170): num/den[k*ns + s] += sum over the avg_pool2d(kernel s,
- * stride 1, padding s/2) fraction fields of (fp-ft)^2 and fp^2+ft^2; the caller divides by N*ho*wo (ho = H+2*(s/2)-s+1). */
+ * stride 1, padding s/2) fraction fields of (fp-ft)^2 and fp^2+ft^2; the caller divides by N*ho*wo (ho = H+2*(s/2)-s+1).
+ * Scales are 1..64; more than 4 thresholds or scales, a scale outside that range and n or N <= 0 are refused with P2I_EINVAL.
+ * Counts, bit plane, the integer regression sums and the power-of-two FSS sums are compared exactly over sizes, block
+ * boundaries and grid-stride trips by tests/test_metric_kernels_gpu.py (cases: tests/metric_cases.py). */
 int p2i_metrics_pointwise(const float* pred, const float* target, int64_t n, const float* thresholds_host, int nt,
                           int apply_transform, float* sums2, unsigned long long* counts, uint8_t* bits, void* stream);
 int p2i_metrics_fss(const uint8_t* bits, int N, int H, int W, int nt, const int* scales_host, int ns, float* num, float* den,

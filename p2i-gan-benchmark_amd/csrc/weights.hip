@@ -512,6 +512,9 @@ extern "C" int p2i_doconv_fold_fwd(const float* W, const float* D, const float* 
   P2I_REQUIRE(ksz == 1 || ksz == 3, "DO-Conv kernel size must be 1 or 3");
   P2I_REQUIRE(groups >= 1 && O % groups == 0 && I % groups == 0, "channels not divisible by groups");
   P2I_REQUIRE(ksz == 1 || (D && D_diag), "3x3 DO-Conv needs D and D_diag");
+  // the skip `+ x.repeat_interleave(rep, dim=1)` exists for I * rep == O only (its centre-tap identity then lies inside the group)
+  P2I_REQUIRE(identity_rep == 0 || (identity_rep > 0 && ksz == 3 && (long long)I * identity_rep == O),
+              "identity_rep needs a 3x3 layer with I * identity_rep == O");
   hipStream_t s = (hipStream_t)stream;
   const int nt = ksz * ksz, Opad = (O + 31) / 32 * 32, Ipad = (I + 31) / 32 * 32;
   if (groups > 1 || Opad != O) (void)p2i::memset_async(wp_f, 0, sizeof(float) * (size_t)nt * I * Opad, s);
