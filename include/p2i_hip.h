@@ -584,6 +584,31 @@ int p2i_krig_predict(const int* pix, const float* alpha, const float* mean, cons
                      int R, int T, int nsets, int H, int W, int cap, float* out, void* stream);
 int p2i_idw_all(const int* pix, const float* z, const int* counts, int F, int H, int W, int cap, float power, float* out, void* stream);
 
+/* ---- kriging variance and leave-one-out (LOO) cross-validation of the classical baselines (no counterpart in
+ * the reference).  Symbols, systems (f0, R, T, nsys, np, cap) and the frame rules are those of the block above; W = L^-1, u = K^-1 1
+ * (row 0 of each system's sol), s = 1^T u, c0(p, i) = C(|p - x_i|) + nugget [p = x_i], c00 = psill + nugget.
+ * p2i_krig_invert: Winv [nsys][np][np] fp32 = the inverse of each system's factor L (lower triangular, zeros above, identity on the
+ *   padding), by 32-wide tiles; Winv must not alias L.
+ * p2i_krig_variance: var [F][H W] = max(0, c00 - |W k(p)|^2 + (1 - u^T k(p))^2 / s), k(p) = [c0(p, i)]_i, written to the R frames of
+ *   each system; exactly 0 on a gauge pixel; NaN everywhere for a system without gauges, with status != 0 or of a degenerate sample
+ *   (cand[b] < 0; cand may be NULL).  sol, status as left by p2i_krig_solve / p2i_krig_factor for the same (f0, R, nsys, np).
+ * p2i_krig_loo: colsq [nsys][np] fp64 (scratch) = the column square-sums of Winv; then for gauge i of each of the systems' frames
+ *   B_ii = colsq_i - u_i^2 / s, pred [F][cap] = z_i - alpha_i / B_ii, var [F][cap] = 1 / B_ii; NaN for a frame with fewer than 2
+ *   gauges, of a degenerate sample or of a system with status != 0; 0 past the frame's count.
+ * p2i_idw_loo: pred [F][cap] = sum_{j != i} w_j z_j / sum_{j != i} w_j, w_j = |x_i - x_j|^-power (fp32 weights, fp64 sums); NaN with
+ *   fewer than 2 gauges; 0 past the count.
+ * p2i_loo_scores: out [5] fp64 = (n, sum e, sum |e|, sum e^2, sum e^2 / var) with e = z - pred over the entries i < counts[f] whose
+ *   pred (and var, unless var is NULL: then out[4] = 0) is not NaN; part [F][5] fp64 is scratch.  Fixed order. */
+int p2i_krig_invert(const float* L, int nsys, int np, float* Winv, void* stream);
+int p2i_krig_variance(const float* Winv, const double* sol, const int* pix, const int* counts, const int* status, const int* cand,
+                      const float* params, int model, int f0, int R, int T, int nsys, int np, int H, int W, int cap, float* var,
+                      void* stream);
+int p2i_krig_loo(const float* Winv, const double* sol, const float* alpha, const float* z, const int* counts, const int* status,
+                 const int* cand, int f0, int R, int T, int nsys, int np, int cap, double* colsq, float* pred, float* var, void* stream);
+int p2i_idw_loo(const int* pix, const float* z, const int* counts, int F, int cap, float power, float* pred, void* stream);
+int p2i_loo_scores(const float* z, const float* pred, const float* var, const int* counts, int F, int cap, double* part, double* out,
+                   void* stream);
+
 /* ---- scale-aware verification: fractions skill score and radially averaged power spectra (no counterpart in
  * the reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform
  * and uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <= P2I_SCALE_MAX_CROP.

@@ -7,36 +7,15 @@
 // Number formats: the covariance matrix and its factor are fp32 (fmaf); every long sum that feeds a result (substitutions, 1^T u,
 // 1^T v, the predictor's sum over gauges, IDW's numerator and denominator) is accumulated in fp64 from fp32 terms; the variogram
 // (bins and fit) is fp64 throughout.  Every sum has a fixed order (no atomics): results are identical from run to run.
-#include "common.h"
+#include "krig_common.h"
 
 namespace p2i {
 namespace {
 
-constexpr int TS = 32;            // tile of the factorisation; systems are padded to a multiple of it
 constexpr int MAX_LAGS = 32;
 constexpr int N_CAND = 25;        // range candidates a_c = w 2^((c - 6) / 3)
 constexpr int BIN_THREADS = 64;
-constexpr int PCHUNK = 128;       // gauges staged in LDS per predictor pass
 constexpr int RC = 8;             // right-hand sides fed from one covariance evaluation
-
-__device__ __forceinline__ double block_sum_d(double v, double* red) {   // red: 256 doubles of LDS; fixed tree, 256 threads
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
-// C(h) = psill (1 - g(h / a)): exponential g(r) = 1 - exp(-r); spherical g(r) = 1.5 r - 0.5 r^3 below 1, 1 beyond
-__device__ __forceinline__ float cov_f(float h, float psill, float a, int model) {
-  const float r = h / a;
-  if (model == 0) return psill * expf(-r);
-  return r < 1.f ? psill * (1.f - (1.5f * r - 0.5f * r * r * r)) : 0.f;
-}
 
 // ---- compaction: one workgroup per frame.  pix / z [F][cap] (entries past the count are zero), info[f] = count (may exceed cap:
 // the host refuses), info[F + f] = 1 if the frame's mask pattern differs from that of frame 0 of its sample
@@ -516,9 +495,6 @@ __global__ __launch_bounds__(256) void idw_all_kernel(const int* __restrict__ pi
   if (p < HW) out[(size_t)f * HW + p] = n == 0 ? 0.f : (hit ? hitv : (float)(num / den));
 }
 
-constexpr int MAX_NP = 4096;       // fp64 vector of the solve in LDS: 32 KiB
-constexpr int MAX_SIDE = 16384;    // squared pixel distances stay in int32
-
 }  // namespace
 }  // namespace p2i
 
@@ -550,13 +526,6 @@ extern "C" int p2i_krig_fit(const double* part, int B, int nparts, int n_lags, d
   P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
   P2I_LAUNCH(krig_fit_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, part, nparts, n_lags, lag_width, model, bins, fit, cand, params);
   return launch_status();
-}
-
-static int krig_sys_check(int f0, int R, int T, int nsys, int np, int cap) {
-  P2I_REQUIRE(R > 0 && T > 0 && f0 >= 0 && nsys > 0 && nsys <= 65535, "bad system range");
-  P2I_REQUIRE(R == 1 || (R == T && f0 % T == 0), "a system spans one frame or one whole sample");
-  P2I_REQUIRE(np > 0 && np % TS == 0 && np <= cap && cap <= MAX_NP, "padded size %d must be a multiple of %d within cap %d", np, TS, cap);
-  return P2I_OK;
 }
 
 extern "C" int p2i_krig_factor(const int* pix, const int* counts, const float* params, int model, int f0, int R, int T, int nsys, int np,

@@ -1,0 +1,42 @@
+// What the classical baselines (classical.hip) and their uncertainty / cross-validation kernels (krig_uq.hip) share: the tile and
+// size limits, the covariance function, the fixed-tree fp64 block sum and the check of a system range.
+#pragma once
+#include "common.h"
+
+namespace p2i {
+namespace {
+
+constexpr int TS = 32;            // tile of the factorisation; systems are padded to a multiple of it
+constexpr int PCHUNK = 128;       // gauges staged in LDS per predictor pass
+constexpr int MAX_NP = 4096;      // fp64 vector of the solve in LDS: 32 KiB
+constexpr int MAX_SIDE = 16384;   // squared pixel distances stay in int32
+
+__device__ __forceinline__ double block_sum_d(double v, double* red) {   // red: 256 doubles of LDS; fixed tree, 256 threads
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// C(h) = psill (1 - g(h / a)): exponential g(r) = 1 - exp(-r); spherical g(r) = 1.5 r - 0.5 r^3 below 1, 1 beyond
+__device__ __forceinline__ float cov_f(float h, float psill, float a, int model) {
+  const float r = h / a;
+  if (model == 0) return psill * expf(-r);
+  return r < 1.f ? psill * (1.f - (1.5f * r - 0.5f * r * r * r)) : 0.f;
+}
+
+}  // namespace
+
+static inline int krig_sys_check(int f0, int R, int T, int nsys, int np, int cap) {
+  P2I_REQUIRE(R > 0 && T > 0 && f0 >= 0 && nsys > 0 && nsys <= 65535, "bad system range");
+  P2I_REQUIRE(R == 1 || (R == T && f0 % T == 0), "a system spans one frame or one whole sample");
+  P2I_REQUIRE(np > 0 && np % TS == 0 && np <= cap && cap <= MAX_NP, "padded size %d must be a multiple of %d within cap %d", np, TS, cap);
+  return P2I_OK;
+}
+
+}  // namespace p2i

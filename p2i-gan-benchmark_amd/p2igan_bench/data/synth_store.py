@@ -28,3 +28,11 @@ def write_train_zarr(root: str, n_events: int = 4, frames_per_event: int = 30, h
     g.require_group("index").create_dataset("windows", np.asarray(rows, dtype=np.int32))
     g.attrs.update(suggested_window=window)
     return len(rows)
+
+
+def write_test_zarr(root: str, n_events: int = 2, frames_per_event: int = 20, h: int = 32, w: int = 32, seed: int = 2024) -> None:
+    """Creates `root` as a flat store of whole events (`event_01`, ... uint8 (T, h, w)): the layout the test split reads."""
+    g = zarr_lite.Group(str(root), "w")
+    for e in range(n_events):
+        fr = seeded.synthetic_event(frames_per_event, h, w, seed=seed + e).numpy()
+        g.create_dataset("event_%02d" % (e + 1), fr, chunks=fr.shape)

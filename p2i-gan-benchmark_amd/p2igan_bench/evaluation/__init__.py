@@ -19,6 +19,9 @@ scale (``scale.py``, section 15; no counterpart in the reference): ``run_scale``
 thresholds x neighbourhood sizes, the smallest useful scale, and the radially averaged power spectra with their log-spectral distance
 and high-wavenumber ratio against the truth's.  ``ScaleEvaluator`` is its streaming form (one host sync in ``compute``).
 
+loo (``loo.py``, section 16; no counterpart in the reference): ``run_loo`` cross-validates a classical baseline leave-one-out at the
+gauges of every test event and writes ``loo.json``, ``loo.txt`` and ``loo_data.npz``; it needs no gridded truth.
+
 ``_common.py`` holds what the units share."""
 from ._common import crop_mask, crop_origin, ensure_thw_shape, selection, transform_mmhr, truth_lut  # noqa: F401
 from .exp1 import DEFAULT_THRESHOLDS, PSS_BINS, PSS_MIN_VALUE, Exp1Evaluator, pss_bin, pss_edges, run_exp1  # noqa: F401
@@ -28,5 +31,6 @@ from .exp2_chrome import (EXP2_GREYS, EXP2_IDX_BAD, EXP2_IDX_BG, EXP2_IDX_EDGE, 
                           PAPER_SUB, exp2_chrome, exp2_layout, exp2_palette, paper_cmap, write_exp2_gif)
 from .exp3 import (EXP3_MAX_POINTS, EXP3_MIN_VALUE, EXP3_SEED, LOGFREQ_EDGES, SCATTER_COLORS, Exp3Evaluator, Exp3Result,  # noqa: F401
                    compute_exp3, linregress, run_exp3, write_exp3_figures)
+from .loo import loo_lines, run_loo  # noqa: F401
 from .scale import (DEFAULT_SCALES, ScaleEvaluator, check_overflow, fss_value, ring_counts, ring_index, ring_list, run_scale,  # noqa: F401
                     scale_lines, spectrum_scores, twiddle, useful_scale, write_scale_figure, write_scale_outputs)

@@ -1,0 +1,98 @@
+"""Leave-one-out (LOO) gauge cross-validation of the classical baselines over the test events (no counterpart in
+the reference): the one score that needs no gridded truth, so the one that also holds on gauge-only data.  Every gauge of a frame is
+predicted from the frame's other gauges by the model's ``cross_validate`` (csrc/krig_uq.hip); the sums behind the scores are taken on
+the device, chunk by chunk, and added per event and overall on the host."""
+from __future__ import annotations
+
+import json
+import math
+import os
+from typing import Any, Dict, Optional
+
+import numpy as np
+import torch
+
+from ._common import transform_mmhr
+
+def _coded(sums, with_var: bool, scale: float) -> Dict[str, float]:
+    from ..models.classical import loo_summary
+    out = loo_summary(sums, with_var)
+    for k in ("ME", "MAE", "RMSE"):
+        out[k] *= scale
+    return out
+
+
+def _mmhr(z, pred, scale: float) -> Dict[str, float]:
+    """ME / MAE / RMSE of the rain rates: the evaluation's transform on z and on the LOO prediction (coded units x scale), then e."""
+    if len(z) == 0:
+        return {"ME_mmhr": math.nan, "MAE_mmhr": math.nan, "RMSE_mmhr": math.nan}
+    e = transform_mmhr(z.astype(np.float64) * scale) - transform_mmhr(pred.astype(np.float64) * scale)
+    return {"ME_mmhr": float(e.mean()), "MAE_mmhr": float(np.abs(e).mean()), "RMSE_mmhr": float(np.sqrt((e * e).mean()))}
+
+
+def loo_lines(result: Dict[str, Any]):
+    """The text table of a run_loo result."""
+    keys = ["n", "ME", "MAE", "RMSE"] + (["MSDR"] if "MSDR" in result["overall"] else []) + ["ME_mmhr", "MAE_mmhr", "RMSE_mmhr"]
+    lines = [f"leave-one-out cross-validation: {result['model_name']}  (coded units x {result['output_scale']:g}; *_mmhr in mm/h)",
+             "event".ljust(12) + "".join(k.rjust(14) for k in keys)]
+    for name, row in list(result["events"].items()) + [("overall", result["overall"])]:
+        lines.append(name.ljust(12) + "".join((f"{row[k]:d}" if k == "n" else f"{row[k]:.6g}").rjust(14) for k in keys))
+    return lines
+
+
+def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_scale: float = 255.0, stride: int = 16) -> Dict[str, Any]:
+    """Cross-validate cfg's classical model on every test event, in consecutive chunks of `stride` frames as infer_event_chunks forms
+    them (each chunk is one sample of a fitted variogram).  Writes loo.json / loo.txt (scores per event and overall) and loo_data.npz
+    (per gauge: event, frame, y, x, z, LOO prediction, LOO variance; coded units, unscaled) under out_dir; returns loo.json's content."""
+    from ..models import CLASSICAL, build_generator
+    name = str(cfg.get("model", {}).get("name", "model")).lower()
+    if name not in CLASSICAL:
+        raise RuntimeError(f"leave-one-out cross-validation is defined for the classical baselines {sorted(CLASSICAL)} only: "
+                           f"model.name '{name}' is a learnt model and would need one training per gauge")
+    dev = torch.device(device or cfg.get("device", "cuda:0"))
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("the MI355X path needs a GPU: there is no CPU fallback")
+    from ..data.dataloader import P2IDataModule
+    loader = P2IDataModule(cfg).test_dataloader()
+    if loader is None or len(loader.dataset) == 0:
+        raise RuntimeError("Test dataloader is not configured or empty.")
+    G = build_generator(cfg).to(dev).eval()
+    scale, stride = float(output_scale), max(1, int(stride))
+    with_var = name == "kriging"
+    events, cols = {}, {k: [] for k in ("event", "frame", "y", "x", "z", "pred", "var")}
+    total = np.zeros(5)
+    for ei, batch in enumerate(loader):
+        _, masked, masks = [t.permute(0, 1, 4, 2, 3).contiguous().to(dev) for t in batch]
+        sums, ez, ep = np.zeros(5), [], []
+        for s in range(0, masked.shape[1], stride):
+            res = G.cross_validate(masked[:, s:s + stride].contiguous(), masks[:, s:s + stride].contiguous())
+            sums += np.asarray(res.sums().cpu().tolist())
+            counts = res.counts.cpu().numpy()
+            pix, z, pred = res.pix.cpu().numpy(), res.z.cpu().numpy(), res.pred.cpu().numpy()
+            var = res.var.cpu().numpy() if with_var else np.full(z.shape, np.nan, np.float32)
+            for f, n in enumerate(counts):
+                n = min(int(n), z.shape[1])
+                cols["event"].append(np.full(n, ei + 1, np.int32))
+                cols["frame"].append(np.full(n, s + f, np.int32))
+                cols["y"].append((pix[f, :n] >> 16).astype(np.int32))
+                cols["x"].append((pix[f, :n] & 0xffff).astype(np.int32))
+                cols["z"].append(z[f, :n])
+                cols["pred"].append(pred[f, :n])
+                cols["var"].append(var[f, :n])
+                ok = ~np.isnan(pred[f, :n]) & (~np.isnan(var[f, :n]) if with_var else True)
+                ez.append(z[f, :n][ok])
+                ep.append(pred[f, :n][ok])
+        ez, ep = np.concatenate(ez), np.concatenate(ep)
+        events[f"event_{ei + 1:02d}"] = {**_coded(sums.tolist(), with_var, scale), **_mmhr(ez, ep, scale)}
+        total += sums
+    data = {k: np.concatenate(v) for k, v in cols.items()}
+    ok = ~np.isnan(data["pred"]) & (~np.isnan(data["var"]) if with_var else True)
+    result = {"model_name": name, "output_scale": scale, "stride": stride, "events": events,
+              "overall": {**_coded(total.tolist(), with_var, scale), **_mmhr(data["z"][ok], data["pred"][ok], scale)}}
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "loo.json"), "w") as fh:
+        json.dump(result, fh, indent=2)
+    with open(os.path.join(out_dir, "loo.txt"), "w") as fh:
+        fh.write("\n".join(loo_lines(result)) + "\n")
+    np.savez(os.path.join(out_dir, "loo_data.npz"), **data)
+    return result

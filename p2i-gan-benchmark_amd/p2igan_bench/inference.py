@@ -51,3 +51,12 @@ def infer_event_chunks(generator, masked: torch.Tensor, masks: torch.Tensor, str
     L = masked.shape[1]
     parts = [generator(masked[:, s:s + stride].contiguous(), masks[:, s:s + stride].contiguous())[0] for s in range(0, L, stride)]
     return (torch.cat(parts, dim=0) * float(output_scale)).clamp(min=0.0)
+
+
+@torch.no_grad()
+def infer_event_variance(generator, masked: torch.Tensor, masks: torch.Tensor, stride: int = 16, output_scale: float = 255.0) -> torch.Tensor:
+    """The kriging variance of infer_event_chunks' predictions, chunk by chunk: (L, 1, H, W) float32 = sigma^2 x output_scale^2 (NaN
+    over a frame without a model)."""
+    L = masked.shape[1]
+    parts = [generator.forward_uq(masked[:, s:s + stride].contiguous(), masks[:, s:s + stride].contiguous())[1][0] for s in range(0, L, stride)]
+    return torch.cat(parts, dim=0) * float(output_scale) ** 2

@@ -3,10 +3,14 @@
 
 Both take the generators' (masked_frames, masks) pair, (B, T, 1, H, W) fp32 on the device, and return (B, T, 1, H, W).  The gauges
 of frame (b, t) are its pixels with mask != 0 in raster order, their values masked_frames there, their coordinates pixel indices.
-Neither has parameters (state_dict() is empty) and both are deterministic from run to run."""
+Neither has parameters (state_dict() is empty) and both are deterministic from run to run.
+
+Uncertainty and validation (csrc/krig_uq.hip): KrigingGenerator.forward_uq adds the kriging variance map, and
+cross_validate of either model predicts every gauge from the frame's other gauges (leave-one-out) and scores the residuals."""
 from __future__ import annotations
 
 import logging
+import math
 from typing import Any, Dict
 
 import torch
@@ -30,6 +34,33 @@ def _frames(masked_frames, masks, who):
         raise RuntimeError(f"{who} runs on the HIP path only (CUDA tensors)")
     b, t, _, h, w = masked_frames.shape
     return masked_frames.reshape(b, t, h, w).contiguous().float(), masks.reshape(b, t, h, w).contiguous().float()
+
+
+class LOOResult:
+    """Leave-one-out cross-validation of one call.  pix, z, pred, var: (B*T, cap) on the device, rows as ops.krig_compact packs them
+    (pred is NaN where a frame has no model or fewer than 2 gauges, everything is 0 past the frame's count; var is None for IDW);
+    counts (B*T,) int32; status: the kriging systems' factorisation flags (None for IDW)."""
+
+    def __init__(self, pix, z, pred, var, counts, status):
+        self.pix, self.z, self.pred, self.var, self.counts, self.status = pix, z, pred, var, counts, status
+
+    def sums(self) -> torch.Tensor:
+        """(5,) fp64 on the device: n, sum e, sum |e|, sum e^2, sum e^2 / var over the gauges with a prediction, e = z - pred."""
+        return ops.loo_scores(self.z, self.pred, self.var, self.counts)
+
+    def scores(self) -> Dict[str, float]:
+        """n, ME, MAE, RMSE (and MSDR = mean(e^2 / var) where there is a variance) of those gauges."""
+        return loo_summary(self.sums().cpu().tolist(), self.var is not None)
+
+
+def loo_summary(sums, with_var: bool) -> Dict[str, float]:
+    """The scores of ops.loo_scores' sums (n, sum e, sum |e|, sum e^2, sum e^2 / var); NaN when no gauge has a prediction."""
+    n = int(sums[0])
+    d = float(n) if n else math.nan
+    out = {"n": n, "ME": sums[1] / d, "MAE": sums[2] / d, "RMSE": math.sqrt(sums[3] / d)}
+    if with_var:
+        out["MSDR"] = sums[4] / d
+    return out
 
 
 class _ClassicalBase(nn.Module):
@@ -84,6 +115,21 @@ class KrigingGenerator(_ClassicalBase):
 
     @torch.no_grad()
     def forward(self, masked_frames, masks):
+        return self._krige(masked_frames, masks)["pred"]
+
+    @torch.no_grad()
+    def forward_uq(self, masked_frames, masks):
+        """(prediction, kriging variance), both (B, T, 1, H, W).  The prediction is forward()'s; the variance is 0 on a gauge pixel and
+        NaN over a frame without a model (no gauges, a degenerate fitted sample, a failed factorisation)."""
+        out = self._krige(masked_frames, masks, variance=True)
+        return out["pred"], out["var"]
+
+    @torch.no_grad()
+    def cross_validate(self, masked_frames, masks) -> LOOResult:
+        """Leave-one-out at every gauge from the one factorisation per system (Dubrule 1983): no refits."""
+        return self._krige(masked_frames, masks, predict=False, loo=True)["loo"]
+
+    def _krige(self, masked_frames, masks, predict=True, variance=False, loo=False):
         b, t, _, h, w = masked_frames.shape
         pix, z, info, counts, shared = self._compact(masked_frames, masks)
         f, dev = b * t, masked_frames.device
@@ -97,21 +143,38 @@ class KrigingGenerator(_ClassicalBase):
         r = t if (shared and self.share_sets) else 1
         nsys = f // r
         np_ = max(ops.KRIG_TILE, _round_up(int(counts.max()), ops.KRIG_TILE))
-        per = max(1, min(nsys, _FACTOR_BYTES // (np_ * np_ * 4)))
+        inverse = variance or loo            # these also hold the factor's inverse: two workspaces per system
+        per = max(1, min(nsys, _FACTOR_BYTES // (np_ * np_ * 4 * (2 if inverse else 1))))
         work = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
+        winv = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32) if inverse else None
         status = torch.zeros(nsys, device=dev, dtype=torch.int32)
         alpha = torch.empty(f, pix.shape[1], device=dev, dtype=torch.float32)
         mean = torch.empty(f, device=dev, dtype=torch.float32)
+        var = torch.empty(f, h * w, device=dev, dtype=torch.float32) if variance else None
+        loo_pred, loo_var = (torch.empty_like(z), torch.empty_like(z)) if loo else (None, None)
         for s0 in range(0, nsys, per):
             ns = min(per, nsys - s0)
-            ops.krig_factor(pix, info, params, self.variogram_model, s0 * r, r, t, ns, np_, work, status[s0:s0 + ns])
-            ops.krig_solve(work, z, info, status[s0:s0 + ns], cand, s0 * r, r, t, ns, np_, alpha, mean)
-        out = ops.krig_predict(pix, alpha, mean, info, params, self.variogram_model, r, t, h, w)
+            st = status[s0:s0 + ns]
+            ops.krig_factor(pix, info, params, self.variogram_model, s0 * r, r, t, ns, np_, work, st)
+            sol = ops.krig_solve(work, z, info, st, cand, s0 * r, r, t, ns, np_, alpha, mean)
+            if inverse:
+                ops.krig_invert(work, ns, np_, winv)
+            if variance:
+                ops.krig_variance(winv, sol, pix, info, st, cand, params, self.variogram_model, s0 * r, r, t, ns, np_, h, w, var)
+            if loo:
+                ops.krig_loo(winv, sol, alpha, z, info, st, cand, s0 * r, r, t, ns, np_, loo_pred, loo_var)
+        out = {}
+        if predict:
+            out["pred"] = ops.krig_predict(pix, alpha, mean, info, params, self.variogram_model, r, t, h, w).view(b, t, 1, h, w)
         self.last_status = status
         failed = int(status.sum()) * r
         if failed:
             logging.warning("kriging: %d frame(s) met a non-positive pivot and predict their gauge mean", failed)
-        return out.view(b, t, 1, h, w)
+        if variance:
+            out["var"] = var.view(b, t, 1, h, w)
+        if loo:
+            out["loo"] = LOOResult(pix, z, loo_pred, loo_var, info[:f], status)
+        return out
 
 
 class IDWGenerator(_ClassicalBase):
@@ -128,6 +191,12 @@ class IDWGenerator(_ClassicalBase):
         b, t, _, h, w = masked_frames.shape
         pix, z, info, _, _ = self._compact(masked_frames, masks)
         return ops.idw_all(pix, z, info, h, w, self.power).view(b, t, 1, h, w)
+
+    @torch.no_grad()
+    def cross_validate(self, masked_frames, masks) -> LOOResult:
+        """Leave-one-out at every gauge: the same weights over the frame's other gauges."""
+        pix, z, info, _, _ = self._compact(masked_frames, masks)
+        return LOOResult(pix, z, ops.idw_loo(pix, z, info, self.power), None, info[:pix.shape[0]], None)
 
 
 CLASSICAL = {"kriging": KrigingGenerator, "idw": IDWGenerator}

@@ -1580,7 +1580,8 @@ def krig_factor(pix, info, params, model, f0, R, T, nsys, np_, L, status):
 
 
 def krig_solve(L, z, info, status, cand, f0, R, T, nsys, np_, alpha, mean):
-    """Dual coefficients alpha (F, cap) and mean (F,) of the frames of the nsys factored systems (written in place)."""
+    """Dual coefficients alpha (F, cap) and mean (F,) of the frames of the nsys factored systems (written in place).  Returns the fp64
+    solutions sol (nsys, R + 1, np_): row 0 is u = K^-1 1, row 1 + t is K^-1 z of the system's frame t."""
     lib = _hip.load()
     F, cap = z.shape
     _krig_t("krig_solve", L, torch.float32)
@@ -1597,6 +1598,7 @@ def krig_solve(L, z, info, status, cand, f0, R, T, nsys, np_, alpha, mean):
     sol = torch.empty(nsys, R + 1, np_, device=z.device, dtype=torch.float64)
     _hip.check(lib.p2i_krig_solve(_ptr(L), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), f0, R, T, nsys, np_, cap, _ptr(sol), _ptr(alpha),
                                   _ptr(mean), _stream()), "p2i_krig_solve")
+    return sol
 
 
 def krig_predict(pix, alpha, mean, info, params, model, R, T, H, W):
@@ -1626,6 +1628,97 @@ def idw_all(pix, z, info, H, W, power=2.0):
         raise ValueError("idw_all: power must be positive")
     out = torch.empty(F, H * W, device=pix.device, dtype=torch.float32)
     _hip.check(lib.p2i_idw_all(_ptr(pix), _ptr(z), _ptr(info), F, H, W, cap, float(power), _ptr(out), _stream()), "p2i_idw_all")
+    return out
+
+
+# ---- kriging variance and leave-one-out cross-validation (csrc/krig_uq.hip)
+LOO_NSUM = 5             # (n, sum e, sum |e|, sum e^2, sum e^2 / var)
+
+
+def krig_invert(L, nsys, np_, Winv):
+    """Winv (>= nsys * np_ * np_ fp32, not L) = the inverse of each system's Cholesky factor: lower triangular, identity on the padding."""
+    lib = _hip.load()
+    _krig_t("krig_invert", L, torch.float32)
+    _krig_t("krig_invert", Winv, torch.float32)
+    if nsys < 1 or np_ < KRIG_TILE or np_ % KRIG_TILE or np_ > KRIG_MAX_CAP:
+        raise RuntimeError(f"krig_invert: bad system shape {nsys} x {np_}")
+    if min(L.numel(), Winv.numel()) < nsys * np_ * np_ or L.data_ptr() == Winv.data_ptr():
+        raise RuntimeError("krig_invert: workspace too small, or the inverse would overwrite the factor")
+    _hip.check(lib.p2i_krig_invert(_ptr(L), nsys, np_, _ptr(Winv), _stream()), "p2i_krig_invert")
+
+
+def krig_variance(Winv, sol, pix, info, status, cand, params, model, f0, R, T, nsys, np_, H, W, var):
+    """Kriging variance of the R frames of each of the nsys systems into var (F, H*W), in place: c00 - |Winv k(p)|^2 +
+    (1 - u^T k(p))^2 / s clamped at 0, exactly 0 on a gauge pixel, NaN for a system without a model."""
+    lib = _hip.load()
+    F, cap = pix.shape
+    _krig_t("krig_variance", Winv, torch.float32)
+    _krig_t("krig_variance", sol, torch.float64, (nsys, R + 1, np_))
+    _krig_t("krig_variance", pix, torch.int32)
+    _krig_t("krig_variance", info, torch.int32, (2 * F,))
+    _krig_t("krig_variance", status, torch.int32, (nsys,))
+    if cand is not None:
+        _krig_t("krig_variance", cand, torch.int32, (F // T,))
+    _krig_t("krig_variance", params, torch.float32, (F // T, 4))
+    _krig_t("krig_variance", var, torch.float32, (F, H * W))
+    _krig_sys("krig_variance", f0, R, T, nsys, F, np_, cap)
+    if Winv.numel() < nsys * np_ * np_:
+        raise RuntimeError("krig_variance: inverse workspace too small")
+    _hip.check(lib.p2i_krig_variance(_ptr(Winv), _ptr(sol), _ptr(pix), _ptr(info), _ptr(status), _ptr(cand), _ptr(params), int(model), f0,
+                                     R, T, nsys, np_, H, W, cap, _ptr(var), _stream()), "p2i_krig_variance")
+
+
+def krig_loo(Winv, sol, alpha, z, info, status, cand, f0, R, T, nsys, np_, pred, var):
+    """Leave-one-out prediction and variance of every gauge of the nsys systems' frames into pred, var (F, cap), in place."""
+    lib = _hip.load()
+    F, cap = z.shape
+    _krig_t("krig_loo", Winv, torch.float32)
+    _krig_t("krig_loo", sol, torch.float64, (nsys, R + 1, np_))
+    _krig_t("krig_loo", alpha, torch.float32, (F, cap))
+    _krig_t("krig_loo", z, torch.float32)
+    _krig_t("krig_loo", info, torch.int32, (2 * F,))
+    _krig_t("krig_loo", status, torch.int32, (nsys,))
+    if cand is not None:
+        _krig_t("krig_loo", cand, torch.int32, (F // T,))
+    _krig_t("krig_loo", pred, torch.float32, (F, cap))
+    _krig_t("krig_loo", var, torch.float32, (F, cap))
+    _krig_sys("krig_loo", f0, R, T, nsys, F, np_, cap)
+    if Winv.numel() < nsys * np_ * np_:
+        raise RuntimeError("krig_loo: inverse workspace too small")
+    colsq = torch.empty(nsys, np_, device=z.device, dtype=torch.float64)
+    _hip.check(lib.p2i_krig_loo(_ptr(Winv), _ptr(sol), _ptr(alpha), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), f0, R, T, nsys, np_, cap,
+                                _ptr(colsq), _ptr(pred), _ptr(var), _stream()), "p2i_krig_loo")
+
+
+def idw_loo(pix, z, info, power=2.0):
+    """pred (F, cap): all-gauge IDW at each gauge from the frame's other gauges (NaN with fewer than 2, 0 past the count)."""
+    lib = _hip.load()
+    F, cap = pix.shape
+    _krig_t("idw_loo", pix, torch.int32)
+    _krig_t("idw_loo", z, torch.float32, (F, cap))
+    _krig_t("idw_loo", info, torch.int32, (2 * F,))
+    if not power > 0:
+        raise ValueError("idw_loo: power must be positive")
+    pred = torch.empty(F, cap, device=pix.device, dtype=torch.float32)
+    _hip.check(lib.p2i_idw_loo(_ptr(pix), _ptr(z), _ptr(info), F, cap, float(power), _ptr(pred), _stream()), "p2i_idw_loo")
+    return pred
+
+
+def loo_scores(z, pred, var, counts):
+    """(LOO_NSUM,) fp64 on the device: n, sum e, sum |e|, sum e^2, sum e^2 / var with e = z - pred over the entries i < counts[f] of
+    the (F, cap) arrays whose pred (and var; None: the last sum is 0) is not NaN."""
+    lib = _hip.load()
+    F, cap = z.shape
+    _krig_t("loo_scores", z, torch.float32)
+    _krig_t("loo_scores", pred, torch.float32, (F, cap))
+    if var is not None:
+        _krig_t("loo_scores", var, torch.float32, (F, cap))
+    _krig_t("loo_scores", counts, torch.int32)
+    if counts.numel() < F:
+        raise RuntimeError("loo_scores: one count per frame expected")
+    part = torch.empty(F, LOO_NSUM, device=z.device, dtype=torch.float64)
+    out = torch.empty(LOO_NSUM, device=z.device, dtype=torch.float64)
+    _hip.check(lib.p2i_loo_scores(_ptr(z), _ptr(pred), _ptr(var), _ptr(counts), F, cap, _ptr(part), _ptr(out), _stream()), "p2i_loo_scores")
     return out
 
 

@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 from p2igan_bench.data import zarr_lite  # noqa: E402
 from p2igan_bench.data.dataloader import P2IDataModule  # noqa: E402
-from p2igan_bench.inference import infer_event, infer_event_chunks  # noqa: E402
+from p2igan_bench.inference import infer_event, infer_event_chunks, infer_event_variance  # noqa: E402
 from p2igan_bench.models import CLASSICAL, build_generator  # noqa: E402
 
 
@@ -37,6 +37,8 @@ def parse_args(argv=None):
     p.add_argument("--overlap", type=int, default=12)
     p.add_argument("--output-scale", type=float, default=255.0)
     p.add_argument("--overwrite", action="store_true")
+    p.add_argument("--variance-output", type=Path, default=None,
+                   help="kriging only: a second zarr with the kriging variance x output-scale^2 under the same event keys")
     p.add_argument("--log-level", type=str, default="INFO")
     return p.parse_args(argv)
 
@@ -71,6 +73,8 @@ def main(argv=None):
         raise RuntimeError("the MI355X path needs a GPU: there is no CPU fallback")
     name = cfg.get("model", {}).get("name", "model")
     classical = str(name).lower() in CLASSICAL         # parameter-free: no checkpoint to resolve or load
+    if args.variance_output is not None and str(name).lower() != "kriging":
+        raise RuntimeError(f"--variance-output needs model.name 'kriging', the one model with a variance (got '{name}')")
     ckpt = None if classical else resolve_checkpoint(cfg, args)
     loader = P2IDataModule(cfg).test_dataloader()
     if loader is None or len(loader.dataset) == 0:
@@ -80,6 +84,10 @@ def main(argv=None):
         if not args.overwrite:
             raise FileExistsError(f"Output already exists: {out}")
         shutil.rmtree(out)
+    if args.variance_output is not None and args.variance_output.exists():
+        if not args.overwrite:
+            raise FileExistsError(f"Output already exists: {args.variance_output}")
+        shutil.rmtree(args.variance_output)
     group = zarr_lite.Group(str(out), "w")
     group.attrs.update({"config_path": str(args.config), "checkpoint": None if ckpt is None else str(ckpt), "model_name": name,
                         "data_root": cfg.get("data", {}).get("test", {}).get("data_root"), "passes": int(args.passes),
@@ -89,7 +97,7 @@ def main(argv=None):
         state = torch.load(ckpt, map_location=dev, weights_only=True)
         G.load_state_dict(state["generator"] if isinstance(state, dict) and "generator" in state else state)
     G.eval()
-    results = {}
+    results, variances = {}, {}
     for p in range(max(1, args.passes)):
         t0 = time.time()
         for i, batch in enumerate(loader):
@@ -99,11 +107,20 @@ def main(argv=None):
             else:
                 comp = infer_event(G, masked, masks, max(1, args.stride), max(0, args.overlap), args.output_scale).cpu().numpy()
             key = f"event_{i + 1:02d}"
+            if args.variance_output is not None and p == 0:       # a function of gauge positions and variogram: the same every pass
+                variances[key] = infer_event_variance(G, masked, masks, max(1, args.stride), args.output_scale).cpu().numpy()
             results[key] = comp if p == 0 else results[key] + (comp - results[key]) / float(p + 1)
             if (i + 1) % max(1, args.log_every) == 0:
                 logging.info("Pass %d | %d samples | %.2f samples/sec", p + 1, i + 1, (i + 1) / max(time.time() - t0, 1e-6))
     for key, comp in results.items():
         group.create_dataset(key, comp.astype(np.float32), chunks=comp.shape)
+    if args.variance_output is not None:
+        vgroup = zarr_lite.Group(str(args.variance_output), "w")
+        vgroup.attrs.update({"config_path": str(args.config), "model_name": name, "quantity": "kriging_variance",
+                             "data_root": cfg.get("data", {}).get("test", {}).get("data_root"), "output_scale": float(args.output_scale)})
+        for key, v in variances.items():
+            vgroup.create_dataset(key, v.astype(np.float32), chunks=v.shape)
+        logging.info("Kriging variance saved to %s", args.variance_output)
     logging.info("Inference completed. Output saved to %s", out)
 
 
