@@ -609,6 +609,37 @@ int p2i_idw_loo(const int* pix, const float* z, const int* counts, int F, int ca
 int p2i_loo_scores(const float* z, const float* pred, const float* var, const int* counts, int F, int cap, double* part, double* out,
                    void* stream);
 
+/* ---- space-time ordinary kriging (no counterpart in the reference): every pixel of every frame of a sample
+ * from all gauges of all frames of that sample, one system per sample.  Point i of a sample has pixel (y_i, x_i), frame t_i and value
+ * z_i; the points are the frames' gauges as p2i_krig_compact leaves them, frame-major.  Distance d = sqrt(dy^2 + dx^2 + kappa^2
+ * dt^2), kappa > 0 in pixels per frame, inside the covariance of the classical block; params [B][4] fp32 = (nugget, psill, range a,
+ * kappa) per sample.  pix / z / counts are p2i_krig_compact's per-frame arrays with row length fcap; cap (a multiple of 32, <= 4096)
+ * is the row length of the per-sample arrays; systems are padded to np (a multiple of 32, <= cap).  All sums run in a fixed order.
+ * The solve is p2i_krig_solve with the samples standing in for frames (F = B, R = T = 1, z = stz, counts = stcounts): a sample
+ * without gauges gets (0, 0), a degenerate or failed one its gauge mean over all its frames.
+ * p2i_stkrig_gather: stpix [B][cap] ((y << 16) | x), stt [B][cap] (frame index), stz [B][cap] (all zero past the count), stcounts [B]
+ *   = the sum of the sample's frame counts (it may exceed cap: only the first cap points are stored, the caller refuses).
+ * p2i_stkrig_bins: fp64 partial bins part [B][n_tlags + 1][chunks][n_lags][3] = (pairs, sum (z_i - z_j)^2 / 2, sum h), h the SPATIAL
+ *   distance: temporal lag u = 0 holds the pairs i < j of one frame, u >= 1 all pairs (i in frame t, j in frame t + u); a pair with h
+ *   < n_lags lag_width goes to bin (u, min(floor(h / lag_width), n_lags - 1)).  n_lags <= 32, n_tlags <= 7 and < T.
+ * p2i_stkrig_fit: bins [B][n_tlags + 1][n_lags][3] (the chunks added in order), then for the 17 x 25 candidates kappa_q = 2^((q - 6) /
+ *   2), a_c = lag_width 2^((c - 6) / 3) the count-weighted least squares (nugget, psill) of gamma = nugget + psill g(sqrt(hbar^2 +
+ *   (kappa_q u)^2) / a_c) over the non-empty bins, with p2i_krig_fit's fallbacks; fit [B][5] fp64 = (nugget, psill, range, kappa,
+ *   weighted SSE) of the smallest SSE, cand [B] = its q 25 + c (the lowest on a tie) or -1 (degenerate sample), params [B][4].
+ * p2i_stkrig_factor: L [nsys][np][np] fp32 = the Cholesky factor of K = [C(d(i, j))] + nugget I of samples s0 .. s0 + nsys - 1, by
+ *   p2i_krig_factor's panel / update kernels; status[s] is set to 1 where a pivot is not > 0 (the caller zeroes it beforehand).
+ * p2i_stkrig_predict: out [B][T][H W] = mean[b] + sum_i alpha[b][i] (C(d((t, p), i)) + nugget [p = x_i and t = t_i]). */
+int p2i_stkrig_gather(const int* pix, const float* z, const int* counts, int B, int T, int fcap, int cap, int* stpix, int* stt,
+                      float* stz, int* stcounts, void* stream);
+int p2i_stkrig_bins(const int* pix, const float* z, const int* counts, int B, int T, int cap, int chunks, int n_lags, int n_tlags,
+                    double lag_width, double* part, void* stream);
+int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags, int n_tlags, double lag_width, int model, double* bins,
+                   double* fit, int* cand, float* params, void* stream);
+int p2i_stkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, int model, int s0, int nsys, int np,
+                      int cap, float* L, int* status, void* stream);
+int p2i_stkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
+                       const float* params, int model, int B, int T, int H, int W, int cap, float* out, void* stream);
+
 /* ---- scale-aware verification: fractions skill score and radially averaged power spectra (no counterpart in
  * the reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform
  * and uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <= P2I_SCALE_MAX_CROP.

@@ -500,6 +500,16 @@ __global__ __launch_bounds__(256) void idw_all_kernel(const int* __restrict__ pi
 
 using namespace p2i;
 
+// the panel / update driver over the lower tiles of nsys built systems (krig_common.h): shared with the space-time build of stkrig.hip
+void p2i::krig_factor_tiles(float* L, int nsys, int np, int* status, hipStream_t s) {
+  const int nt = np / TS;
+  for (int k = 0; k < nt; ++k) {
+    P2I_LAUNCH(krig_panel_kernel, dim3(nsys), dim3(256), 0, s, L, np, k * TS, status);
+    const int rem = nt - k - 1;
+    if (rem > 0) P2I_LAUNCH(krig_update_kernel, dim3(rem, rem, nsys), dim3(256), 0, s, L, np, k * TS);
+  }
+}
+
 extern "C" int p2i_krig_compact(const float* masked, const float* mask, int B, int T, int H, int W, int cap, int* pix, float* z, int* info,
                                 void* stream) {
   P2I_REQUIRE(masked && mask && pix && z && info, "null pointer");
@@ -536,11 +546,7 @@ extern "C" int p2i_krig_factor(const int* pix, const int* counts, const float* p
   hipStream_t s = (hipStream_t)stream;
   const int nt = np / TS;
   P2I_LAUNCH(krig_build_kernel, dim3(nt, nt, nsys), dim3(256), 0, s, pix, counts, params, model, f0, R, T, cap, np, L);
-  for (int k = 0; k < nt; ++k) {
-    P2I_LAUNCH(krig_panel_kernel, dim3(nsys), dim3(256), 0, s, L, np, k * TS, status);
-    const int rem = nt - k - 1;
-    if (rem > 0) P2I_LAUNCH(krig_update_kernel, dim3(rem, rem, nsys), dim3(256), 0, s, L, np, k * TS);
-  }
+  krig_factor_tiles(L, nsys, np, status, s);
   return launch_status();
 }
 

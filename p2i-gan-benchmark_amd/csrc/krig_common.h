@@ -39,4 +39,8 @@ static inline int krig_sys_check(int f0, int R, int T, int nsys, int np, int cap
   return P2I_OK;
 }
 
+// classical.hip: the right-looking tiled Cholesky (panel, trailing update per 32 columns) over nsys systems whose lower tiles are
+// already built in L [nsys][np][np]; status[s] is set where a pivot is not > 0.  The caller checks launch_status().
+void krig_factor_tiles(float* L, int nsys, int np, int* status, hipStream_t s);
+
 }  // namespace p2i

@@ -1,0 +1,356 @@
+// Space-time ordinary kriging: every pixel of every frame of a sample from ALL gauges of ALL frames of that
+// sample, one system per sample, with the metric space-time distance d = sqrt(dy^2 + dx^2 + kappa^2 dt^2) (kappa in pixels per frame)
+// inside the covariance of krig_common.h.  Stages: per-frame compaction (classical.hip) -> gather into per-sample point sets ->
+// [space-time variogram bins -> (kappa, range) candidate fit] -> covariance build + the shared tiled Cholesky (classical.hip) ->
+// p2i_krig_solve with the samples standing in for frames -> predictor.
+//
+// Number formats as in classical.hip: K, its factor and c0 are fp32; the predictor's sum over the points is fp64; the variogram is
+// fp64 throughout.  Every sum has a fixed order (no atomics).
+#include "krig_common.h"
+
+namespace p2i {
+namespace {
+
+constexpr int MAX_LAGS = 32;
+constexpr int MAX_TLAGS = 7;      // temporal lags u = 0 .. 7
+constexpr int N_RANGE = 25;       // range candidates a_c = w 2^((c - 6) / 3)
+constexpr int N_KAPPA = 17;       // anisotropy candidates kappa_q = 2^((q - 6) / 2) px / frame
+constexpr int N_CAND = N_RANGE * N_KAPPA;
+constexpr int BIN_THREADS = 64;
+constexpr int FG = 8;             // target frames fed from one spatial d^2 of the predictor
+
+// the one distance of the build and of the predictor (an explicit fma: both round alike, so a gauge is reproduced in its own frame)
+__device__ __forceinline__ float st_dist(int d2, int dt, float k2) {
+  const float ft = (float)dt;
+  return sqrtf(fmaf(k2, ft * ft, (float)d2));
+}
+
+__device__ __forceinline__ double g_d(double r, int model) {
+  return model == 0 ? 1.0 - exp(-r) : (r < 1.0 ? 1.5 * r - 0.5 * r * r * r : 1.0);
+}
+
+// ---- gather: one workgroup per sample walks its T frames in order (the running offset is the exclusive scan of their counts) and
+// appends each frame's gauges; stpix / stt / stz [B][cap] are zero past the count, stcounts[b] = the sum (it may exceed cap: the host
+// has refused before)
+__global__ __launch_bounds__(256) void stkrig_gather_kernel(const int* __restrict__ pix, const float* __restrict__ z,
+                                                            const int* __restrict__ counts, int T, int fcap, int cap,
+                                                            int* __restrict__ stpix, int* __restrict__ stt, float* __restrict__ stz,
+                                                            int* __restrict__ stcounts) {
+  const int b = blockIdx.x;
+  int off = 0;
+  for (int t = 0; t < T; ++t) {
+    const int f = b * T + t;
+    const int n = min(counts[f], fcap);
+    for (int i = threadIdx.x; i < n; i += 256) {
+      const int o = off + i;
+      if (o < cap) {
+        stpix[(size_t)b * cap + o] = pix[(size_t)f * fcap + i];
+        stt[(size_t)b * cap + o] = t;
+        stz[(size_t)b * cap + o] = z[(size_t)f * fcap + i];
+      }
+    }
+    off += n;
+  }
+  for (int o = min(off, cap) + threadIdx.x; o < cap; o += 256) {
+    stpix[(size_t)b * cap + o] = 0;
+    stt[(size_t)b * cap + o] = 0;
+    stz[(size_t)b * cap + o] = 0.f;
+  }
+  if (threadIdx.x == 0) stcounts[b] = off;
+}
+
+// ---- space-time variogram bins.  Workgroup (chunk, u, sample) takes temporal lag u: for every frame t < T - u the rows i = chunk
+// (mod chunks) of frame t against the gauges j of frame t + u (j > i when u = 0, all j otherwise), binned by the SPATIAL distance.
+// One temporal lag per workgroup keeps krig_bins_kernel's [bin][thread] LDS image (40 KiB) at its size with all 32 lags.
+// part [B][n_tlags + 1][chunks][n_lags][3] = (pairs, sum of (z_i - z_j)^2 / 2, sum of h)
+__global__ __launch_bounds__(BIN_THREADS) void stkrig_bins_kernel(const int* __restrict__ pix, const float* __restrict__ z,
+                                                                  const int* __restrict__ counts, int T, int cap, int n_lags,
+                                                                  double lagw, double* __restrict__ part) {
+  __shared__ double sg[MAX_LAGS][BIN_THREADS];
+  __shared__ double sh[MAX_LAGS][BIN_THREADS];
+  __shared__ unsigned sc[MAX_LAGS][BIN_THREADS];
+  const int b = blockIdx.z, u = blockIdx.y, nu = gridDim.y, ch = blockIdx.x, nch = gridDim.x, tid = threadIdx.x;
+  for (int k = 0; k < n_lags; ++k) {
+    sg[k][tid] = 0.0;
+    sh[k][tid] = 0.0;
+    sc[k][tid] = 0u;
+  }
+  const double hmax = (double)n_lags * lagw;
+  for (int t = 0; t + u < T; ++t) {
+    const int fa = b * T + t, fb = fa + u;
+    const int na = min(counts[fa], cap), nb = min(counts[fb], cap);
+    const int* pa = pix + (size_t)fa * cap;
+    const int* pb = pix + (size_t)fb * cap;
+    const float* za = z + (size_t)fa * cap;
+    const float* zb = z + (size_t)fb * cap;
+    for (int i = ch; i < na; i += nch) {
+      const int pi = pa[i];
+      const double zi = (double)za[i];
+      for (int j = (u == 0 ? i + 1 : 0) + tid; j < nb; j += BIN_THREADS) {
+        const int pj = pb[j];
+        const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
+        const double h = sqrt((double)(dy * dy + dx * dx));
+        if (h < hmax) {
+          const int k = min((int)floor(h / lagw), n_lags - 1);
+          const double d = zi - (double)zb[j];
+          sg[k][tid] += 0.5 * (d * d);
+          sh[k][tid] += h;
+          sc[k][tid] += 1u;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < n_lags; k += BIN_THREADS) {
+    double g = 0.0, h = 0.0, c = 0.0;
+    for (int t = 0; t < BIN_THREADS; ++t) {
+      g += sg[k][t];
+      h += sh[k][t];
+      c += (double)sc[k][t];
+    }
+    double* o = part + ((((size_t)b * nu + u) * nch + ch) * n_lags + k) * 3;
+    o[0] = c;
+    o[1] = g;
+    o[2] = h;
+  }
+}
+
+// ---- fit: one workgroup per sample.  Adds the chunks' partial bins in order, then candidate q 25 + c fits (nugget, psill) of
+// gamma = nugget + psill g(sqrt(hbar^2 + (kappa_q u)^2) / a_c) by krig_fit_kernel's count-weighted normal equations and fallbacks;
+// thread 0 keeps the smallest SSE (lowest q 25 + c on a tie, so that bins of u = 0 alone give the spatial fit with q = 0).
+// bins [B][nu][n_lags][3], fit [B][5] = (nugget, psill, range, kappa, sse), cand [B] = q 25 + c (-1: degenerate), params [B][4] fp32 =
+// (nugget, psill, range, kappa) (a harmless (0, 1, w, 1) when degenerate)
+__global__ __launch_bounds__(256) void stkrig_fit_kernel(const double* __restrict__ part, int nu, int nch, int n_lags, double lagw,
+                                                         int model, double* __restrict__ bins, double* __restrict__ fit,
+                                                         int* __restrict__ cand, float* __restrict__ params) {
+  __shared__ double sn[(MAX_TLAGS + 1) * MAX_LAGS], sgam[(MAX_TLAGS + 1) * MAX_LAGS], shb[(MAX_TLAGS + 1) * MAX_LAGS];
+  __shared__ double c_sse[N_CAND], c_nug[N_CAND], c_ps[N_CAND];
+  __shared__ int c_ok[N_CAND];
+  const int b = blockIdx.x, tid = threadIdx.x, nb = nu * n_lags;
+  for (int e = tid; e < nb; e += 256) {
+    const int u = e / n_lags, k = e % n_lags;
+    double c = 0.0, g = 0.0, h = 0.0;
+    for (int p = 0; p < nch; ++p) {
+      const double* q = part + ((((size_t)b * nu + u) * nch + p) * n_lags + k) * 3;
+      c += q[0];
+      g += q[1];
+      h += q[2];
+    }
+    double* o = bins + ((size_t)b * nb + e) * 3;
+    o[0] = c;
+    o[1] = g;
+    o[2] = h;
+    sn[e] = c;
+    sgam[e] = c > 0.0 ? g / c : 0.0;
+    shb[e] = c > 0.0 ? h / c : 0.0;
+  }
+  __syncthreads();
+  for (int cd = tid; cd < N_CAND; cd += 256) {
+    const double kap = exp2((double)(cd / N_RANGE - 6) * 0.5);
+    const double a = lagw * exp2((double)(cd % N_RANGE - 6) / 3.0);
+    double S0 = 0.0, S1 = 0.0, S2 = 0.0, T0 = 0.0, T1 = 0.0;
+    for (int e = 0; e < nb; ++e) {
+      if (!(sn[e] > 0.0)) continue;
+      const double ku = kap * (double)(e / n_lags);
+      const double d = e < n_lags ? shb[e] : sqrt(shb[e] * shb[e] + ku * ku);
+      const double g = g_d(d / a, model);
+      S0 += sn[e];
+      S1 += sn[e] * g;
+      S2 += sn[e] * g * g;
+      T0 += sn[e] * sgam[e];
+      T1 += sn[e] * g * sgam[e];
+    }
+    const double det = S0 * S2 - S1 * S1;
+    double nug = -1.0, ps = 0.0;
+    if (det > 1e-12 * S0 * S2) {
+      ps = (S0 * T1 - S1 * T0) / det;
+      nug = (T0 - ps * S1) / S0;
+    }
+    if (nug < 0.0) {
+      nug = 0.0;
+      ps = S2 > 0.0 ? T1 / S2 : 0.0;
+    }
+    double sse = 0.0;
+    for (int e = 0; e < nb; ++e) {
+      if (!(sn[e] > 0.0)) continue;
+      const double ku = kap * (double)(e / n_lags);
+      const double d = e < n_lags ? shb[e] : sqrt(shb[e] * shb[e] + ku * ku);
+      const double r = sgam[e] - nug - ps * g_d(d / a, model);
+      sse += sn[e] * r * r;
+    }
+    c_ok[cd] = (S0 > 0.0 && ps > 0.0) ? 1 : 0;
+    c_sse[cd] = sse;
+    c_nug[cd] = nug;
+    c_ps[cd] = ps;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int best = -1;
+    for (int c = 0; c < N_CAND; ++c)
+      if (c_ok[c] && (best < 0 || c_sse[c] < c_sse[best])) best = c;
+    double* o = fit + (size_t)b * 5;
+    float* pf = params + (size_t)b * 4;
+    cand[b] = best;
+    if (best >= 0) {
+      const double kap = exp2((double)(best / N_RANGE - 6) * 0.5);
+      const double a = lagw * exp2((double)(best % N_RANGE - 6) / 3.0);
+      o[0] = c_nug[best];
+      o[1] = c_ps[best];
+      o[2] = a;
+      o[3] = kap;
+      o[4] = c_sse[best];
+      pf[0] = (float)c_nug[best];
+      pf[1] = (float)c_ps[best];
+      pf[2] = (float)a;
+      pf[3] = (float)kap;
+    } else {
+      o[0] = o[1] = o[2] = o[3] = o[4] = 0.0;
+      pf[0] = 0.f;
+      pf[1] = 1.f;
+      pf[2] = (float)lagw;
+      pf[3] = 1.f;
+    }
+  }
+}
+
+// ---- covariance matrix of the point set of sample s0 + s, lower tiles only; identity on the padding (krig_build_kernel's layout)
+__global__ __launch_bounds__(256) void stkrig_build_kernel(const int* __restrict__ stpix, const int* __restrict__ stt,
+                                                           const int* __restrict__ stcounts, const float* __restrict__ params, int model,
+                                                           int s0, int cap, int np, float* __restrict__ A) {
+  if (blockIdx.x > blockIdx.y) return;
+  const int s = blockIdx.z, b = s0 + s;
+  const int n = min(stcounts[b], np);
+  const float nug = params[b * 4], psill = params[b * 4 + 1], a = params[b * 4 + 2], kap = params[b * 4 + 3];
+  const float k2 = kap * kap;
+  const int* px = stpix + (size_t)b * cap;
+  const int* pt = stt + (size_t)b * cap;
+  float* As = A + (size_t)s * np * np;
+  const int j = blockIdx.x * TS + (threadIdx.x & 31);
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    const int i = blockIdx.y * TS + (threadIdx.x >> 5) + 8 * rr;
+    float v = i == j ? 1.f : 0.f;
+    if (i < n && j < n) {
+      const int pi = px[i], pj = px[j];
+      const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
+      v = cov_f(st_dist(dy * dy + dx * dx, pt[i] - pt[j], k2), psill, a, model) + (i == j ? nug : 0.f);
+    }
+    As[(size_t)i * np + j] = v;
+  }
+}
+
+// ---- predictor: out[b][t][p] = mean[b] + sum_i alpha[b][i] c0((t, p), i), one pixel per thread.  The points are staged in LDS PCHUNK
+// at a time; the integer spatial d^2 of a (pixel, point) pair is taken once and feeds the FG target frames of the group
+// (blockIdx.z), each adding kappa^2 (t - t_i)^2.  Spherical: a pair spatially beyond the range adds nothing to any frame.
+__global__ __launch_bounds__(256) void stkrig_predict_kernel(const int* __restrict__ stpix, const int* __restrict__ stt,
+                                                             const float* __restrict__ alpha, const float* __restrict__ mean,
+                                                             const int* __restrict__ stcounts, const float* __restrict__ params,
+                                                             int model, int T, int W, int HW, int cap, float* __restrict__ out) {
+  __shared__ int spix[PCHUNK];
+  __shared__ int st[PCHUNK];
+  __shared__ float sa[PCHUNK];
+  const int b = blockIdx.y, t0 = blockIdx.z * FG;
+  const int nr = min(FG, T - t0);
+  const int n = min(stcounts[b], cap);
+  const float nug = params[b * 4], psill = params[b * 4 + 1], a = params[b * 4 + 2], kap = params[b * 4 + 3];
+  const float k2 = kap * kap;
+  const float a2 = model == 1 ? a * a : 3.0e38f;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int py = p / W, px = p % W;
+  double acc[FG];
+#pragma unroll
+  for (int q = 0; q < FG; ++q) acc[q] = 0.0;
+  for (int i0 = 0; i0 < n; i0 += PCHUNK) {
+    __syncthreads();
+    if (threadIdx.x < PCHUNK) {
+      const bool in = i0 + (int)threadIdx.x < n;
+      const size_t e = (size_t)b * cap + i0 + threadIdx.x;
+      spix[threadIdx.x] = in ? stpix[e] : 0;
+      st[threadIdx.x] = in ? stt[e] : 0;
+      sa[threadIdx.x] = in ? alpha[e] : 0.f;
+    }
+    __syncthreads();
+    const int cnt = min(PCHUNK, n - i0);
+    for (int i = 0; i < cnt; ++i) {
+      const int g = spix[i];
+      const int dy = py - (g >> 16), dx = px - (g & 0xffff);
+      const int d2 = dy * dy + dx * dx;
+      if ((float)d2 >= a2) continue;
+      const int dt0 = t0 - st[i];
+      const double ai = (double)sa[i];
+#pragma unroll
+      for (int q = 0; q < FG; ++q) {
+        const int dt = dt0 + q;
+        const float c0 = cov_f(st_dist(d2, dt, k2), psill, a, model) + ((d2 | dt) == 0 ? nug : 0.f);
+        acc[q] = fma(ai, (double)c0, acc[q]);
+      }
+    }
+  }
+  if (p < HW) {
+    const double m = (double)mean[b];
+#pragma unroll
+    for (int q = 0; q < FG; ++q)
+      if (q < nr) out[((size_t)b * T + t0 + q) * HW + p] = (float)(m + acc[q]);
+  }
+}
+
+}  // namespace
+}  // namespace p2i
+
+using namespace p2i;
+
+extern "C" int p2i_stkrig_gather(const int* pix, const float* z, const int* counts, int B, int T, int fcap, int cap, int* stpix,
+                                 int* stt, float* stz, int* stcounts, void* stream) {
+  P2I_REQUIRE(pix && z && counts && stpix && stt && stz && stcounts, "null pointer");
+  P2I_REQUIRE(B > 0 && T > 0 && (long long)B * T <= 65535, "bad sample shape %d x %d", B, T);
+  P2I_REQUIRE(fcap > 0 && cap > 0 && cap % TS == 0 && cap <= MAX_NP, "cap must be a multiple of %d, at most %d (got %d)", TS, MAX_NP, cap);
+  P2I_LAUNCH(stkrig_gather_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, pix, z, counts, T, fcap, cap, stpix, stt, stz, stcounts);
+  return launch_status();
+}
+
+extern "C" int p2i_stkrig_bins(const int* pix, const float* z, const int* counts, int B, int T, int cap, int chunks, int n_lags,
+                               int n_tlags, double lag_width, double* part, void* stream) {
+  P2I_REQUIRE(pix && z && counts && part, "null pointer");
+  P2I_REQUIRE(B > 0 && B <= 65535 && T > 0 && (long long)B * T <= 65535 && cap > 0 && chunks > 0 && chunks <= 1024, "bad variogram shape");
+  P2I_REQUIRE(n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "n_lags must be 1..%d with a positive lag width", MAX_LAGS);
+  P2I_REQUIRE(n_tlags >= 0 && n_tlags <= MAX_TLAGS && n_tlags < T, "n_tlags must be 0..%d and below T", MAX_TLAGS);
+  P2I_LAUNCH(stkrig_bins_kernel, dim3(chunks, n_tlags + 1, B), dim3(BIN_THREADS), 0, (hipStream_t)stream, pix, z, counts, T, cap, n_lags,
+             lag_width, part);
+  return launch_status();
+}
+
+extern "C" int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags, int n_tlags, double lag_width, int model, double* bins,
+                              double* fit, int* cand, float* params, void* stream) {
+  P2I_REQUIRE(part && bins && fit && cand && params, "null pointer");
+  P2I_REQUIRE(B > 0 && chunks > 0 && n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "bad fit shape");
+  P2I_REQUIRE(n_tlags >= 0 && n_tlags <= MAX_TLAGS, "n_tlags must be 0..%d", MAX_TLAGS);
+  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
+  P2I_LAUNCH(stkrig_fit_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, part, n_tlags + 1, chunks, n_lags, lag_width, model, bins, fit,
+             cand, params);
+  return launch_status();
+}
+
+extern "C" int p2i_stkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, int model, int s0, int nsys,
+                                 int np, int cap, float* L, int* status, void* stream) {
+  P2I_REQUIRE(stpix && stt && stcounts && params && L && status, "null pointer");
+  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
+  if (int rc = krig_sys_check(s0, 1, 1, nsys, np, cap)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int nt = np / TS;
+  P2I_LAUNCH(stkrig_build_kernel, dim3(nt, nt, nsys), dim3(256), 0, s, stpix, stt, stcounts, params, model, s0, cap, np, L);
+  krig_factor_tiles(L, nsys, np, status, s);
+  return launch_status();
+}
+
+extern "C" int p2i_stkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
+                                  const float* params, int model, int B, int T, int H, int W, int cap, float* out, void* stream) {
+  P2I_REQUIRE(stpix && stt && alpha && mean && stcounts && params && out, "null pointer");
+  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
+  P2I_REQUIRE(H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE, "bad frame shape");
+  P2I_REQUIRE(B > 0 && B <= 65535 && T > 0 && ceil_div(T, FG) <= 65535, "bad sample shape %d x %d", B, T);
+  P2I_REQUIRE(cap > 0 && cap % TS == 0 && cap <= MAX_NP, "cap must be a multiple of %d, at most %d (got %d)", TS, MAX_NP, cap);
+  const int HW = H * W;
+  P2I_LAUNCH(stkrig_predict_kernel, dim3(ceil_div(HW, 256), B, ceil_div(T, FG)), dim3(256), 0, (hipStream_t)stream, stpix, stt, alpha, mean,
+             stcounts, params, model, T, W, HW, cap, out);
+  return launch_status();
+}

@@ -140,6 +140,11 @@ SIGNATURES = {
     "p2i_krig_invert": [_P, _I, _I, _P, _P],
     "p2i_krig_variance": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "p2i_krig_loo": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "p2i_stkrig_gather": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "p2i_stkrig_bins": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F64, _P, _P],
+    "p2i_stkrig_fit": [_P, _I, _I, _I, _I, _F64, _I, _P, _P, _P, _P, _P],
+    "p2i_stkrig_factor": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "p2i_stkrig_predict": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "p2i_idw_loo": [_P, _P, _P, _I, _I, _F, _P, _P],
     "p2i_loo_scores": [_P, _P, _P, _P, _I, _I, _P, _P, _P],
     "p2i_scale_fss": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(C.c_double), _I, C.POINTER(C.c_int), _I, _I,

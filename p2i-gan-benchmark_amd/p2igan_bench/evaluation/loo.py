@@ -47,8 +47,11 @@ def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_s
     from ..models import CLASSICAL, build_generator
     name = str(cfg.get("model", {}).get("name", "model")).lower()
     if name not in CLASSICAL:
-        raise RuntimeError(f"leave-one-out cross-validation is defined for the classical baselines {sorted(CLASSICAL)} only: "
+        raise RuntimeError(f"leave-one-out cross-validation is defined for the classical baselines {sorted(set(CLASSICAL) - {'stkriging'})} only: "
                            f"model.name '{name}' is a learnt model and would need one training per gauge")
+    if name == "stkriging":
+        from ..models.classical import ST_NO_LOO
+        raise RuntimeError(ST_NO_LOO)
     dev = torch.device(device or cfg.get("device", "cuda:0"))
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise RuntimeError("the MI355X path needs a GPU: there is no CPU fallback")

@@ -6,7 +6,10 @@ of frame (b, t) are its pixels with mask != 0 in raster order, their values mask
 Neither has parameters (state_dict() is empty) and both are deterministic from run to run.
 
 Uncertainty and validation (csrc/krig_uq.hip): KrigingGenerator.forward_uq adds the kriging variance map, and
-cross_validate of either model predicts every gauge from the frame's other gauges (leave-one-out) and scores the residuals."""
+cross_validate of either model predicts every gauge from the frame's other gauges (leave-one-out) and scores the residuals.
+
+Space-time kriging (csrc/stkrig.hip): SpaceTimeKrigingGenerator kriges every pixel of every frame of a sample
+from all gauges of all frames of that sample, one system per sample, with a metric space-time covariance."""
 from __future__ import annotations
 
 import logging
@@ -64,11 +67,13 @@ def loo_summary(sums, with_var: bool) -> Dict[str, float]:
 
 
 class _ClassicalBase(nn.Module):
+    DEFAULT_MAX_POINTS = 1024
+
     def __init__(self, config: Dict[str, Any]):
         super().__init__()
         self.config = config
         mc = config.get("model", {})
-        self.max_points = int(mc.get("max_points", 1024))
+        self.max_points = int(mc.get("max_points", self.DEFAULT_MAX_POINTS))
         if not 1 <= self.max_points <= ops.KRIG_MAX_CAP:
             raise ValueError(f"model.max_points must be in [1, {ops.KRIG_MAX_CAP}] (got {self.max_points})")
 
@@ -199,4 +204,87 @@ class IDWGenerator(_ClassicalBase):
         return LOOResult(pix, z, ops.idw_loo(pix, z, info, self.power), None, info[:pix.shape[0]], None)
 
 
-CLASSICAL = {"kriging": KrigingGenerator, "idw": IDWGenerator}
+class SpaceTimeKrigingGenerator(_ClassicalBase):
+    """Ordinary kriging of every pixel of every frame of a sample from ALL gauges of ALL frames of that sample: one system per sample,
+    global in space and time, with the distance sqrt(dy^2 + dx^2 + kappa^2 dt^2) (kappa in pixels per frame) inside the covariance.
+    model.variogram = {"model", "fit": true, "n_lags": 16, "n_tlags": 3} fits (nugget, psill, range, kappa) per sample on the device;
+    {"model", "fit": false, "nugget", "psill", "range", "time_scale"} takes them as given (time_scale is kappa).  model.max_points
+    (default 4096) bounds the points of one sample.
+
+    There is no forward_uq and no cross_validate: leaving out one (site, frame) observation while the same site's neighbouring
+    frames stay in would flatter the method; the honest score is leave-one-site-out."""
+
+    DEFAULT_MAX_POINTS = 4096
+
+    def __init__(self, config: Dict[str, Any]):
+        super().__init__(config)
+        mc = config.get("model", {})
+        vg = dict(mc.get("variogram") or {})
+        name = str(vg.get("model", "exponential")).lower()
+        if name not in ops.KRIG_MODELS:
+            raise ValueError(f"model.variogram.model must be one of {sorted(ops.KRIG_MODELS)} (got '{name}')")
+        self.variogram_model = ops.KRIG_MODELS[name]
+        self.fit = bool(vg.get("fit", True))
+        self.n_lags = int(vg.get("n_lags", 16))
+        self.n_tlags = int(vg.get("n_tlags", 3))
+        if self.fit:
+            if not 1 <= self.n_lags <= ops.KRIG_MAX_LAGS:
+                raise ValueError(f"model.variogram.n_lags must be in [1, {ops.KRIG_MAX_LAGS}] (got {self.n_lags})")
+            if not 0 <= self.n_tlags <= ops.STKRIG_MAX_TLAGS:
+                raise ValueError(f"model.variogram.n_tlags must be in [0, {ops.STKRIG_MAX_TLAGS}] (got {self.n_tlags})")
+        else:
+            try:
+                self.fixed = (float(vg["nugget"]), float(vg["psill"]), float(vg["range"]), float(vg["time_scale"]))
+            except KeyError as e:
+                raise ValueError(f"model.variogram with fit=false needs nugget, psill, range and time_scale (missing {e})") from None
+            if not (self.fixed[0] >= 0 and self.fixed[1] > 0 and self.fixed[2] > 0 and self.fixed[3] > 0):
+                raise ValueError("model.variogram: nugget >= 0, psill > 0, range > 0 and time_scale > 0 are required")
+        self.last_fit = None         # {"bins", "fit", "cand", "q", "c"} device tensors of the last call (fit=true)
+        self.last_status = None      # per-sample int32 of the last call: 1 where the factorisation met a non-positive pivot
+
+    def cross_validate(self, masked_frames, masks):
+        raise RuntimeError(ST_NO_LOO)
+
+    @torch.no_grad()
+    def forward(self, masked_frames, masks):
+        b, t, _, h, w = masked_frames.shape
+        pix, z, info, counts, _ = self._compact(masked_frames, masks)
+        per_sample = counts.view(b, t).sum(dim=1)
+        if int(per_sample.max()) > self.max_points:
+            raise ValueError(f"{type(self).__name__}: a sample has {int(per_sample.max())} space-time points ({t} frames), more than "
+                             f"model.max_points = {self.max_points}: use shorter chunks (scripts/infer.py --stride)")
+        dev = masked_frames.device
+        np_ = max(ops.KRIG_TILE, _round_up(int(per_sample.max()), ops.KRIG_TILE))
+        stpix, stt, stz, stinfo = ops.stkrig_gather(pix, z, info, b, t, np_)
+        cand = None
+        if self.fit:
+            lag_width = (min(h, w) / 2.0) / self.n_lags
+            bins, fit, cand, params = ops.stkrig_variogram(pix, z, info, b, t, self.n_lags, min(self.n_tlags, t - 1), lag_width,
+                                                           self.variogram_model)
+            q = torch.div(cand, ops.KRIG_CANDIDATES, rounding_mode="floor")
+            self.last_fit = {"bins": bins, "fit": fit, "cand": cand, "q": q, "c": cand - q * ops.KRIG_CANDIDATES}
+        else:
+            params = torch.tensor(self.fixed, dtype=torch.float32).repeat(b, 1).to(dev)
+        per = max(1, min(b, _FACTOR_BYTES // (np_ * np_ * 4)))
+        work = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
+        status = torch.zeros(b, device=dev, dtype=torch.int32)
+        alpha = torch.empty(b, np_, device=dev, dtype=torch.float32)
+        mean = torch.empty(b, device=dev, dtype=torch.float32)
+        for s0 in range(0, b, per):
+            ns = min(per, b - s0)
+            st = status[s0:s0 + ns]
+            ops.stkrig_factor(stpix, stt, stinfo, params, self.variogram_model, s0, ns, np_, work, st)
+            ops.krig_solve(work, stz, stinfo, st, cand, s0, 1, 1, ns, np_, alpha, mean)      # the samples stand in for frames
+        out = ops.stkrig_predict(stpix, stt, alpha, mean, stinfo, params, self.variogram_model, t, h, w)
+        self.last_status = status
+        failed = int(status.sum())
+        if failed:
+            logging.warning("space-time kriging: %d sample(s) met a non-positive pivot and predict their gauge mean", failed)
+        return out.view(b, t, 1, h, w)
+
+
+ST_NO_LOO = ("space-time kriging ('stkriging') has no leave-one-out cross-validation: leaving out one (site, frame) observation while "
+              "the same site's neighbouring frames stay in would flatter the method; the honest score is leave-one-site-out, which "
+              "is not implemented")
+
+CLASSICAL = {"kriging": KrigingGenerator, "idw": IDWGenerator, "stkriging": SpaceTimeKrigingGenerator}

@@ -1631,6 +1631,97 @@ def idw_all(pix, z, info, H, W, power=2.0):
     return out
 
 
+# ---- space-time ordinary kriging (csrc/stkrig.hip)
+STKRIG_MAX_TLAGS = 7
+STKRIG_KAPPAS = 17       # anisotropy candidates kappa_q = 2^((q - 6) / 2) px / frame; candidate index = q * KRIG_CANDIDATES + c
+STKRIG_BIN_CHUNKS = 16   # workgroups per (sample, temporal lag) of the variogram pass (fixed: the partials are added in order)
+
+
+def stkrig_gather(pix, z, info, B, T, cap):
+    """The per-frame gauges of krig_compact as per-sample space-time point sets, frame-major: stpix, stt (frame index), stz (B, cap)
+    (zero past the count) and stinfo (2*B,) int32 whose first B entries are the samples' point counts (the rest is zero, so that it
+    stands in for krig_compact's info in krig_solve)."""
+    lib = _hip.load()
+    F = B * T
+    fcap = pix.shape[1]
+    _krig_t("stkrig_gather", pix, torch.int32, (F, fcap))
+    _krig_t("stkrig_gather", z, torch.float32, (F, fcap))
+    _krig_t("stkrig_gather", info, torch.int32, (2 * F,))
+    if cap < KRIG_TILE or cap % KRIG_TILE or cap > KRIG_MAX_CAP:
+        raise ValueError(f"stkrig_gather: cap must be a multiple of {KRIG_TILE} in [{KRIG_TILE}, {KRIG_MAX_CAP}] (got {cap})")
+    dev = pix.device
+    stpix = torch.empty(B, cap, device=dev, dtype=torch.int32)
+    stt = torch.empty(B, cap, device=dev, dtype=torch.int32)
+    stz = torch.empty(B, cap, device=dev, dtype=torch.float32)
+    stinfo = torch.zeros(2 * B, device=dev, dtype=torch.int32)
+    _hip.check(lib.p2i_stkrig_gather(_ptr(pix), _ptr(z), _ptr(info), B, T, fcap, cap, _ptr(stpix), _ptr(stt), _ptr(stz), _ptr(stinfo),
+                                     _stream()), "p2i_stkrig_gather")
+    return stpix, stt, stz, stinfo
+
+
+def stkrig_variogram(pix, z, info, B, T, n_lags, n_tlags, lag_width, model):
+    """Space-time empirical variogram per sample and its (kappa, range) candidate fit, fp64 on the device.  Returns bins (B, n_tlags + 1,
+    n_lags, 3) fp64 (pairs, sum of semivariances, sum of spatial distances), fit (B, 5) fp64 (nugget, psill, range, kappa, weighted
+    SSE), cand (B,) int32 (q * 25 + c; -1: degenerate sample) and params (B, 4) fp32 (nugget, psill, range, kappa)."""
+    lib = _hip.load()
+    F = B * T
+    cap = pix.shape[1]
+    _krig_t("stkrig_variogram", pix, torch.int32, (F, cap))
+    _krig_t("stkrig_variogram", z, torch.float32, (F, cap))
+    _krig_t("stkrig_variogram", info, torch.int32, (2 * F,))
+    if not (1 <= n_lags <= KRIG_MAX_LAGS) or not lag_width > 0:
+        raise ValueError(f"stkrig_variogram: n_lags must be 1..{KRIG_MAX_LAGS} and the lag width positive")
+    if not (0 <= n_tlags <= STKRIG_MAX_TLAGS and n_tlags < T):
+        raise ValueError(f"stkrig_variogram: n_tlags must be 0..{STKRIG_MAX_TLAGS} and below T = {T} (got {n_tlags})")
+    dev = pix.device
+    part = torch.empty(B, n_tlags + 1, STKRIG_BIN_CHUNKS, n_lags, 3, device=dev, dtype=torch.float64)
+    bins = torch.empty(B, n_tlags + 1, n_lags, 3, device=dev, dtype=torch.float64)
+    fit = torch.empty(B, 5, device=dev, dtype=torch.float64)
+    cand = torch.empty(B, device=dev, dtype=torch.int32)
+    params = torch.empty(B, 4, device=dev, dtype=torch.float32)
+    _hip.check(lib.p2i_stkrig_bins(_ptr(pix), _ptr(z), _ptr(info), B, T, cap, STKRIG_BIN_CHUNKS, n_lags, n_tlags, float(lag_width),
+                                   _ptr(part), _stream()), "p2i_stkrig_bins")
+    _hip.check(lib.p2i_stkrig_fit(_ptr(part), B, STKRIG_BIN_CHUNKS, n_lags, n_tlags, float(lag_width), int(model), _ptr(bins), _ptr(fit),
+                                  _ptr(cand), _ptr(params), _stream()), "p2i_stkrig_fit")
+    return bins, fit, cand, params
+
+
+def stkrig_factor(stpix, stt, stinfo, params, model, s0, nsys, np_, L, status):
+    """Cholesky factors of the space-time covariance systems of samples s0 .. s0 + nsys - 1 into L (>= nsys * np_ * np_ fp32); status
+    (nsys,) int32 (zeroed by the caller) is set where a pivot was not positive."""
+    lib = _hip.load()
+    B, cap = stpix.shape
+    _krig_t("stkrig_factor", stpix, torch.int32)
+    _krig_t("stkrig_factor", stt, torch.int32, (B, cap))
+    _krig_t("stkrig_factor", stinfo, torch.int32, (2 * B,))
+    _krig_t("stkrig_factor", params, torch.float32, (B, 4))
+    _krig_t("stkrig_factor", L, torch.float32)
+    _krig_t("stkrig_factor", status, torch.int32, (nsys,))
+    _krig_sys("stkrig_factor", s0, 1, 1, nsys, B, np_, cap)
+    if L.numel() < nsys * np_ * np_:
+        raise RuntimeError("stkrig_factor: factor workspace too small")
+    _hip.check(lib.p2i_stkrig_factor(_ptr(stpix), _ptr(stt), _ptr(stinfo), _ptr(params), int(model), s0, nsys, np_, cap, _ptr(L),
+                                     _ptr(status), _stream()), "p2i_stkrig_factor")
+
+
+def stkrig_predict(stpix, stt, alpha, mean, stinfo, params, model, T, H, W):
+    """out (B, T, H*W) = mean_b + sum_i alpha_i c0((t, p), i) over the sample's space-time points."""
+    lib = _hip.load()
+    B, cap = stpix.shape
+    _krig_t("stkrig_predict", stpix, torch.int32)
+    _krig_t("stkrig_predict", stt, torch.int32, (B, cap))
+    _krig_t("stkrig_predict", alpha, torch.float32, (B, cap))
+    _krig_t("stkrig_predict", mean, torch.float32, (B,))
+    _krig_t("stkrig_predict", stinfo, torch.int32, (2 * B,))
+    _krig_t("stkrig_predict", params, torch.float32, (B, 4))
+    if T < 1 or H < 1 or W < 1 or cap % KRIG_TILE or cap > KRIG_MAX_CAP:
+        raise RuntimeError(f"stkrig_predict: bad shape T {T}, {H} x {W}, cap {cap}")
+    out = torch.empty(B, T, H * W, device=stpix.device, dtype=torch.float32)
+    _hip.check(lib.p2i_stkrig_predict(_ptr(stpix), _ptr(stt), _ptr(alpha), _ptr(mean), _ptr(stinfo), _ptr(params), int(model), B, T, H, W,
+                                      cap, _ptr(out), _stream()), "p2i_stkrig_predict")
+    return out
+
+
 # ---- kriging variance and leave-one-out cross-validation (csrc/krig_uq.hip, DESIGN.md section 16)
 LOO_NSUM = 5             # (n, sum e, sum |e|, sum e^2, sum e^2 / var)
 

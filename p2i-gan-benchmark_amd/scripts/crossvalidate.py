@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Leave-one-out gauge cross-validation of a classical baseline (model.name: kriging / idw) over the test events: every gauge is
 predicted from the other gauges of its frame, which needs no gridded truth.  Writes loo.json, loo.txt and loo_data.npz
-(p2igan_bench/evaluation/loo.py)."""
+(p2igan_bench/evaluation/loo.py).  The space-time baseline `stkriging` is refused: its honest score is
+leave-one-site-out, which is not built."""
 from __future__ import annotations
 
 import argparse
