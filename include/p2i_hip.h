@@ -640,6 +640,27 @@ int p2i_stkrig_factor(const int* stpix, const int* stt, const int* stcounts, con
 int p2i_stkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
                        const float* params, int model, int B, int T, int H, int W, int cap, float* out, void* stream);
 
+/* ---- leave-one-site-out (LOSO) cross-validation of space-time kriging (no counterpart in the reference).  A
+ * site is the set of a sample's points that share a pixel (at most one per frame).  With W = L^-1, u = K^-1 1, s = 1^T u and alpha the
+ * dual coefficients, for a site S: B_SS = (W^T W)_SS - u_S u_S^T / s, e_S = B_SS^-1 alpha_S, zhat_-S = z_S - e_S, sigma^2_-S =
+ * diag(B_SS^-1).  The system is built by p2i_stkrig_factor / p2i_krig_solve / p2i_krig_invert on the site-major point set.  W is fp32,
+ * everything after it fp64; all sums run in a fixed order.
+ * p2i_stkrig_gather_sites: the sample's points sorted by (pixel, frame) in p2i_stkrig_gather's layout (stpix, stt, stz [B][cap],
+ *   stcounts [B]), with site_start [B][cap + 1] (the first point of site g; entries nsites[b] .. cap hold the point count), nsites [B],
+ *   psite [B][cap] (site of a sorted point, -1 past the count), back [B][cap] (t fcap + rank within frame t, -1 past the count) and
+ *   fsite [B T][fcap] (site of a frame's gauge in p2i_krig_compact's layout, -1 past the frame's count).  fcap, cap <= 4096.
+ * p2i_stkrig_site_gram: gram [nsys][np / 32][2][32][32] fp64: for column tile J the tiles G[J][J] and G[J + 1][J] of G = Winv^T Winv
+ *   (the second is zero for the last J).  A run of at most 32 consecutive columns lies inside these.
+ * p2i_stkrig_loso: for every site of samples s0 .. s0 + nsys - 1 writes zhat_-S to pred and sigma^2_-S to var, both [B T][fcap] in
+ *   p2i_krig_compact's layout, at the site's points only (the caller zeroes them).  NaN for a site whose B_SS has a pivot not > 0 and
+ *   for every point of a sample with one site only, a degenerate fit (cand[b] < 0; cand may be NULL) or status[s] != 0.  T <= 32. */
+int p2i_stkrig_gather_sites(const int* pix, const float* z, const int* counts, int B, int T, int fcap, int cap, int* stpix, int* stt,
+                            float* stz, int* stcounts, int* site_start, int* nsites, int* psite, int* back, int* fsite, void* stream);
+int p2i_stkrig_site_gram(const float* Winv, int nsys, int np, double* gram, void* stream);
+int p2i_stkrig_loso(const double* gram, const double* sol, const float* alpha, const float* stz, const int* stcounts,
+                    const int* site_start, const int* nsites, const int* back, const int* status, const int* cand, int s0, int T,
+                    int nsys, int np, int fcap, int cap, float* pred, float* var, void* stream);
+
 /* ---- scale-aware verification: fractions skill score and radially averaged power spectra (no counterpart in
  * the reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform
  * and uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <= P2I_SCALE_MAX_CROP.

@@ -145,6 +145,9 @@ SIGNATURES = {
     "p2i_stkrig_fit": [_P, _I, _I, _I, _I, _F64, _I, _P, _P, _P, _P, _P],
     "p2i_stkrig_factor": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
     "p2i_stkrig_predict": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "p2i_stkrig_gather_sites": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "p2i_stkrig_site_gram": [_P, _I, _I, _P, _P],
+    "p2i_stkrig_loso": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "p2i_idw_loo": [_P, _P, _P, _I, _I, _F, _P, _P],
     "p2i_loo_scores": [_P, _P, _P, _P, _I, _I, _P, _P, _P],
     "p2i_scale_fss": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(C.c_double), _I, C.POINTER(C.c_int), _I, _I,

@@ -20,7 +20,8 @@ thresholds x neighbourhood sizes, the smallest useful scale, and the radially av
 and high-wavenumber ratio against the truth's.  ``ScaleEvaluator`` is its streaming form (one host sync in ``compute``).
 
 loo (``loo.py``, section 16; no counterpart in the reference): ``run_loo`` cross-validates a classical baseline leave-one-out at the
-gauges of every test event and writes ``loo.json``, ``loo.txt`` and ``loo_data.npz``; it needs no gridded truth.
+gauges of every test event and writes ``loo.json``, ``loo.txt`` and ``loo_data.npz``; it needs no gridded truth.  ``run_loso`` (section 18) is the same with whole sites left out, the score of the
+space-time baseline; it writes ``loso.json``, ``loso.txt`` and ``loso_data.npz``.
 
 ``_common.py`` holds what the units share."""
 from ._common import crop_mask, crop_origin, ensure_thw_shape, selection, transform_mmhr, truth_lut  # noqa: F401
@@ -31,6 +32,6 @@ from .exp2_chrome import (EXP2_GREYS, EXP2_IDX_BAD, EXP2_IDX_BG, EXP2_IDX_EDGE, 
                           PAPER_SUB, exp2_chrome, exp2_layout, exp2_palette, paper_cmap, write_exp2_gif)
 from .exp3 import (EXP3_MAX_POINTS, EXP3_MIN_VALUE, EXP3_SEED, LOGFREQ_EDGES, SCATTER_COLORS, Exp3Evaluator, Exp3Result,  # noqa: F401
                    compute_exp3, linregress, run_exp3, write_exp3_figures)
-from .loo import loo_lines, run_loo  # noqa: F401
+from .loo import loo_lines, loso_lines, run_loo, run_loso  # noqa: F401
 from .scale import (DEFAULT_SCALES, ScaleEvaluator, check_overflow, fss_value, ring_counts, ring_index, ring_list, run_scale,  # noqa: F401
                     scale_lines, spectrum_scores, twiddle, useful_scale, write_scale_figure, write_scale_outputs)

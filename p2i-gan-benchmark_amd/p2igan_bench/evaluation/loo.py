@@ -1,7 +1,11 @@
 """Leave-one-out (LOO) gauge cross-validation of the classical baselines over the test events (no counterpart in
 the reference): the one score that needs no gridded truth, so the one that also holds on gauge-only data.  Every gauge of a frame is
 predicted from the frame's other gauges by the model's ``cross_validate`` (csrc/krig_uq.hip); the sums behind the scores are taken on
-the device, chunk by chunk, and added per event and overall on the host."""
+the device, chunk by chunk, and added per event and overall on the host.
+
+Leave-one-site-out (LOSO; csrc/stkrig_loso.hip) is the same loop over the models' ``cross_validate_sites``: a
+site (a gauge pixel in all frames of a chunk) is left out as a whole.  It is the score of the space-time baseline `stkriging`, whose
+point-wise LOO would flatter it; for `kriging` and `idw` it equals LOO and puts the three in one table over the same targets."""
 from __future__ import annotations
 
 import json
@@ -30,21 +34,26 @@ def _mmhr(z, pred, scale: float) -> Dict[str, float]:
     return {"ME_mmhr": float(e.mean()), "MAE_mmhr": float(np.abs(e).mean()), "RMSE_mmhr": float(np.sqrt((e * e).mean()))}
 
 
-def loo_lines(result: Dict[str, Any]):
+def loo_lines(result: Dict[str, Any], title: str = "leave-one-out"):
     """The text table of a run_loo result."""
     keys = ["n", "ME", "MAE", "RMSE"] + (["MSDR"] if "MSDR" in result["overall"] else []) + ["ME_mmhr", "MAE_mmhr", "RMSE_mmhr"]
-    lines = [f"leave-one-out cross-validation: {result['model_name']}  (coded units x {result['output_scale']:g}; *_mmhr in mm/h)",
+    lines = [f"{title} cross-validation: {result['model_name']}  (coded units x {result['output_scale']:g}; *_mmhr in mm/h)",
              "event".ljust(12) + "".join(k.rjust(14) for k in keys)]
     for name, row in list(result["events"].items()) + [("overall", result["overall"])]:
         lines.append(name.ljust(12) + "".join((f"{row[k]:d}" if k == "n" else f"{row[k]:.6g}").rjust(14) for k in keys))
     return lines
 
 
+def loso_lines(result: Dict[str, Any]):
+    """The text table of a run_loso result."""
+    return loo_lines(result, "leave-one-site-out")
+
+
 def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_scale: float = 255.0, stride: int = 16) -> Dict[str, Any]:
     """Cross-validate cfg's classical model on every test event, in consecutive chunks of `stride` frames as infer_event_chunks forms
     them (each chunk is one sample of a fitted variogram).  Writes loo.json / loo.txt (scores per event and overall) and loo_data.npz
     (per gauge: event, frame, y, x, z, LOO prediction, LOO variance; coded units, unscaled) under out_dir; returns loo.json's content."""
-    from ..models import CLASSICAL, build_generator
+    from ..models import CLASSICAL
     name = str(cfg.get("model", {}).get("name", "model")).lower()
     if name not in CLASSICAL:
         raise RuntimeError(f"leave-one-out cross-validation is defined for the classical baselines {sorted(set(CLASSICAL) - {'stkriging'})} only: "
@@ -52,6 +61,26 @@ def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_s
     if name == "stkriging":
         from ..models.classical import ST_NO_LOO
         raise RuntimeError(ST_NO_LOO)
+    return _run(cfg, out_dir, device, output_scale, stride, name, False)
+
+
+def run_loso(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_scale: float = 255.0, stride: int = 16) -> Dict[str, Any]:
+    """run_loo with whole sites left out (the models' cross_validate_sites), for all three classical baselines.  A chunk of `stride`
+    frames is one sample, so a site is a gauge pixel over the chunk's frames; `stkriging` takes chunks of at most 32 frames.  Writes
+    loso.json / loso.txt and loso_data.npz (loo_data.npz's columns plus site, the site's index within its chunk) under out_dir."""
+    from ..models import CLASSICAL
+    from .. import ops
+    name = str(cfg.get("model", {}).get("name", "model")).lower()
+    if name not in CLASSICAL:
+        raise RuntimeError(f"leave-one-site-out cross-validation is defined for the classical baselines {sorted(CLASSICAL)} only: "
+                           f"model.name '{name}' is a learnt model and would need one training per site")
+    if name == "stkriging" and int(stride) > ops.KRIG_TILE:
+        raise ValueError(f"leave-one-site-out of 'stkriging' takes chunks of at most {ops.KRIG_TILE} frames: --stride {int(stride)} is too long")
+    return _run(cfg, out_dir, device, output_scale, stride, name, True)
+
+
+def _run(cfg, out_dir, device, output_scale, stride, name, by_site):
+    from ..models import build_generator
     dev = torch.device(device or cfg.get("device", "cuda:0"))
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise RuntimeError("the MI355X path needs a GPU: there is no CPU fallback")
@@ -61,14 +90,17 @@ def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_s
         raise RuntimeError("Test dataloader is not configured or empty.")
     G = build_generator(cfg).to(dev).eval()
     scale, stride = float(output_scale), max(1, int(stride))
-    with_var = name == "kriging"
-    events, cols = {}, {k: [] for k in ("event", "frame", "y", "x", "z", "pred", "var")}
+    with_var = name == "kriging" or (by_site and name == "stkriging")
+    stem = "loso" if by_site else "loo"
+    events, cols = {}, {k: [] for k in ("event", "frame", "y", "x", "z", "pred", "var") + (("site",) if by_site else ())}
     total = np.zeros(5)
     for ei, batch in enumerate(loader):
         _, masked, masks = [t.permute(0, 1, 4, 2, 3).contiguous().to(dev) for t in batch]
         sums, ez, ep = np.zeros(5), [], []
         for s in range(0, masked.shape[1], stride):
-            res = G.cross_validate(masked[:, s:s + stride].contiguous(), masks[:, s:s + stride].contiguous())
+            res = (G.cross_validate_sites if by_site else G.cross_validate)(masked[:, s:s + stride].contiguous(),
+                                                                            masks[:, s:s + stride].contiguous())
+            site = res.site.cpu().numpy() if by_site else None
             sums += np.asarray(res.sums().cpu().tolist())
             counts = res.counts.cpu().numpy()
             pix, z, pred = res.pix.cpu().numpy(), res.z.cpu().numpy(), res.pred.cpu().numpy()
@@ -82,6 +114,8 @@ def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_s
                 cols["z"].append(z[f, :n])
                 cols["pred"].append(pred[f, :n])
                 cols["var"].append(var[f, :n])
+                if by_site:
+                    cols["site"].append(site[f, :n])
                 ok = ~np.isnan(pred[f, :n]) & (~np.isnan(var[f, :n]) if with_var else True)
                 ez.append(z[f, :n][ok])
                 ep.append(pred[f, :n][ok])
@@ -93,9 +127,9 @@ def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_s
     result = {"model_name": name, "output_scale": scale, "stride": stride, "events": events,
               "overall": {**_coded(total.tolist(), with_var, scale), **_mmhr(data["z"][ok], data["pred"][ok], scale)}}
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, "loo.json"), "w") as fh:
+    with open(os.path.join(out_dir, f"{stem}.json"), "w") as fh:
         json.dump(result, fh, indent=2)
-    with open(os.path.join(out_dir, "loo.txt"), "w") as fh:
-        fh.write("\n".join(loo_lines(result)) + "\n")
-    np.savez(os.path.join(out_dir, "loo_data.npz"), **data)
+    with open(os.path.join(out_dir, f"{stem}.txt"), "w") as fh:
+        fh.write("\n".join(loso_lines(result) if by_site else loo_lines(result)) + "\n")
+    np.savez(os.path.join(out_dir, f"{stem}_data.npz"), **data)
     return result

@@ -9,7 +9,9 @@ Uncertainty and validation (csrc/krig_uq.hip): KrigingGene
 cross_validate of either model predicts every gauge from the frame's other gauges (leave-one-out) and scores the residuals.
 
 Space-time kriging (csrc/stkrig.hip): SpaceTimeKrigingGenerator kriges every pixel of every frame of a sample
-from all gauges of all frames of that sample, one system per sample, with a metric space-time covariance."""
+from all gauges of all frames of that sample, one system per sample, with a metric space-time covariance.  Its truth-free score is
+leave-one-site-out (csrc/stkrig_loso.hip): cross_validate_sites of all three models predicts every point of a
+site (a gauge pixel in all the sample's frames) with the whole site left out."""
 from __future__ import annotations
 
 import logging
@@ -42,10 +44,11 @@ def _frames(masked_frames, masks, who):
 class LOOResult:
     """Leave-one-out cross-validation of one call.  pix, z, pred, var: (B*T, cap) on the device, rows as ops.krig_compact packs them
     (pred is NaN where a frame has no model or fewer than 2 gauges, everything is 0 past the frame's count; var is None for IDW);
-    counts (B*T,) int32; status: the kriging systems' factorisation flags (None for IDW)."""
+    counts (B*T,) int32; status: the kriging systems' factorisation flags (None for IDW).  site (cross_validate_sites only, else
+    None): (B*T, cap) int32, the rank of the gauge's pixel among the sample's distinct gauge pixels in raster order, -1 past the count."""
 
-    def __init__(self, pix, z, pred, var, counts, status):
-        self.pix, self.z, self.pred, self.var, self.counts, self.status = pix, z, pred, var, counts, status
+    def __init__(self, pix, z, pred, var, counts, status, site=None):
+        self.pix, self.z, self.pred, self.var, self.counts, self.status, self.site = pix, z, pred, var, counts, status, site
 
     def sums(self) -> torch.Tensor:
         """(5,) fp64 on the device: n, sum e, sum |e|, sum e^2, sum e^2 / var over the gauges with a prediction, e = z - pred."""
@@ -64,6 +67,19 @@ def loo_summary(sums, with_var: bool) -> Dict[str, float]:
     if with_var:
         out["MSDR"] = sums[4] / d
     return out
+
+
+def _sites_of_frames(res: LOOResult, masks) -> LOOResult:
+    """res with its site field filled for a model whose systems are per frame (leaving a site out is leaving a gauge out there): the
+    rank of each gauge's pixel in the raster-order union of the sample's masks."""
+    b, t, _, h, w = masks.shape
+    union = (masks.reshape(b, t, h * w) != 0).any(dim=1)
+    rank = (torch.cumsum(union, dim=1, dtype=torch.int32) - 1).to(torch.int32)
+    pix = res.pix.view(b, t * res.pix.shape[1]).long()
+    site = torch.gather(rank, 1, (pix >> 16) * w + (pix & 0xffff)).view_as(res.pix)
+    past = torch.arange(res.pix.shape[1], device=site.device)[None, :] >= res.counts[:, None]
+    res.site = site.masked_fill(past, -1).contiguous()
+    return res
 
 
 class _ClassicalBase(nn.Module):
@@ -134,6 +150,11 @@ class KrigingGenerator(_ClassicalBase):
         """Leave-one-out at every gauge from the one factorisation per system (Dubrule 1983): no refits."""
         return self._krige(masked_frames, masks, predict=False, loo=True)["loo"]
 
+    @torch.no_grad()
+    def cross_validate_sites(self, masked_frames, masks) -> LOOResult:
+        """cross_validate's result with its site field filled: the systems are per frame, so leaving a site out is leaving a gauge out."""
+        return _sites_of_frames(self.cross_validate(masked_frames, masks), masks)
+
     def _krige(self, masked_frames, masks, predict=True, variance=False, loo=False):
         b, t, _, h, w = masked_frames.shape
         pix, z, info, counts, shared = self._compact(masked_frames, masks)
@@ -203,6 +224,11 @@ class IDWGenerator(_ClassicalBase):
         pix, z, info, _, _ = self._compact(masked_frames, masks)
         return LOOResult(pix, z, ops.idw_loo(pix, z, info, self.power), None, info[:pix.shape[0]], None)
 
+    @torch.no_grad()
+    def cross_validate_sites(self, masked_frames, masks) -> LOOResult:
+        """cross_validate's result with its site field filled: a frame's weights see that frame only."""
+        return _sites_of_frames(self.cross_validate(masked_frames, masks), masks)
+
 
 class SpaceTimeKrigingGenerator(_ClassicalBase):
     """Ordinary kriging of every pixel of every frame of a sample from ALL gauges of ALL frames of that sample: one system per sample,
@@ -212,7 +238,7 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
     (default 4096) bounds the points of one sample.
 
     There is no forward_uq and no cross_validate: leaving out one (site, frame) observation while the same site's neighbouring
-    frames stay in would flatter the method; the honest score is leave-one-site-out."""
+    frames stay in would flatter the method; the honest score is leave-one-site-out, cross_validate_sites."""
 
     DEFAULT_MAX_POINTS = 4096
 
@@ -245,26 +271,34 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
     def cross_validate(self, masked_frames, masks):
         raise RuntimeError(ST_NO_LOO)
 
-    @torch.no_grad()
-    def forward(self, masked_frames, masks):
-        b, t, _, h, w = masked_frames.shape
+    def _points(self, masked_frames, masks):
+        """(pix, z, info of the frames, padded size of the samples' systems) after the host checks."""
+        b, t = masked_frames.shape[:2]
         pix, z, info, counts, _ = self._compact(masked_frames, masks)
         per_sample = counts.view(b, t).sum(dim=1)
         if int(per_sample.max()) > self.max_points:
             raise ValueError(f"{type(self).__name__}: a sample has {int(per_sample.max())} space-time points ({t} frames), more than "
                              f"model.max_points = {self.max_points}: use shorter chunks (scripts/infer.py --stride)")
+        return pix, z, info, max(ops.KRIG_TILE, _round_up(int(per_sample.max()), ops.KRIG_TILE))
+
+    def _variogram(self, pix, z, info, b, t, h, w):
+        """(cand or None, params (B, 4) fp32): the per-sample fit (kept in last_fit) or the fixed parameters."""
+        if not self.fit:
+            return None, torch.tensor(self.fixed, dtype=torch.float32).repeat(b, 1).to(pix.device)
+        lag_width = (min(h, w) / 2.0) / self.n_lags
+        bins, fit, cand, params = ops.stkrig_variogram(pix, z, info, b, t, self.n_lags, min(self.n_tlags, t - 1), lag_width,
+                                                       self.variogram_model)
+        q = torch.div(cand, ops.KRIG_CANDIDATES, rounding_mode="floor")
+        self.last_fit = {"bins": bins, "fit": fit, "cand": cand, "q": q, "c": cand - q * ops.KRIG_CANDIDATES}
+        return cand, params
+
+    @torch.no_grad()
+    def forward(self, masked_frames, masks):
+        b, t, _, h, w = masked_frames.shape
+        pix, z, info, np_ = self._points(masked_frames, masks)
         dev = masked_frames.device
-        np_ = max(ops.KRIG_TILE, _round_up(int(per_sample.max()), ops.KRIG_TILE))
         stpix, stt, stz, stinfo = ops.stkrig_gather(pix, z, info, b, t, np_)
-        cand = None
-        if self.fit:
-            lag_width = (min(h, w) / 2.0) / self.n_lags
-            bins, fit, cand, params = ops.stkrig_variogram(pix, z, info, b, t, self.n_lags, min(self.n_tlags, t - 1), lag_width,
-                                                           self.variogram_model)
-            q = torch.div(cand, ops.KRIG_CANDIDATES, rounding_mode="floor")
-            self.last_fit = {"bins": bins, "fit": fit, "cand": cand, "q": q, "c": cand - q * ops.KRIG_CANDIDATES}
-        else:
-            params = torch.tensor(self.fixed, dtype=torch.float32).repeat(b, 1).to(dev)
+        cand, params = self._variogram(pix, z, info, b, t, h, w)
         per = max(1, min(b, _FACTOR_BYTES // (np_ * np_ * 4)))
         work = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
         status = torch.zeros(b, device=dev, dtype=torch.int32)
@@ -282,9 +316,43 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
             logging.warning("space-time kriging: %d sample(s) met a non-positive pivot and predict their gauge mean", failed)
         return out.view(b, t, 1, h, w)
 
+    @torch.no_grad()
+    def cross_validate_sites(self, masked_frames, masks) -> LOOResult:
+        """Leave-one-site-out at every point: a site (a gauge pixel in all the sample's frames) is left out as a whole and its points
+        are predicted from the other sites, by the block form of Dubrule's identity on one factorisation and one inverse per sample
+        (DESIGN.md section 18).  pred and var are NaN for a sample with one site only, a degenerate fit or a failed factorisation."""
+        b, t, _, h, w = masked_frames.shape
+        pix, z, info, np_ = self._points(masked_frames, masks)
+        if t > ops.KRIG_TILE:
+            raise ValueError(f"{type(self).__name__}: leave-one-site-out takes at most {ops.KRIG_TILE} frames per sample (got {t}): use "
+                             f"shorter chunks (scripts/crossvalidate.py --stride)")
+        dev = masked_frames.device
+        sites = ops.stkrig_gather_sites(pix, z, info, b, t, np_)
+        cand, params = self._variogram(pix, z, info, b, t, h, w)
+        per = max(1, min(b, _FACTOR_BYTES // (np_ * np_ * 4 * 2)))      # the factor and its inverse: two workspaces per sample
+        work = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
+        winv = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
+        status = torch.zeros(b, device=dev, dtype=torch.int32)
+        alpha = torch.empty(b, np_, device=dev, dtype=torch.float32)
+        mean = torch.empty(b, device=dev, dtype=torch.float32)
+        pred, var = torch.zeros_like(z), torch.zeros_like(z)
+        for s0 in range(0, b, per):
+            ns = min(per, b - s0)
+            st = status[s0:s0 + ns]
+            ops.stkrig_factor(sites["stpix"], sites["stt"], sites["stinfo"], params, self.variogram_model, s0, ns, np_, work, st)
+            sol = ops.krig_solve(work, sites["stz"], sites["stinfo"], st, cand, s0, 1, 1, ns, np_, alpha, mean)
+            ops.krig_invert(work, ns, np_, winv)
+            gram = ops.stkrig_site_gram(winv, ns, np_)
+            ops.stkrig_loso(gram, sol, alpha, sites, st, cand, s0, t, ns, np_, pred, var)
+        self.last_status = status
+        failed = int(status.sum())
+        if failed:
+            logging.warning("space-time kriging: %d sample(s) met a non-positive pivot and have no leave-one-site-out scores", failed)
+        return LOOResult(pix, z, pred, var, info[:b * t], status, sites["fsite"])
+
 
 ST_NO_LOO = ("space-time kriging ('stkriging') has no leave-one-out cross-validation: leaving out one (site, frame) observation while "
-              "the same site's neighbouring frames stay in would flatter the method; the honest score is leave-one-site-out, which "
-              "is not implemented")
+              "the same site's neighbouring frames stay in would flatter the method; the honest score is leave-one-site-out: "
+              "cross_validate_sites, evaluation.run_loso, scripts/crossvalidate.py --by-site")
 
 CLASSICAL = {"kriging": KrigingGenerator, "idw": IDWGenerator, "stkriging": SpaceTimeKrigingGenerator}

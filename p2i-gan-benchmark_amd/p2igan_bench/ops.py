@@ -1722,6 +1722,78 @@ def stkrig_predict(stpix, stt, alpha, mean, stinfo, params, model, T, H, W):
     return out
 
 
+# ---- leave-one-site-out cross-validation of space-time kriging (csrc/stkrig_loso.hip)
+def stkrig_gather_sites(pix, z, info, B, T, cap):
+    """The per-frame gauges of krig_compact as per-sample point sets sorted by (pixel, frame), so that a site (the points of one
+    pixel) is a contiguous run.  Returns a dict: stpix, stt, stz (B, cap) and stinfo (2*B,) as stkrig_gather returns them, site_start
+    (B, cap + 1) int32 (first point of each site; the point count from entry nsites[b] on), nsites (B,), psite (B, cap) (site of a
+    sorted point, -1 past the count), back (B, cap) (t * fcap + rank in frame t, -1 past the count) and fsite (B*T, fcap) (site of
+    a frame's gauge in krig_compact's layout, -1 past the frame's count)."""
+    lib = _hip.load()
+    F = B * T
+    fcap = pix.shape[1]
+    _krig_t("stkrig_gather_sites", pix, torch.int32, (F, fcap))
+    _krig_t("stkrig_gather_sites", z, torch.float32, (F, fcap))
+    _krig_t("stkrig_gather_sites", info, torch.int32, (2 * F,))
+    if cap < KRIG_TILE or cap % KRIG_TILE or cap > KRIG_MAX_CAP or fcap > KRIG_MAX_CAP:
+        raise ValueError(f"stkrig_gather_sites: cap must be a multiple of {KRIG_TILE} in [{KRIG_TILE}, {KRIG_MAX_CAP}] (got {cap})")
+    dev = pix.device
+    out = {k: torch.empty(B, cap, device=dev, dtype=torch.int32) for k in ("stpix", "stt", "psite", "back")}
+    out["stz"] = torch.empty(B, cap, device=dev, dtype=torch.float32)
+    out["stinfo"] = torch.zeros(2 * B, device=dev, dtype=torch.int32)
+    out["site_start"] = torch.empty(B, cap + 1, device=dev, dtype=torch.int32)
+    out["nsites"] = torch.empty(B, device=dev, dtype=torch.int32)
+    out["fsite"] = torch.empty(F, fcap, device=dev, dtype=torch.int32)
+    _hip.check(lib.p2i_stkrig_gather_sites(_ptr(pix), _ptr(z), _ptr(info), B, T, fcap, cap, _ptr(out["stpix"]), _ptr(out["stt"]),
+                                           _ptr(out["stz"]), _ptr(out["stinfo"]), _ptr(out["site_start"]), _ptr(out["nsites"]),
+                                           _ptr(out["psite"]), _ptr(out["back"]), _ptr(out["fsite"]), _stream()), "p2i_stkrig_gather_sites")
+    return out
+
+
+def stkrig_site_gram(Winv, nsys, np_):
+    """gram (nsys, np_ / 32, 2, 32, 32) fp64: per column tile J the tiles (J, J) and (J + 1, J) of Winv^T Winv, the band that holds
+    every run of at most 32 consecutive columns."""
+    lib = _hip.load()
+    _krig_t("stkrig_site_gram", Winv, torch.float32)
+    if nsys < 1 or np_ < KRIG_TILE or np_ % KRIG_TILE or np_ > KRIG_MAX_CAP:
+        raise RuntimeError(f"stkrig_site_gram: bad system shape {nsys} x {np_}")
+    if Winv.numel() < nsys * np_ * np_:
+        raise RuntimeError("stkrig_site_gram: inverse workspace too small")
+    gram = torch.empty(nsys, np_ // KRIG_TILE, 2, KRIG_TILE, KRIG_TILE, device=Winv.device, dtype=torch.float64)
+    _hip.check(lib.p2i_stkrig_site_gram(_ptr(Winv), nsys, np_, _ptr(gram), _stream()), "p2i_stkrig_site_gram")
+    return gram
+
+
+def stkrig_loso(gram, sol, alpha, sites, status, cand, s0, T, nsys, np_, pred, var):
+    """Leave-one-site-out prediction and variance of every point of samples s0 .. s0 + nsys - 1 into pred, var (B*T, fcap), in place,
+    at the points only (the caller zeroes both).  sites: stkrig_gather_sites' dict; gram, sol, alpha, status as stkrig_site_gram,
+    krig_solve and stkrig_factor leave them for the same (s0, nsys, np_)."""
+    lib = _hip.load()
+    B, cap = sites["stz"].shape
+    F, fcap = pred.shape
+    if not 1 <= T <= KRIG_TILE or F != B * T:
+        raise ValueError(f"stkrig_loso: a site block is at most {KRIG_TILE} frames wide (got T = {T}, {F} frames of {B} samples)")
+    _krig_t("stkrig_loso", gram, torch.float64, (nsys, np_ // KRIG_TILE, 2, KRIG_TILE, KRIG_TILE))
+    _krig_t("stkrig_loso", sol, torch.float64, (nsys, 2, np_))
+    _krig_t("stkrig_loso", alpha, torch.float32, (B, cap))
+    _krig_t("stkrig_loso", sites["stz"], torch.float32)
+    _krig_t("stkrig_loso", sites["stinfo"], torch.int32, (2 * B,))
+    _krig_t("stkrig_loso", sites["site_start"], torch.int32, (B, cap + 1))
+    _krig_t("stkrig_loso", sites["nsites"], torch.int32, (B,))
+    _krig_t("stkrig_loso", sites["back"], torch.int32, (B, cap))
+    _krig_t("stkrig_loso", status, torch.int32, (nsys,))
+    if cand is not None:
+        _krig_t("stkrig_loso", cand, torch.int32, (B,))
+    _krig_t("stkrig_loso", pred, torch.float32)
+    _krig_t("stkrig_loso", var, torch.float32, (F, fcap))
+    _krig_sys("stkrig_loso", s0, 1, 1, nsys, B, np_, cap)
+    if fcap > KRIG_MAX_CAP:
+        raise RuntimeError(f"stkrig_loso: frame rows of {fcap} exceed {KRIG_MAX_CAP}")
+    _hip.check(lib.p2i_stkrig_loso(_ptr(gram), _ptr(sol), _ptr(alpha), _ptr(sites["stz"]), _ptr(sites["stinfo"]), _ptr(sites["site_start"]),
+                                   _ptr(sites["nsites"]), _ptr(sites["back"]), _ptr(status), _ptr(cand), s0, T, nsys, np_, fcap, cap,
+                                   _ptr(pred), _ptr(var), _stream()), "p2i_stkrig_loso")
+
+
 # ---- kriging variance and leave-one-out cross-validation (csrc/krig_uq.hip, DESIGN.md section 16)
 LOO_NSUM = 5             # (n, sum e, sum |e|, sum e^2, sum e^2 / var)
 

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Leave-one-out gauge cross-validation of a classical baseline (model.name: kriging / idw) over the test events: every gauge is
 predicted from the other gauges of its frame, which needs no gridded truth.  Writes loo.json, loo.txt and loo_data.npz
-(p2igan_bench/evaluation/loo.py).  The space-time baseline `stkriging` is refused: its honest score is
-leave-one-site-out, which is not built."""
+(p2igan_bench/evaluation/loo.py).  The space-time baseline `stkriging` is refused there: its honest score is
+leave-one-site-out, --by-site: a site, a gauge pixel over all frames of a chunk of --stride frames, is left
+out as a whole.  --by-site takes kriging, idw and stkriging (chunks of at most 32 frames) and writes loso.json, loso.txt and
+loso_data.npz."""
 from __future__ import annotations
 
 import argparse
@@ -17,7 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from p2igan_bench.evaluation import loo_lines, run_loo  # noqa: E402
+from p2igan_bench.evaluation import loo_lines, loso_lines, run_loo, run_loso  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -26,6 +28,7 @@ def parse_args(argv=None):
     p.add_argument("--data-root", type=Path, default=None)
     p.add_argument("--output", type=Path, required=True)
     p.add_argument("--stride", type=int, default=16)
+    p.add_argument("--by-site", action="store_true", help="leave whole sites out (leave-one-site-out); the score of stkriging")
     p.add_argument("--device", type=str, default=None)
     p.add_argument("--output-scale", type=float, default=255.0)
     p.add_argument("--log-level", type=str, default="INFO")
@@ -41,8 +44,9 @@ def main(argv=None):
     np.random.seed(cfg.get("seed", 42))
     if args.data_root is not None:
         cfg.setdefault("data", {}).setdefault("test", {})["data_root"] = str(args.data_root)
-    result = run_loo(cfg, str(args.output), device=args.device, output_scale=args.output_scale, stride=args.stride)
-    for line in loo_lines(result):
+    run, lines = (run_loso, loso_lines) if args.by_site else (run_loo, loo_lines)
+    result = run(cfg, str(args.output), device=args.device, output_scale=args.output_scale, stride=args.stride)
+    for line in lines(result):
         logging.info("%s", line)
     return result
 
