@@ -51,6 +51,80 @@ __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0
 // TOGETHER from clamped addresses and masked afterwards: loads under a per-element condition (`if (res) v += res[di]`) make
 // hipcc branch around each one and wait for it before the next -- 64 serialised HBM round trips per lane, measured at 50-60k
 // cycles per workgroup on the generator's dgrad launches (a quarter of the kernel).
+//
+// Every epilogue form below is cut into BATCHES with two halves: *_fetch computes a batch's addresses and issues its residual / mask
+// loads, *_finish does the arithmetic and the stores.  The one-tile functions (epilogue_tile16, epilogue_pair16) run them back to
+// back -- load, wait, compute, store: one memory round trip per batch stands open; epilogue_pipelined issues batch k+1's loads in
+// front of batch k's arithmetic, so that only the first batch's round trip is exposed, at the price of one more batch of operand
+// registers.  `primed`: the caller has already fetched batch 0 into slot 0 (ahead of work that covers that round trip too).
+// One scheduling fence per batch in either form: without it hipcc hoists the loads of EVERY tile of the workgroup to the top and
+// the register allocation grows by ~100.  fetch(slot, k) / finish(slot, k): slot = k & 1 is the operand buffer; both are
+// compile-time constants once the loop is unrolled.
+template <int NB, typename Fetch, typename Finish>
+__device__ __forceinline__ void epilogue_pipelined(Fetch fetch, Finish finish, bool primed = false) {
+  if (!primed) fetch(0, 0);
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    if (k + 1 < NB) fetch((k + 1) & 1, k + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    finish(k & 1, k);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// one batch of epilogue_tile16: 8 of the tile's 16 registers (h8 = 0, 1), 32-bit element offsets (tensors are < 2^31 elements: check_desc)
+struct EpiOps8 {
+  int di[8];
+  bool ok[8];
+  float rv[8], mv[8], bv[8];
+};
+__device__ __forceinline__ void epi_tile16_fetch(EpiOps8& b, int h8, int o_base, int lhi, int Cm, bool pv, size_t pos_off, size_t chan_stride,
+                                                 const float* __restrict__ bias, const float* __restrict__ res, const float* __restrict__ mask_y) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int r = h8 * 8 + k;
+    const int o = o_base + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+    b.ok[k] = pv && o < Cm;
+    b.di[k] = b.ok[k] ? (int)((size_t)o * chan_stride + pos_off) : 0;
+  }
+  if (res) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) b.rv[k] = res[b.di[k]];
+  }
+  if (mask_y) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) b.mv[k] = mask_y[b.di[k]];
+  }
+  // (the bias values too: loaded next to their use, under the per-element branches of the activation, each one is waited for alone)
+  if (bias) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int r = h8 * 8 + k;
+      const int o = o_base + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+      b.bv[k] = bias[o < Cm ? o : 0];
+    }
+  }
+}
+__device__ __forceinline__ void epi_tile16_finish(const EpiOps8& b, int h8, const f32x16& acc, const float* __restrict__ bias, int act_epi,
+                                                  const float* __restrict__ res, const float* __restrict__ mask_y, int mask_act,
+                                                  float* __restrict__ dst, bool atomic_out) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    float v = acc[h8 * 8 + k];
+    if (bias) v += b.bv[k];
+    v = act_apply(v, act_epi);
+    if (res) v += b.rv[k];
+    if (mask_y) v = act_grad(v, b.mv[k], mask_act);
+    if (b.ok[k]) {
+      if (atomic_out) atomicAdd(dst + b.di[k], v);
+      else dst[b.di[k]] = v;
+    }
+  }
+}
+// The serial form, one tile per call, for the f32 engines and the symmetric split-pipe kernels (two workgroups per CU cover each
+// other's round trips, or the register budget is full).  Written out in one piece, not through the two halves above: spelled
+// through them the f32 engines' kernels came out with other schedules and register counts (+-2 .. 8), and those kernels are not
+// what the pipelined form is for.  patch_gemm_x6p_kernel pipelines the halves itself, across its tiles.
 __device__ __forceinline__ void epilogue_tile16(const f32x16& acc, int o_base, int lhi, int Cm, bool pv, size_t pos_off, size_t chan_stride,
                                                 const float* __restrict__ bias, int act_epi, const float* __restrict__ res,
                                                 const float* __restrict__ mask_y, int mask_act, float* __restrict__ dst,
@@ -104,11 +178,35 @@ __device__ __forceinline__ void epilogue_tile16(const f32x16& acc, int o_base, i
 // (and 4 dwordx4 loads per epilogue tensor) per tile.  Requirements, checked by the caller: the wave's 32 positions are 8 aligned
 // groups of 4 consecutive destination elements (tile width >= 4 positions, destination row pitch and tile origin multiples of 4),
 // validity is per group (nW % 4 == 0).  pos4_off: element offset of THIS lane's group (lane & 7) inside a channel; pv4: group valid.
+// One tile is one batch here (epilogue_pipelined over the wave's TM tiles): epi_tile16_v4_fetch issues the 4 + 4 dwordx4 operand
+// loads of a tile, epi_tile16_v4_finish sends the accumulators through the image, computes and stores.
 typedef float f32x4e __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void epilogue_tile16_v4(const f32x16& acc, float* __restrict__ tile_lds, int o_base, int lane, int Cm,
-                                                   size_t pos4_off, bool pv4, size_t chan_stride,
-                                                   const float* __restrict__ bias, int act_epi, const float* __restrict__ res,
-                                                   const float* __restrict__ mask_y, int mask_act, float* __restrict__ dst, bool atomic_out = false) {
+struct EpiOps4v {
+  int di[4];
+  bool ok[4];
+  f32x4e rv[4], mv[4];
+  float bv[4];
+};
+__device__ __forceinline__ void epi_tile16_v4_fetch(EpiOps4v& b, int o_base, int lane, int Cm, size_t pos4_off, bool pv4, size_t chan_stride,
+                                                    const float* __restrict__ bias, const float* __restrict__ res, const float* __restrict__ mask_y) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int o = o_base + k * 8 + (lane >> 3);                 // channel of this lane's k-th group
+    b.ok[k] = pv4 && o < Cm;
+    b.di[k] = b.ok[k] ? (int)((size_t)o * chan_stride + pos4_off) : 0;
+    b.bv[k] = bias ? bias[o < Cm ? o : 0] : 0.f;
+  }
+  if (res) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b.rv[k] = *reinterpret_cast<const f32x4e*>(res + b.di[k]);
+  }
+  if (mask_y) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b.mv[k] = *reinterpret_cast<const f32x4e*>(mask_y + b.di[k]);
+  }
+}
+__device__ __forceinline__ void epi_tile16_v4_finish(const EpiOps4v& b, const f32x16& acc, float* __restrict__ tile_lds, int lane, int act_epi, const float* __restrict__ res,
+                                                     const float* __restrict__ mask_y, int mask_act, float* __restrict__ dst, bool atomic_out) {
   constexpr int PITCH = 36;
   const int l31 = lane & 31, lhi = lane >> 5;
 #pragma unroll
@@ -117,42 +215,24 @@ __device__ __forceinline__ void epilogue_tile16_v4(const f32x16& acc, float* __r
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const int p4 = (lane & 7) * 4;
-  int di[4];
-  bool ok[4];
-  f32x4e v[4], rv[4], mv[4];
+  f32x4e v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const f32x4e*>(tile_lds + (k * 8 + (lane >> 3)) * PITCH + p4);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int ch = k * 8 + (lane >> 3);                       // channel of this lane's k-th group
-    const int o = o_base + ch;
-    ok[k] = pv4 && o < Cm;
-    di[k] = ok[k] ? (int)((size_t)o * chan_stride + pos4_off) : 0;
-    v[k] = *reinterpret_cast<const f32x4e*>(tile_lds + ch * PITCH + p4);
-  }
-  if (res) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) rv[k] = *reinterpret_cast<const f32x4e*>(res + di[k]);
-  }
-  if (mask_y) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) mv[k] = *reinterpret_cast<const f32x4e*>(mask_y + di[k]);
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int o = o_base + k * 8 + (lane >> 3);
-    const float bv = bias ? bias[o < Cm ? o : 0] : 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float x = act_apply(v[k][e] + bv, act_epi);
-      if (res) x += rv[k][e];
-      if (mask_y) x = act_grad(x, mv[k][e], mask_act);
+      float x = act_apply(v[k][e] + b.bv[k], act_epi);
+      if (res) x += b.rv[k][e];
+      if (mask_y) x = act_grad(x, b.mv[k][e], mask_act);
       v[k][e] = x;
     }
-    if (ok[k]) {
+    if (b.ok[k]) {
       if (atomic_out) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) atomicAdd(dst + di[k] + e, v[k][e]);
+        for (int e = 0; e < 4; ++e) atomicAdd(dst + b.di[k] + e, v[k][e]);
       } else {
-        *reinterpret_cast<f32x4e*>(dst + di[k]) = v[k];
+        *reinterpret_cast<f32x4e*>(dst + b.di[k]) = v[k];
       }
     }
   }
@@ -163,12 +243,53 @@ __device__ __forceinline__ void epilogue_tile16_v4(const f32x16& acc, float* __r
 // stride-2 data gradient, destination row pitch even): element r of both tiles belongs to the same lane and to adjacent
 // addresses, so residual / mask are fetched and the result is stored as float2 -- full 128-B lines per 16 lanes instead of two
 // half-used ones per class (WRITE_SIZE of the fused strided dgrad was 1.6x its algorithmic bytes).  pos_off: class pW=0, even.
+// Batches of 4 registers (h4 = 0 .. 3: 8 floats in flight per tensor): the <32,128,1,*,4> instances of the f32 fused engine must stay
+// below 256 VGPRs to keep two workgroups per CU, and keep the serial form.
+typedef float f32x2e __attribute__((ext_vector_type(2)));
+struct EpiOps4p {
+  int di[4];
+  bool ok[4];
+  f32x2e rv[4], mv[4];
+};
+__device__ __forceinline__ void epi_pair16_fetch(EpiOps4p& b, int h4, int o_base, int lhi, int Cm, bool pv, size_t pos_off, size_t chan_stride,
+                                                 const float* __restrict__ res, const float* __restrict__ mask_y) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int r = h4 * 4 + k;
+    const int o = o_base + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+    b.ok[k] = pv && o < Cm;
+    b.di[k] = b.ok[k] ? (int)((size_t)o * chan_stride + pos_off) : 0;
+  }
+  if (res) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b.rv[k] = *reinterpret_cast<const f32x2e*>(res + b.di[k]);
+  }
+  if (mask_y) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b.mv[k] = *reinterpret_cast<const f32x2e*>(mask_y + b.di[k]);
+  }
+}
+__device__ __forceinline__ void epi_pair16_finish(const EpiOps4p& b, int h4, const f32x16& acc0, const f32x16& acc1,
+                                                  const float* __restrict__ res, const float* __restrict__ mask_y, int mask_act,
+                                                  float* __restrict__ dst, bool atomic_out) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int r = h4 * 4 + k;
+    f32x2e v;
+    v[0] = acc0[r]; v[1] = acc1[r];
+    if (res) { v[0] += b.rv[k][0]; v[1] += b.rv[k][1]; }
+    if (mask_y) { v[0] = act_grad(v[0], b.mv[k][0], mask_act); v[1] = act_grad(v[1], b.mv[k][1], mask_act); }
+    if (b.ok[k]) {
+      if (atomic_out) { atomicAdd(dst + b.di[k], v[0]); atomicAdd(dst + b.di[k] + 1, v[1]); }
+      else *reinterpret_cast<f32x2e*>(dst + b.di[k]) = v;
+    }
+  }
+}
 __device__ __forceinline__ void epilogue_pair16(const f32x16& acc0, const f32x16& acc1, int o_base, int lhi, int Cm, bool pv, size_t pos_off,
                                                 size_t chan_stride, const float* __restrict__ res, const float* __restrict__ mask_y,
                                                 int mask_act, float* __restrict__ dst, bool atomic_out = false) {
   // atomic_out: both values are ADDED to a pre-zeroed destination (split-K partial sums: res rides with one split only, the mask
-  // factor distributes over the sum)
-  typedef float f32x2e __attribute__((ext_vector_type(2)));
+  // factor distributes over the sum).  The serial form in one piece, as epilogue_tile16.
   // batches of 4 (8 floats in flight per tensor): the <32,128,1,*,4> instances must stay below 256 VGPRs to keep two workgroups per CU
 #pragma unroll
   for (int h4 = 0; h4 < 4; ++h4) {

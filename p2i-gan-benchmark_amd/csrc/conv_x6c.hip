@@ -131,7 +131,7 @@ struct X6cGeom {
   int tap_w[9];
   int fused_atomic;     // FUSED kernels with split-K: the class pairs are ADDED to a zeroed destination
   int stagger;          // waves 4-7 (the SIMD partners of waves 0-3) run a stage's staging work AFTER its first taps instead of before
-  int vec4_epi;         // epilogue through LDS with 16-byte global accesses (epilogue_tile16_v4): host-checked alignment / extents
+  int vec4_epi;         // epilogue through LDS with 16-byte global accesses (epi_tile16_v4_*): host-checked alignment / extents
   // PRE kernels (round 4 experiment): the source as pre-split bf16 planes [plane][b][k/8][frame, pixel][8] (split_planes_kernel):
   // 16-byte units; plane p starts plane_units units behind plane p - 1
   const u32x4c* splanes;
@@ -854,6 +854,54 @@ __global__ __launch_bounds__(64 * (4 + NPW)) void patch_gemm_x6p_kernel(const X6
       if (i < NR) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
     }
   };
+  // ---- epilogue geometry and the operand buffers of its batches (conv_common.h: epi_*_fetch / epi_*_finish).  They depend on
+  // blockIdx, wave and lane only and stand in front of the tap loop because a wave issues its FIRST batch of bias / residual /
+  // mask loads before the loop's work is over (below); every further batch is fetched one ahead by epilogue_pipelined.
+  const int dHW = g.dT * g.dH * g.dW;
+  const int mynb = (TN == 2 && producer) ? 1 : 0;                         // consumer: position block 0, producer: block 1
+  const bool has_epi = wave < 2 * NCW;                                    // (a second producer wave per SIMD has no share in the epilogue)
+  // split-K launches add linear partial sums into a zeroed destination: bias / residual ride with split 0, no activation
+  const bool split = FUSED ? g.fused_atomic != 0 : g.ksplit > 1;
+  const float* const bias_q = (split && blockIdx.z) ? nullptr : g.bias;
+  const float* const res_q = (split && blockIdx.z) ? nullptr : g.res;
+  const bool blk1 = TN == 2 && producer;
+  const int gw = j0w + (blk1 ? pjw_[TN - 1] : pjw_[0]), gh = j0h + (blk1 ? pjh_[TN - 1] : pjh_[0]), gn = j0b + (blk1 ? pjb_[TN - 1] : pjb_[0]);
+  const bool pvld = gn < nimg && gh < g.nH && gw < g.nW;
+  const int gb_ = gn / g.nT, glt = gn - gb_ * g.nT;
+  const size_t img0 = (size_t)gb_ * g.Cm * dHW + (size_t)(glt * g.oT + g.pT) * g.dH * g.dW;
+  const size_t pos0 = img0 + (size_t)(2 * gh) * g.dW + 2 * gw;             // FUSED: class (0, 0) of the position's 2 x 2 destination block
+  const size_t pos = img0 + (size_t)gh * g.dW + gw;
+  // EPI4, 16-byte accesses: this lane's group = positions 4 (lane & 7) .. + 3 of the block (one channel per lane and pass)
+  const int pg = cw * 32 * TN + mynb * 32 + 4 * (lane & 7);
+  const int qw = pg & JWm, qh = (pg >> g.ljw) & JHm, qb = pg >> (g.ljw + g.ljh);
+  const int hw = j0w + qw, hh = j0h + qh, hn = j0b + qb;
+  const bool pv4 = hn < nimg && hh < g.nH && hw < g.nW;
+  const int hb = hn / g.nT, hlt = hn - hb * g.nT;
+  const size_t pos4 = (size_t)hb * g.Cm * dHW + (size_t)(hlt * g.oT + g.pT) * g.dH * g.dW + (size_t)hh * g.dW + hw;
+  float* xch = reinterpret_cast<float*>(wbuf);                            // [4 consumers][NCLS][TM][16][64] floats <= 64 KB
+  float* tl = xch + 4 * NCLS * TM * 16 * 64 + wave * (32 * 36);          // EPI4: wave-private 32 x 36 image behind the exchange area
+  EpiOps4p ops_p[FUSED ? 2 : 1];
+  EpiOps4v ops_v[(!FUSED && EPI4) ? 2 : 1];
+  EpiOps8 ops_t[(!FUSED && !EPI4) ? 2 : 1];
+  // batch k of the wave: FUSED (destination row ph, tile i, registers 4 h4 ..) = (k / (4 TM), (k / 4) % TM, k & 3);
+  // EPI4 tile k; plain (tile i, registers 8 h8 ..) = (k / 2, k & 1)
+  auto fetch = [&](int slot, int k) {
+    if constexpr (FUSED)
+      epi_pair16_fetch(ops_p[slot], k & 3, o0 + ((k >> 2) % TM) * 32, lhi, g.Cm, pvld, pos0 + (size_t)(k / (4 * TM)) * g.dW, (size_t)dHW, res_q, g.mask_y);
+    else if constexpr (EPI4)
+      epi_tile16_v4_fetch(ops_v[slot], o0 + k * 32, lane, g.Cm, pos4, pv4, (size_t)dHW, bias_q, res_q, g.mask_y);
+    else
+      epi_tile16_fetch(ops_t[slot], k & 1, o0 + (k >> 1) * 32, lhi, g.Cm, pvld, pos, (size_t)dHW, bias_q, res_q, g.mask_y);
+  };
+  // Where the first batch goes out.  A wave may issue it only behind its last hand-counted `s_waitcnt vmcnt(n)`: a compiler-issued
+  // load in front of one of those makes it return before the asm loads it counts have landed.  The producers' last counted wait
+  // is in their final stage; the consumers have none after the prologue (their loop waits on lgkmcnt only).
+  //   * producers: right behind their loop -- they are done while the consumers still run the last stage, which covers the trip;
+  //   * consumers of the 32 x 128 tile (EARLY_C): at the top of the last stage, under its nine taps of MFMAs (119 VGPRs of 168);
+  //   * every other consumer: behind the loop, in front of the exchange -- the loads fly while the accumulators drain into xch.
+  //     Inside the loop the batch has to live in registers across the back edge: the 64-channel tiles (219 VGPRs of 256) spilled
+  //     28 / 47 registers with it, the 32 x 256 tile has 149 of 168 and the fused kernel 245 of 256.
+  constexpr bool EARLY_C = !FUSED && TN == 1;
   const u32x4c* wlane = wbuf + lhi * MB + l31;
   if (!producer) {
     {
@@ -892,6 +940,7 @@ __global__ __launch_bounds__(64 * (4 + NPW)) void patch_gemm_x6p_kernel(const X6
 #pragma unroll
       for (int b = 0; b < NSTG; ++b, ++s) {
         const u32x4c* wsl = wlane + (s % RING) * WST;
+        if constexpr (EARLY_C) { if (s + 1 == nst) fetch(0, 0); }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < TPS - 1; ++t) {
@@ -922,7 +971,10 @@ __global__ __launch_bounds__(64 * (4 + NPW)) void patch_gemm_x6p_kernel(const X6
   // ---- epilogue, shared: the consumer keeps its first position block and parks the second one in LDS (every LDS image is dead
   // now: all operand reads returned before the last stage barrier), its producer partner (same SIMD) picks it up, so that all
   // eight waves load residual / mask values and store, as in the symmetric kernel
-  float* xch = reinterpret_cast<float*>(wbuf);                            // [4 consumers][NCLS][TM][16][64] floats <= 64 KB
+  // Every form runs its batches as one software pipeline (epilogue_pipelined) whose first batch is already in flight (EARLY_C) or
+  // goes out here; the barrier of the exchange waits for the LDS writes only, so those loads stay in flight across it.
+  if (TN == 1 && producer) return;
+  if (has_epi && !(EARLY_C && !producer)) fetch(0, 0);
   if constexpr (TN == 2) {
     if (!producer) {
 #pragma unroll
@@ -932,60 +984,35 @@ __global__ __launch_bounds__(64 * (4 + NPW)) void patch_gemm_x6p_kernel(const X6
 #pragma unroll
           for (int r = 0; r < 16; ++r) xch[(((cw * NCLS + q) * TM + i) * 16 + r) * 64 + lane] = acc[q][i][1][r];
     }
-    __syncthreads();
-    if (wave >= 2 * NCW) return;                                          // (a second producer wave per SIMD has no share in the epilogue)
-    if (producer) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   // own xch writes done (not vmcnt: the first batch stays in flight)
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");                                        // (no xch read moves above the barrier)
+    if (!has_epi) return;
+    if (producer) {                                                       // (its own accumulators were never used: block 1 moves into slot 0)
 #pragma unroll
       for (int q = 0; q < NCLS; ++q)
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc[q][i][1][r] = xch[(((cw * NCLS + q) * TM + i) * 16 + r) * 64 + lane];
+          for (int r = 0; r < 16; ++r) acc[q][i][0][r] = xch[(((cw * NCLS + q) * TM + i) * 16 + r) * 64 + lane];
     }
-  } else {
-    if (producer) return;
   }
-  const int dHW = g.dT * g.dH * g.dW;
-#pragma unroll
-  for (int nb = 0; nb < TN; ++nb) {
-    if (TN == 2 && (nb == 1) != producer) continue;                       // consumer: block 0, producer: block 1
-    const int gw = j0w + pjw_[nb], gh = j0h + pjh_[nb], gn = j0b + pjb_[nb];
-    const bool pvld = gn < nimg && gh < g.nH && gw < g.nW;
-    const int gb_ = gn / g.nT, glt = gn - gb_ * g.nT;
-    if constexpr (FUSED) {
-      const size_t pos0 = (size_t)gb_ * g.Cm * dHW + (size_t)(glt * g.oT + g.pT) * g.dH * g.dW + (size_t)(2 * gh) * g.dW + 2 * gw;
-#pragma unroll
-      for (int ph = 0; ph < 2; ++ph)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-          epilogue_pair16(acc[2 * ph][i][nb], acc[2 * ph + 1][i][nb], o0 + i * 32, lhi, g.Cm, pvld, pos0 + (size_t)ph * g.dW, (size_t)dHW,
-                          (g.fused_atomic && blockIdx.z) ? nullptr : g.res, g.mask_y, g.mask_act, g.dst, g.fused_atomic != 0);
-    } else if constexpr (EPI4) {
-      // 16-byte accesses: this lane's group = positions 4 (lane & 7) .. + 3 of the block (one channel per lane and pass)
-      const int pg = cw * 32 * TN + nb * 32 + 4 * (lane & 7);
-      const int qw = pg & JWm, qh = (pg >> g.ljw) & JHm, qb = pg >> (g.ljw + g.ljh);
-      const int hw = j0w + qw, hh = j0h + qh, hn = j0b + qb;
-      const bool pv4 = hn < nimg && hh < g.nH && hw < g.nW;
-      const int hb = hn / g.nT, hlt = hn - hb * g.nT;
-      const size_t pos4 = (size_t)hb * g.Cm * dHW + (size_t)(hlt * g.oT + g.pT) * g.dH * g.dW + (size_t)hh * g.dW + hw;
-      float* tl = xch + 4 * NCLS * TM * 16 * 64 + wave * (32 * 36);      // wave-private 32 x 36 image behind the exchange area
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-        if (g.ksplit > 1)
-          epilogue_tile16_v4(acc[0][i][nb], tl, o0 + i * 32, lane, g.Cm, pos4, pv4, (size_t)dHW, blockIdx.z ? nullptr : g.bias, P2I_ACT_NONE,
-                             blockIdx.z ? nullptr : g.res, g.mask_y, g.mask_act, g.dst, true);
-        else
-          epilogue_tile16_v4(acc[0][i][nb], tl, o0 + i * 32, lane, g.Cm, pos4, pv4, (size_t)dHW, g.bias, g.act_epi, g.res, g.mask_y, g.mask_act, g.dst);
-    } else {
-      const size_t pos = (size_t)gb_ * g.Cm * dHW + (size_t)(glt * g.oT + g.pT) * g.dH * g.dW + (size_t)gh * g.dW + gw;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-        if (g.ksplit > 1)
-          epilogue_tile16(acc[0][i][nb], o0 + i * 32, lhi, g.Cm, pvld, pos, (size_t)dHW, blockIdx.z ? nullptr : g.bias, P2I_ACT_NONE,
-                          blockIdx.z ? nullptr : g.res, g.mask_y, g.mask_act, g.dst, true);
-        else
-          epilogue_tile16(acc[0][i][nb], o0 + i * 32, lhi, g.Cm, pvld, pos, (size_t)dHW, g.bias, g.act_epi, g.res, g.mask_y, g.mask_act, g.dst);
-    }
+  if constexpr (FUSED) {
+    auto finish = [&](int slot, int k) {
+      const int ph = k / (4 * TM), i = (k >> 2) % TM;
+      epi_pair16_finish(ops_p[slot], k & 3, acc[2 * ph][i][0], acc[2 * ph + 1][i][0], res_q, g.mask_y, g.mask_act, g.dst, split);
+    };
+    epilogue_pipelined<8 * TM>(fetch, finish, true);
+  } else if constexpr (EPI4) {
+    if (split) epilogue_pipelined<TM>(fetch, [&](int slot, int k) {
+      epi_tile16_v4_finish(ops_v[slot], acc[0][k][0], tl, lane, P2I_ACT_NONE, res_q, g.mask_y, g.mask_act, g.dst, true); }, true);
+    else epilogue_pipelined<TM>(fetch, [&](int slot, int k) {
+      epi_tile16_v4_finish(ops_v[slot], acc[0][k][0], tl, lane, g.act_epi, g.res, g.mask_y, g.mask_act, g.dst, false); }, true);
+  } else {
+    if (split) epilogue_pipelined<2 * TM>(fetch, [&](int slot, int k) {
+      epi_tile16_finish(ops_t[slot], k & 1, acc[0][k >> 1][0], bias_q, P2I_ACT_NONE, res_q, g.mask_y, g.mask_act, g.dst, true); }, true);
+    else epilogue_pipelined<2 * TM>(fetch, [&](int slot, int k) {
+      epi_tile16_finish(ops_t[slot], k & 1, acc[0][k >> 1][0], g.bias, g.act_epi, g.res, g.mask_y, g.mask_act, g.dst, false); }, true);
   }
 #ifdef P2I_STAMP
   if (p2i_stamp_buf && lane == 0) {

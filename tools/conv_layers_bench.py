@@ -1,5 +1,7 @@
 """Every conv-engine launch shape of one configs[1] train step, timed in isolation (HIP events on the launch stream).
-usage: python tools/conv_layers_bench.py [B=8] [iters=10] [which=all|fwd|dgrad|wgrad] [filter substring]
+usage: python tools/conv_layers_bench.py [B=8] [iters=10] [which=all|fwd|dgrad|wgrad|epi] [filter substring]
+which=epi: the epilogue forms of a train step instead -- fwd (ReLU), fwd_res (+ residual: second conv of a ResBlock), dgrad_add,
+dgrad_mask (the act' mask of the layer below: ReLU in the generator, LeakyReLU in the discriminators).
 Also the workload for the rocprofv3 --pmc passes (profiles/README.md)."""
 import os
 import sys
@@ -60,10 +62,14 @@ for name, spec, (c, t, h, w) in LAYERS:
     wp_f, wp_d = ops.weight_pack(torch.randn(spec.cout, spec.cin, spec.ntaps, device=dev) * 0.05)
     fl = 2.0 * B * spec.cout * spec.cin * spec.ntaps * to * ho * wo
     # (the generator's DO-Conv layers have no bias)
+    mact = ops.ACT_RELU if name.startswith("G") else ops.ACT_LEAKY
     for kind, fn in (("fwd", lambda: ops.conv_fwd(spec, x, wp_f, act=ops.ACT_RELU)),
+                     ("fwd_res", lambda: ops.conv_fwd(spec, x, wp_f, residual=dy)),
                      ("dgrad", lambda: ops.conv_dgrad(spec, dy, wp_d, xs, add=x)),
+                     ("dgrad_add", lambda: ops.conv_dgrad(spec, dy, wp_d, xs, add=x)),
+                     ("dgrad_mask", lambda: ops.conv_dgrad(spec, dy, wp_d, xs, mask_y=x, mask_act=mact)),
                      ("wgrad", lambda: ops.conv_wgrad(spec, x, dy, want_bias=not name.startswith("G l")))):
-        if which not in ("all", kind):
+        if kind not in (("fwd", "dgrad", "wgrad") if which == "all" else ("fwd", "fwd_res", "dgrad_add", "dgrad_mask") if which == "epi" else (which,)):
             continue
         for _ in range(2):
             fn()
@@ -75,4 +81,4 @@ for name, spec, (c, t, h, w) in LAYERS:
         e1.record()
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) * 1e3 / n
-        print(f"B={B} {name:22s} {kind:5s} {us:8.1f} us {fl / us / 1e6:7.1f} TF plan={plan(kind)}", flush=True)
+        print(f"B={B} {name:22s} {kind:10s} {us:8.1f} us {fl / us / 1e6:7.1f} TF plan={plan(kind)}", flush=True)
