@@ -661,6 +661,36 @@ int p2i_stkrig_loso(const double* gram, const double* sol, const float* alpha, c
                     const int* site_start, const int* nsites, const int* back, const int* status, const int* cand, int s0, int T,
                     int nsys, int np, int fcap, int cap, float* pred, float* var, void* stream);
 
+/* ---- Lagrangian space-time ordinary kriging (no counterpart in the reference): the space-time block above with
+ * its distance measured in the frame that moves with the rain, d = sqrt((dy - v_y dt)^2 + (dx - v_x dt)^2 + kappa^2 dt^2), dy, dx, dt
+ * the integer pixel and frame differences of two points and v = (v_y, v_x) the sample's advection velocity in pixels per frame.  The
+ * nugget applies at dt = 0 and dy = dx = 0 only.  vel [B][2] fp64 and velf [B][2] fp32 hold (v_y, v_x) per sample; the velocity
+ * estimate and the bins are fp64, K, its factor and c0 fp32, the predictor's sum fp64.  All sums run in a fixed order.  Gather, fit,
+ * solve, inverse and the leave-one-site-out entry points are the space-time block's (p2i_stkrig_gather, p2i_stkrig_fit,
+ * p2i_krig_solve, p2i_krig_invert, p2i_stkrig_gather_sites, p2i_stkrig_site_gram, p2i_stkrig_loso), unchanged.
+ * p2i_lagkrig_velocity: candidates v = (i, j) vstep, |i|, |j| <= nhalf <= 16, index c = (i + nhalf) n + (j + nhalf), n = 2 nhalf + 1.
+ *   Over the pairs (gauge a in frame t, gauge b in frame t + u), 1 <= u <= n_tlags (<= 7, < T), of p2i_krig_compact's per-frame
+ *   arrays, with w = exp(-|x_b - x_a - v u|^2 / (2 bandwidth^2)) (bandwidth in pixels): part [B][chunks][n n][3] = the partial sums
+ *   of (w, w (z_a - z_b)^2 / 2, w over the pairs with x_b != x_a) of workgroup `chunks` index (it takes the rows a = chunk mod chunks).
+ * p2i_lagkrig_pick: adds the chunks in order into weight [B][n n] = W(v) = sum w, support [B][n n] = N(v) = sum w over the pairs of
+ *   distinct pixels and score [B][n n] = (sum w (z_a - z_b)^2 / 2) / W(v) (+inf where W(v) = 0), and takes the candidate of the
+ *   smallest score among those with N(v) >= N(0) / 2; ties go to the smaller i^2 + j^2, then to the lower c (no pair, or zero
+ *   variance: v = 0).  vel, velf [B][2] = (i, j) vstep, vcand [B] = c.
+ * p2i_lagkrig_bins: p2i_stkrig_bins with h = |x_j - x_i - v u| for a pair (i in frame t, j in frame t + u); the same part layout, to
+ *   be fitted by p2i_stkrig_fit.  With vel = 0 the bins are p2i_stkrig_bins' bit for bit.
+ * p2i_lagkrig_factor, p2i_lagkrig_predict: p2i_stkrig_factor and p2i_stkrig_predict with the distance above (one device function
+ *   serves both and is symmetric in its two points bit for bit, so a gauge is reproduced in its own frame at nugget 0). */
+int p2i_lagkrig_velocity(const int* pix, const float* z, const int* counts, int B, int T, int cap, int chunks, int n_tlags, int nhalf,
+                         double vstep, double bandwidth, double* part, void* stream);
+int p2i_lagkrig_pick(const double* part, int B, int chunks, int nhalf, double vstep, double* score, double* weight, double* support,
+                     double* vel, float* velf, int* vcand, void* stream);
+int p2i_lagkrig_bins(const int* pix, const float* z, const int* counts, const double* vel, int B, int T, int cap, int chunks, int n_lags,
+                     int n_tlags, double lag_width, double* part, void* stream);
+int p2i_lagkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, const float* velf, int model, int s0,
+                       int nsys, int np, int cap, float* L, int* status, void* stream);
+int p2i_lagkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
+                        const float* params, const float* velf, int model, int B, int T, int H, int W, int cap, float* out, void* stream);
+
 /* ---- scale-aware verification: fractions skill score and radially averaged power spectra (no counterpart in
  * the reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform
  * and uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <= P2I_SCALE_MAX_CROP.

@@ -4,8 +4,8 @@ predicted from the frame's other gauges by the model's ``cross_validate`` (csrc/
 the device, chunk by chunk, and added per event and overall on the host.
 
 Leave-one-site-out (LOSO; csrc/stkrig_loso.hip) is the same loop over the models' ``cross_validate_sites``: a
-site (a gauge pixel in all frames of a chunk) is left out as a whole.  It is the score of the space-time baseline `stkriging`, whose
-point-wise LOO would flatter it; for `kriging` and `idw` it equals LOO and puts the three in one table over the same targets."""
+site (a gauge pixel in all frames of a chunk) is left out as a whole.  It is the score of the space-time baselines `stkriging` and
+`lagkriging`, whose point-wise LOO would flatter them; for `kriging` and `idw` it equals LOO and puts all in one table over the same targets."""
 from __future__ import annotations
 
 import json
@@ -54,33 +54,36 @@ def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_s
     them (each chunk is one sample of a fitted variogram).  Writes loo.json / loo.txt (scores per event and overall) and loo_data.npz
     (per gauge: event, frame, y, x, z, LOO prediction, LOO variance; coded units, unscaled) under out_dir; returns loo.json's content."""
     from ..models import CLASSICAL
+    from ..models.classical import SPACE_TIME
     name = str(cfg.get("model", {}).get("name", "model")).lower()
     if name not in CLASSICAL:
-        raise RuntimeError(f"leave-one-out cross-validation is defined for the classical baselines {sorted(set(CLASSICAL) - {'stkriging'})} only: "
+        raise RuntimeError(f"leave-one-out cross-validation is defined for the classical baselines {sorted(set(CLASSICAL) - set(SPACE_TIME))} only: "
                            f"model.name '{name}' is a learnt model and would need one training per gauge")
-    if name == "stkriging":
-        from ..models.classical import ST_NO_LOO
-        raise RuntimeError(ST_NO_LOO)
+    if name in SPACE_TIME:
+        from ..models.classical import LAG_NO_LOO, ST_NO_LOO
+        raise RuntimeError(ST_NO_LOO if name == "stkriging" else LAG_NO_LOO)
     return _run(cfg, out_dir, device, output_scale, stride, name, False)
 
 
 def run_loso(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_scale: float = 255.0, stride: int = 16) -> Dict[str, Any]:
-    """run_loo with whole sites left out (the models' cross_validate_sites), for all three classical baselines.  A chunk of `stride`
-    frames is one sample, so a site is a gauge pixel over the chunk's frames; `stkriging` takes chunks of at most 32 frames.  Writes
+    """run_loo with whole sites left out (the models' cross_validate_sites), for all classical baselines.  A chunk of `stride`
+    frames is one sample, so a site is a gauge pixel over the chunk's frames; `stkriging` and `lagkriging` take chunks of at most 32 frames.  Writes
     loso.json / loso.txt and loso_data.npz (loo_data.npz's columns plus site, the site's index within its chunk) under out_dir."""
     from ..models import CLASSICAL
+    from ..models.classical import SPACE_TIME
     from .. import ops
     name = str(cfg.get("model", {}).get("name", "model")).lower()
     if name not in CLASSICAL:
         raise RuntimeError(f"leave-one-site-out cross-validation is defined for the classical baselines {sorted(CLASSICAL)} only: "
                            f"model.name '{name}' is a learnt model and would need one training per site")
-    if name == "stkriging" and int(stride) > ops.KRIG_TILE:
-        raise ValueError(f"leave-one-site-out of 'stkriging' takes chunks of at most {ops.KRIG_TILE} frames: --stride {int(stride)} is too long")
+    if name in SPACE_TIME and int(stride) > ops.KRIG_TILE:
+        raise ValueError(f"leave-one-site-out of '{name}' takes chunks of at most {ops.KRIG_TILE} frames: --stride {int(stride)} is too long")
     return _run(cfg, out_dir, device, output_scale, stride, name, True)
 
 
 def _run(cfg, out_dir, device, output_scale, stride, name, by_site):
     from ..models import build_generator
+    from ..models.classical import SPACE_TIME
     dev = torch.device(device or cfg.get("device", "cuda:0"))
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise RuntimeError("the MI355X path needs a GPU: there is no CPU fallback")
@@ -90,7 +93,7 @@ def _run(cfg, out_dir, device, output_scale, stride, name, by_site):
         raise RuntimeError("Test dataloader is not configured or empty.")
     G = build_generator(cfg).to(dev).eval()
     scale, stride = float(output_scale), max(1, int(stride))
-    with_var = name == "kriging" or (by_site and name == "stkriging")
+    with_var = name == "kriging" or (by_site and name in SPACE_TIME)
     stem = "loso" if by_site else "loo"
     events, cols = {}, {k: [] for k in ("event", "frame", "y", "x", "z", "pred", "var") + (("site",) if by_site else ())}
     total = np.zeros(5)

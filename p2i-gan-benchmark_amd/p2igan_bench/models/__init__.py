@@ -2,14 +2,15 @@
 
 The P2I-GAN family and the STDK (spatio-temporal DeepKriging) baseline are built on the HIP path, and so are two parameter-free
 classical baselines the reference does not have: ordinary kriging and all-gauge IDW (models/classical.py),
-and space-time ordinary kriging over all frames of a sample (`stkriging`).
+space-time ordinary kriging over all frames of a sample (`stkriging`) and its Lagrangian form with a fitted
+advection velocity (`lagkriging`).
 The purely spatial DK baseline and the `simple` fallback stub are out of this build's scope and raise a clear
 error."""
 from typing import Any, Dict
 
 import torch.nn as nn
 
-from .classical import CLASSICAL, IDWGenerator, KrigingGenerator, SpaceTimeKrigingGenerator
+from .classical import CLASSICAL, IDWGenerator, KrigingGenerator, LagrangianKrigingGenerator, SpaceTimeKrigingGenerator
 from .p2igan import P2IDiscriminator, P2IGenerator
 from .stdk import STDKGenerator
 
@@ -27,7 +28,7 @@ def build_generator(cfg: Dict[str, Any]) -> nn.Module:
         return STDKGenerator(cfg, length=data_cfg.get("sample_length", 16))
     if name in CLASSICAL:
         return CLASSICAL[name](cfg)
-    raise NotImplementedError(f"model '{name}': only 'p2igan', 'stdk', 'kriging', 'idw' and 'stkriging' are implemented on the MI355X path")
+    raise NotImplementedError(f"model '{name}': only 'p2igan', 'stdk', 'kriging', 'idw', 'stkriging' and 'lagkriging' are implemented on the MI355X path")
 
 
 def build_discriminator(cfg: Dict[str, Any]) -> nn.Module:
@@ -41,4 +42,4 @@ def build_discriminator(cfg: Dict[str, Any]) -> nn.Module:
 
 
 __all__ = ["build_generator", "build_discriminator", "P2IGenerator", "P2IDiscriminator", "STDKGenerator",
-           "KrigingGenerator", "IDWGenerator", "SpaceTimeKrigingGenerator"]
+           "KrigingGenerator", "IDWGenerator", "SpaceTimeKrigingGenerator", "LagrangianKrigingGenerator"]

@@ -10,8 +10,11 @@ cross_validate of either model predicts every gauge from the frame's other gauge
 
 Space-time kriging (csrc/stkrig.hip): SpaceTimeKrigingGenerator kriges every pixel of every frame of a sample
 from all gauges of all frames of that sample, one system per sample, with a metric space-time covariance.  Its truth-free score is
-leave-one-site-out (csrc/stkrig_loso.hip): cross_validate_sites of all three models predicts every point of a
-site (a gauge pixel in all the sample's frames) with the whole site left out."""
+leave-one-site-out (csrc/stkrig_loso.hip): cross_validate_sites of all models predicts every point of a
+site (a gauge pixel in all the sample's frames) with the whole site left out.
+
+Lagrangian space-time kriging (csrc/lagkrig.hip): LagrangianKrigingGenerator measures the space-time distance
+in the frame that moves with the rain, with an advection velocity per sample that it estimates from the gauges."""
 from __future__ import annotations
 
 import logging
@@ -292,6 +295,12 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         self.last_fit = {"bins": bins, "fit": fit, "cand": cand, "q": q, "c": cand - q * ops.KRIG_CANDIDATES}
         return cand, params
 
+    def _factor(self, stpix, stt, stinfo, params, s0, ns, np_, work, st):
+        ops.stkrig_factor(stpix, stt, stinfo, params, self.variogram_model, s0, ns, np_, work, st)
+
+    def _predict(self, stpix, stt, alpha, mean, stinfo, params, t, h, w):
+        return ops.stkrig_predict(stpix, stt, alpha, mean, stinfo, params, self.variogram_model, t, h, w)
+
     @torch.no_grad()
     def forward(self, masked_frames, masks):
         b, t, _, h, w = masked_frames.shape
@@ -307,9 +316,9 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         for s0 in range(0, b, per):
             ns = min(per, b - s0)
             st = status[s0:s0 + ns]
-            ops.stkrig_factor(stpix, stt, stinfo, params, self.variogram_model, s0, ns, np_, work, st)
+            self._factor(stpix, stt, stinfo, params, s0, ns, np_, work, st)
             ops.krig_solve(work, stz, stinfo, st, cand, s0, 1, 1, ns, np_, alpha, mean)      # the samples stand in for frames
-        out = ops.stkrig_predict(stpix, stt, alpha, mean, stinfo, params, self.variogram_model, t, h, w)
+        out = self._predict(stpix, stt, alpha, mean, stinfo, params, t, h, w)
         self.last_status = status
         failed = int(status.sum())
         if failed:
@@ -339,7 +348,7 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         for s0 in range(0, b, per):
             ns = min(per, b - s0)
             st = status[s0:s0 + ns]
-            ops.stkrig_factor(sites["stpix"], sites["stt"], sites["stinfo"], params, self.variogram_model, s0, ns, np_, work, st)
+            self._factor(sites["stpix"], sites["stt"], sites["stinfo"], params, s0, ns, np_, work, st)
             sol = ops.krig_solve(work, sites["stz"], sites["stinfo"], st, cand, s0, 1, 1, ns, np_, alpha, mean)
             ops.krig_invert(work, ns, np_, winv)
             gram = ops.stkrig_site_gram(winv, ns, np_)
@@ -351,8 +360,84 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         return LOOResult(pix, z, pred, var, info[:b * t], status, sites["fsite"])
 
 
+class LagrangianKrigingGenerator(SpaceTimeKrigingGenerator):
+    """Space-time kriging in the frame that moves with the rain: SpaceTimeKrigingGenerator with the distance
+    sqrt((dy - v_y dt)^2 + (dx - v_x dt)^2 + kappa^2 dt^2), one advection velocity v = (v_y, v_x) in pixels per frame per sample.
+    model.variogram is SpaceTimeKrigingGenerator's.  model.advection = {"fit": true, "vmax": 4.0, "vstep": 0.5, "n_tlags": 3,
+    "bandwidth": 1.5} estimates v per sample on the device from the gauges alone, over the candidates (i, j) vstep with |i|, |j| <=
+    round(vmax / vstep) (ops.lagkrig_velocity; bandwidth in lag widths of the variogram binning); {"fit": false, "vy", "vx"} takes it
+    as given.  last_fit holds "velocity" (B, 2) fp64 and, with a fitted velocity, the "score", "weight" and "support" tables (B, n, n) and "vcand";
+    with a fitted variogram SpaceTimeKrigingGenerator's keys too.  As there, no forward_uq and no cross_validate; cross_validate_sites
+    fits the velocity and the variogram once from all sites (no refits)."""
+
+    def __init__(self, config: Dict[str, Any]):
+        super().__init__(config)
+        adv = dict(config.get("model", {}).get("advection") or {})
+        self.fit_velocity = bool(adv.get("fit", True))
+        if self.fit_velocity:
+            self.vmax, self.vstep = float(adv.get("vmax", 4.0)), float(adv.get("vstep", 0.5))
+            self.adv_tlags, self.bandwidth = int(adv.get("n_tlags", 3)), float(adv.get("bandwidth", 1.5))
+            if not (self.vstep > 0 and self.vmax >= 0 and math.isfinite(self.vmax) and math.isfinite(self.vstep)):
+                raise ValueError(f"model.advection: vstep > 0 and vmax >= 0 are required (got vmax {self.vmax}, vstep {self.vstep})")
+            self.nhalf = int(math.floor(self.vmax / self.vstep + 0.5))
+            if self.nhalf > ops.LAGKRIG_MAX_VHALF:
+                raise ValueError(f"model.advection: round(vmax / vstep) = {self.nhalf} gives {(2 * self.nhalf + 1) ** 2} candidate velocities, "
+                                 f"more than the {ops.LAGKRIG_MAX_CANDIDATES} (|i|, |j| <= {ops.LAGKRIG_MAX_VHALF}) the kernel takes")
+            if not 0 <= self.adv_tlags <= ops.STKRIG_MAX_TLAGS:
+                raise ValueError(f"model.advection.n_tlags must be in [0, {ops.STKRIG_MAX_TLAGS}] (got {self.adv_tlags})")
+            if not (self.bandwidth > 0 and math.isfinite(self.bandwidth)):
+                raise ValueError(f"model.advection.bandwidth must be positive (got {self.bandwidth})")
+            if not 1 <= self.n_lags <= ops.KRIG_MAX_LAGS:          # the bandwidth's unit
+                raise ValueError(f"model.variogram.n_lags must be in [1, {ops.KRIG_MAX_LAGS}] (got {self.n_lags})")
+        else:
+            try:
+                self.fixed_v = (float(adv["vy"]), float(adv["vx"]))
+            except KeyError as e:
+                raise ValueError(f"model.advection with fit=false needs vy and vx (missing {e})") from None
+            if not all(math.isfinite(v) for v in self.fixed_v):
+                raise ValueError(f"model.advection: vy and vx must be finite (got {self.fixed_v})")
+        self._velf = None
+
+    def cross_validate(self, masked_frames, masks):
+        raise RuntimeError(LAG_NO_LOO)
+
+    def _variogram(self, pix, z, info, b, t, h, w):
+        """(cand or None, params): the velocity first (kept for _factor and _predict), then the variogram on the advected distance."""
+        lag_width = (min(h, w) / 2.0) / self.n_lags
+        if self.fit_velocity:
+            score, weight, support, vel, velf, vcand = ops.lagkrig_velocity(pix, z, info, b, t, min(self.adv_tlags, t - 1), self.nhalf, self.vstep,
+                                                                            self.bandwidth * lag_width)
+            last = {"velocity": vel, "score": score, "weight": weight, "support": support, "vcand": vcand}
+        else:
+            vel = torch.tensor(self.fixed_v, dtype=torch.float64).repeat(b, 1).to(pix.device)
+            velf = vel.float()
+            last = {"velocity": vel}
+        self._velf = velf
+        cand = None
+        if self.fit:
+            bins, fit, cand, params = ops.lagkrig_variogram(pix, z, info, vel, b, t, self.n_lags, min(self.n_tlags, t - 1), lag_width,
+                                                            self.variogram_model)
+            q = torch.div(cand, ops.KRIG_CANDIDATES, rounding_mode="floor")
+            last.update({"bins": bins, "fit": fit, "cand": cand, "q": q, "c": cand - q * ops.KRIG_CANDIDATES})
+        else:
+            params = torch.tensor(self.fixed, dtype=torch.float32).repeat(b, 1).to(pix.device)
+        self.last_fit = last
+        return cand, params
+
+    def _factor(self, stpix, stt, stinfo, params, s0, ns, np_, work, st):
+        ops.lagkrig_factor(stpix, stt, stinfo, params, self._velf, self.variogram_model, s0, ns, np_, work, st)
+
+    def _predict(self, stpix, stt, alpha, mean, stinfo, params, t, h, w):
+        return ops.lagkrig_predict(stpix, stt, alpha, mean, stinfo, params, self._velf, self.variogram_model, t, h, w)
+
+
 ST_NO_LOO = ("space-time kriging ('stkriging') has no leave-one-out cross-validation: leaving out one (site, frame) observation while "
               "the same site's neighbouring frames stay in would flatter the method; the honest score is leave-one-site-out: "
               "cross_validate_sites, evaluation.run_loso, scripts/crossvalidate.py --by-site")
 
-CLASSICAL = {"kriging": KrigingGenerator, "idw": IDWGenerator, "stkriging": SpaceTimeKrigingGenerator}
+LAG_NO_LOO = ST_NO_LOO.replace("space-time kriging ('stkriging')", "Lagrangian space-time kriging ('lagkriging')")
+
+SPACE_TIME = ("stkriging", "lagkriging")          # one system per sample: no point-wise leave-one-out, LOSO chunks of at most 32 frames
+
+CLASSICAL = {"kriging": KrigingGenerator, "idw": IDWGenerator, "stkriging": SpaceTimeKrigingGenerator,
+             "lagkriging": LagrangianKrigingGenerator}

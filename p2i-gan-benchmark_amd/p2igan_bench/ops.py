@@ -1794,8 +1794,117 @@ def stkrig_loso(gram, sol, alpha, sites, status, cand, s0, T, nsys, np_, pred, v
                                    _ptr(pred), _ptr(var), _stream()), "p2i_stkrig_loso")
 
 
+# ---- Lagrangian space-time kriging (csrc/lagkrig.hip)
+LAGKRIG_MAX_VHALF = 16                                   # candidate velocities (i s, j s), |i|, |j| <= nhalf <= 16
+LAGKRIG_MAX_CANDIDATES = (2 * LAGKRIG_MAX_VHALF + 1) ** 2   # 33 x 33 = 1089: the largest grid the velocity kernels take
+LAGKRIG_VEL_CHUNKS = 32                                  # workgroups per (sample, candidate block) of the velocity pass (fixed: added in order)
+
+
+def _lag_vel(who, vel, dtype, B):
+    _krig_t(who, vel, dtype, (B, 2))
+
+
+def lagkrig_velocity(pix, z, info, B, T, n_tlags, nhalf, vstep, bandwidth):
+    """The advection velocity of every sample from its gauges: over the (2 nhalf + 1)^2 candidates v = (i, j) vstep (px / frame) and the
+    pairs (gauge a in frame t, gauge b in frame t + u), 1 <= u <= n_tlags, with w = exp(-|x_b - x_a - v u|^2 / (2 bandwidth^2)):
+    weight = sum w, score = sum w (z_a - z_b)^2 / 2 / weight (+inf where the weight is 0), support = sum w over the pairs of distinct
+    pixels.  The estimate is the candidate of the smallest score among those with support >= support(v = 0) / 2; ties go to the
+    smaller |v|^2, then to the lower index.  fp64 on the device.  Returns score, weight, support (B, n, n) fp64 (n = 2 nhalf + 1,
+    [i + nhalf][j + nhalf]), vel (B, 2) fp64 = (v_y, v_x), velf its fp32 copy and vcand (B,) int32 = (i + nhalf) n + (j + nhalf)."""
+    lib = _hip.load()
+    F = B * T
+    cap = pix.shape[1]
+    _krig_t("lagkrig_velocity", pix, torch.int32, (F, cap))
+    _krig_t("lagkrig_velocity", z, torch.float32, (F, cap))
+    _krig_t("lagkrig_velocity", info, torch.int32, (2 * F,))
+    if not (0 <= n_tlags <= STKRIG_MAX_TLAGS and n_tlags < T):
+        raise ValueError(f"lagkrig_velocity: n_tlags must be 0..{STKRIG_MAX_TLAGS} and below T = {T} (got {n_tlags})")
+    if not 0 <= nhalf <= LAGKRIG_MAX_VHALF:
+        raise ValueError(f"lagkrig_velocity: at most {LAGKRIG_MAX_CANDIDATES} candidates, nhalf <= {LAGKRIG_MAX_VHALF} (got {nhalf})")
+    if not (vstep > 0 and bandwidth > 0):
+        raise ValueError("lagkrig_velocity: the velocity step and the bandwidth must be positive")
+    dev = pix.device
+    n = 2 * nhalf + 1
+    part = torch.empty(B, LAGKRIG_VEL_CHUNKS, n * n, 3, device=dev, dtype=torch.float64)
+    score = torch.empty(B, n, n, device=dev, dtype=torch.float64)
+    weight = torch.empty(B, n, n, device=dev, dtype=torch.float64)
+    support = torch.empty(B, n, n, device=dev, dtype=torch.float64)
+    vel = torch.empty(B, 2, device=dev, dtype=torch.float64)
+    velf = torch.empty(B, 2, device=dev, dtype=torch.float32)
+    vcand = torch.empty(B, device=dev, dtype=torch.int32)
+    _hip.check(lib.p2i_lagkrig_velocity(_ptr(pix), _ptr(z), _ptr(info), B, T, cap, LAGKRIG_VEL_CHUNKS, n_tlags, nhalf, float(vstep),
+                                        float(bandwidth), _ptr(part), _stream()), "p2i_lagkrig_velocity")
+    _hip.check(lib.p2i_lagkrig_pick(_ptr(part), B, LAGKRIG_VEL_CHUNKS, nhalf, float(vstep), _ptr(score), _ptr(weight), _ptr(support), _ptr(vel),
+                                    _ptr(velf), _ptr(vcand), _stream()), "p2i_lagkrig_pick")
+    return score, weight, support, vel, velf, vcand
+
+
+def lagkrig_variogram(pix, z, info, vel, B, T, n_lags, n_tlags, lag_width, model):
+    """stkrig_variogram with the pairs of temporal lag u binned by the advected spatial distance |x_j - x_i - v u|, vel (B, 2) fp64; the
+    fit is p2i_stkrig_fit's, unchanged.  With vel = 0 the bins are stkrig_variogram's bit for bit."""
+    lib = _hip.load()
+    F = B * T
+    cap = pix.shape[1]
+    _krig_t("lagkrig_variogram", pix, torch.int32, (F, cap))
+    _krig_t("lagkrig_variogram", z, torch.float32, (F, cap))
+    _krig_t("lagkrig_variogram", info, torch.int32, (2 * F,))
+    _lag_vel("lagkrig_variogram", vel, torch.float64, B)
+    if not (1 <= n_lags <= KRIG_MAX_LAGS) or not lag_width > 0:
+        raise ValueError(f"lagkrig_variogram: n_lags must be 1..{KRIG_MAX_LAGS} and the lag width positive")
+    if not (0 <= n_tlags <= STKRIG_MAX_TLAGS and n_tlags < T):
+        raise ValueError(f"lagkrig_variogram: n_tlags must be 0..{STKRIG_MAX_TLAGS} and below T = {T} (got {n_tlags})")
+    dev = pix.device
+    part = torch.empty(B, n_tlags + 1, STKRIG_BIN_CHUNKS, n_lags, 3, device=dev, dtype=torch.float64)
+    bins = torch.empty(B, n_tlags + 1, n_lags, 3, device=dev, dtype=torch.float64)
+    fit = torch.empty(B, 5, device=dev, dtype=torch.float64)
+    cand = torch.empty(B, device=dev, dtype=torch.int32)
+    params = torch.empty(B, 4, device=dev, dtype=torch.float32)
+    _hip.check(lib.p2i_lagkrig_bins(_ptr(pix), _ptr(z), _ptr(info), _ptr(vel), B, T, cap, STKRIG_BIN_CHUNKS, n_lags, n_tlags,
+                                    float(lag_width), _ptr(part), _stream()), "p2i_lagkrig_bins")
+    _hip.check(lib.p2i_stkrig_fit(_ptr(part), B, STKRIG_BIN_CHUNKS, n_lags, n_tlags, float(lag_width), int(model), _ptr(bins), _ptr(fit),
+                                  _ptr(cand), _ptr(params), _stream()), "p2i_stkrig_fit")
+    return bins, fit, cand, params
+
+
+def lagkrig_factor(stpix, stt, stinfo, params, velf, model, s0, nsys, np_, L, status):
+    """stkrig_factor with the Lagrangian distance; velf (B, 2) fp32 = (v_y, v_x) per sample."""
+    lib = _hip.load()
+    B, cap = stpix.shape
+    _krig_t("lagkrig_factor", stpix, torch.int32)
+    _krig_t("lagkrig_factor", stt, torch.int32, (B, cap))
+    _krig_t("lagkrig_factor", stinfo, torch.int32, (2 * B,))
+    _krig_t("lagkrig_factor", params, torch.float32, (B, 4))
+    _lag_vel("lagkrig_factor", velf, torch.float32, B)
+    _krig_t("lagkrig_factor", L, torch.float32)
+    _krig_t("lagkrig_factor", status, torch.int32, (nsys,))
+    _krig_sys("lagkrig_factor", s0, 1, 1, nsys, B, np_, cap)
+    if L.numel() < nsys * np_ * np_:
+        raise RuntimeError("lagkrig_factor: factor workspace too small")
+    _hip.check(lib.p2i_lagkrig_factor(_ptr(stpix), _ptr(stt), _ptr(stinfo), _ptr(params), _ptr(velf), int(model), s0, nsys, np_, cap, _ptr(L),
+                                      _ptr(status), _stream()), "p2i_lagkrig_factor")
+
+
+def lagkrig_predict(stpix, stt, alpha, mean, stinfo, params, velf, model, T, H, W):
+    """out (B, T, H*W) = mean_b + sum_i alpha_i c0((t, p), i) over the sample's space-time points, Lagrangian distance."""
+    lib = _hip.load()
+    B, cap = stpix.shape
+    _krig_t("lagkrig_predict", stpix, torch.int32)
+    _krig_t("lagkrig_predict", stt, torch.int32, (B, cap))
+    _krig_t("lagkrig_predict", alpha, torch.float32, (B, cap))
+    _krig_t("lagkrig_predict", mean, torch.float32, (B,))
+    _krig_t("lagkrig_predict", stinfo, torch.int32, (2 * B,))
+    _krig_t("lagkrig_predict", params, torch.float32, (B, 4))
+    _lag_vel("lagkrig_predict", velf, torch.float32, B)
+    if T < 1 or H < 1 or W < 1 or cap % KRIG_TILE or cap > KRIG_MAX_CAP:
+        raise RuntimeError(f"lagkrig_predict: bad shape T {T}, {H} x {W}, cap {cap}")
+    out = torch.empty(B, T, H * W, device=stpix.device, dtype=torch.float32)
+    _hip.check(lib.p2i_lagkrig_predict(_ptr(stpix), _ptr(stt), _ptr(alpha), _ptr(mean), _ptr(stinfo), _ptr(params), _ptr(velf), int(model), B,
+                                       T, H, W, cap, _ptr(out), _stream()), "p2i_lagkrig_predict")
+    return out
+
+
 # ---- kriging variance and leave-one-out cross-validation (csrc/krig_uq.hip, DESIGN.md section 16)
-LOO_NSUM = 5             # (n, sum e, sum |e|, sum e^2, sum e^2 / var)
+LOO_NSUM = 5            # (n, sum e, sum |e|, sum e^2, sum e^2 / var)
 
 
 def krig_invert(L, nsys, np_, Winv):

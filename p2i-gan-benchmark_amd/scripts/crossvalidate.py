@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Leave-one-out gauge cross-validation of a classical baseline (model.name: kriging / idw) over the test events: every gauge is
 predicted from the other gauges of its frame, which needs no gridded truth.  Writes loo.json, loo.txt and loo_data.npz
-(p2igan_bench/evaluation/loo.py).  The space-time baseline `stkriging` is refused there: its honest score is
-leave-one-site-out, --by-site: a site, a gauge pixel over all frames of a chunk of --stride frames, is left
-out as a whole.  --by-site takes kriging, idw and stkriging (chunks of at most 32 frames) and writes loso.json, loso.txt and
-loso_data.npz."""
+(p2igan_bench/evaluation/loo.py).  The space-time baselines `stkriging` and `lagkriging` are refused there:
+their honest score is leave-one-site-out, --by-site: a site, a gauge pixel over all frames of a chunk of
+--stride frames, is left out as a whole.  --by-site takes kriging, idw, stkriging and lagkriging (the last two in chunks of at
+most 32 frames) and writes loso.json, loso.txt and loso_data.npz."""
 from __future__ import annotations
 
 import argparse
@@ -28,7 +28,7 @@ def parse_args(argv=None):
     p.add_argument("--data-root", type=Path, default=None)
     p.add_argument("--output", type=Path, required=True)
     p.add_argument("--stride", type=int, default=16)
-    p.add_argument("--by-site", action="store_true", help="leave whole sites out (leave-one-site-out); the score of stkriging")
+    p.add_argument("--by-site", action="store_true", help="leave whole sites out (leave-one-site-out); the score of stkriging and lagkriging")
     p.add_argument("--device", type=str, default=None)
     p.add_argument("--output-scale", type=float, default=255.0)
     p.add_argument("--log-level", type=str, default="INFO")
