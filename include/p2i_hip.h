@@ -691,6 +691,29 @@ int p2i_lagkrig_factor(const int* stpix, const int* stt, const int* stcounts, co
 int p2i_lagkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
                         const float* params, const float* velf, int model, int B, int T, int H, int W, int cap, float* out, void* stream);
 
+/* ---- moving-neighbourhood space-time ordinary kriging (no counterpart in the reference): every target is
+ * predicted from its k nearest points in the space-time metric, from a k x k system of its own.  pix / z / counts are
+ * p2i_krig_compact's per-frame arrays (fcap slots per frame, B T frames); there is no limit on the points of a sample.  params [B][4]
+ * fp32 = (nugget, psill, range, kappa); cand [B] (nullable: p2i_stkrig_fit's, < 0 marks a degenerate sample).
+ * Candidates of a target in frame t: the points of its sample in frames t' with |t' - t| <= frames (0 <= frames < T).  Key, fp64:
+ * (dy^2 + dx^2) + (kappa kappa) dt^2, one rounded product and one rounded sum.  Neighbours: the first m = min(k, candidates) in
+ * ascending (key, frame, raster index), 1 <= k <= 64.  With K_ij = C(d(i, j)) + nugget [i = j], c0_i = C(d(target, i)) + nugget [same
+ * pixel and frame], d the fp32 distance of the space-time block above: K a = c0, K u = 1, mu = (1^T a - 1) / 1^T u, lambda = a - mu u,
+ * prediction lambda^T z, variance psill + nugget - lambda^T c0 - mu clamped at 0 (exactly 0 on a gauge pixel in its own frame).  K, its
+ * factor and c0 are fp32, every sum fp64 in a fixed order.  stat [B][2] fp64 (written): the sample's gauge mean and point count.
+ * Rules: a sample without gauges gives 0 and NaN variance; a degenerate sample its gauge mean and NaN; a target without a candidate
+ * the sample's gauge mean and NaN; a non-positive pivot the mean of the selected values and NaN, and adds 1 to status [B] (int32,
+ * zeroed by the caller).
+ * p2i_lkrig_predict: out, var (nullable) [B][T][H W]; nbr (nullable) [B][T][H W][k] int32 = the selection of the kernel itself, point
+ *   index t' fcap + slot in selection order, -1 past m.
+ * p2i_lkrig_loso: the points as targets, each without the candidates at its own pixel (leave-one-site-out); pred, var [B T][fcap], 0
+ *   past the frame's count, NaN where no candidate is left or the sample is degenerate. */
+int p2i_lkrig_predict(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
+                      int frames, int B, int T, int H, int W, int fcap, double* stat, float* out, float* var, int* status, int* nbr,
+                      void* stream);
+int p2i_lkrig_loso(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k, int frames,
+                   int B, int T, int fcap, double* stat, float* pred, float* var, int* status, void* stream);
+
 /* ---- scale-aware verification: fractions skill score and radially averaged power spectra (no counterpart in
  * the reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform
  * and uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <= P2I_SCALE_MAX_CROP.

@@ -30,6 +30,13 @@ __device__ __forceinline__ float cov_f(float h, float psill, float a, int model)
   return r < 1.f ? psill * (1.f - (1.5f * r - 0.5f * r * r * r)) : 0.f;
 }
 
+// the one space-time distance of stkrig.hip's build and predictor and of lkrig.hip (an explicit fma: all round alike, so a gauge is
+// reproduced in its own frame)
+__device__ __forceinline__ float st_dist(int d2, int dt, float k2) {
+  const float ft = (float)dt;
+  return sqrtf(fmaf(k2, ft * ft, (float)d2));
+}
+
 }  // namespace
 
 static inline int krig_sys_check(int f0, int R, int T, int nsys, int np, int cap) {

@@ -19,12 +19,6 @@ constexpr int N_CAND = N_RANGE * N_KAPPA;
 constexpr int BIN_THREADS = 64;
 constexpr int FG = 8;             // target frames fed from one spatial d^2 of the predictor
 
-// the one distance of the build and of the predictor (an explicit fma: both round alike, so a gauge is reproduced in its own frame)
-__device__ __forceinline__ float st_dist(int d2, int dt, float k2) {
-  const float ft = (float)dt;
-  return sqrtf(fmaf(k2, ft * ft, (float)d2));
-}
-
 __device__ __forceinline__ double g_d(double r, int model) {
   return model == 0 ? 1.0 - exp(-r) : (r < 1.0 ? 1.5 * r - 0.5 * r * r * r : 1.0);
 }

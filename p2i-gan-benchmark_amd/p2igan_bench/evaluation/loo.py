@@ -5,7 +5,8 @@ the device, chunk by chunk, and added per event and overall on the host.
 
 Leave-one-site-out (LOSO; csrc/stkrig_loso.hip) is the same loop over the models' ``cross_validate_sites``: a
 site (a gauge pixel in all frames of a chunk) is left out as a whole.  It is the score of the space-time baselines `stkriging` and
-`lagkriging`, whose point-wise LOO would flatter them; for `kriging` and `idw` it equals LOO and puts all in one table over the same targets."""
+`lagkriging`, whose point-wise LOO would flatter them, and of `localkriging`, which scores it with its own kernel and takes chunks of
+any length; for `kriging` and `idw` it equals LOO and puts all in one table over the same targets."""
 from __future__ import annotations
 
 import json
@@ -57,11 +58,14 @@ def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_s
     from ..models.classical import SPACE_TIME
     name = str(cfg.get("model", {}).get("name", "model")).lower()
     if name not in CLASSICAL:
-        raise RuntimeError(f"leave-one-out cross-validation is defined for the classical baselines {sorted(set(CLASSICAL) - set(SPACE_TIME))} only: "
+        raise RuntimeError(f"leave-one-out cross-validation is defined for the classical baselines {sorted(set(CLASSICAL) - set(SPACE_TIME) - {'localkriging'})} only: "
                            f"model.name '{name}' is a learnt model and would need one training per gauge")
     if name in SPACE_TIME:
         from ..models.classical import LAG_NO_LOO, ST_NO_LOO
         raise RuntimeError(ST_NO_LOO if name == "stkriging" else LAG_NO_LOO)
+    if name == "localkriging":
+        from ..models.classical import LOCAL_NO_LOO
+        raise RuntimeError(LOCAL_NO_LOO)
     return _run(cfg, out_dir, device, output_scale, stride, name, False)
 
 
@@ -93,7 +97,7 @@ def _run(cfg, out_dir, device, output_scale, stride, name, by_site):
         raise RuntimeError("Test dataloader is not configured or empty.")
     G = build_generator(cfg).to(dev).eval()
     scale, stride = float(output_scale), max(1, int(stride))
-    with_var = name == "kriging" or (by_site and name in SPACE_TIME)
+    with_var = name == "kriging" or (by_site and (name in SPACE_TIME or name == "localkriging"))
     stem = "loso" if by_site else "loo"
     events, cols = {}, {k: [] for k in ("event", "frame", "y", "x", "z", "pred", "var") + (("site",) if by_site else ())}
     total = np.zeros(5)

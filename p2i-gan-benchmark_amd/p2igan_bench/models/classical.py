@@ -14,7 +14,11 @@ leave-one-site-out (csrc/stkrig_loso.hip): cross_validate_
 site (a gauge pixel in all the sample's frames) with the whole site left out.
 
 Lagrangian space-time kriging (csrc/lagkrig.hip): LagrangianKrigingGenerator measures the space-time distance
-in the frame that moves with the rain, with an advection velocity per sample that it estimates from the gauges."""
+in the frame that moves with the rain, with an advection velocity per sample that it estimates from the gauges.
+
+Moving-neighbourhood space-time kriging (csrc/lkrig.hip): LocalKrigingGenerator predicts every target from its
+k nearest points in the space-time metric, from a small system of its own: no limit on the points of a sample, the kriging variance
+and leave-one-site-out from the same kernel."""
 from __future__ import annotations
 
 import logging
@@ -233,6 +237,30 @@ class IDWGenerator(_ClassicalBase):
         return _sites_of_frames(self.cross_validate(masked_frames, masks), masks)
 
 
+def _st_variogram_config(self, mc):
+    """model.variogram of the space-time models on `self`: variogram_model, fit, n_lags, n_tlags and, with fit=false, fixed."""
+    vg = dict(mc.get("variogram") or {})
+    name = str(vg.get("model", "exponential")).lower()
+    if name not in ops.KRIG_MODELS:
+        raise ValueError(f"model.variogram.model must be one of {sorted(ops.KRIG_MODELS)} (got '{name}')")
+    self.variogram_model = ops.KRIG_MODELS[name]
+    self.fit = bool(vg.get("fit", True))
+    self.n_lags = int(vg.get("n_lags", 16))
+    self.n_tlags = int(vg.get("n_tlags", 3))
+    if self.fit:
+        if not 1 <= self.n_lags <= ops.KRIG_MAX_LAGS:
+            raise ValueError(f"model.variogram.n_lags must be in [1, {ops.KRIG_MAX_LAGS}] (got {self.n_lags})")
+        if not 0 <= self.n_tlags <= ops.STKRIG_MAX_TLAGS:
+            raise ValueError(f"model.variogram.n_tlags must be in [0, {ops.STKRIG_MAX_TLAGS}] (got {self.n_tlags})")
+    else:
+        try:
+            self.fixed = (float(vg["nugget"]), float(vg["psill"]), float(vg["range"]), float(vg["time_scale"]))
+        except KeyError as e:
+            raise ValueError(f"model.variogram with fit=false needs nugget, psill, range and time_scale (missing {e})") from None
+        if not (self.fixed[0] >= 0 and self.fixed[1] > 0 and self.fixed[2] > 0 and self.fixed[3] > 0):
+            raise ValueError("model.variogram: nugget >= 0, psill > 0, range > 0 and time_scale > 0 are required")
+
+
 class SpaceTimeKrigingGenerator(_ClassicalBase):
     """Ordinary kriging of every pixel of every frame of a sample from ALL gauges of ALL frames of that sample: one system per sample,
     global in space and time, with the distance sqrt(dy^2 + dx^2 + kappa^2 dt^2) (kappa in pixels per frame) inside the covariance.
@@ -247,27 +275,7 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
 
     def __init__(self, config: Dict[str, Any]):
         super().__init__(config)
-        mc = config.get("model", {})
-        vg = dict(mc.get("variogram") or {})
-        name = str(vg.get("model", "exponential")).lower()
-        if name not in ops.KRIG_MODELS:
-            raise ValueError(f"model.variogram.model must be one of {sorted(ops.KRIG_MODELS)} (got '{name}')")
-        self.variogram_model = ops.KRIG_MODELS[name]
-        self.fit = bool(vg.get("fit", True))
-        self.n_lags = int(vg.get("n_lags", 16))
-        self.n_tlags = int(vg.get("n_tlags", 3))
-        if self.fit:
-            if not 1 <= self.n_lags <= ops.KRIG_MAX_LAGS:
-                raise ValueError(f"model.variogram.n_lags must be in [1, {ops.KRIG_MAX_LAGS}] (got {self.n_lags})")
-            if not 0 <= self.n_tlags <= ops.STKRIG_MAX_TLAGS:
-                raise ValueError(f"model.variogram.n_tlags must be in [0, {ops.STKRIG_MAX_TLAGS}] (got {self.n_tlags})")
-        else:
-            try:
-                self.fixed = (float(vg["nugget"]), float(vg["psill"]), float(vg["range"]), float(vg["time_scale"]))
-            except KeyError as e:
-                raise ValueError(f"model.variogram with fit=false needs nugget, psill, range and time_scale (missing {e})") from None
-            if not (self.fixed[0] >= 0 and self.fixed[1] > 0 and self.fixed[2] > 0 and self.fixed[3] > 0):
-                raise ValueError("model.variogram: nugget >= 0, psill > 0, range > 0 and time_scale > 0 are required")
+        _st_variogram_config(self, config.get("model", {}))
         self.last_fit = None         # {"bins", "fit", "cand", "q", "c"} device tensors of the last call (fit=true)
         self.last_status = None      # per-sample int32 of the last call: 1 where the factorisation met a non-positive pivot
 
@@ -431,13 +439,84 @@ class LagrangianKrigingGenerator(SpaceTimeKrigingGenerator):
         return ops.lagkrig_predict(stpix, stt, alpha, mean, stinfo, params, self._velf, self.variogram_model, t, h, w)
 
 
+class LocalKrigingGenerator(_ClassicalBase):
+    """Space-time ordinary kriging in a moving neighbourhood: every pixel of every frame from its k nearest
+    points of the sample in the metric dy^2 + dx^2 + kappa^2 dt^2, among the frames within `frames` of its own, from a small system
+    of its own (csrc/lkrig.hip).  model.variogram is SpaceTimeKrigingGenerator's; model.neighbourhood = {"k": 32, "frames": 2} with k in
+    1 .. 64 and frames >= 0 (clipped to T - 1).  model.max_points bounds the gauges of one frame; the points of a sample are unbounded.
+
+    forward_uq adds the kriging variance of the same systems, and cross_validate_sites is the same kernel with the gauges as targets
+    and the target's own site out of the candidates: no inverse and no frame limit.  cross_validate is refused as for stkriging (with
+    frames = 0 leave-one-site-out is leave-one-out).  last_status (B,) int32 counts the targets that met a non-positive pivot."""
+
+    def __init__(self, config: Dict[str, Any]):
+        super().__init__(config)
+        mc = config.get("model", {})
+        _st_variogram_config(self, mc)
+        nb = dict(mc.get("neighbourhood") or {})
+        k, frames = nb.get("k", 32), nb.get("frames", 2)
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.LKRIG_MAX_K:
+            raise ValueError(f"model.neighbourhood.k must be an integer in [1, {ops.LKRIG_MAX_K}] (got {k!r})")
+        if isinstance(frames, bool) or not isinstance(frames, int) or frames < 0:
+            raise ValueError(f"model.neighbourhood.frames must be an integer >= 0 (got {frames!r})")
+        self.k, self.frames = k, frames
+        self.last_fit = None         # SpaceTimeKrigingGenerator's keys (fit=true)
+        self.last_status = None      # (B,) int32 of the last call: targets that met a non-positive pivot
+        self.last_neighbours = None  # (B, T, H*W, k) int32 of the last forward(..., neighbours=True), else None
+
+    _variogram = SpaceTimeKrigingGenerator._variogram
+
+    def cross_validate(self, masked_frames, masks):
+        raise RuntimeError(LOCAL_NO_LOO)
+
+    def _warn(self, status, what):
+        self.last_status = status
+        failed = int(status.sum())
+        if failed:
+            logging.warning("local kriging: %d %s met a non-positive pivot and take the mean of their neighbours", failed, what)
+
+    def _run(self, masked_frames, masks, variance, neighbours):
+        b, t, _, h, w = masked_frames.shape
+        pix, z, info, _, _ = self._compact(masked_frames, masks)
+        cand, params = self._variogram(pix, z, info, b, t, h, w)
+        out, var, status, nbr = ops.lkrig_predict(pix, z, info, params, cand, self.variogram_model, self.k, min(self.frames, t - 1), b, t,
+                                                  h, w, variance, neighbours)
+        self.last_neighbours = nbr
+        self._warn(status, "pixel(s)")
+        return out.view(b, t, 1, h, w), (var.view(b, t, 1, h, w) if variance else None)
+
+    @torch.no_grad()
+    def forward(self, masked_frames, masks, neighbours=False):
+        """The prediction (B, T, 1, H, W).  neighbours=True (a debug argument) keeps the kernel's selection in last_neighbours."""
+        return self._run(masked_frames, masks, False, neighbours)[0]
+
+    @torch.no_grad()
+    def forward_uq(self, masked_frames, masks):
+        """(prediction, kriging variance), both (B, T, 1, H, W).  The prediction is forward()'s; the variance is 0 on a gauge pixel in its
+        own frame and NaN where a rule stood in for the system."""
+        return self._run(masked_frames, masks, True, False)
+
+    @torch.no_grad()
+    def cross_validate_sites(self, masked_frames, masks) -> LOOResult:
+        """Leave-one-site-out at every point: its k nearest points among the other sites, within `frames` frames.  pred and var are NaN
+        where no candidate is left and over a degenerate fitted sample."""
+        b, t, _, h, w = masked_frames.shape
+        pix, z, info, _, _ = self._compact(masked_frames, masks)
+        cand, params = self._variogram(pix, z, info, b, t, h, w)
+        pred, var, status = ops.lkrig_loso(pix, z, info, params, cand, self.variogram_model, self.k, min(self.frames, t - 1), b, t)
+        self._warn(status, "point(s)")
+        return _sites_of_frames(LOOResult(pix, z, pred, var, info[:b * t], status), masks)
+
+
 ST_NO_LOO = ("space-time kriging ('stkriging') has no leave-one-out cross-validation: leaving out one (site, frame) observation while "
               "the same site's neighbouring frames stay in would flatter the method; the honest score is leave-one-site-out: "
               "cross_validate_sites, evaluation.run_loso, scripts/crossvalidate.py --by-site")
 
 LAG_NO_LOO = ST_NO_LOO.replace("space-time kriging ('stkriging')", "Lagrangian space-time kriging ('lagkriging')")
 
+LOCAL_NO_LOO = ST_NO_LOO.replace("space-time kriging ('stkriging')", "moving-neighbourhood space-time kriging ('localkriging')")
+
 SPACE_TIME = ("stkriging", "lagkriging")          # one system per sample: no point-wise leave-one-out, LOSO chunks of at most 32 frames
 
 CLASSICAL = {"kriging": KrigingGenerator, "idw": IDWGenerator, "stkriging": SpaceTimeKrigingGenerator,
-             "lagkriging": LagrangianKrigingGenerator}
+             "lagkriging": LagrangianKrigingGenerator, "localkriging": LocalKrigingGenerator}

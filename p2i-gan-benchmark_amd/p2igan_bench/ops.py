@@ -1903,6 +1903,62 @@ def lagkrig_predict(stpix, stt, alpha, mean, stinfo, params, velf, model, T, H, 
     return out
 
 
+# ---- moving-neighbourhood space-time kriging (csrc/lkrig.hip)
+LKRIG_MAX_K = 64         # neighbours per target: one lane of the target's wave each
+
+
+def _lkrig_args(who, pix, z, info, params, cand, B, T, k, frames):
+    F = B * T
+    fcap = pix.shape[1]
+    _krig_t(who, pix, torch.int32, (F, fcap))
+    _krig_t(who, z, torch.float32, (F, fcap))
+    _krig_t(who, info, torch.int32, (2 * F,))
+    _krig_t(who, params, torch.float32, (B, 4))
+    if cand is not None:
+        _krig_t(who, cand, torch.int32, (B,))
+    if not 1 <= k <= LKRIG_MAX_K:
+        raise ValueError(f"{who}: k must be 1..{LKRIG_MAX_K} (got {k})")
+    if not 0 <= frames < T:
+        raise ValueError(f"{who}: the temporal half-window must be 0..T - 1 = {T - 1} (got {frames})")
+    return fcap
+
+
+def lkrig_predict(pix, z, info, params, cand, model, k, frames, B, T, H, W, variance=False, neighbours=False):
+    """Moving-neighbourhood space-time ordinary kriging of every pixel of every frame from krig_compact's per-frame arrays: each target
+    from its k nearest points (key dy^2 + dx^2 + kappa^2 dt^2, ties by frame then raster index) within `frames` frames of its own.
+    params (B, 4) fp32 = (nugget, psill, range, kappa); cand (B,) int32 or None (< 0: degenerate sample).  Returns out (B, T, H*W),
+    var (the same shape, or None), status (B,) int32 = targets that met a non-positive pivot, and nbr (B, T, H*W, k) int32 (the
+    kernel's own selection as frame * fcap + slot, -1 past the candidates; None unless asked for)."""
+    lib = _hip.load()
+    fcap = _lkrig_args("lkrig_predict", pix, z, info, params, cand, B, T, k, frames)
+    if H < 1 or W < 1:
+        raise RuntimeError(f"lkrig_predict: bad frame shape {H} x {W}")
+    dev = pix.device
+    stat = torch.empty(B, 2, device=dev, dtype=torch.float64)
+    out = torch.empty(B, T, H * W, device=dev, dtype=torch.float32)
+    var = torch.empty(B, T, H * W, device=dev, dtype=torch.float32) if variance else None
+    nbr = torch.empty(B, T, H * W, k, device=dev, dtype=torch.int32) if neighbours else None
+    status = torch.zeros(B, device=dev, dtype=torch.int32)
+    _hip.check(lib.p2i_lkrig_predict(_ptr(pix), _ptr(z), _ptr(info), _ptr(params), _ptr(cand), int(model), k, frames, B, T, H, W, fcap,
+                                     _ptr(stat), _ptr(out), _ptr(var), _ptr(status), _ptr(nbr), _stream()), "p2i_lkrig_predict")
+    return out, var, status, nbr
+
+
+def lkrig_loso(pix, z, info, params, cand, model, k, frames, B, T):
+    """lkrig_predict with the points as targets and every point at the target's own pixel taken out of the candidates: leave-one-site-out
+    without an inverse.  Returns pred, var (B*T, fcap) (0 past the frame's count, NaN where no candidate is left or the sample is
+    degenerate) and status (B,) int32."""
+    lib = _hip.load()
+    fcap = _lkrig_args("lkrig_loso", pix, z, info, params, cand, B, T, k, frames)
+    dev = pix.device
+    stat = torch.empty(B, 2, device=dev, dtype=torch.float64)
+    pred, var = torch.empty_like(z), torch.empty_like(z)
+    status = torch.zeros(B, device=dev, dtype=torch.int32)
+    _hip.check(lib.p2i_lkrig_loso(_ptr(pix), _ptr(z), _ptr(info), _ptr(params), _ptr(cand), int(model), k, frames, B, T, fcap, _ptr(stat),
+                                  _ptr(pred), _ptr(var), _ptr(status), _stream()), "p2i_lkrig_loso")
+    return pred, var, status
+
+
 # ---- kriging variance and leave-one-out cross-validation (csrc/krig_uq.hip, DESIGN.md section 16)
 LOO_NSUM = 5            # (n, sum e, sum |e|, sum e^2, sum e^2 / var)
 

@@ -38,7 +38,7 @@ def parse_args(argv=None):
     p.add_argument("--output-scale", type=float, default=255.0)
     p.add_argument("--overwrite", action="store_true")
     p.add_argument("--variance-output", type=Path, default=None,
-                   help="kriging only: a second zarr with the kriging variance x output-scale^2 under the same event keys")
+                   help="kriging and localkriging only: a second zarr with the kriging variance x output-scale^2 under the same event keys")
     p.add_argument("--log-level", type=str, default="INFO")
     return p.parse_args(argv)
 
@@ -73,8 +73,8 @@ def main(argv=None):
         raise RuntimeError("the MI355X path needs a GPU: there is no CPU fallback")
     name = cfg.get("model", {}).get("name", "model")
     classical = str(name).lower() in CLASSICAL         # parameter-free: no checkpoint to resolve or load
-    if args.variance_output is not None and str(name).lower() != "kriging":
-        raise RuntimeError(f"--variance-output needs model.name 'kriging', the one model with a variance (got '{name}')")
+    if args.variance_output is not None and str(name).lower() not in ("kriging", "localkriging"):
+        raise RuntimeError(f"--variance-output needs model.name 'kriging' or 'localkriging', the models with a variance (got '{name}')")
     ckpt = None if classical else resolve_checkpoint(cfg, args)
     loader = P2IDataModule(cfg).test_dataloader()
     if loader is None or len(loader.dataset) == 0:
