@@ -713,6 +713,18 @@ int p2i_lkrig_predict(const int* pix, const float* z, const int* counts, const f
                       void* stream);
 int p2i_lkrig_loso(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k, int frames,
                    int B, int T, int fcap, double* stat, float* pred, float* var, int* status, void* stream);
+/* The same two in the Lagrangian frame: velf [B][2] fp32 = (v_y, v_x) in pixels per frame, one velocity per
+ * sample.  Key, fp64, every operation rounded once and none fused: with fdt = t - t' (target minus point), e_y = (t_y - g_y) - v_y fdt
+ * and e_x likewise (one product, one sum each), key = ((e_y e_y + e_x e_x) + (kappa kappa) dt^2); the order is (key, point index).  d
+ * in K and c0 is the fp32 Lagrangian distance of the block above (sqrt((dy - v_y dt)^2 + (dx - v_x dt)^2 + kappa^2 dt^2)); the nugget
+ * stays on the same pixel and frame, leave-one-site-out leaves out the target's pixel in every frame, and everything else is as
+ * above.  With v = 0 the key and the selection are those of p2i_lkrig_predict / _loso bit for bit. */
+int p2i_lkrig_predict_lag(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
+                          int frames, int B, int T, int H, int W, int fcap, double* stat, float* out, float* var, int* status, int* nbr,
+                          const float* velf, void* stream);
+int p2i_lkrig_loso_lag(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
+                       int frames, int B, int T, int fcap, double* stat, float* pred, float* var, int* status, const float* velf,
+                       void* stream);
 
 /* ---- scale-aware verification: fractions skill score and radially averaged power spectra (no counterpart in
  * the reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform

@@ -37,6 +37,17 @@ __device__ __forceinline__ float st_dist(int d2, int dt, float k2) {
   return sqrtf(fmaf(k2, ft * ft, (float)d2));
 }
 
+// the one Lagrangian distance of lagkrig.hip's build and predictor and of lkrig.hip's LAG kernels (lag_dist = sqrt of lag_d2): fdy,
+// fdx, ft are the integer differences (point a minus point b) as floats.  fmaf rounds -v ft + d once, and swapping a and b negates all
+// three exactly, so both orders give the same value bit for bit; at ft = 0 it is sqrt(dy^2 + dx^2), whatever v is.
+__device__ __forceinline__ float lag_d2(float fdy, float fdx, float ft, float vy, float vx, float k2) {
+  const float ey = fmaf(-vy, ft, fdy), ex = fmaf(-vx, ft, fdx);
+  return fmaf(ey, ey, fmaf(ex, ex, k2 * (ft * ft)));
+}
+__device__ __forceinline__ float lag_dist(float fdy, float fdx, float ft, float vy, float vx, float k2) {
+  return sqrtf(lag_d2(fdy, fdx, ft, vy, vx, k2));
+}
+
 }  // namespace
 
 static inline int krig_sys_check(int f0, int R, int T, int nsys, int np, int cap) {

@@ -20,17 +20,6 @@ constexpr int VPAIR = 32;         // pairs of one batch of its separable weight 
 constexpr int MAX_VHALF = 16;     // candidate grid (2 nhalf + 1)^2 <= 33 x 33
 constexpr int VGRID = 2 * MAX_VHALF + 1;
 
-// the one distance of the build and of the predictor (lag_dist = sqrt of lag_d2): fdy, fdx, ft are the integer differences (point a
-// minus point b) as floats.  fmaf rounds -v ft + d once, and swapping a and b negates all three exactly, so both orders give the
-// same value bit for bit; at ft = 0 it is sqrt(dy^2 + dx^2), whatever v is.
-__device__ __forceinline__ float lag_d2(float fdy, float fdx, float ft, float vy, float vx, float k2) {
-  const float ey = fmaf(-vy, ft, fdy), ex = fmaf(-vx, ft, fdx);
-  return fmaf(ey, ey, fmaf(ex, ex, k2 * (ft * ft)));
-}
-__device__ __forceinline__ float lag_dist(float fdy, float fdx, float ft, float vy, float vx, float k2) {
-  return sqrtf(lag_d2(fdy, fdx, ft, vy, vx, k2));
-}
-
 // ---- velocity score.  Workgroup (chunk, sample) holds ALL candidates v = (i s, j s), index c = (i + nhalf) n + (j + nhalf), n = 2 nhalf
 // + 1: thread tid takes c = tid and c = tid + blockDim.x (blockDim.x = the candidates rounded up to a wave, at most 1024; n n <= 1089).
 // For every temporal lag u = 1 .. n_tlags and frame t < T - u the gauges j of frame t + u are staged in LDS VCHUNK at a time (as

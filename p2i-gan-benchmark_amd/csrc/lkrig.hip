@@ -12,6 +12,10 @@
 //              entries, left-looking Cholesky by columns with fp64 dot products; the two substitutions (right-hand sides c0 and 1)
 //              in fp64 with the column's pivot broadcast from its lane.
 // Every sum has a fixed order; the count of failed targets is an integer atomic.
+//
+// LAG: the same kernels in the frame that moves with the rain, one velocity v = (v_y, v_x) per sample (velf, fp32).
+// The key becomes (e_y^2 + e_x^2) + kappa^2 dt^2 with e = (target - point) - v dt in fp64, every operation rounded once; K and c0 take
+// lag_dist in place of st_dist.  Everything else, and every LAG = false instantiation, is as it was.
 #include "krig_common.h"
 
 namespace p2i {
@@ -27,6 +31,7 @@ struct LkArgs {
   const float* params;
   const int* cand;
   const double* stat;
+  const float* velf;     // [B][2] = (v_y, v_x), read by the LAG kernels only (else null)
   int model, k, frames, T, fcap;
   double none;           // +inf, the key of an empty list entry: handed in by the host so that the wave-uniform threshold starts from a
                          // loaded scalar pair (as a 64-bit scalar literal the compiler's move keeps 32 bits of it)
@@ -72,9 +77,10 @@ __global__ __launch_bounds__(256) void lkrig_stat_kernel(const float* __restrict
 // One target (frame t of sample b, pixel (ty, tx)) by the whole wave.  excl >= 0: the candidates at pixel code excl are left out
 // (leave-one-site-out).  Returns through pred / var (all lanes alike) and m, the number of neighbours; nbr (nullable) gets the
 // selection, -1 past m.  fail: 1 where a pivot was not positive.
-template <int KC>
+template <int KC, bool LAG>
 __device__ __forceinline__ void lk_target(const LkArgs& A, float* __restrict__ sK, int b, int t, int ty, int tx, int excl, float nug,
-                                          float psill, float a, float kap, float& pred, float& var, int& fail, int* __restrict__ nbr) {
+                                          float psill, float a, float kap, float vy, float vx, float& pred, float& var, int& fail,
+                                          int* __restrict__ nbr) {
   constexpr int S = KC + 1;
   const int lane = threadIdx.x;
   const int k = A.k;
@@ -93,6 +99,12 @@ __device__ __forceinline__ void lk_target(const LkArgs& A, float* __restrict__ s
       if (tp < 0 || tp >= A.T) continue;
       const size_t f = (size_t)b * A.T + tp;
       const int n = min(A.counts[f], A.fcap);
+      double oy = 0.0, ox = 0.0;               // LAG: v (t - t'), one rounded product per axis
+      if constexpr (LAG) {
+        const double fdt = (double)(t - tp);
+        oy = __dmul_rn((double)vy, fdt);
+        ox = __dmul_rn((double)vx, fdt);
+      }
       for (int c0 = 0; c0 < n; c0 += 64) {
         const int slot = c0 + lane;
         bool ok = slot < n;
@@ -101,7 +113,12 @@ __device__ __forceinline__ void lk_target(const LkArgs& A, float* __restrict__ s
         if (ok) {
           const int g = A.pix[f * A.fcap + slot];
           const int dy = ty - (g >> 16), dx = tx - (g & 0xffff);
-          ck = __dadd_rn((double)(dy * dy + dx * dx), kdt);
+          if constexpr (LAG) {
+            const double ey = __dadd_rn((double)dy, -oy), ex = __dadd_rn((double)dx, -ox);
+            ck = __dadd_rn(__dadd_rn(__dmul_rn(ey, ey), __dmul_rn(ex, ex)), kdt);
+          } else {
+            ck = __dadd_rn((double)(dy * dy + dx * dx), kdt);
+          }
           ok = g != excl;
         }
         unsigned long long todo = __ballot(ok && lk_before(ck, ci, tk, ti));
@@ -150,7 +167,12 @@ __device__ __forceinline__ void lk_target(const LkArgs& A, float* __restrict__ s
   if (mine) {
     const int dy = ty - gy, dx = tx - gx, dt = t - gt;
     const int d2 = dy * dy + dx * dx;
-    c0 = cov_f(st_dist(d2, dt, k2), psill, a, A.model) + ((d2 | dt) == 0 ? nug : 0.f);
+    float h;
+    if constexpr (LAG)
+      h = lag_dist((float)dy, (float)dx, (float)dt, vy, vx, k2);
+    else
+      h = st_dist(d2, dt, k2);
+    c0 = cov_f(h, psill, a, A.model) + ((d2 | dt) == 0 ? nug : 0.f);
   }
   const bool at_gauge = lane_d(ekey, 0) == 0.0;      // key 0: the same pixel in the same frame (kappa > 0)
   __syncthreads();               // the previous target's reads of sK are done
@@ -158,7 +180,12 @@ __device__ __forceinline__ void lk_target(const LkArgs& A, float* __restrict__ s
     const int pj = lane_i(g, j), tj = lane_i(gt, j);
     if (mine && lane >= j) {
       const int dy = gy - (pj >> 16), dx = gx - (pj & 0xffff);
-      sK[lane * S + j] = cov_f(st_dist(dy * dy + dx * dx, gt - tj, k2), psill, a, A.model) + (lane == j ? nug : 0.f);
+      float h;
+      if constexpr (LAG)
+        h = lag_dist((float)dy, (float)dx, (float)(gt - tj), vy, vx, k2);
+      else
+        h = st_dist(dy * dy + dx * dx, gt - tj, k2);
+      sK[lane * S + j] = cov_f(h, psill, a, A.model) + (lane == j ? nug : 0.f);
     }
   }
   __syncthreads();
@@ -240,13 +267,18 @@ __device__ __forceinline__ int lk_sample(const LkArgs& A, int b, float& nug, flo
   return 1;
 }
 
-template <int KC>
+template <int KC, bool LAG>
 __global__ __launch_bounds__(64) void lkrig_predict_kernel(LkArgs A, int W, int HW, float* __restrict__ out, float* __restrict__ var,
                                                            int* __restrict__ status, int* __restrict__ nbr) {
   __shared__ float sK[KC * (KC + 1)];
   const int b = blockIdx.z, t = blockIdx.y;
   float nug, psill, a, kap, out0 = 0.f;
   const int live = lk_sample(A, b, nug, psill, a, kap, out0);
+  float vy = 0.f, vx = 0.f;
+  if constexpr (LAG) {
+    vy = A.velf[b * 2];
+    vx = A.velf[b * 2 + 1];
+  }
   int failed = 0;
   for (int q = 0; q < LK_TPB; ++q) {
     const int p = blockIdx.x * LK_TPB + q;
@@ -256,7 +288,7 @@ __global__ __launch_bounds__(64) void lkrig_predict_kernel(LkArgs A, int W, int 
     float pr = out0, vr = __builtin_nanf("");
     if (live) {
       int fail;
-      lk_target<KC>(A, sK, b, t, p / W, p % W, -1, nug, psill, a, kap, pr, vr, fail, nb);
+      lk_target<KC, LAG>(A, sK, b, t, p / W, p % W, -1, nug, psill, a, kap, vy, vx, pr, vr, fail, nb);
       failed += fail;
     } else if (nb != nullptr && (int)threadIdx.x < A.k) {
       nb[threadIdx.x] = -1;
@@ -270,7 +302,7 @@ __global__ __launch_bounds__(64) void lkrig_predict_kernel(LkArgs A, int W, int 
 }
 
 // the points as targets, each without the candidates at its own pixel; pred / var [B T][fcap], 0 past the frame's count
-template <int KC>
+template <int KC, bool LAG>
 __global__ __launch_bounds__(64) void lkrig_loso_kernel(LkArgs A, float* __restrict__ pred, float* __restrict__ var, int* __restrict__ status) {
   __shared__ float sK[KC * (KC + 1)];
   const int b = blockIdx.z, t = blockIdx.y;
@@ -278,6 +310,11 @@ __global__ __launch_bounds__(64) void lkrig_loso_kernel(LkArgs A, float* __restr
   const int n = min(A.counts[f], A.fcap);
   float nug, psill, a, kap, out0 = 0.f;
   const int live = lk_sample(A, b, nug, psill, a, kap, out0);
+  float vy = 0.f, vx = 0.f;
+  if constexpr (LAG) {
+    vy = A.velf[b * 2];
+    vx = A.velf[b * 2 + 1];
+  }
   int failed = 0;
   for (int q = 0; q < LK_TPB; ++q) {
     const int i = blockIdx.x * LK_TPB + q;
@@ -288,7 +325,7 @@ __global__ __launch_bounds__(64) void lkrig_loso_kernel(LkArgs A, float* __restr
       if (live) {
         const int g = A.pix[f * A.fcap + i];
         int fail;
-        lk_target<KC>(A, sK, b, t, g >> 16, g & 0xffff, g, nug, psill, a, kap, pr, vr, fail, nullptr);
+        lk_target<KC, LAG>(A, sK, b, t, g >> 16, g & 0xffff, g, nug, psill, a, kap, vy, vx, pr, vr, fail, nullptr);
         failed += fail;
         if (vr != vr && !fail) pr = vr;      // no candidate left: no score
       }
@@ -316,35 +353,62 @@ int lk_check(const LkArgs& A, int B) {
 
 using namespace p2i;
 
-extern "C" int p2i_lkrig_predict(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
-                                 int frames, int B, int T, int H, int W, int fcap, double* stat, float* out, float* var, int* status,
-                                 int* nbr, void* stream) {
-  const LkArgs A{pix, z, counts, params, cand, stat, model, k, frames, T, fcap, HUGE_VAL};
+namespace {
+
+template <bool LAG>
+int lk_predict(const LkArgs& A, int B, int H, int W, double* stat, float* out, float* var, int* status, int* nbr, void* stream) {
   if (int rc = lk_check(A, B)) return rc;
-  P2I_REQUIRE(out && status, "null pointer");
+  P2I_REQUIRE(out && status && (!LAG || A.velf), "null pointer");
   P2I_REQUIRE(H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE, "bad frame shape");
   hipStream_t s = (hipStream_t)stream;
   const int HW = H * W;
-  P2I_LAUNCH(lkrig_stat_kernel, dim3(B), dim3(256), 0, s, z, counts, T, fcap, stat);
-  const dim3 grid(ceil_div(HW, LK_TPB), T, B);
-  if (k <= 32)
-    P2I_LAUNCH(lkrig_predict_kernel<32>, grid, dim3(64), 0, s, A, W, HW, out, var, status, nbr);
+  P2I_LAUNCH(lkrig_stat_kernel, dim3(B), dim3(256), 0, s, A.z, A.counts, A.T, A.fcap, stat);
+  const dim3 grid(ceil_div(HW, LK_TPB), A.T, B);
+  if (A.k <= 32)
+    P2I_LAUNCH((lkrig_predict_kernel<32, LAG>), grid, dim3(64), 0, s, A, W, HW, out, var, status, nbr);
   else
-    P2I_LAUNCH(lkrig_predict_kernel<64>, grid, dim3(64), 0, s, A, W, HW, out, var, status, nbr);
+    P2I_LAUNCH((lkrig_predict_kernel<64, LAG>), grid, dim3(64), 0, s, A, W, HW, out, var, status, nbr);
   return launch_status();
+}
+
+template <bool LAG>
+int lk_loso(const LkArgs& A, int B, double* stat, float* pred, float* var, int* status, void* stream) {
+  if (int rc = lk_check(A, B)) return rc;
+  P2I_REQUIRE(pred && var && status && (!LAG || A.velf), "null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  P2I_LAUNCH(lkrig_stat_kernel, dim3(B), dim3(256), 0, s, A.z, A.counts, A.T, A.fcap, stat);
+  const dim3 grid(ceil_div(A.fcap, LK_TPB), A.T, B);
+  if (A.k <= 32)
+    P2I_LAUNCH((lkrig_loso_kernel<32, LAG>), grid, dim3(64), 0, s, A, pred, var, status);
+  else
+    P2I_LAUNCH((lkrig_loso_kernel<64, LAG>), grid, dim3(64), 0, s, A, pred, var, status);
+  return launch_status();
+}
+
+}  // namespace
+
+extern "C" int p2i_lkrig_predict(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
+                                 int frames, int B, int T, int H, int W, int fcap, double* stat, float* out, float* var, int* status,
+                                 int* nbr, void* stream) {
+  return lk_predict<false>(LkArgs{pix, z, counts, params, cand, stat, nullptr, model, k, frames, T, fcap, HUGE_VAL}, B, H, W, stat, out, var, status,
+                           nbr, stream);
 }
 
 extern "C" int p2i_lkrig_loso(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
                               int frames, int B, int T, int fcap, double* stat, float* pred, float* var, int* status, void* stream) {
-  const LkArgs A{pix, z, counts, params, cand, stat, model, k, frames, T, fcap, HUGE_VAL};
-  if (int rc = lk_check(A, B)) return rc;
-  P2I_REQUIRE(pred && var && status, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  P2I_LAUNCH(lkrig_stat_kernel, dim3(B), dim3(256), 0, s, z, counts, T, fcap, stat);
-  const dim3 grid(ceil_div(fcap, LK_TPB), T, B);
-  if (k <= 32)
-    P2I_LAUNCH(lkrig_loso_kernel<32>, grid, dim3(64), 0, s, A, pred, var, status);
-  else
-    P2I_LAUNCH(lkrig_loso_kernel<64>, grid, dim3(64), 0, s, A, pred, var, status);
-  return launch_status();
+  return lk_loso<false>(LkArgs{pix, z, counts, params, cand, stat, nullptr, model, k, frames, T, fcap, HUGE_VAL}, B, stat, pred, var, status, stream);
+}
+
+// the same two in the Lagrangian frame: velf [B][2] fp32 = (v_y, v_x) per sample
+extern "C" int p2i_lkrig_predict_lag(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model,
+                                     int k, int frames, int B, int T, int H, int W, int fcap, double* stat, float* out, float* var,
+                                     int* status, int* nbr, const float* velf, void* stream) {
+  return lk_predict<true>(LkArgs{pix, z, counts, params, cand, stat, velf, model, k, frames, T, fcap, HUGE_VAL}, B, H, W, stat, out, var, status,
+                          nbr, stream);
+}
+
+extern "C" int p2i_lkrig_loso_lag(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
+                                  int frames, int B, int T, int fcap, double* stat, float* pred, float* var, int* status, const float* velf,
+                                  void* stream) {
+  return lk_loso<true>(LkArgs{pix, z, counts, params, cand, stat, velf, model, k, frames, T, fcap, HUGE_VAL}, B, stat, pred, var, status, stream);
 }

@@ -155,6 +155,8 @@ SIGNATURES = {
     "p2i_lagkrig_predict": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "p2i_lkrig_predict": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "p2i_lkrig_loso": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "p2i_lkrig_predict_lag": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "p2i_lkrig_loso_lag": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "p2i_idw_loo": [_P, _P, _P, _I, _I, _F, _P, _P],
     "p2i_loo_scores": [_P, _P, _P, _P, _I, _I, _P, _P, _P],
     "p2i_scale_fss": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(C.c_double), _I, C.POINTER(C.c_int), _I, _I,

@@ -5,8 +5,8 @@ the device, chunk by chunk, and added per event and overall on the host.
 
 Leave-one-site-out (LOSO; csrc/stkrig_loso.hip) is the same loop over the models' ``cross_validate_sites``: a
 site (a gauge pixel in all frames of a chunk) is left out as a whole.  It is the score of the space-time baselines `stkriging` and
-`lagkriging`, whose point-wise LOO would flatter them, and of `localkriging`, which scores it with its own kernel and takes chunks of
-any length; for `kriging` and `idw` it equals LOO and puts all in one table over the same targets."""
+`lagkriging`, whose point-wise LOO would flatter them, and of `localkriging` and `locallagkriging`, which score it with their own kernel and take
+chunks of any length; for `kriging` and `idw` it equals LOO and puts all in one table over the same targets."""
 from __future__ import annotations
 
 import json
@@ -55,17 +55,17 @@ def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_s
     them (each chunk is one sample of a fitted variogram).  Writes loo.json / loo.txt (scores per event and overall) and loo_data.npz
     (per gauge: event, frame, y, x, z, LOO prediction, LOO variance; coded units, unscaled) under out_dir; returns loo.json's content."""
     from ..models import CLASSICAL
-    from ..models.classical import SPACE_TIME
+    from ..models.classical import LOCAL, SPACE_TIME
     name = str(cfg.get("model", {}).get("name", "model")).lower()
     if name not in CLASSICAL:
-        raise RuntimeError(f"leave-one-out cross-validation is defined for the classical baselines {sorted(set(CLASSICAL) - set(SPACE_TIME) - {'localkriging'})} only: "
+        raise RuntimeError(f"leave-one-out cross-validation is defined for the classical baselines {sorted(set(CLASSICAL) - set(SPACE_TIME) - set(LOCAL))} only: "
                            f"model.name '{name}' is a learnt model and would need one training per gauge")
     if name in SPACE_TIME:
         from ..models.classical import LAG_NO_LOO, ST_NO_LOO
         raise RuntimeError(ST_NO_LOO if name == "stkriging" else LAG_NO_LOO)
-    if name == "localkriging":
-        from ..models.classical import LOCAL_NO_LOO
-        raise RuntimeError(LOCAL_NO_LOO)
+    if name in LOCAL:
+        from ..models.classical import LOCAL_LAG_NO_LOO, LOCAL_NO_LOO
+        raise RuntimeError(LOCAL_NO_LOO if name == "localkriging" else LOCAL_LAG_NO_LOO)
     return _run(cfg, out_dir, device, output_scale, stride, name, False)
 
 
@@ -87,7 +87,7 @@ def run_loso(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_
 
 def _run(cfg, out_dir, device, output_scale, stride, name, by_site):
     from ..models import build_generator
-    from ..models.classical import SPACE_TIME
+    from ..models.classical import LOCAL, SPACE_TIME
     dev = torch.device(device or cfg.get("device", "cuda:0"))
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise RuntimeError("the MI355X path needs a GPU: there is no CPU fallback")
@@ -97,7 +97,7 @@ def _run(cfg, out_dir, device, output_scale, stride, name, by_site):
         raise RuntimeError("Test dataloader is not configured or empty.")
     G = build_generator(cfg).to(dev).eval()
     scale, stride = float(output_scale), max(1, int(stride))
-    with_var = name == "kriging" or (by_site and (name in SPACE_TIME or name == "localkriging"))
+    with_var = name == "kriging" or (by_site and (name in SPACE_TIME or name in LOCAL))
     stem = "loso" if by_site else "loo"
     events, cols = {}, {k: [] for k in ("event", "frame", "y", "x", "z", "pred", "var") + (("site",) if by_site else ())}
     total = np.zeros(5)

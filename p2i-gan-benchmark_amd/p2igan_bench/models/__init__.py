@@ -3,7 +3,8 @@
 The P2I-GAN family and the STDK (spatio-temporal DeepKriging) baseline are built on the HIP path, and so are two parameter-free
 classical baselines the reference does not have: ordinary kriging and all-gauge IDW (models/classical.py),
 space-time ordinary kriging over all frames of a sample (`stkriging`) and its Lagrangian form with a fitted
-advection velocity (`lagkriging`), and space-time kriging in a moving neighbourhood (`localkriging`, section 20).
+advection velocity (`lagkriging`), and space-time kriging in a moving neighbourhood (`localkriging`, section 20)
+and its Lagrangian form (`locallagkriging`, section 21).
 The purely spatial DK baseline and the `simple` fallback stub are out of this build's scope and raise a clear
 error."""
 from typing import Any, Dict
@@ -11,7 +12,7 @@ from typing import Any, Dict
 import torch.nn as nn
 
 from .classical import (CLASSICAL, IDWGenerator, KrigingGenerator, LagrangianKrigingGenerator, LocalKrigingGenerator,
-                        SpaceTimeKrigingGenerator)
+                        LocalLagrangianKrigingGenerator, SpaceTimeKrigingGenerator)
 from .p2igan import P2IDiscriminator, P2IGenerator
 from .stdk import STDKGenerator
 
@@ -29,7 +30,7 @@ def build_generator(cfg: Dict[str, Any]) -> nn.Module:
         return STDKGenerator(cfg, length=data_cfg.get("sample_length", 16))
     if name in CLASSICAL:
         return CLASSICAL[name](cfg)
-    raise NotImplementedError(f"model '{name}': only 'p2igan', 'stdk', 'kriging', 'idw', 'stkriging', 'lagkriging' and 'localkriging' are implemented on the MI355X path")
+    raise NotImplementedError(f"model '{name}': only 'p2igan', 'stdk', 'kriging', 'idw', 'stkriging', 'lagkriging', 'localkriging' and 'locallagkriging' are implemented on the MI355X path")
 
 
 def build_discriminator(cfg: Dict[str, Any]) -> nn.Module:
@@ -43,4 +44,5 @@ def build_discriminator(cfg: Dict[str, Any]) -> nn.Module:
 
 
 __all__ = ["build_generator", "build_discriminator", "P2IGenerator", "P2IDiscriminator", "STDKGenerator",
-           "KrigingGenerator", "IDWGenerator", "SpaceTimeKrigingGenerator", "LagrangianKrigingGenerator", "LocalKrigingGenerator"]
+           "KrigingGenerator", "IDWGenerator", "SpaceTimeKrigingGenerator", "LagrangianKrigingGenerator", "LocalKrigingGenerator",
+           "LocalLagrangianKrigingGenerator"]

@@ -18,7 +18,8 @@ in the frame that moves with the rain, with an advection velocity per sample tha
 
 Moving-neighbourhood space-time kriging (csrc/lkrig.hip): LocalKrigingGenerator predicts every target from its
 k nearest points in the space-time metric, from a small system of its own: no limit on the points of a sample, the kriging variance
-and leave-one-site-out from the same kernel."""
+and leave-one-site-out from the same kernel.  LocalLagrangianKrigingGenerator is the same in the Lagrangian
+frame: the neighbours are the nearest in the frame that moves with the rain, where a site's copies in other frames are new support."""
 from __future__ import annotations
 
 import logging
@@ -261,6 +262,35 @@ def _st_variogram_config(self, mc):
             raise ValueError("model.variogram: nugget >= 0, psill > 0, range > 0 and time_scale > 0 are required")
 
 
+def _advection_config(self, mc):
+    """model.advection of the Lagrangian models on `self` (after _st_variogram_config): fit_velocity and, fitted, vmax, vstep, nhalf,
+    adv_tlags and bandwidth; with fit=false, fixed_v."""
+    adv = dict(mc.get("advection") or {})
+    self.fit_velocity = bool(adv.get("fit", True))
+    if self.fit_velocity:
+        self.vmax, self.vstep = float(adv.get("vmax", 4.0)), float(adv.get("vstep", 0.5))
+        self.adv_tlags, self.bandwidth = int(adv.get("n_tlags", 3)), float(adv.get("bandwidth", 1.5))
+        if not (self.vstep > 0 and self.vmax >= 0 and math.isfinite(self.vmax) and math.isfinite(self.vstep)):
+            raise ValueError(f"model.advection: vstep > 0 and vmax >= 0 are required (got vmax {self.vmax}, vstep {self.vstep})")
+        self.nhalf = int(math.floor(self.vmax / self.vstep + 0.5))
+        if self.nhalf > ops.LAGKRIG_MAX_VHALF:
+            raise ValueError(f"model.advection: round(vmax / vstep) = {self.nhalf} gives {(2 * self.nhalf + 1) ** 2} candidate velocities, "
+                             f"more than the {ops.LAGKRIG_MAX_CANDIDATES} (|i|, |j| <= {ops.LAGKRIG_MAX_VHALF}) the kernel takes")
+        if not 0 <= self.adv_tlags <= ops.STKRIG_MAX_TLAGS:
+            raise ValueError(f"model.advection.n_tlags must be in [0, {ops.STKRIG_MAX_TLAGS}] (got {self.adv_tlags})")
+        if not (self.bandwidth > 0 and math.isfinite(self.bandwidth)):
+            raise ValueError(f"model.advection.bandwidth must be positive (got {self.bandwidth})")
+        if not 1 <= self.n_lags <= ops.KRIG_MAX_LAGS:          # the bandwidth's unit
+            raise ValueError(f"model.variogram.n_lags must be in [1, {ops.KRIG_MAX_LAGS}] (got {self.n_lags})")
+    else:
+        try:
+            self.fixed_v = (float(adv["vy"]), float(adv["vx"]))
+        except KeyError as e:
+            raise ValueError(f"model.advection with fit=false needs vy and vx (missing {e})") from None
+        if not all(math.isfinite(v) for v in self.fixed_v):
+            raise ValueError(f"model.advection: vy and vx must be finite (got {self.fixed_v})")
+
+
 class SpaceTimeKrigingGenerator(_ClassicalBase):
     """Ordinary kriging of every pixel of every frame of a sample from ALL gauges of ALL frames of that sample: one system per sample,
     global in space and time, with the distance sqrt(dy^2 + dx^2 + kappa^2 dt^2) (kappa in pixels per frame) inside the covariance.
@@ -380,30 +410,7 @@ class LagrangianKrigingGenerator(SpaceTimeKrigingGenerator):
 
     def __init__(self, config: Dict[str, Any]):
         super().__init__(config)
-        adv = dict(config.get("model", {}).get("advection") or {})
-        self.fit_velocity = bool(adv.get("fit", True))
-        if self.fit_velocity:
-            self.vmax, self.vstep = float(adv.get("vmax", 4.0)), float(adv.get("vstep", 0.5))
-            self.adv_tlags, self.bandwidth = int(adv.get("n_tlags", 3)), float(adv.get("bandwidth", 1.5))
-            if not (self.vstep > 0 and self.vmax >= 0 and math.isfinite(self.vmax) and math.isfinite(self.vstep)):
-                raise ValueError(f"model.advection: vstep > 0 and vmax >= 0 are required (got vmax {self.vmax}, vstep {self.vstep})")
-            self.nhalf = int(math.floor(self.vmax / self.vstep + 0.5))
-            if self.nhalf > ops.LAGKRIG_MAX_VHALF:
-                raise ValueError(f"model.advection: round(vmax / vstep) = {self.nhalf} gives {(2 * self.nhalf + 1) ** 2} candidate velocities, "
-                                 f"more than the {ops.LAGKRIG_MAX_CANDIDATES} (|i|, |j| <= {ops.LAGKRIG_MAX_VHALF}) the kernel takes")
-            if not 0 <= self.adv_tlags <= ops.STKRIG_MAX_TLAGS:
-                raise ValueError(f"model.advection.n_tlags must be in [0, {ops.STKRIG_MAX_TLAGS}] (got {self.adv_tlags})")
-            if not (self.bandwidth > 0 and math.isfinite(self.bandwidth)):
-                raise ValueError(f"model.advection.bandwidth must be positive (got {self.bandwidth})")
-            if not 1 <= self.n_lags <= ops.KRIG_MAX_LAGS:          # the bandwidth's unit
-                raise ValueError(f"model.variogram.n_lags must be in [1, {ops.KRIG_MAX_LAGS}] (got {self.n_lags})")
-        else:
-            try:
-                self.fixed_v = (float(adv["vy"]), float(adv["vx"]))
-            except KeyError as e:
-                raise ValueError(f"model.advection with fit=false needs vy and vx (missing {e})") from None
-            if not all(math.isfinite(v) for v in self.fixed_v):
-                raise ValueError(f"model.advection: vy and vx must be finite (got {self.fixed_v})")
+        _advection_config(self, config.get("model", {}))
         self._velf = None
 
     def cross_validate(self, masked_frames, masks):
@@ -463,6 +470,7 @@ class LocalKrigingGenerator(_ClassicalBase):
         self.last_fit = None         # SpaceTimeKrigingGenerator's keys (fit=true)
         self.last_status = None      # (B,) int32 of the last call: targets that met a non-positive pivot
         self.last_neighbours = None  # (B, T, H*W, k) int32 of the last forward(..., neighbours=True), else None
+        self._velf = None            # (B, 2) fp32 of the last call's velocities where _variogram fits them (LocalLagrangianKrigingGenerator)
 
     _variogram = SpaceTimeKrigingGenerator._variogram
 
@@ -480,7 +488,7 @@ class LocalKrigingGenerator(_ClassicalBase):
         pix, z, info, _, _ = self._compact(masked_frames, masks)
         cand, params = self._variogram(pix, z, info, b, t, h, w)
         out, var, status, nbr = ops.lkrig_predict(pix, z, info, params, cand, self.variogram_model, self.k, min(self.frames, t - 1), b, t,
-                                                  h, w, variance, neighbours)
+                                                  h, w, variance, neighbours, self._velf)
         self.last_neighbours = nbr
         self._warn(status, "pixel(s)")
         return out.view(b, t, 1, h, w), (var.view(b, t, 1, h, w) if variance else None)
@@ -503,9 +511,31 @@ class LocalKrigingGenerator(_ClassicalBase):
         b, t, _, h, w = masked_frames.shape
         pix, z, info, _, _ = self._compact(masked_frames, masks)
         cand, params = self._variogram(pix, z, info, b, t, h, w)
-        pred, var, status = ops.lkrig_loso(pix, z, info, params, cand, self.variogram_model, self.k, min(self.frames, t - 1), b, t)
+        pred, var, status = ops.lkrig_loso(pix, z, info, params, cand, self.variogram_model, self.k, min(self.frames, t - 1), b, t,
+                                           self._velf)
         self._warn(status, "point(s)")
         return _sites_of_frames(LOOResult(pix, z, pred, var, info[:b * t], status), masks)
+
+
+class LocalLagrangianKrigingGenerator(LocalKrigingGenerator):
+    """LocalKrigingGenerator in the frame that moves with the rain: the k nearest points in the metric
+    (dy - v_y dt)^2 + (dx - v_x dt)^2 + kappa^2 dt^2, one advection velocity v = (v_y, v_x) in pixels per frame per sample, and
+    LagrangianKrigingGenerator's distance inside the target's system.  In that frame a site's copies in the neighbouring frames sit at
+    x - v dt, at different places: they are spatial support and no duplicates.  model.variogram and model.neighbourhood are
+    LocalKrigingGenerator's, model.advection is LagrangianKrigingGenerator's, and so is the order of the fits: the velocity first, then
+    the variogram on the advected distance, each once per sample from all sites (cross_validate_sites does not refit).  last_fit holds
+    LagrangianKrigingGenerator's keys.  forward, forward_uq, forward(..., neighbours=True) and cross_validate_sites are the parent's;
+    no point limit and no frame limit."""
+
+    def __init__(self, config: Dict[str, Any]):
+        super().__init__(config)
+        _advection_config(self, config.get("model", {}))
+        self._velf = None
+
+    _variogram = LagrangianKrigingGenerator._variogram
+
+    def cross_validate(self, masked_frames, masks):
+        raise RuntimeError(LOCAL_LAG_NO_LOO)
 
 
 ST_NO_LOO = ("space-time kriging ('stkriging') has no leave-one-out cross-validation: leaving out one (site, frame) observation while "
@@ -516,7 +546,13 @@ LAG_NO_LOO = ST_NO_LOO.replace("space-time kriging ('stkriging')", "Lagrangian s
 
 LOCAL_NO_LOO = ST_NO_LOO.replace("space-time kriging ('stkriging')", "moving-neighbourhood space-time kriging ('localkriging')")
 
+LOCAL_LAG_NO_LOO = ST_NO_LOO.replace("space-time kriging ('stkriging')",
+                                     "moving-neighbourhood Lagrangian space-time kriging ('locallagkriging')")
+
+LOCAL = ("localkriging", "locallagkriging")      # one system per target: no point-wise leave-one-out, LOSO of any length, a variance map
+
 SPACE_TIME = ("stkriging", "lagkriging")          # one system per sample: no point-wise leave-one-out, LOSO chunks of at most 32 frames
 
 CLASSICAL = {"kriging": KrigingGenerator, "idw": IDWGenerator, "stkriging": SpaceTimeKrigingGenerator,
-             "lagkriging": LagrangianKrigingGenerator, "localkriging": LocalKrigingGenerator}
+             "lagkriging": LagrangianKrigingGenerator, "localkriging": LocalKrigingGenerator,
+             "locallagkriging": LocalLagrangianKrigingGenerator}

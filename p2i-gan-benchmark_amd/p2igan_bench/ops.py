@@ -1923,14 +1923,18 @@ def _lkrig_args(who, pix, z, info, params, cand, B, T, k, frames):
     return fcap
 
 
-def lkrig_predict(pix, z, info, params, cand, model, k, frames, B, T, H, W, variance=False, neighbours=False):
+def lkrig_predict(pix, z, info, params, cand, model, k, frames, B, T, H, W, variance=False, neighbours=False, velf=None):
     """Moving-neighbourhood space-time ordinary kriging of every pixel of every frame from krig_compact's per-frame arrays: each target
     from its k nearest points (key dy^2 + dx^2 + kappa^2 dt^2, ties by frame then raster index) within `frames` frames of its own.
     params (B, 4) fp32 = (nugget, psill, range, kappa); cand (B,) int32 or None (< 0: degenerate sample).  Returns out (B, T, H*W),
     var (the same shape, or None), status (B,) int32 = targets that met a non-positive pivot, and nbr (B, T, H*W, k) int32 (the
-    kernel's own selection as frame * fcap + slot, -1 past the candidates; None unless asked for)."""
+    kernel's own selection as frame * fcap + slot, -1 past the candidates; None unless asked for).
+    velf (B, 2) fp32 = (v_y, v_x) per sample: the same in the Lagrangian frame, key (dy - v_y dt)^2 + (dx - v_x
+    dt)^2 + kappa^2 dt^2 and lagkrig's distance inside the system."""
     lib = _hip.load()
     fcap = _lkrig_args("lkrig_predict", pix, z, info, params, cand, B, T, k, frames)
+    if velf is not None:
+        _lag_vel("lkrig_predict", velf, torch.float32, B)
     if H < 1 or W < 1:
         raise RuntimeError(f"lkrig_predict: bad frame shape {H} x {W}")
     dev = pix.device
@@ -1939,21 +1943,32 @@ def lkrig_predict(pix, z, info, params, cand, model, k, frames, B, T, H, W, vari
     var = torch.empty(B, T, H * W, device=dev, dtype=torch.float32) if variance else None
     nbr = torch.empty(B, T, H * W, k, device=dev, dtype=torch.int32) if neighbours else None
     status = torch.zeros(B, device=dev, dtype=torch.int32)
+    if velf is not None:
+        _hip.check(lib.p2i_lkrig_predict_lag(_ptr(pix), _ptr(z), _ptr(info), _ptr(params), _ptr(cand), int(model), k, frames, B, T, H, W, fcap,
+                                             _ptr(stat), _ptr(out), _ptr(var), _ptr(status), _ptr(nbr), _ptr(velf), _stream()),
+                   "p2i_lkrig_predict_lag")
+        return out, var, status, nbr
     _hip.check(lib.p2i_lkrig_predict(_ptr(pix), _ptr(z), _ptr(info), _ptr(params), _ptr(cand), int(model), k, frames, B, T, H, W, fcap,
                                      _ptr(stat), _ptr(out), _ptr(var), _ptr(status), _ptr(nbr), _stream()), "p2i_lkrig_predict")
     return out, var, status, nbr
 
 
-def lkrig_loso(pix, z, info, params, cand, model, k, frames, B, T):
+def lkrig_loso(pix, z, info, params, cand, model, k, frames, B, T, velf=None):
     """lkrig_predict with the points as targets and every point at the target's own pixel taken out of the candidates: leave-one-site-out
     without an inverse.  Returns pred, var (B*T, fcap) (0 past the frame's count, NaN where no candidate is left or the sample is
-    degenerate) and status (B,) int32."""
+    degenerate) and status (B,) int32.  velf: as in lkrig_predict."""
     lib = _hip.load()
     fcap = _lkrig_args("lkrig_loso", pix, z, info, params, cand, B, T, k, frames)
+    if velf is not None:
+        _lag_vel("lkrig_loso", velf, torch.float32, B)
     dev = pix.device
     stat = torch.empty(B, 2, device=dev, dtype=torch.float64)
     pred, var = torch.empty_like(z), torch.empty_like(z)
     status = torch.zeros(B, device=dev, dtype=torch.int32)
+    if velf is not None:
+        _hip.check(lib.p2i_lkrig_loso_lag(_ptr(pix), _ptr(z), _ptr(info), _ptr(params), _ptr(cand), int(model), k, frames, B, T, fcap,
+                                          _ptr(stat), _ptr(pred), _ptr(var), _ptr(status), _ptr(velf), _stream()), "p2i_lkrig_loso_lag")
+        return pred, var, status
     _hip.check(lib.p2i_lkrig_loso(_ptr(pix), _ptr(z), _ptr(info), _ptr(params), _ptr(cand), int(model), k, frames, B, T, fcap, _ptr(stat),
                                   _ptr(pred), _ptr(var), _ptr(status), _stream()), "p2i_lkrig_loso")
     return pred, var, status

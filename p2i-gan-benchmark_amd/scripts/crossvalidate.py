@@ -4,7 +4,7 @@ predicted from the other gauges of its frame, which needs no gridded truth.  Wri
 (p2igan_bench/evaluation/loo.py).  The space-time baselines `stkriging` and `lagkriging` are refused there:
 their honest score is leave-one-site-out, --by-site: a site, a gauge pixel over all frames of a chunk of
 --stride frames, is left out as a whole.  --by-site takes kriging, idw, stkriging and lagkriging (the last two in chunks of at
-most 32 frames) and localkriging (chunks of any length; it too is refused without --by-site) and writes loso.json, loso.txt and
+most 32 frames) and localkriging and locallagkriging (chunks of any length; they too are refused without --by-site) and writes loso.json, loso.txt and
 loso_data.npz."""
 from __future__ import annotations
 

@@ -21,6 +21,9 @@ from p2igan_bench.data import zarr_lite  # noqa: E402
 from p2igan_bench.data.dataloader import P2IDataModule  # noqa: E402
 from p2igan_bench.inference import infer_event, infer_event_chunks, infer_event_variance  # noqa: E402
 from p2igan_bench.models import CLASSICAL, build_generator  # noqa: E402
+from p2igan_bench.models.classical import LOCAL  # noqa: E402
+
+VARIANCE_MODELS = ("kriging",) + LOCAL          # the models with a forward_uq
 
 
 def parse_args(argv=None):
@@ -38,7 +41,7 @@ def parse_args(argv=None):
     p.add_argument("--output-scale", type=float, default=255.0)
     p.add_argument("--overwrite", action="store_true")
     p.add_argument("--variance-output", type=Path, default=None,
-                   help="kriging and localkriging only: a second zarr with the kriging variance x output-scale^2 under the same event keys")
+                   help="kriging, localkriging and locallagkriging only: a second zarr with the kriging variance x output-scale^2 under the same event keys")
     p.add_argument("--log-level", type=str, default="INFO")
     return p.parse_args(argv)
 
@@ -73,8 +76,9 @@ def main(argv=None):
         raise RuntimeError("the MI355X path needs a GPU: there is no CPU fallback")
     name = cfg.get("model", {}).get("name", "model")
     classical = str(name).lower() in CLASSICAL         # parameter-free: no checkpoint to resolve or load
-    if args.variance_output is not None and str(name).lower() not in ("kriging", "localkriging"):
-        raise RuntimeError(f"--variance-output needs model.name 'kriging' or 'localkriging', the models with a variance (got '{name}')")
+    if args.variance_output is not None and str(name).lower() not in VARIANCE_MODELS:
+        raise RuntimeError(f"--variance-output needs model.name 'kriging', 'localkriging' or 'locallagkriging', the models with a variance "
+                           f"(got '{name}')")
     ckpt = None if classical else resolve_checkpoint(cfg, args)
     loader = P2IDataModule(cfg).test_dataloader()
     if loader is None or len(loader.dataset) == 0:
