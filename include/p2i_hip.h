@@ -757,6 +757,56 @@ int p2i_scale_rings(const double* psd, int T, int S, const int* order, const dou
                     int R, double* P, void* stream);
 int p2i_scale_spectrum_merge(const double* P, const int* nanflag, int64_t T, int R, double* out, void* stream);
 
+/* ---- probabilistic verification of a prediction and its variance against the truth (no counterpart in the
+ * reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], each with its own
+ * extent and crop origin); the crop is rows x cols.  Scored on the inputs' own 0-255 scale in fp64: per pixel mu = pred, s2 = var
+ * (var == NULL: var_scalar for every pixel), y = truth, sigma = sqrt(s2), Phi / phi the standard normal cdf / pdf, predictive
+ * distribution N(mu, s2), left-censored at 0 when `censor`; mu' = max(mu, 0) under censoring, mu otherwise; e = y - mu';
+ * z = (y - mu) / sigma, l = -mu / sigma.  rank[rows * cols] (int32; NULL: every pixel) selects the pixels with rank >= 0.  A
+ * selected pixel is SKIPPED when mu, s2 or y is NaN, s2 < 0, or (censor and y < 0); every other selected pixel is scored.
+ * p2i_prob_record: the record's word counts nf (fp64) and ni (int64) for these sizes (K thresholds, L levels, E edges -> NS = E + 1
+ *   sigma-bins, NB PIT bins, RB reliability bins).  A record is nf doubles followed by ni int64:
+ *     fp64  [0] sum CRPS   sigma > 0, plain:    sigma [z (2 Phi(z) - 1) + 2 phi(z) - 1/sqrt(pi)]
+ *                          sigma > 0, censored: sigma [-l Phi(l)^2 + z (2 Phi(z) - 1) + 2 phi(z) - 2 phi(l) Phi(l)
+ *                                                      - (1 - Phi(l sqrt 2)) / sqrt(pi)];  sigma == 0: |e|
+ *           [1] sum e  [2] sum |e|  [3] sum e^2  [4] sum s2  [5] sum z  [6] sum z^2 (the last two over sigma > 0 only)
+ *           [7 ..+L)   sum of interval widths hi - lo per level: lo, hi = mu -+ h sigma, both clamped at 0 under censoring
+ *           [..+K)     sum p per threshold: p = Phi((mu - xq) / sigma); sigma == 0: p = 1[transform_mmhr(mu') >= q]
+ *           [..+K)     sum (p - o)^2 per threshold: o = 1[transform_mmhr(y) >= q] through exp1's uint8 table / device pow
+ *           [..+NS)    sum s2 per sigma-bin: bin = the number of edges <= sigma (0: underflow, E: overflow)
+ *           [..+NS)    sum e^2 per sigma-bin
+ *     int64 [0] scored pixels  [1] skipped pixels  [2] scored pixels with sigma == 0
+ *           [3 ..+L)   pixels with lo <= y <= hi per level
+ *           [..+K)     sum o per threshold
+ *           [..+NB)    PIT histogram in units of 2^-32: weight 1 in bin min(floor(u NB), NB - 1), u = Phi(z); sigma == 0: u = 0,
+ *                      0.5, 1 for y <, ==, > mu'.  Censored, sigma > 0 and y == 0: with P0 = Phi(l) and m = min(floor(P0 NB),
+ *                      NB - 1), rint(2^32 (P0 - m / NB) / P0) in bin m (P0 == 0: weight 1 in bin 0) ...
+ *           [..+NB)    ... and the PIT prefix table: rint(2^32 / (NB P0)) at m - 1 when m > 0, standing for that weight in every
+ *                      bin 0 .. m - 1: histogram[j] = pit[j] + sum_{i >= j} prefix[i]
+ *           [..+NS)    pixels per sigma-bin
+ *           [..+K RB)  pixels per (threshold, reliability bin min(floor(p RB), RB - 1))
+ *           [..+K RB)  sum o per (threshold, reliability bin)
+ *           [..+K RB)  sum rint(2^32 p) per (threshold, reliability bin)
+ * p2i_prob_accumulate: one aligned piece of T frames; writes one record per P2I_PROB_WG_PIXELS consecutive pixels of the piece
+ *   (frame-major, row-major) to part (part_words = its capacity in 64-bit words).  thresholds (mm/h), xq (the same on the pixel
+ *   scale), halfwidths (Phi^-1((1 + level) / 2)) and edges (ascending) are HOST arrays.  No floating-point atomics: the same bits on
+ *   every run.
+ * p2i_prob_merge: acc[w] += the sum of part[0 .. nparts)[w] in a fixed order (64 strided partial sums in ascending record order, then
+ *   a tree), w < nf as fp64, the rest as int64. */
+#define P2I_PROB_MAX_LEVELS 8
+#define P2I_PROB_MAX_EDGES 16
+#define P2I_PROB_MAX_PIT_BINS 64
+#define P2I_PROB_MAX_REL_BINS 32
+#define P2I_PROB_WG_PIXELS 1024
+int p2i_prob_record(int nthr, int nlevels, int nedges, int pit_bins, int rel_bins, int* nf, int* ni);
+int p2i_prob_accumulate(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* var, int var_dtype, int vh,
+                        int vw, int vtop, int vleft, double var_scalar, const void* truth, int truth_dtype, int gh, int gw, int gtop,
+                        int gleft, int64_t T, int rows, int cols, const int* rank, const double* lut, const double* thresholds_host,
+                        const double* xq_host, int nthr, const double* halfwidths_host, int nlevels, const double* edges_host,
+                        int nedges, int pit_bins, int rel_bins, int censor, int divide_by_3, double* part, int64_t part_words,
+                        void* stream);
+int p2i_prob_merge(const double* part, int64_t nparts, int nf, int ni, double* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

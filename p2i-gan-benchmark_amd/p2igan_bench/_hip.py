@@ -166,6 +166,11 @@ SIGNATURES = {
     "p2i_scale_dft_cols": [_P, _I, _I, _P, _P, _P],
     "p2i_scale_rings": [_P, _I, _I, _P, _P, _P, _P, _I, _P, _P],
     "p2i_scale_spectrum_merge": [_P, _P, _L, _I, _P, _P],
+    "p2i_prob_record": [_I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "p2i_prob_accumulate": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F64, _P, _I, _I, _I, _I, _I, _L, _I, _I, _P, _P,
+                            C.POINTER(C.c_double), C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I,
+                            _I, _I, _I, _I, _P, _L, _P],
+    "p2i_prob_merge": [_P, _L, _I, _I, _P, _P],
 }
 
 

@@ -23,6 +23,11 @@ loo (``loo.py``, section 16; no counterpart in the reference): ``run_loo`` cross
 gauges of every test event and writes ``loo.json``, ``loo.txt`` and ``loo_data.npz``; it needs no gridded truth.  ``run_loso`` (section 18) is the same with whole sites left out, the score of the
 space-time baseline; it writes ``loso.json``, ``loso.txt`` and ``loso_data.npz``.
 
+prob (``prob.py``, section 22; no counterpart in the reference): ``run_prob`` scores a prediction with its variance as a Gaussian,
+left-censored at 0, against the truth: CRPS, PIT histogram, interval coverage and sharpness, standardised error, spread against skill
+and Brier / reliability / ROC of the rain-rate exceedances, per method "dressed" (its own MSE as the variance) and with its variance
+map.  ``run_prob_points`` does the same for cross-validation columns; ``ProbEvaluator`` is the streaming form.
+
 ``_common.py`` holds what the units share."""
 from ._common import crop_mask, crop_origin, ensure_thw_shape, selection, transform_mmhr, truth_lut  # noqa: F401
 from .exp1 import DEFAULT_THRESHOLDS, PSS_BINS, PSS_MIN_VALUE, Exp1Evaluator, pss_bin, pss_edges, run_exp1  # noqa: F401
@@ -35,3 +40,6 @@ from .exp3 import (EXP3_MAX_POINTS, EXP3_MIN_VALUE, EXP3_SEED, LOGFREQ_EDGES, SC
 from .loo import loo_lines, loso_lines, run_loo, run_loso  # noqa: F401
 from .scale import (DEFAULT_SCALES, ScaleEvaluator, check_overflow, fss_value, ring_counts, ring_index, ring_list, run_scale,  # noqa: F401
                     scale_lines, spectrum_scores, twiddle, useful_scale, write_scale_figure, write_scale_outputs)
+from .prob import (DEFAULT_LEVELS, DEFAULT_PIT_BINS, DEFAULT_REL_BINS, DEFAULT_SIGMA_EDGES, ProbEvaluator, half_width,  # noqa: F401
+                   pixel_threshold, prob_arrays, prob_lines, prob_scores, roc_area, run_prob, run_prob_points, unpack_record,
+                   write_prob_figure, write_prob_outputs)

@@ -50,7 +50,21 @@ def loso_lines(result: Dict[str, Any]):
     return loo_lines(result, "leave-one-site-out")
 
 
-def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_scale: float = 255.0, stride: int = 16) -> Dict[str, Any]:
+def _has_variance(name: str, by_site: bool) -> bool:
+    from ..models.classical import LOCAL, SPACE_TIME
+    return name == "kriging" or (by_site and (name in SPACE_TIME or name in LOCAL))
+
+
+def check_prob(cfg: Dict[str, Any], by_site: bool) -> None:
+    """The probabilistic verification of a cross-validation scores N(pred, var): RuntimeError for a run without a variance."""
+    name = str(cfg.get("model", {}).get("name", "model")).lower()
+    if not _has_variance(name, by_site):
+        raise RuntimeError(f"--prob scores the predictive distribution N(pred, var) of a cross-validation: model.name '{name}' "
+                           f"{'leave-one-site-out' if by_site else 'leave-one-out'} has no variance")
+
+
+def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_scale: float = 255.0, stride: int = 16,
+            prob: bool = False) -> Dict[str, Any]:
     """Cross-validate cfg's classical model on every test event, in consecutive chunks of `stride` frames as infer_event_chunks forms
     them (each chunk is one sample of a fitted variogram).  Writes loo.json / loo.txt (scores per event and overall) and loo_data.npz
     (per gauge: event, frame, y, x, z, LOO prediction, LOO variance; coded units, unscaled) under out_dir; returns loo.json's content."""
@@ -66,10 +80,11 @@ def run_loo(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_s
     if name in LOCAL:
         from ..models.classical import LOCAL_LAG_NO_LOO, LOCAL_NO_LOO
         raise RuntimeError(LOCAL_NO_LOO if name == "localkriging" else LOCAL_LAG_NO_LOO)
-    return _run(cfg, out_dir, device, output_scale, stride, name, False)
+    return _run(cfg, out_dir, device, output_scale, stride, name, False, prob)
 
 
-def run_loso(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_scale: float = 255.0, stride: int = 16) -> Dict[str, Any]:
+def run_loso(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_scale: float = 255.0, stride: int = 16,
+             prob: bool = False) -> Dict[str, Any]:
     """run_loo with whole sites left out (the models' cross_validate_sites), for all classical baselines.  A chunk of `stride`
     frames is one sample, so a site is a gauge pixel over the chunk's frames; `stkriging` and `lagkriging` take chunks of at most 32 frames.  Writes
     loso.json / loso.txt and loso_data.npz (loo_data.npz's columns plus site, the site's index within its chunk) under out_dir."""
@@ -82,12 +97,13 @@ def run_loso(cfg: Dict[str, Any], out_dir, device: Optional[str] = None, output_
                            f"model.name '{name}' is a learnt model and would need one training per site")
     if name in SPACE_TIME and int(stride) > ops.KRIG_TILE:
         raise ValueError(f"leave-one-site-out of '{name}' takes chunks of at most {ops.KRIG_TILE} frames: --stride {int(stride)} is too long")
-    return _run(cfg, out_dir, device, output_scale, stride, name, True)
+    return _run(cfg, out_dir, device, output_scale, stride, name, True, prob)
 
 
-def _run(cfg, out_dir, device, output_scale, stride, name, by_site):
+def _run(cfg, out_dir, device, output_scale, stride, name, by_site, prob=False):
     from ..models import build_generator
-    from ..models.classical import LOCAL, SPACE_TIME
+    if prob:
+        check_prob(cfg, by_site)
     dev = torch.device(device or cfg.get("device", "cuda:0"))
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise RuntimeError("the MI355X path needs a GPU: there is no CPU fallback")
@@ -97,7 +113,7 @@ def _run(cfg, out_dir, device, output_scale, stride, name, by_site):
         raise RuntimeError("Test dataloader is not configured or empty.")
     G = build_generator(cfg).to(dev).eval()
     scale, stride = float(output_scale), max(1, int(stride))
-    with_var = name == "kriging" or (by_site and (name in SPACE_TIME or name in LOCAL))
+    with_var = _has_variance(name, by_site)
     stem = "loso" if by_site else "loo"
     events, cols = {}, {k: [] for k in ("event", "frame", "y", "x", "z", "pred", "var") + (("site",) if by_site else ())}
     total = np.zeros(5)
@@ -139,4 +155,10 @@ def _run(cfg, out_dir, device, output_scale, stride, name, by_site):
     with open(os.path.join(out_dir, f"{stem}.txt"), "w") as fh:
         fh.write("\n".join(loso_lines(result) if by_site else loo_lines(result)) + "\n")
     np.savez(os.path.join(out_dir, f"{stem}_data.npz"), **data)
+    if prob:
+        # prob.json / prob.txt / prob_data.npz: the columns' N(pred, var) against z on the output scale (points without a prediction
+        # or a variance carry NaN and are counted as skipped)
+        from .prob import run_prob_points, write_prob_outputs
+        write_prob_outputs(out_dir, run_prob_points(data["z"], data["pred"], data["var"], scale, name=name, device=dev), stem="prob",
+                           figure=False)
     return result

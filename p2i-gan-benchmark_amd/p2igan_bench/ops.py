@@ -2327,3 +2327,53 @@ def scale_spectrum_merge(P, nanflag):
     out = torch.empty(2 * R + 1, device=P.device, dtype=torch.float64)
     _hip.check(_hip.load().p2i_scale_spectrum_merge(_ptr(P), _ptr(nanflag), T, R, _ptr(out), _stream()), "p2i_scale_spectrum_merge")
     return out
+
+
+# ---- probabilistic verification of variance maps (csrc/eval_prob.hip; p2igan_bench/evaluation/prob.py drives these) ----
+PROB_MAX_LEVELS = 8
+PROB_MAX_EDGES = 16
+PROB_MAX_PIT_BINS = 64
+PROB_MAX_REL_BINS = 32
+PROB_WG_PIXELS = 1024
+
+
+def prob_record(nthr: int, nlevels: int, nedges: int, pit_bins: int, rel_bins: int):
+    """(nf, ni): the fp64 and int64 word counts of a record for these sizes (layout: include/p2i_hip.h)."""
+    nf, ni = C.c_int(0), C.c_int(0)
+    _hip.check(_hip.load().p2i_prob_record(nthr, nlevels, nedges, pit_bins, rel_bins, C.byref(nf), C.byref(ni)), "p2i_prob_record")
+    return int(nf.value), int(ni.value)
+
+
+def prob_accumulate(pred, var, truth, ptl, vtl, gtl, rows, cols, rank, lut, thresholds, xq, halfwidths, edges, pit_bins, rel_bins,
+                    censor, divide_by_3, part):
+    """One aligned piece: pred, truth [T, H, W] (their own H, W) with crop origins ptl / gtl of the rows x cols crop; ``var`` is a
+    third such input with origin vtl, or a float (one variance for every pixel).  rank [rows * cols] int32 or None (every pixel).
+    Writes ceil(T * rows * cols / PROB_WG_PIXELS) records to part (fp64 words; the int64 sections travel as their bits)."""
+    T = pred.shape[0]
+    if truth.shape[0] != T or len(xq) != len(thresholds):
+        raise RuntimeError("prob_accumulate: frame count / thresholds")
+    pin, gin = _eval_input(pred, ptl), _eval_input(truth, gtl)
+    if isinstance(var, torch.Tensor):
+        if var.shape[0] != T:
+            raise RuntimeError("prob_accumulate: the variance's frame count")
+        vin, v0 = _eval_input(var, vtl), 0.0
+    else:
+        vin, v0 = (None, 0, 0, 0, 0, 0), float(var)
+    nf, ni = prob_record(len(thresholds), len(halfwidths), len(edges), pit_bins, rel_bins)
+    nwg = -(-T * rows * cols // PROB_WG_PIXELS)
+    bufs = [(lut, torch.float64, 256), (part, torch.float64, nwg * (nf + ni))]
+    if rank is not None:
+        bufs.append((rank, torch.int32, rows * cols))
+    _eval_bufs("prob_accumulate", *bufs)
+    _hip.check(_hip.load().p2i_prob_accumulate(
+        *pin, *vin, v0, *gin, T, rows, cols, _ptr(rank) if rank is not None else None, _ptr(lut), _f64s(thresholds), _f64s(xq),
+        len(thresholds), _f64s(halfwidths), len(halfwidths), _f64s(edges), len(edges), pit_bins, rel_bins, int(bool(censor)),
+        int(divide_by_3), _ptr(part), part.numel(), _stream()), "p2i_prob_accumulate")
+
+
+def prob_merge(part, nf, ni, acc):
+    """acc [nf + ni] += the records of part (a multiple of nf + ni words), summed in a fixed order: fp64 words as fp64, the rest as int64."""
+    if part.numel() == 0 or part.numel() % (nf + ni):
+        raise RuntimeError("prob_merge: bad buffer")
+    _eval_bufs("prob_merge", (part, torch.float64, part.numel()), (acc, torch.float64, nf + ni))
+    _hip.check(_hip.load().p2i_prob_merge(_ptr(part), part.numel() // (nf + ni), nf, ni, _ptr(acc), _stream()), "p2i_prob_merge")

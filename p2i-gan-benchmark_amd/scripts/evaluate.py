@@ -22,6 +22,12 @@ With ``--scale DIRS [--scales N ...]`` it also runs the scale-aware verification
 ``--thresholds`` x the neighbourhood sizes, and the radially averaged power spectra) on the whole crop and writes DIRS/metrics.json,
 DIRS/metrics.txt (``FSS_<name>_thr<q>_n<n>: value`` and ``LSD_<name>: value`` lines), DIRS/scale_data.npz and DIRS/scale_panels.pdf.
 It needs ``--mode radar``; the other outputs do not depend on it.
+
+With ``--prob DIRP [--variance NAME=V.zarr ...] [--levels L ...] [--no-censor]`` it also runs the probabilistic verification
+(run_prob) on the mode's pixels: every method "dressed" with its own in-sample MSE as the variance, and every method named by a
+``--variance`` (a zarr of sigma^2 x output_scale^2 under the prediction's event keys, as ``scripts/infer.py --variance-output``
+writes it) with its variance map.  Writes DIRP/metrics.json, DIRP/metrics.txt (``CRPS_<name>_<kind>: value``, ``COV90_...``,
+``BRIER_..._thr<q>`` ... lines), DIRP/prob_data.npz and DIRP/prob_panels.pdf.  The other outputs do not depend on it.
 """
 from __future__ import annotations
 
@@ -38,6 +44,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from p2igan_bench.data import zarr_lite  # noqa: E402
 from p2igan_bench.evaluation import (DEFAULT_SCALES, DEFAULT_THRESHOLDS, crop_mask, run_exp1, run_exp2, run_exp2_paper_zarr,  # noqa: E402
                                      run_exp3, run_scale, write_scale_outputs)
+from p2igan_bench.evaluation.prob import DEFAULT_LEVELS, half_width, pixel_threshold, run_prob, write_prob_outputs  # noqa: E402
 
 
 def _method(spec: str):
@@ -75,7 +82,33 @@ def parse_args(argv=None):
                    "neighbourhood sizes, radial power spectra) and write its outputs into DIR")
     p.add_argument("--scales", type=int, nargs="+", default=list(DEFAULT_SCALES), metavar="N", help="FSS neighbourhood sizes in pixels "
                    "(at most 16)")
+    p.add_argument("--prob", default=None, metavar="DIR", help="also run the probabilistic verification (CRPS, PIT, coverage, "
+                   "spread-skill, Brier / reliability / ROC) and write its outputs into DIR")
+    p.add_argument("--variance", type=_method, action="append", default=[], metavar="NAME=ZARR",
+                   help="the variance zarr of method NAME (repeatable; needs --prob)")
+    p.add_argument("--levels", type=float, nargs="+", default=list(DEFAULT_LEVELS), metavar="L", help="nominal levels of the central "
+                   "intervals (at most 8, each in (0, 1))")
+    p.add_argument("--no-censor", action="store_true", help="score the plain Gaussian instead of the one left-censored at 0")
     args = p.parse_args(argv)
+    if args.variance and not args.prob:
+        p.error("--variance needs --prob")
+    if args.prob:
+        unknown = [n for n, _ in args.variance if n not in [m for m, _ in args.method]]
+        if unknown:
+            p.error(f"--variance names a method that no --method gives: {unknown}")
+        if len({n for n, _ in args.variance}) != len(args.variance):
+            p.error("--variance names repeat")
+        if not 0 < len(args.levels) <= 8:
+            p.error("--levels takes 1 to 8 levels")
+        if not 0 < len(args.thresholds) <= 8:
+            p.error("--thresholds takes 1 to 8 thresholds")
+        try:
+            for v in args.levels:
+                half_width(v)
+            for q in args.thresholds:
+                pixel_threshold(q, True)
+        except ValueError as e:
+            p.error(str(e))
     if args.scale and args.mode != "radar":
         p.error("--scale scores the whole crop: it needs --mode radar")
     if args.scale and not 0 < len(args.scales) <= 16:
@@ -103,6 +136,13 @@ def check_events(truth_keys: List[str], method: str, keys) -> None:
     missing = [k for k in truth_keys if k not in keys]
     if missing:
         raise ValueError(f"method {method!r} lacks truth event {missing[0]!r}" + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+
+
+def check_output_scale(name: str, pred_attrs, var_attrs) -> None:
+    """The variance is sigma^2 x output_scale^2 of the prediction's scale: where both zarrs record an output_scale they must agree."""
+    a, b = pred_attrs.get("output_scale"), var_attrs.get("output_scale")
+    if a is not None and b is not None and float(a) != float(b):
+        raise ValueError(f"method {name!r}: the prediction was written with output_scale {a}, its variance with {b}")
 
 
 def format_lines(metrics) -> List[str]:
@@ -169,6 +209,20 @@ def main(argv=None):
         write_scale_outputs(args.scale, ms)
         print(f"wrote {os.path.join(args.scale, 'metrics.json')} and the scale figure")
     paths = {name: path for name, path in args.method}
+    if args.prob:
+        variances = {}
+        for name, path in args.variance:
+            g = zarr_lite.Group(path, "r")
+            try:
+                check_events(list(truth), name, set(g.array_keys()))
+                check_output_scale(name, zarr_lite.Group(paths[name], "r").attrs, g.attrs)
+            except ValueError as e:
+                raise SystemExit(f"{path}: {e}")
+            variances[name] = {k: np.asarray(g[k][:]) for k in truth}
+        mp = run_prob(preds, variances, truth, mask, args.mode, args.crop_size, thresholds=tuple(args.thresholds),
+                      levels=tuple(args.levels), censor=not args.no_censor, divide_by_3=True, device=args.device)
+        write_prob_outputs(args.prob, mp)
+        print(f"wrote {os.path.join(args.prob, 'metrics.json')} and the probability figure")
     if args.exp2:
         run_exp2(paths, args.truth, args.observation, mask, args.exp2, args.crop_size, None, 0.0, 0.0, args.gif_fps, divide_by_3=True,
                  mode=args.mode, device=args.device, zoom=args.exp2_zoom)
