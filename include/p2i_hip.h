@@ -807,6 +807,38 @@ int p2i_prob_accumulate(const void* pred, int pred_dtype, int ph, int pw, int pt
                         void* stream);
 int p2i_prob_merge(const double* part, int64_t nparts, int nf, int ni, double* acc, void* stream);
 
+/* ---- object-based verification: connected rain objects and their integer moments, for SAL and the object population (DESIGN.md
+ * section 23; no counterpart in the reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous
+ * [T][h][w], the transform and uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <=
+ * P2I_OBJECTS_MAX_CROP.  R = the transformed pixel (mm/h) and Q = rint(R 2^24) (half-even; 0 for a NaN), Q < 2^32.  Levels: nthr
+ * absolute thresholds (HOST array, <= P2I_EXP1_MAX_THR) give the mask R >= q, and one relative level, the last, R >= max(sal_factor
+ * Rmax, sal_floor) with Rmax the maximum of the field's own crop in that frame; NaN compares false.  nlev = nthr + 1.  An object is
+ * a connected component (connectivity 4 or 8, no wrap, cut at the crop edge) of a level's mask; its label is the smallest raster
+ * index y S + x of its pixels.  All results are integers below 200 2^24 2^10 2^20 < 2^62 and do not depend on the path or the run.
+ * p2i_objects_quantize: field 0 (prediction) or 1 (truth) of one aligned piece of T frames: q[T][2][S S] (uint32) = Q,
+ *   bits[T][2][S S] (uint16) = bit j set where the pixel is in level j's mask, rec[T][2][5] (int64) = sum Q, sum Q y, sum Q x over
+ *   the crop, max Q, 1 if the crop holds a NaN.
+ * p2i_objects_label: labels[T][2][nlev][S S] = a set pixel's object label, all ones elsewhere; wide == 0: uint16 labels, one
+ *   workgroup per record with the labels in LDS, S <= P2I_OBJECTS_LDS_CROP; wide != 0: uint32 labels in the caller's workspace, tiles
+ *   of P2I_OBJECTS_TILE^2 labelled in LDS, united across their borders and flattened, any S.
+ * p2i_objects_count: lev[T][2][nlev][5] (int64) = objects, their total area, sum Q, sum Q y, sum Q x over object pixels;
+ *   counts[T 2 nlev] (int64) = the objects again, contiguous for the scan.
+ * p2i_objects_scan: offsets[n + 1] (int64) = the exclusive prefix of counts[n], offsets[n] = the total.
+ * p2i_objects_fill: table[rows][6] (int64, ZEROED by the caller, rows = offsets[T 2 nlev]) = per record, from offsets[record], its
+ *   objects in ascending label order: label, area, sum Q, max Q, sum Q y, sum Q x.  Overwrites labels. */
+#define P2I_OBJECTS_LDS_CROP 128
+#define P2I_OBJECTS_TILE 64
+#define P2I_OBJECTS_MAX_CROP 1024
+int p2i_objects_quantize(const void* x, int dtype, int h, int w, int top, int left, int T, int S, int field, const double* lut,
+                         const double* thresholds_host, int nthr, double sal_factor, double sal_floor, int divide_by_3, uint32_t* q,
+                         uint16_t* bits, int64_t* rec, void* stream);
+int p2i_objects_label(const uint16_t* bits, int T, int S, int nlev, int connectivity, int wide, void* labels, void* stream);
+int p2i_objects_count(const void* labels, int wide, const uint32_t* q, int T, int S, int nlev, int64_t* lev, int64_t* counts,
+                      void* stream);
+int p2i_objects_scan(const int64_t* counts, int64_t n, int64_t* offsets, void* stream);
+int p2i_objects_fill(void* labels, int wide, const uint32_t* q, int T, int S, int nlev, const int64_t* offsets, int64_t rows,
+                     int64_t* table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,11 @@ SIGNATURES = {
                             C.POINTER(C.c_double), C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I,
                             _I, _I, _I, _I, _P, _L, _P],
     "p2i_prob_merge": [_P, _L, _I, _I, _P, _P],
+    "p2i_objects_quantize": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(C.c_double), _I, _F64, _F64, _I, _P, _P, _P, _P],
+    "p2i_objects_label": [_P, _I, _I, _I, _I, _I, _P, _P],
+    "p2i_objects_count": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
+    "p2i_objects_scan": [_P, _L, _P, _P],
+    "p2i_objects_fill": [_P, _I, _P, _I, _I, _I, _P, _L, _P, _P],
 }
 
 

@@ -28,6 +28,10 @@ left-censored at 0, against the truth: CRPS, PIT histogram, interval coverage an
 and Brier / reliability / ROC of the rain-rate exceedances, per method "dressed" (its own MSE as the variance) and with its variance
 map.  ``run_prob_points`` does the same for cross-validation columns; ``ProbEvaluator`` is the streaming form.
 
+objects (``objects.py``, section 23; no counterpart in the reference): ``run_objects`` labels the connected rain objects of every
+frame at the absolute thresholds and at one relative level and returns per method and level SAL (structure, amplitude, location)
+against the truth and the object population of both sides.  ``ObjectEvaluator`` is the streaming form (one host read per launch).
+
 ``_common.py`` holds what the units share."""
 from ._common import crop_mask, crop_origin, ensure_thw_shape, selection, transform_mmhr, truth_lut  # noqa: F401
 from .exp1 import DEFAULT_THRESHOLDS, PSS_BINS, PSS_MIN_VALUE, Exp1Evaluator, pss_bin, pss_edges, run_exp1  # noqa: F401
@@ -43,3 +47,5 @@ from .scale import (DEFAULT_SCALES, ScaleEvaluator, check_overflow, fss_value, r
 from .prob import (DEFAULT_LEVELS, DEFAULT_PIT_BINS, DEFAULT_REL_BINS, DEFAULT_SIGMA_EDGES, ProbEvaluator, half_width,  # noqa: F401
                    pixel_threshold, prob_arrays, prob_lines, prob_scores, roc_area, run_prob, run_prob_points, unpack_record,
                    write_prob_figure, write_prob_outputs)
+from .objects import (DEFAULT_SAL_FACTOR, DEFAULT_SAL_FLOOR, ObjectEvaluator, level_keys, objects_lines, run_objects, sal_frames,  # noqa: F401
+                      sal_summary, write_objects_figure, write_objects_outputs)

@@ -2329,6 +2329,63 @@ def scale_spectrum_merge(P, nanflag):
     return out
 
 
+# ---- object-based verification: connected rain objects (csrc/eval_objects.hip; p2igan_bench/evaluation/objects.py drives these) ----
+OBJECTS_LDS_CROP = 128
+OBJECTS_TILE = 64
+
+
+def _objects_labels(labels, wide, n):
+    _eval_bufs("objects labels", (labels, torch.int32 if wide else torch.int16, n))
+
+
+def objects_quantize(x, tl, field, S, lut, thresholds, sal_factor, sal_floor, divide_by_3, q, bits, rec):
+    """Field 0 (prediction) / 1 (truth) of one aligned piece x [T, H, W]: q [T, 2, S * S] (int32 holding uint32) = rint(R * 2^24),
+    bits [T, 2, S * S] (int16) = the level masks (bit j: threshold j; bit len(thresholds): the relative level), rec [T, 2, 5] (int64) =
+    sum Q, sum Q y, sum Q x, max Q, NaN flag."""
+    T, K = x.shape[0], len(thresholds)
+    if field not in (0, 1) or not 0 < K <= EXP1_MAX_THR or not 0 < S <= SCALE_MAX_CROP:
+        raise RuntimeError("objects_quantize: field / thresholds / crop")
+    _eval_bufs("objects_quantize", (lut, torch.float64, 256), (q, torch.int32, T * 2 * S * S), (bits, torch.int16, T * 2 * S * S),
+               (rec, torch.int64, T * 2 * 5))
+    _hip.check(_hip.load().p2i_objects_quantize(*_eval_input(x, tl), T, S, field, _ptr(lut), _f64s(thresholds), K, float(sal_factor),
+                                                float(sal_floor), int(divide_by_3), _ptr(q), _ptr(bits), _ptr(rec), _stream()),
+               "p2i_objects_quantize")
+
+
+def objects_label(bits, T, S, nlev, connectivity, labels, wide):
+    """labels [T, 2, nlev, S * S] (int16 holding uint16, or int32 holding uint32 when ``wide``) = the canonical object label of every
+    set pixel, all ones elsewhere.  Not ``wide``: labels in LDS (S <= OBJECTS_LDS_CROP); ``wide``: tiles, border merge and flatten."""
+    _eval_bufs("objects_label", (bits, torch.int16, T * 2 * S * S))
+    _objects_labels(labels, wide, T * 2 * nlev * S * S)
+    _hip.check(_hip.load().p2i_objects_label(_ptr(bits), T, S, nlev, int(connectivity), int(bool(wide)), _ptr(labels), _stream()),
+               "p2i_objects_label")
+
+
+def objects_count(labels, wide, q, T, S, nlev, lev, counts):
+    """lev [T, 2, nlev, 5] (int64) = objects, area, sum Q, sum Q y, sum Q x over object pixels; counts [T * 2 * nlev] (int64)."""
+    _objects_labels(labels, wide, T * 2 * nlev * S * S)
+    _eval_bufs("objects_count", (q, torch.int32, T * 2 * S * S), (lev, torch.int64, T * 2 * nlev * 5), (counts, torch.int64, T * 2 * nlev))
+    _hip.check(_hip.load().p2i_objects_count(_ptr(labels), int(bool(wide)), _ptr(q), T, S, nlev, _ptr(lev), _ptr(counts), _stream()),
+               "p2i_objects_count")
+
+
+def objects_scan(counts, offsets):
+    """offsets [n + 1] (int64) = the exclusive prefix of counts [n] and, last, their total."""
+    n = counts.numel()
+    _eval_bufs("objects_scan", (counts, torch.int64, n), (offsets, torch.int64, n + 1))
+    _hip.check(_hip.load().p2i_objects_scan(_ptr(counts), n, _ptr(offsets), _stream()), "p2i_objects_scan")
+
+
+def objects_fill(labels, wide, q, T, S, nlev, offsets, table):
+    """table [rows, 6] (int64, zeroed, rows = offsets[-1]): per record its objects in ascending label order as label, area, sum Q,
+    max Q, sum Q y, sum Q x.  Overwrites labels."""
+    rows = table.shape[0]
+    _objects_labels(labels, wide, T * 2 * nlev * S * S)
+    _eval_bufs("objects_fill", (q, torch.int32, T * 2 * S * S), (offsets, torch.int64, T * 2 * nlev + 1), (table, torch.int64, rows * 6))
+    _hip.check(_hip.load().p2i_objects_fill(_ptr(labels), int(bool(wide)), _ptr(q), T, S, nlev, _ptr(offsets), rows,
+                                            _ptr(table) if rows else None, _stream()), "p2i_objects_fill")
+
+
 # ---- probabilistic verification of variance maps (csrc/eval_prob.hip; p2igan_bench/evaluation/prob.py drives these) ----
 PROB_MAX_LEVELS = 8
 PROB_MAX_EDGES = 16

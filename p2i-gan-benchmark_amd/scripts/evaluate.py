@@ -28,6 +28,12 @@ With ``--prob DIRP [--variance NAME=V.zarr ...] [--levels L ...] [--no-censor]``
 ``--variance`` (a zarr of sigma^2 x output_scale^2 under the prediction's event keys, as ``scripts/infer.py --variance-output``
 writes it) with its variance map.  Writes DIRP/metrics.json, DIRP/metrics.txt (``CRPS_<name>_<kind>: value``, ``COV90_...``,
 ``BRIER_..._thr<q>`` ... lines), DIRP/prob_data.npz and DIRP/prob_panels.pdf.  The other outputs do not depend on it.
+
+With ``--objects DIRO [--connectivity {4,8}] [--sal-factor F] [--sal-floor Q]`` it also runs the object-based verification
+(run_objects: the connected rain objects at ``--thresholds`` and at the relative level R >= max(F Rmax, Q), their population and SAL)
+on the whole crop and writes DIRO/metrics.json, DIRO/metrics.txt (``SAL_<name>_<level>: S=.. A=.. L=..`` and ``OBJ_<name>_<level>:
+pred=.. truth=..`` lines), DIRO/objects_data.npz and DIRO/objects_panels.pdf.  It needs ``--mode radar``; the other outputs do not
+depend on it.
 """
 from __future__ import annotations
 
@@ -44,6 +50,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from p2igan_bench.data import zarr_lite  # noqa: E402
 from p2igan_bench.evaluation import (DEFAULT_SCALES, DEFAULT_THRESHOLDS, crop_mask, run_exp1, run_exp2, run_exp2_paper_zarr,  # noqa: E402
                                      run_exp3, run_scale, write_scale_outputs)
+from p2igan_bench.evaluation.objects import (DEFAULT_SAL_FACTOR, DEFAULT_SAL_FLOOR, run_objects, write_objects_outputs)  # noqa: E402
 from p2igan_bench.evaluation.prob import DEFAULT_LEVELS, half_width, pixel_threshold, run_prob, write_prob_outputs  # noqa: E402
 
 
@@ -89,7 +96,20 @@ def parse_args(argv=None):
     p.add_argument("--levels", type=float, nargs="+", default=list(DEFAULT_LEVELS), metavar="L", help="nominal levels of the central "
                    "intervals (at most 8, each in (0, 1))")
     p.add_argument("--no-censor", action="store_true", help="score the plain Gaussian instead of the one left-censored at 0")
+    p.add_argument("--objects", default=None, metavar="DIR", help="also run the object-based verification (connected rain objects, "
+                   "their population, SAL) and write its outputs into DIR")
+    p.add_argument("--connectivity", type=int, choices=(4, 8), default=8, help="pixel connectivity of the objects")
+    p.add_argument("--sal-factor", type=float, default=DEFAULT_SAL_FACTOR, metavar="F", help="the relative level's share of the "
+                   "frame's maximum (default 1/15)")
+    p.add_argument("--sal-floor", type=float, default=DEFAULT_SAL_FLOOR, metavar="Q", help="the relative level's floor in mm/h "
+                   "(default 0.1)")
     args = p.parse_args(argv)
+    if args.objects and args.mode != "radar":
+        p.error("--objects labels the whole crop: it needs --mode radar")
+    if args.objects and not 0 < len(args.thresholds) <= 8:
+        p.error("--thresholds takes 1 to 8 thresholds")
+    if args.objects and not (0.0 < args.sal_factor <= 1.0 and args.sal_floor >= 0.0):
+        p.error("--sal-factor lies in (0, 1] and --sal-floor is >= 0")
     if args.variance and not args.prob:
         p.error("--variance needs --prob")
     if args.prob:
@@ -208,6 +228,13 @@ def main(argv=None):
                        device=args.device, mode=args.mode)
         write_scale_outputs(args.scale, ms)
         print(f"wrote {os.path.join(args.scale, 'metrics.json')} and the scale figure")
+    if args.objects:
+        frames = {}
+        mo = run_objects(preds, truth, args.crop_size, thresholds=tuple(args.thresholds), connectivity=args.connectivity,
+                         sal_factor=args.sal_factor, sal_floor=args.sal_floor, divide_by_3=True, device=args.device, mode=args.mode,
+                         frames_out=frames)
+        write_objects_outputs(args.objects, mo, frames)
+        print(f"wrote {os.path.join(args.objects, 'metrics.json')} and the SAL diagrams")
     paths = {name: path for name, path in args.method}
     if args.prob:
         variances = {}
