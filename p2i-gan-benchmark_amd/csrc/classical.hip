@@ -12,9 +12,7 @@
 namespace p2i {
 namespace {
 
-constexpr int MAX_LAGS = 32;
 constexpr int N_CAND = 25;        // range candidates a_c = w 2^((c - 6) / 3)
-constexpr int BIN_THREADS = 64;
 constexpr int RC = 8;             // right-hand sides fed from one covariance evaluation
 
 // ---- compaction: one workgroup per frame.  pix / z [F][cap] (entries past the count are zero), info[f] = count (may exceed cap:
@@ -62,21 +60,15 @@ __global__ __launch_bounds__(256) void krig_compact_kernel(const float* __restri
   }
 }
 
-// ---- empirical variogram.  Workgroup (chunk, frame) takes the rows i = chunk (mod chunks) of the frame's pairs i < j; every thread
-// keeps its own bins in LDS ([bin][thread]: no conflicts, no dynamic register indexing) and the threads are added in thread order.
+// ---- empirical variogram.  Workgroup (chunk, frame) takes the rows i = chunk (mod chunks) of the frame's pairs i < j into the
+// [bin][thread] image of krig_common.h.
 // part [F][chunks][n_lags][3] = (pairs, sum of (z_i - z_j)^2 / 2, sum of h)
 __global__ __launch_bounds__(BIN_THREADS) void krig_bins_kernel(const int* __restrict__ pix, const float* __restrict__ z,
                                                                 const int* __restrict__ counts, int cap, int n_lags, double lagw,
                                                                 double* __restrict__ part) {
-  __shared__ double sg[MAX_LAGS][BIN_THREADS];
-  __shared__ double sh[MAX_LAGS][BIN_THREADS];
-  __shared__ unsigned sc[MAX_LAGS][BIN_THREADS];
+  VarioBins bins = vario_bins_lds();
   const int f = blockIdx.y, ch = blockIdx.x, nch = gridDim.x, tid = threadIdx.x;
-  for (int k = 0; k < n_lags; ++k) {
-    sg[k][tid] = 0.0;
-    sh[k][tid] = 0.0;
-    sc[k][tid] = 0u;
-  }
+  bins.clear(n_lags);
   const int n = min(counts[f], cap);
   const int* px = pix + (size_t)f * cap;
   const float* zf = z + (size_t)f * cap;
@@ -87,29 +79,10 @@ __global__ __launch_bounds__(BIN_THREADS) void krig_bins_kernel(const int* __res
     for (int j = i + 1 + tid; j < n; j += BIN_THREADS) {
       const int pj = px[j];
       const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
-      const double h = sqrt((double)(dy * dy + dx * dx));
-      if (h < hmax) {
-        const int k = min((int)floor(h / lagw), n_lags - 1);
-        const double d = zi - (double)zf[j];
-        sg[k][tid] += 0.5 * (d * d);
-        sh[k][tid] += h;
-        sc[k][tid] += 1u;
-      }
+      bins.add(sqrt((double)(dy * dy + dx * dx)), hmax, lagw, n_lags, zi, zf + j);
     }
   }
-  __syncthreads();
-  for (int k = tid; k < n_lags; k += BIN_THREADS) {
-    double g = 0.0, h = 0.0, c = 0.0;
-    for (int t = 0; t < BIN_THREADS; ++t) {
-      g += sg[k][t];
-      h += sh[k][t];
-      c += (double)sc[k][t];
-    }
-    double* o = part + (((size_t)f * nch + ch) * n_lags + k) * 3;
-    o[0] = c;
-    o[1] = g;
-    o[2] = h;
-  }
+  bins.reduce(n_lags, part, (size_t)f * nch + ch);
 }
 
 // ---- fit: one workgroup per sample.  Adds the sample's partial bins in order, then thread c < 25 fits (nugget, psill) for the range
@@ -142,39 +115,11 @@ __global__ __launch_bounds__(64) void krig_fit_kernel(const double* __restrict__
   __syncthreads();
   if (tid < N_CAND) {
     const double a = lagw * exp2((double)(tid - 6) / 3.0);
-    double S0 = 0.0, S1 = 0.0, S2 = 0.0, T0 = 0.0, T1 = 0.0;
-    for (int k = 0; k < n_lags; ++k) {
-      if (!(sn[k] > 0.0)) continue;
-      const double r = shb[k] / a;
-      const double g = model == 0 ? 1.0 - exp(-r) : (r < 1.0 ? 1.5 * r - 0.5 * r * r * r : 1.0);
-      S0 += sn[k];
-      S1 += sn[k] * g;
-      S2 += sn[k] * g * g;
-      T0 += sn[k] * sgam[k];
-      T1 += sn[k] * g * sgam[k];
-    }
-    const double det = S0 * S2 - S1 * S1;
-    double nug = -1.0, ps = 0.0;
-    if (det > 1e-12 * S0 * S2) {
-      ps = (S0 * T1 - S1 * T0) / det;
-      nug = (T0 - ps * S1) / S0;
-    }
-    if (nug < 0.0) {
-      nug = 0.0;
-      ps = S2 > 0.0 ? T1 / S2 : 0.0;
-    }
-    double sse = 0.0;
-    for (int k = 0; k < n_lags; ++k) {
-      if (!(sn[k] > 0.0)) continue;
-      const double r = shb[k] / a;
-      const double g = model == 0 ? 1.0 - exp(-r) : (r < 1.0 ? 1.5 * r - 0.5 * r * r * r : 1.0);
-      const double e = sgam[k] - nug - ps * g;
-      sse += sn[k] * e * e;
-    }
-    c_ok[tid] = (S0 > 0.0 && ps > 0.0) ? 1 : 0;
-    c_sse[tid] = sse;
-    c_nug[tid] = nug;
-    c_ps[tid] = ps;
+    const FitCand r = vario_fit_candidate(sn, sgam, n_lags, [&](int k) { return g_d(shb[k] / a, model); });
+    c_ok[tid] = r.ok;
+    c_sse[tid] = r.sse;
+    c_nug[tid] = r.nug;
+    c_ps[tid] = r.ps;
   }
   __syncthreads();
   if (tid == 0) {
@@ -208,24 +153,14 @@ __global__ __launch_bounds__(64) void krig_fit_kernel(const double* __restrict__
 __global__ __launch_bounds__(256) void krig_build_kernel(const int* __restrict__ pix, const int* __restrict__ counts,
                                                          const float* __restrict__ params, int model, int f0, int R, int T, int cap, int np,
                                                          float* __restrict__ A) {
-  if (blockIdx.x > blockIdx.y) return;
   const int s = blockIdx.z, f = f0 + s * R, b = f / T;
-  const int n = min(counts[f], np);
   const float nug = params[b * 4], psill = params[b * 4 + 1], a = params[b * 4 + 2];
   const int* px = pix + (size_t)f * cap;
-  float* As = A + (size_t)s * np * np;
-  const int j = blockIdx.x * TS + (threadIdx.x & 31);
-#pragma unroll
-  for (int rr = 0; rr < 4; ++rr) {
-    const int i = blockIdx.y * TS + (threadIdx.x >> 5) + 8 * rr;
-    float v = i == j ? 1.f : 0.f;
-    if (i < n && j < n) {
-      const int pi = px[i], pj = px[j];
-      const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
-      v = cov_f(sqrtf((float)(dy * dy + dx * dx)), psill, a, model) + (i == j ? nug : 0.f);
-    }
-    As[(size_t)i * np + j] = v;
-  }
+  cov_tile_write(A + (size_t)s * np * np, min(counts[f], np), np, [&](int i, int j) {
+    const int pi = px[i], pj = px[j];
+    const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
+    return cov_f(sqrtf((float)(dy * dy + dx * dx)), psill, a, model) + (i == j ? nug : 0.f);
+  });
 }
 
 // ---- one panel of the right-looking Cholesky: factor the diagonal tile at k0 in LDS, then solve the rows below it against it (one
@@ -515,7 +450,7 @@ extern "C" int p2i_krig_compact(const float* masked, const float* mask, int B, i
   P2I_REQUIRE(masked && mask && pix && z && info, "null pointer");
   P2I_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE, "bad frame shape %d x %d x %d x %d", B, T, H, W);
   P2I_REQUIRE((long long)B * T <= 65535, "at most 65535 frames per call (got %lld)", (long long)B * T);
-  P2I_REQUIRE(cap > 0 && cap % TS == 0 && cap <= MAX_NP, "cap must be a multiple of %d, at most %d (got %d)", TS, MAX_NP, cap);
+  if (int rc = krig_cap_check(cap)) return rc;
   P2I_LAUNCH(krig_compact_kernel, dim3(B * T), dim3(256), 0, (hipStream_t)stream, masked, mask, B * T, T, H * W, W, cap, pix, z, info);
   return launch_status();
 }
@@ -524,7 +459,7 @@ extern "C" int p2i_krig_bins(const int* pix, const float* z, const int* counts, 
                              double* part, void* stream) {
   P2I_REQUIRE(pix && z && counts && part, "null pointer");
   P2I_REQUIRE(F > 0 && F <= 65535 && cap > 0 && chunks > 0 && chunks <= 1024, "bad variogram shape");
-  P2I_REQUIRE(n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "n_lags must be 1..%d with a positive lag width", MAX_LAGS);
+  if (int rc = krig_lags_check(n_lags, lag_width)) return rc;
   P2I_LAUNCH(krig_bins_kernel, dim3(chunks, F), dim3(BIN_THREADS), 0, (hipStream_t)stream, pix, z, counts, cap, n_lags, lag_width, part);
   return launch_status();
 }
@@ -533,7 +468,7 @@ extern "C" int p2i_krig_fit(const double* part, int B, int nparts, int n_lags, d
                             int* cand, float* params, void* stream) {
   P2I_REQUIRE(part && bins && fit && cand && params, "null pointer");
   P2I_REQUIRE(B > 0 && nparts > 0 && n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "bad fit shape");
-  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
+  if (int rc = krig_model_check(model)) return rc;
   P2I_LAUNCH(krig_fit_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, part, nparts, n_lags, lag_width, model, bins, fit, cand, params);
   return launch_status();
 }
@@ -541,7 +476,7 @@ extern "C" int p2i_krig_fit(const double* part, int B, int nparts, int n_lags, d
 extern "C" int p2i_krig_factor(const int* pix, const int* counts, const float* params, int model, int f0, int R, int T, int nsys, int np,
                                int cap, float* L, int* status, void* stream) {
   P2I_REQUIRE(pix && counts && params && L && status, "null pointer");
-  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
+  if (int rc = krig_model_check(model)) return rc;
   if (int rc = krig_sys_check(f0, R, T, nsys, np, cap)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int nt = np / TS;
@@ -564,8 +499,7 @@ extern "C" int p2i_krig_solve(const float* L, const float* z, const int* counts,
 extern "C" int p2i_krig_predict(const int* pix, const float* alpha, const float* mean, const int* counts, const float* params, int model,
                                 int f0, int R, int T, int nsets, int H, int W, int cap, float* out, void* stream) {
   P2I_REQUIRE(pix && alpha && mean && counts && params && out, "null pointer");
-  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
-  P2I_REQUIRE(H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE, "bad frame shape");
+  if (int rc = krig_frame_check(model, H, W)) return rc;
   if (int rc = krig_sys_check(f0, R, T, nsets, TS, cap)) return rc;
   const int HW = H * W;
   P2I_REQUIRE(ceil_div(R, RC) <= 65535, "too many frames per set");

@@ -1,5 +1,6 @@
-// What the classical baselines (classical.hip) and their uncertainty / cross-validation kernels (krig_uq.hip) share: the tile and
-// size limits, the covariance function, the fixed-tree fp64 block sum and the check of a system range.
+// What the kriging files (classical.hip, krig_uq.hip, stkrig.hip, stkrig_loso.hip, lagkrig.hip, lkrig.hip) share: the tile and size
+// limits, the covariance function and the space-time distances, the fixed-tree fp64 block sum, the variogram's bin image and fit
+// candidate, the covariance tile writer and the host-side checks.
 #pragma once
 #include "common.h"
 
@@ -10,6 +11,10 @@ constexpr int TS = 32;            // tile of the factorisation; systems are padd
 constexpr int PCHUNK = 128;       // gauges staged in LDS per predictor pass
 constexpr int MAX_NP = 4096;      // fp64 vector of the solve in LDS: 32 KiB
 constexpr int MAX_SIDE = 16384;   // squared pixel distances stay in int32
+constexpr int MAX_LAGS = 32;      // spatial variogram bins
+constexpr int MAX_TLAGS = 7;      // temporal lags u = 0 .. 7
+constexpr int BIN_THREADS = 64;   // threads of a variogram bins workgroup
+constexpr int FG = 8;             // target frames fed from one (pixel, point) pair of the space-time predictor
 
 __device__ __forceinline__ double block_sum_d(double v, double* red) {   // red: 256 doubles of LDS; fixed tree, 256 threads
   red[threadIdx.x] = v;
@@ -30,6 +35,11 @@ __device__ __forceinline__ float cov_f(float h, float psill, float a, int model)
   return r < 1.f ? psill * (1.f - (1.5f * r - 0.5f * r * r * r)) : 0.f;
 }
 
+// the variogram's g(r) in fp64, as the fits evaluate it
+__device__ __forceinline__ double g_d(double r, int model) {
+  return model == 0 ? 1.0 - exp(-r) : (r < 1.0 ? 1.5 * r - 0.5 * r * r * r : 1.0);
+}
+
 // the one space-time distance of stkrig.hip's build and predictor and of lkrig.hip (an explicit fma: all round alike, so a gauge is
 // reproduced in its own frame)
 __device__ __forceinline__ float st_dist(int d2, int dt, float k2) {
@@ -37,7 +47,7 @@ __device__ __forceinline__ float st_dist(int d2, int dt, float k2) {
   return sqrtf(fmaf(k2, ft * ft, (float)d2));
 }
 
-// the one Lagrangian distance of lagkrig.hip's build and predictor and of lkrig.hip's LAG kernels (lag_dist = sqrt of lag_d2): fdy,
+// the one Lagrangian distance of stkrig.hip's LAG build and predictor and of lkrig.hip's LAG kernels (lag_dist = sqrt of lag_d2): fdy,
 // fdx, ft are the integer differences (point a minus point b) as floats.  fmaf rounds -v ft + d once, and swapping a and b negates all
 // three exactly, so both orders give the same value bit for bit; at ft = 0 it is sqrt(dy^2 + dx^2), whatever v is.
 __device__ __forceinline__ float lag_d2(float fdy, float fdx, float ft, float vy, float vx, float k2) {
@@ -48,8 +58,130 @@ __device__ __forceinline__ float lag_dist(float fdy, float fdx, float ft, float 
   return sqrtf(lag_d2(fdy, fdx, ft, vy, vx, k2));
 }
 
+// ---- the variogram bins of one workgroup of BIN_THREADS threads: three [bin][thread] arrays in LDS (40 KiB; vario_bins_lds() below
+// hands them out).  Every thread keeps its own bins (no conflicts, no dynamic register indexing); reduce() adds the threads in
+// thread order.
+struct VarioBins {
+  double (*sg)[BIN_THREADS];
+  double (*sh)[BIN_THREADS];
+  unsigned (*sc)[BIN_THREADS];
+
+  __device__ __forceinline__ void clear(int n_lags) {
+    const int tid = threadIdx.x;
+    for (int k = 0; k < n_lags; ++k) {
+      sg[k][tid] = 0.0;
+      sh[k][tid] = 0.0;
+      sc[k][tid] = 0u;
+    }
+  }
+  // one pair at distance h (kept if below hmax = n_lags lagw) with the values zi and *zj; *zj is read only for a pair that is kept
+  __device__ __forceinline__ void add(double h, double hmax, double lagw, int n_lags, double zi, const float* __restrict__ zj) {
+    const int tid = threadIdx.x;
+    if (h < hmax) {
+      const int k = min((int)floor(h / lagw), n_lags - 1);
+      const double d = zi - (double)*zj;
+      sg[k][tid] += 0.5 * (d * d);
+      sh[k][tid] += h;
+      sc[k][tid] += 1u;
+    }
+  }
+  // row `row` of part [rows][n_lags][3] = (pairs, sum of (z_i - z_j)^2 / 2, sum of h)
+  __device__ __forceinline__ void reduce(int n_lags, double* __restrict__ part, size_t row) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < n_lags; k += BIN_THREADS) {
+      double g = 0.0, h = 0.0, c = 0.0;
+      for (int t = 0; t < BIN_THREADS; ++t) {
+        g += sg[k][t];
+        h += sh[k][t];
+        c += (double)sc[k][t];
+      }
+      double* o = part + (row * n_lags + k) * 3;
+      o[0] = c;
+      o[1] = g;
+      o[2] = h;
+    }
+  }
+};
+__device__ __forceinline__ VarioBins vario_bins_lds() {
+  __shared__ double sg[MAX_LAGS][BIN_THREADS];
+  __shared__ double sh[MAX_LAGS][BIN_THREADS];
+  __shared__ unsigned sc[MAX_LAGS][BIN_THREADS];
+  return VarioBins{sg, sh, sc};
+}
+
+// ---- one candidate of a variogram fit: (nugget, psill) of gamma = nugget + psill g by count-weighted least squares over the nb bins
+// with sn[e] > 0 pairs and mean semivariance sgam[e]; g_of(e) is the candidate's g at bin e.  A singular system or a negative
+// nugget falls back to nugget = 0.  ok: the candidate has pairs and a positive psill.
+struct FitCand {
+  int ok;
+  double nug, ps, sse;
+};
+template <class G>
+__device__ __forceinline__ FitCand vario_fit_candidate(const double* sn, const double* sgam, int nb, G g_of) {
+  double S0 = 0.0, S1 = 0.0, S2 = 0.0, T0 = 0.0, T1 = 0.0;
+  for (int e = 0; e < nb; ++e) {
+    if (!(sn[e] > 0.0)) continue;
+    const double g = g_of(e);
+    S0 += sn[e];
+    S1 += sn[e] * g;
+    S2 += sn[e] * g * g;
+    T0 += sn[e] * sgam[e];
+    T1 += sn[e] * g * sgam[e];
+  }
+  const double det = S0 * S2 - S1 * S1;
+  double nug = -1.0, ps = 0.0;
+  if (det > 1e-12 * S0 * S2) {
+    ps = (S0 * T1 - S1 * T0) / det;
+    nug = (T0 - ps * S1) / S0;
+  }
+  if (nug < 0.0) {
+    nug = 0.0;
+    ps = S2 > 0.0 ? T1 / S2 : 0.0;
+  }
+  double sse = 0.0;
+  for (int e = 0; e < nb; ++e) {
+    if (!(sn[e] > 0.0)) continue;
+    const double r = sgam[e] - nug - ps * g_of(e);
+    sse += sn[e] * r * r;
+  }
+  return FitCand{(S0 > 0.0 && ps > 0.0) ? 1 : 0, nug, ps, sse};
+}
+
+// ---- one 32 x 32 tile of a covariance matrix As [np][np] by 256 threads over a (tiles, tiles, systems) grid: lower tiles only,
+// entry(i, j) where both are below the n points of the system, identity on the padding
+template <class Entry>
+__device__ __forceinline__ void cov_tile_write(float* __restrict__ As, int n, int np, Entry entry) {
+  if (blockIdx.x > blockIdx.y) return;
+  const int j = blockIdx.x * TS + (threadIdx.x & 31);
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    const int i = blockIdx.y * TS + (threadIdx.x >> 5) + 8 * rr;
+    float v = i == j ? 1.f : 0.f;
+    if (i < n && j < n) v = entry(i, j);
+    As[(size_t)i * np + j] = v;
+  }
+}
+
 }  // namespace
 
+// ---- host-side checks shared by the entry points
+static inline int krig_model_check(int model) {
+  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
+  return P2I_OK;
+}
+static inline int krig_frame_check(int model, int H, int W) {          // a predictor's model and frame
+  if (int rc = krig_model_check(model)) return rc;
+  P2I_REQUIRE(H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE, "bad frame shape");
+  return P2I_OK;
+}
+static inline int krig_cap_check(int cap) {
+  P2I_REQUIRE(cap > 0 && cap % TS == 0 && cap <= MAX_NP, "cap must be a multiple of %d, at most %d (got %d)", TS, MAX_NP, cap);
+  return P2I_OK;
+}
+static inline int krig_lags_check(int n_lags, double lag_width) {
+  P2I_REQUIRE(n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "n_lags must be 1..%d with a positive lag width", MAX_LAGS);
+  return P2I_OK;
+}
 static inline int krig_sys_check(int f0, int R, int T, int nsys, int np, int cap) {
   P2I_REQUIRE(R > 0 && T > 0 && f0 >= 0 && nsys > 0 && nsys <= 65535, "bad system range");
   P2I_REQUIRE(R == 1 || (R == T && f0 % T == 0), "a system spans one frame or one whole sample");

@@ -4,24 +4,21 @@
 // [space-time variogram bins -> (kappa, range) candidate fit] -> covariance build + the shared tiled Cholesky (classical.hip) ->
 // p2i_krig_solve with the samples standing in for frames -> predictor.
 //
-// Number formats as in classical.hip: K, its factor and c0 are fp32; the predictor's sum over the points is fp64; the variogram is
-// fp64 throughout.  Every sum has a fixed order (no atomics).
+// LAG: the bins, build and predictor kernels in the frame that moves with the rain, one velocity v = (v_y, v_x)
+// in pixels per frame per sample (lagkrig.hip estimates it): d = sqrt((dy - v_y dt)^2 + (dx - v_x dt)^2 + kappa^2 dt^2).  The
+// p2i_lagkrig_bins / _factor / _predict entry points are the LAG = true instantiations; the gather, the fit, the Cholesky and the solve
+// do not see the distance and serve both.
+//
+// Number formats as in classical.hip: K, its factor and c0 are fp32 (the velocity enters them as an fp32 copy); the predictor's sum
+// over the points is fp64; the variogram is fp64 throughout.  Every sum has a fixed order (no atomics).
 #include "krig_common.h"
 
 namespace p2i {
 namespace {
 
-constexpr int MAX_LAGS = 32;
-constexpr int MAX_TLAGS = 7;      // temporal lags u = 0 .. 7
 constexpr int N_RANGE = 25;       // range candidates a_c = w 2^((c - 6) / 3)
 constexpr int N_KAPPA = 17;       // anisotropy candidates kappa_q = 2^((q - 6) / 2) px / frame
 constexpr int N_CAND = N_RANGE * N_KAPPA;
-constexpr int BIN_THREADS = 64;
-constexpr int FG = 8;             // target frames fed from one spatial d^2 of the predictor
-
-__device__ __forceinline__ double g_d(double r, int model) {
-  return model == 0 ? 1.0 - exp(-r) : (r < 1.0 ? 1.5 * r - 0.5 * r * r * r : 1.0);
-}
 
 // ---- gather: one workgroup per sample walks its T frames in order (the running offset is the exclusive scan of their counts) and
 // appends each frame's gauges; stpix / stt / stz [B][cap] are zero past the count, stcounts[b] = the sum (it may exceed cap: the host
@@ -55,21 +52,23 @@ __global__ __launch_bounds__(256) void stkrig_gather_kernel(const int* __restric
 
 // ---- space-time variogram bins.  Workgroup (chunk, u, sample) takes temporal lag u: for every frame t < T - u the rows i = chunk
 // (mod chunks) of frame t against the gauges j of frame t + u (j > i when u = 0, all j otherwise), binned by the SPATIAL distance.
-// One temporal lag per workgroup keeps krig_bins_kernel's [bin][thread] LDS image (40 KiB) at its size with all 32 lags.
+// One temporal lag per workgroup keeps the [bin][thread] LDS image of krig_common.h (40 KiB) at its size with all 32 lags.
+// LAG: the advected spatial distance h = |x_j - x_i - v u| in fp64, vel [B][2] fp64 (else null).  With v = 0 the radicand is the same
+// exact integer and every later operation and its order are the same, so the bins are the LAG = false bins bit for bit.
 // part [B][n_tlags + 1][chunks][n_lags][3] = (pairs, sum of (z_i - z_j)^2 / 2, sum of h)
+template <bool LAG>
 __global__ __launch_bounds__(BIN_THREADS) void stkrig_bins_kernel(const int* __restrict__ pix, const float* __restrict__ z,
-                                                                  const int* __restrict__ counts, int T, int cap, int n_lags,
-                                                                  double lagw, double* __restrict__ part) {
-  __shared__ double sg[MAX_LAGS][BIN_THREADS];
-  __shared__ double sh[MAX_LAGS][BIN_THREADS];
-  __shared__ unsigned sc[MAX_LAGS][BIN_THREADS];
+                                                                  const int* __restrict__ counts, const double* __restrict__ vel,
+                                                                  int T, int cap, int n_lags, double lagw, double* __restrict__ part) {
+  VarioBins bins = vario_bins_lds();
   const int b = blockIdx.z, u = blockIdx.y, nu = gridDim.y, ch = blockIdx.x, nch = gridDim.x, tid = threadIdx.x;
-  for (int k = 0; k < n_lags; ++k) {
-    sg[k][tid] = 0.0;
-    sh[k][tid] = 0.0;
-    sc[k][tid] = 0u;
-  }
+  bins.clear(n_lags);
   const double hmax = (double)n_lags * lagw;
+  double oy = 0.0, ox = 0.0;               // LAG: v u
+  if constexpr (LAG) {
+    oy = vel[b * 2] * (double)u;
+    ox = vel[b * 2 + 1] * (double)u;
+  }
   for (int t = 0; t + u < T; ++t) {
     const int fa = b * T + t, fb = fa + u;
     const int na = min(counts[fa], cap), nb = min(counts[fb], cap);
@@ -82,35 +81,23 @@ __global__ __launch_bounds__(BIN_THREADS) void stkrig_bins_kernel(const int* __r
       const double zi = (double)za[i];
       for (int j = (u == 0 ? i + 1 : 0) + tid; j < nb; j += BIN_THREADS) {
         const int pj = pb[j];
-        const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
-        const double h = sqrt((double)(dy * dy + dx * dx));
-        if (h < hmax) {
-          const int k = min((int)floor(h / lagw), n_lags - 1);
-          const double d = zi - (double)zb[j];
-          sg[k][tid] += 0.5 * (d * d);
-          sh[k][tid] += h;
-          sc[k][tid] += 1u;
+        double h;
+        if constexpr (LAG) {
+          const double ey = (double)((pj >> 16) - (pi >> 16)) - oy, ex = (double)((pj & 0xffff) - (pi & 0xffff)) - ox;
+          h = sqrt(ey * ey + ex * ex);
+        } else {
+          const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
+          h = sqrt((double)(dy * dy + dx * dx));
         }
+        bins.add(h, hmax, lagw, n_lags, zi, zb + j);
       }
     }
   }
-  __syncthreads();
-  for (int k = tid; k < n_lags; k += BIN_THREADS) {
-    double g = 0.0, h = 0.0, c = 0.0;
-    for (int t = 0; t < BIN_THREADS; ++t) {
-      g += sg[k][t];
-      h += sh[k][t];
-      c += (double)sc[k][t];
-    }
-    double* o = part + ((((size_t)b * nu + u) * nch + ch) * n_lags + k) * 3;
-    o[0] = c;
-    o[1] = g;
-    o[2] = h;
-  }
+  bins.reduce(n_lags, part, ((size_t)b * nu + u) * nch + ch);
 }
 
 // ---- fit: one workgroup per sample.  Adds the chunks' partial bins in order, then candidate q 25 + c fits (nugget, psill) of
-// gamma = nugget + psill g(sqrt(hbar^2 + (kappa_q u)^2) / a_c) by krig_fit_kernel's count-weighted normal equations and fallbacks;
+// gamma = nugget + psill g(sqrt(hbar^2 + (kappa_q u)^2) / a_c) by the count-weighted normal equations and fallbacks of krig_common.h;
 // thread 0 keeps the smallest SSE (lowest q 25 + c on a tie, so that bins of u = 0 alone give the spatial fit with q = 0).
 // bins [B][nu][n_lags][3], fit [B][5] = (nugget, psill, range, kappa, sse), cand [B] = q 25 + c (-1: degenerate), params [B][4] fp32 =
 // (nugget, psill, range, kappa) (a harmless (0, 1, w, 1) when degenerate)
@@ -142,40 +129,15 @@ __global__ __launch_bounds__(256) void stkrig_fit_kernel(const double* __restric
   for (int cd = tid; cd < N_CAND; cd += 256) {
     const double kap = exp2((double)(cd / N_RANGE - 6) * 0.5);
     const double a = lagw * exp2((double)(cd % N_RANGE - 6) / 3.0);
-    double S0 = 0.0, S1 = 0.0, S2 = 0.0, T0 = 0.0, T1 = 0.0;
-    for (int e = 0; e < nb; ++e) {
-      if (!(sn[e] > 0.0)) continue;
+    const FitCand r = vario_fit_candidate(sn, sgam, nb, [&](int e) {
       const double ku = kap * (double)(e / n_lags);
       const double d = e < n_lags ? shb[e] : sqrt(shb[e] * shb[e] + ku * ku);
-      const double g = g_d(d / a, model);
-      S0 += sn[e];
-      S1 += sn[e] * g;
-      S2 += sn[e] * g * g;
-      T0 += sn[e] * sgam[e];
-      T1 += sn[e] * g * sgam[e];
-    }
-    const double det = S0 * S2 - S1 * S1;
-    double nug = -1.0, ps = 0.0;
-    if (det > 1e-12 * S0 * S2) {
-      ps = (S0 * T1 - S1 * T0) / det;
-      nug = (T0 - ps * S1) / S0;
-    }
-    if (nug < 0.0) {
-      nug = 0.0;
-      ps = S2 > 0.0 ? T1 / S2 : 0.0;
-    }
-    double sse = 0.0;
-    for (int e = 0; e < nb; ++e) {
-      if (!(sn[e] > 0.0)) continue;
-      const double ku = kap * (double)(e / n_lags);
-      const double d = e < n_lags ? shb[e] : sqrt(shb[e] * shb[e] + ku * ku);
-      const double r = sgam[e] - nug - ps * g_d(d / a, model);
-      sse += sn[e] * r * r;
-    }
-    c_ok[cd] = (S0 > 0.0 && ps > 0.0) ? 1 : 0;
-    c_sse[cd] = sse;
-    c_nug[cd] = nug;
-    c_ps[cd] = ps;
+      return g_d(d / a, model);
+    });
+    c_ok[cd] = r.ok;
+    c_sse[cd] = r.sse;
+    c_nug[cd] = r.nug;
+    c_ps[cd] = r.ps;
   }
   __syncthreads();
   if (tid == 0) {
@@ -207,39 +169,46 @@ __global__ __launch_bounds__(256) void stkrig_fit_kernel(const double* __restric
   }
 }
 
-// ---- covariance matrix of the point set of sample s0 + s, lower tiles only; identity on the padding (krig_build_kernel's layout)
+// ---- covariance matrix of the point set of sample s0 + s (the tile writer of krig_common.h); LAG: lag_dist with velf [B][2] fp32
+// (else null) in place of st_dist
+template <bool LAG>
 __global__ __launch_bounds__(256) void stkrig_build_kernel(const int* __restrict__ stpix, const int* __restrict__ stt,
-                                                           const int* __restrict__ stcounts, const float* __restrict__ params, int model,
-                                                           int s0, int cap, int np, float* __restrict__ A) {
-  if (blockIdx.x > blockIdx.y) return;
+                                                           const int* __restrict__ stcounts, const float* __restrict__ params,
+                                                           const float* __restrict__ velf, int model, int s0, int cap, int np,
+                                                           float* __restrict__ A) {
   const int s = blockIdx.z, b = s0 + s;
-  const int n = min(stcounts[b], np);
   const float nug = params[b * 4], psill = params[b * 4 + 1], a = params[b * 4 + 2], kap = params[b * 4 + 3];
+  float vy = 0.f, vx = 0.f;
+  if constexpr (LAG) {
+    vy = velf[b * 2];
+    vx = velf[b * 2 + 1];
+  }
   const float k2 = kap * kap;
   const int* px = stpix + (size_t)b * cap;
   const int* pt = stt + (size_t)b * cap;
-  float* As = A + (size_t)s * np * np;
-  const int j = blockIdx.x * TS + (threadIdx.x & 31);
-#pragma unroll
-  for (int rr = 0; rr < 4; ++rr) {
-    const int i = blockIdx.y * TS + (threadIdx.x >> 5) + 8 * rr;
-    float v = i == j ? 1.f : 0.f;
-    if (i < n && j < n) {
-      const int pi = px[i], pj = px[j];
-      const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
-      v = cov_f(st_dist(dy * dy + dx * dx, pt[i] - pt[j], k2), psill, a, model) + (i == j ? nug : 0.f);
-    }
-    As[(size_t)i * np + j] = v;
-  }
+  cov_tile_write(A + (size_t)s * np * np, min(stcounts[b], np), np, [&](int i, int j) {
+    const int pi = px[i], pj = px[j];
+    const int dy = (pi >> 16) - (pj >> 16), dx = (pi & 0xffff) - (pj & 0xffff);
+    float h;
+    if constexpr (LAG)
+      h = lag_dist((float)dy, (float)dx, (float)(pt[i] - pt[j]), vy, vx, k2);
+    else
+      h = st_dist(dy * dy + dx * dx, pt[i] - pt[j], k2);
+    return cov_f(h, psill, a, model) + (i == j ? nug : 0.f);
+  });
 }
 
-// ---- predictor: out[b][t][p] = mean[b] + sum_i alpha[b][i] c0((t, p), i), one pixel per thread.  The points are staged in LDS PCHUNK
-// at a time; the integer spatial d^2 of a (pixel, point) pair is taken once and feeds the FG target frames of the group
-// (blockIdx.z), each adding kappa^2 (t - t_i)^2.  Spherical: a pair spatially beyond the range adds nothing to any frame.
+// ---- predictor: out[b][t][p] = mean[b] + sum_i alpha[b][i] c0((t, p), i), one pixel per thread, FG target frames per workgroup
+// (blockIdx.z), the points staged in LDS PCHUNK at a time.  The integer pixel differences of a (pixel, point) pair are taken once.
+// LAG = false: their d^2 feeds every frame of the group, each adding kappa^2 (t - t_i)^2; spherical: a pair spatially beyond the
+// range adds nothing to any frame.  LAG = true: each frame takes lag_d2; spherical: a (pixel, point, frame) triple whose squared
+// advected distance reaches range^2 has c0 = 0 and is skipped before the square root.
+template <bool LAG>
 __global__ __launch_bounds__(256) void stkrig_predict_kernel(const int* __restrict__ stpix, const int* __restrict__ stt,
                                                              const float* __restrict__ alpha, const float* __restrict__ mean,
                                                              const int* __restrict__ stcounts, const float* __restrict__ params,
-                                                             int model, int T, int W, int HW, int cap, float* __restrict__ out) {
+                                                             const float* __restrict__ velf, int model, int T, int W, int HW, int cap,
+                                                             float* __restrict__ out) {
   __shared__ int spix[PCHUNK];
   __shared__ int st[PCHUNK];
   __shared__ float sa[PCHUNK];
@@ -247,6 +216,11 @@ __global__ __launch_bounds__(256) void stkrig_predict_kernel(const int* __restri
   const int nr = min(FG, T - t0);
   const int n = min(stcounts[b], cap);
   const float nug = params[b * 4], psill = params[b * 4 + 1], a = params[b * 4 + 2], kap = params[b * 4 + 3];
+  float vy = 0.f, vx = 0.f;
+  if constexpr (LAG) {
+    vy = velf[b * 2];
+    vx = velf[b * 2 + 1];
+  }
   const float k2 = kap * kap;
   const float a2 = model == 1 ? a * a : 3.0e38f;
   const int p = blockIdx.x * 256 + threadIdx.x;
@@ -269,14 +243,24 @@ __global__ __launch_bounds__(256) void stkrig_predict_kernel(const int* __restri
       const int g = spix[i];
       const int dy = py - (g >> 16), dx = px - (g & 0xffff);
       const int d2 = dy * dy + dx * dx;
-      if ((float)d2 >= a2) continue;
+      if constexpr (!LAG)
+        if ((float)d2 >= a2) continue;
+      const float fdy = (float)dy, fdx = (float)dx;
       const int dt0 = t0 - st[i];
       const double ai = (double)sa[i];
 #pragma unroll
       for (int q = 0; q < FG; ++q) {
         const int dt = dt0 + q;
-        const float c0 = cov_f(st_dist(d2, dt, k2), psill, a, model) + ((d2 | dt) == 0 ? nug : 0.f);
-        acc[q] = fma(ai, (double)c0, acc[q]);
+        const auto add = [&](float h) {
+          const float c0 = cov_f(h, psill, a, model) + ((d2 | dt) == 0 ? nug : 0.f);
+          acc[q] = fma(ai, (double)c0, acc[q]);
+        };
+        if constexpr (LAG) {
+          const float s2 = lag_d2(fdy, fdx, (float)dt, vy, vx, k2);
+          if (s2 < a2) add(sqrtf(s2));
+        } else {
+          add(st_dist(d2, dt, k2));
+        }
       }
     }
   }
@@ -302,15 +286,57 @@ extern "C" int p2i_stkrig_gather(const int* pix, const float* z, const int* coun
   return launch_status();
 }
 
+namespace {
+
+// the three stages that see the distance: LAG = true takes the sample velocities (vel fp64 for the bins, velf fp32 for K and c0)
+template <bool LAG>
+int st_bins(const int* pix, const float* z, const int* counts, const double* vel, int B, int T, int cap, int chunks, int n_lags, int n_tlags,
+            double lag_width, double* part, void* stream) {
+  P2I_REQUIRE(pix && z && counts && part && (!LAG || vel), "null pointer");
+  P2I_REQUIRE(B > 0 && B <= 65535 && T > 0 && (long long)B * T <= 65535 && cap > 0 && chunks > 0 && chunks <= 1024, "bad variogram shape");
+  if (int rc = krig_lags_check(n_lags, lag_width)) return rc;
+  P2I_REQUIRE(n_tlags >= 0 && n_tlags <= MAX_TLAGS && n_tlags < T, "n_tlags must be 0..%d and below T", MAX_TLAGS);
+  P2I_LAUNCH(stkrig_bins_kernel<LAG>, dim3(chunks, n_tlags + 1, B), dim3(BIN_THREADS), 0, (hipStream_t)stream, pix, z, counts, vel, T, cap,
+             n_lags, lag_width, part);
+  return launch_status();
+}
+
+template <bool LAG>
+int st_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, const float* velf, int model, int s0, int nsys,
+              int np, int cap, float* L, int* status, void* stream) {
+  P2I_REQUIRE(stpix && stt && stcounts && params && L && status && (!LAG || velf), "null pointer");
+  if (int rc = krig_model_check(model)) return rc;
+  if (int rc = krig_sys_check(s0, 1, 1, nsys, np, cap)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int nt = np / TS;
+  P2I_LAUNCH(stkrig_build_kernel<LAG>, dim3(nt, nt, nsys), dim3(256), 0, s, stpix, stt, stcounts, params, velf, model, s0, cap, np, L);
+  krig_factor_tiles(L, nsys, np, status, s);
+  return launch_status();
+}
+
+template <bool LAG>
+int st_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts, const float* params,
+               const float* velf, int model, int B, int T, int H, int W, int cap, float* out, void* stream) {
+  P2I_REQUIRE(stpix && stt && alpha && mean && stcounts && params && out && (!LAG || velf), "null pointer");
+  if (int rc = krig_frame_check(model, H, W)) return rc;
+  P2I_REQUIRE(B > 0 && B <= 65535 && T > 0 && ceil_div(T, FG) <= 65535, "bad sample shape %d x %d", B, T);
+  if (int rc = krig_cap_check(cap)) return rc;
+  const int HW = H * W;
+  P2I_LAUNCH(stkrig_predict_kernel<LAG>, dim3(ceil_div(HW, 256), B, ceil_div(T, FG)), dim3(256), 0, (hipStream_t)stream, stpix, stt, alpha,
+             mean, stcounts, params, velf, model, T, W, HW, cap, out);
+  return launch_status();
+}
+
+}  // namespace
+
 extern "C" int p2i_stkrig_bins(const int* pix, const float* z, const int* counts, int B, int T, int cap, int chunks, int n_lags,
                                int n_tlags, double lag_width, double* part, void* stream) {
-  P2I_REQUIRE(pix && z && counts && part, "null pointer");
-  P2I_REQUIRE(B > 0 && B <= 65535 && T > 0 && (long long)B * T <= 65535 && cap > 0 && chunks > 0 && chunks <= 1024, "bad variogram shape");
-  P2I_REQUIRE(n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "n_lags must be 1..%d with a positive lag width", MAX_LAGS);
-  P2I_REQUIRE(n_tlags >= 0 && n_tlags <= MAX_TLAGS && n_tlags < T, "n_tlags must be 0..%d and below T", MAX_TLAGS);
-  P2I_LAUNCH(stkrig_bins_kernel, dim3(chunks, n_tlags + 1, B), dim3(BIN_THREADS), 0, (hipStream_t)stream, pix, z, counts, T, cap, n_lags,
-             lag_width, part);
-  return launch_status();
+  return st_bins<false>(pix, z, counts, nullptr, B, T, cap, chunks, n_lags, n_tlags, lag_width, part, stream);
+}
+
+extern "C" int p2i_lagkrig_bins(const int* pix, const float* z, const int* counts, const double* vel, int B, int T, int cap, int chunks,
+                                int n_lags, int n_tlags, double lag_width, double* part, void* stream) {
+  return st_bins<true>(pix, z, counts, vel, B, T, cap, chunks, n_lags, n_tlags, lag_width, part, stream);
 }
 
 extern "C" int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags, int n_tlags, double lag_width, int model, double* bins,
@@ -318,7 +344,7 @@ extern "C" int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags,
   P2I_REQUIRE(part && bins && fit && cand && params, "null pointer");
   P2I_REQUIRE(B > 0 && chunks > 0 && n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "bad fit shape");
   P2I_REQUIRE(n_tlags >= 0 && n_tlags <= MAX_TLAGS, "n_tlags must be 0..%d", MAX_TLAGS);
-  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
+  if (int rc = krig_model_check(model)) return rc;
   P2I_LAUNCH(stkrig_fit_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, part, n_tlags + 1, chunks, n_lags, lag_width, model, bins, fit,
              cand, params);
   return launch_status();
@@ -326,25 +352,21 @@ extern "C" int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags,
 
 extern "C" int p2i_stkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, int model, int s0, int nsys,
                                  int np, int cap, float* L, int* status, void* stream) {
-  P2I_REQUIRE(stpix && stt && stcounts && params && L && status, "null pointer");
-  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
-  if (int rc = krig_sys_check(s0, 1, 1, nsys, np, cap)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int nt = np / TS;
-  P2I_LAUNCH(stkrig_build_kernel, dim3(nt, nt, nsys), dim3(256), 0, s, stpix, stt, stcounts, params, model, s0, cap, np, L);
-  krig_factor_tiles(L, nsys, np, status, s);
-  return launch_status();
+  return st_factor<false>(stpix, stt, stcounts, params, nullptr, model, s0, nsys, np, cap, L, status, stream);
+}
+
+extern "C" int p2i_lagkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, const float* velf, int model,
+                                  int s0, int nsys, int np, int cap, float* L, int* status, void* stream) {
+  return st_factor<true>(stpix, stt, stcounts, params, velf, model, s0, nsys, np, cap, L, status, stream);
 }
 
 extern "C" int p2i_stkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
                                   const float* params, int model, int B, int T, int H, int W, int cap, float* out, void* stream) {
-  P2I_REQUIRE(stpix && stt && alpha && mean && stcounts && params && out, "null pointer");
-  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
-  P2I_REQUIRE(H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE, "bad frame shape");
-  P2I_REQUIRE(B > 0 && B <= 65535 && T > 0 && ceil_div(T, FG) <= 65535, "bad sample shape %d x %d", B, T);
-  P2I_REQUIRE(cap > 0 && cap % TS == 0 && cap <= MAX_NP, "cap must be a multiple of %d, at most %d (got %d)", TS, MAX_NP, cap);
-  const int HW = H * W;
-  P2I_LAUNCH(stkrig_predict_kernel, dim3(ceil_div(HW, 256), B, ceil_div(T, FG)), dim3(256), 0, (hipStream_t)stream, stpix, stt, alpha, mean,
-             stcounts, params, model, T, W, HW, cap, out);
-  return launch_status();
+  return st_predict<false>(stpix, stt, alpha, mean, stcounts, params, nullptr, model, B, T, H, W, cap, out, stream);
+}
+
+extern "C" int p2i_lagkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
+                                   const float* params, const float* velf, int model, int B, int T, int H, int W, int cap, float* out,
+                                   void* stream) {
+  return st_predict<true>(stpix, stt, alpha, mean, stcounts, params, velf, model, B, T, H, W, cap, out, stream);
 }

@@ -13,8 +13,9 @@ from all gauges of all frames of that sample, one system per sample, with a metr
 leave-one-site-out (csrc/stkrig_loso.hip): cross_validate_sites of all models predicts every point of a
 site (a gauge pixel in all the sample's frames) with the whole site left out.
 
-Lagrangian space-time kriging (csrc/lagkrig.hip): LagrangianKrigingGenerator measures the space-time distance
-in the frame that moves with the rain, with an advection velocity per sample that it estimates from the gauges.
+Lagrangian space-time kriging (csrc/lagkrig.hip for the velocity, csrc/stkrig.hip's kernels with it):
+LagrangianKrigingGenerator measures the space-time distance in the frame that moves with the rain, with an advection velocity per
+sample that it estimates from the gauges.
 
 Moving-neighbourhood space-time kriging (csrc/lkrig.hip): LocalKrigingGenerator predicts every target from its
 k nearest points in the space-time metric, from a small system of its own: no limit on the points of a sample, the kriging variance
@@ -308,6 +309,7 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         _st_variogram_config(self, config.get("model", {}))
         self.last_fit = None         # {"bins", "fit", "cand", "q", "c"} device tensors of the last call (fit=true)
         self.last_status = None      # per-sample int32 of the last call: 1 where the factorisation met a non-positive pivot
+        self._velf = None            # (B, 2) fp32 of the last call's velocities where _variogram fits them (LagrangianKrigingGenerator)
 
     def cross_validate(self, masked_frames, masks):
         raise RuntimeError(ST_NO_LOO)
@@ -333,12 +335,6 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         self.last_fit = {"bins": bins, "fit": fit, "cand": cand, "q": q, "c": cand - q * ops.KRIG_CANDIDATES}
         return cand, params
 
-    def _factor(self, stpix, stt, stinfo, params, s0, ns, np_, work, st):
-        ops.stkrig_factor(stpix, stt, stinfo, params, self.variogram_model, s0, ns, np_, work, st)
-
-    def _predict(self, stpix, stt, alpha, mean, stinfo, params, t, h, w):
-        return ops.stkrig_predict(stpix, stt, alpha, mean, stinfo, params, self.variogram_model, t, h, w)
-
     @torch.no_grad()
     def forward(self, masked_frames, masks):
         b, t, _, h, w = masked_frames.shape
@@ -354,9 +350,9 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         for s0 in range(0, b, per):
             ns = min(per, b - s0)
             st = status[s0:s0 + ns]
-            self._factor(stpix, stt, stinfo, params, s0, ns, np_, work, st)
+            ops.stkrig_factor(stpix, stt, stinfo, params, self.variogram_model, s0, ns, np_, work, st, self._velf)
             ops.krig_solve(work, stz, stinfo, st, cand, s0, 1, 1, ns, np_, alpha, mean)      # the samples stand in for frames
-        out = self._predict(stpix, stt, alpha, mean, stinfo, params, t, h, w)
+        out = ops.stkrig_predict(stpix, stt, alpha, mean, stinfo, params, self.variogram_model, t, h, w, self._velf)
         self.last_status = status
         failed = int(status.sum())
         if failed:
@@ -386,7 +382,7 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         for s0 in range(0, b, per):
             ns = min(per, b - s0)
             st = status[s0:s0 + ns]
-            self._factor(sites["stpix"], sites["stt"], sites["stinfo"], params, s0, ns, np_, work, st)
+            ops.stkrig_factor(sites["stpix"], sites["stt"], sites["stinfo"], params, self.variogram_model, s0, ns, np_, work, st, self._velf)
             sol = ops.krig_solve(work, sites["stz"], sites["stinfo"], st, cand, s0, 1, 1, ns, np_, alpha, mean)
             ops.krig_invert(work, ns, np_, winv)
             gram = ops.stkrig_site_gram(winv, ns, np_)
@@ -411,13 +407,13 @@ class LagrangianKrigingGenerator(SpaceTimeKrigingGenerator):
     def __init__(self, config: Dict[str, Any]):
         super().__init__(config)
         _advection_config(self, config.get("model", {}))
-        self._velf = None
 
     def cross_validate(self, masked_frames, masks):
         raise RuntimeError(LAG_NO_LOO)
 
     def _variogram(self, pix, z, info, b, t, h, w):
-        """(cand or None, params): the velocity first (kept for _factor and _predict), then the variogram on the advected distance."""
+        """(cand or None, params): the velocity first (kept in _velf for the factor and the predictor), then the variogram on the
+        advected distance."""
         lag_width = (min(h, w) / 2.0) / self.n_lags
         if self.fit_velocity:
             score, weight, support, vel, velf, vcand = ops.lagkrig_velocity(pix, z, info, b, t, min(self.adv_tlags, t - 1), self.nhalf, self.vstep,
@@ -438,12 +434,6 @@ class LagrangianKrigingGenerator(SpaceTimeKrigingGenerator):
             params = torch.tensor(self.fixed, dtype=torch.float32).repeat(b, 1).to(pix.device)
         self.last_fit = last
         return cand, params
-
-    def _factor(self, stpix, stt, stinfo, params, s0, ns, np_, work, st):
-        ops.lagkrig_factor(stpix, stt, stinfo, params, self._velf, self.variogram_model, s0, ns, np_, work, st)
-
-    def _predict(self, stpix, stt, alpha, mean, stinfo, params, t, h, w):
-        return ops.lagkrig_predict(stpix, stt, alpha, mean, stinfo, params, self._velf, self.variogram_model, t, h, w)
 
 
 class LocalKrigingGenerator(_ClassicalBase):

@@ -1659,64 +1659,83 @@ def stkrig_gather(pix, z, info, B, T, cap):
     return stpix, stt, stz, stinfo
 
 
-def stkrig_variogram(pix, z, info, B, T, n_lags, n_tlags, lag_width, model):
+def stkrig_variogram(pix, z, info, B, T, n_lags, n_tlags, lag_width, model, vel=None, who="stkrig_variogram"):
     """Space-time empirical variogram per sample and its (kappa, range) candidate fit, fp64 on the device.  Returns bins (B, n_tlags + 1,
     n_lags, 3) fp64 (pairs, sum of semivariances, sum of spatial distances), fit (B, 5) fp64 (nugget, psill, range, kappa, weighted
-    SSE), cand (B,) int32 (q * 25 + c; -1: degenerate sample) and params (B, 4) fp32 (nugget, psill, range, kappa)."""
+    SSE), cand (B,) int32 (q * 25 + c; -1: degenerate sample) and params (B, 4) fp32 (nugget, psill, range, kappa).
+    vel (B, 2) fp64 = (v_y, v_x) per sample: the pairs of temporal lag u are binned by the advected spatial distance |x_j - x_i - v u|
+    (DESIGN.md section 19); with vel = 0 the bins are those without it bit for bit.  who: the name that errors report."""
     lib = _hip.load()
     F = B * T
     cap = pix.shape[1]
-    _krig_t("stkrig_variogram", pix, torch.int32, (F, cap))
-    _krig_t("stkrig_variogram", z, torch.float32, (F, cap))
-    _krig_t("stkrig_variogram", info, torch.int32, (2 * F,))
+    _krig_t(who, pix, torch.int32, (F, cap))
+    _krig_t(who, z, torch.float32, (F, cap))
+    _krig_t(who, info, torch.int32, (2 * F,))
+    if vel is not None:
+        _lag_vel(who, vel, torch.float64, B)
     if not (1 <= n_lags <= KRIG_MAX_LAGS) or not lag_width > 0:
-        raise ValueError(f"stkrig_variogram: n_lags must be 1..{KRIG_MAX_LAGS} and the lag width positive")
+        raise ValueError(f"{who}: n_lags must be 1..{KRIG_MAX_LAGS} and the lag width positive")
     if not (0 <= n_tlags <= STKRIG_MAX_TLAGS and n_tlags < T):
-        raise ValueError(f"stkrig_variogram: n_tlags must be 0..{STKRIG_MAX_TLAGS} and below T = {T} (got {n_tlags})")
+        raise ValueError(f"{who}: n_tlags must be 0..{STKRIG_MAX_TLAGS} and below T = {T} (got {n_tlags})")
     dev = pix.device
     part = torch.empty(B, n_tlags + 1, STKRIG_BIN_CHUNKS, n_lags, 3, device=dev, dtype=torch.float64)
     bins = torch.empty(B, n_tlags + 1, n_lags, 3, device=dev, dtype=torch.float64)
     fit = torch.empty(B, 5, device=dev, dtype=torch.float64)
     cand = torch.empty(B, device=dev, dtype=torch.int32)
     params = torch.empty(B, 4, device=dev, dtype=torch.float32)
-    _hip.check(lib.p2i_stkrig_bins(_ptr(pix), _ptr(z), _ptr(info), B, T, cap, STKRIG_BIN_CHUNKS, n_lags, n_tlags, float(lag_width),
-                                   _ptr(part), _stream()), "p2i_stkrig_bins")
+    if vel is not None:
+        _hip.check(lib.p2i_lagkrig_bins(_ptr(pix), _ptr(z), _ptr(info), _ptr(vel), B, T, cap, STKRIG_BIN_CHUNKS, n_lags, n_tlags,
+                                        float(lag_width), _ptr(part), _stream()), "p2i_lagkrig_bins")
+    else:
+        _hip.check(lib.p2i_stkrig_bins(_ptr(pix), _ptr(z), _ptr(info), B, T, cap, STKRIG_BIN_CHUNKS, n_lags, n_tlags, float(lag_width),
+                                       _ptr(part), _stream()), "p2i_stkrig_bins")
     _hip.check(lib.p2i_stkrig_fit(_ptr(part), B, STKRIG_BIN_CHUNKS, n_lags, n_tlags, float(lag_width), int(model), _ptr(bins), _ptr(fit),
                                   _ptr(cand), _ptr(params), _stream()), "p2i_stkrig_fit")
     return bins, fit, cand, params
 
 
-def stkrig_factor(stpix, stt, stinfo, params, model, s0, nsys, np_, L, status):
+def stkrig_factor(stpix, stt, stinfo, params, model, s0, nsys, np_, L, status, velf=None, who="stkrig_factor"):
     """Cholesky factors of the space-time covariance systems of samples s0 .. s0 + nsys - 1 into L (>= nsys * np_ * np_ fp32); status
-    (nsys,) int32 (zeroed by the caller) is set where a pivot was not positive."""
+    (nsys,) int32 (zeroed by the caller) is set where a pivot was not positive.  velf (B, 2) fp32 = (v_y, v_x) per sample: the
+    Lagrangian distance.  who: the name that errors report."""
     lib = _hip.load()
     B, cap = stpix.shape
-    _krig_t("stkrig_factor", stpix, torch.int32)
-    _krig_t("stkrig_factor", stt, torch.int32, (B, cap))
-    _krig_t("stkrig_factor", stinfo, torch.int32, (2 * B,))
-    _krig_t("stkrig_factor", params, torch.float32, (B, 4))
-    _krig_t("stkrig_factor", L, torch.float32)
-    _krig_t("stkrig_factor", status, torch.int32, (nsys,))
-    _krig_sys("stkrig_factor", s0, 1, 1, nsys, B, np_, cap)
+    _krig_t(who, stpix, torch.int32)
+    _krig_t(who, stt, torch.int32, (B, cap))
+    _krig_t(who, stinfo, torch.int32, (2 * B,))
+    _krig_t(who, params, torch.float32, (B, 4))
+    _krig_t(who, L, torch.float32)
+    _krig_t(who, status, torch.int32, (nsys,))
+    _krig_sys(who, s0, 1, 1, nsys, B, np_, cap)
     if L.numel() < nsys * np_ * np_:
-        raise RuntimeError("stkrig_factor: factor workspace too small")
+        raise RuntimeError(f"{who}: factor workspace too small")
+    if velf is not None:
+        _lag_vel(who, velf, torch.float32, B)
+        _hip.check(lib.p2i_lagkrig_factor(_ptr(stpix), _ptr(stt), _ptr(stinfo), _ptr(params), _ptr(velf), int(model), s0, nsys, np_, cap,
+                                          _ptr(L), _ptr(status), _stream()), "p2i_lagkrig_factor")
+        return
     _hip.check(lib.p2i_stkrig_factor(_ptr(stpix), _ptr(stt), _ptr(stinfo), _ptr(params), int(model), s0, nsys, np_, cap, _ptr(L),
                                      _ptr(status), _stream()), "p2i_stkrig_factor")
 
 
-def stkrig_predict(stpix, stt, alpha, mean, stinfo, params, model, T, H, W):
-    """out (B, T, H*W) = mean_b + sum_i alpha_i c0((t, p), i) over the sample's space-time points."""
+def stkrig_predict(stpix, stt, alpha, mean, stinfo, params, model, T, H, W, velf=None, who="stkrig_predict"):
+    """out (B, T, H*W) = mean_b + sum_i alpha_i c0((t, p), i) over the sample's space-time points.  velf, who: as in stkrig_factor."""
     lib = _hip.load()
     B, cap = stpix.shape
-    _krig_t("stkrig_predict", stpix, torch.int32)
-    _krig_t("stkrig_predict", stt, torch.int32, (B, cap))
-    _krig_t("stkrig_predict", alpha, torch.float32, (B, cap))
-    _krig_t("stkrig_predict", mean, torch.float32, (B,))
-    _krig_t("stkrig_predict", stinfo, torch.int32, (2 * B,))
-    _krig_t("stkrig_predict", params, torch.float32, (B, 4))
+    _krig_t(who, stpix, torch.int32)
+    _krig_t(who, stt, torch.int32, (B, cap))
+    _krig_t(who, alpha, torch.float32, (B, cap))
+    _krig_t(who, mean, torch.float32, (B,))
+    _krig_t(who, stinfo, torch.int32, (2 * B,))
+    _krig_t(who, params, torch.float32, (B, 4))
     if T < 1 or H < 1 or W < 1 or cap % KRIG_TILE or cap > KRIG_MAX_CAP:
-        raise RuntimeError(f"stkrig_predict: bad shape T {T}, {H} x {W}, cap {cap}")
+        raise RuntimeError(f"{who}: bad shape T {T}, {H} x {W}, cap {cap}")
     out = torch.empty(B, T, H * W, device=stpix.device, dtype=torch.float32)
+    if velf is not None:
+        _lag_vel(who, velf, torch.float32, B)
+        _hip.check(lib.p2i_lagkrig_predict(_ptr(stpix), _ptr(stt), _ptr(alpha), _ptr(mean), _ptr(stinfo), _ptr(params), _ptr(velf),
+                                           int(model), B, T, H, W, cap, _ptr(out), _stream()), "p2i_lagkrig_predict")
+        return out
     _hip.check(lib.p2i_stkrig_predict(_ptr(stpix), _ptr(stt), _ptr(alpha), _ptr(mean), _ptr(stinfo), _ptr(params), int(model), B, T, H, W,
                                       cap, _ptr(out), _stream()), "p2i_stkrig_predict")
     return out
@@ -1794,14 +1813,14 @@ def stkrig_loso(gram, sol, alpha, sites, status, cand, s0, T, nsys, np_, pred, v
                                    _ptr(pred), _ptr(var), _stream()), "p2i_stkrig_loso")
 
 
-# ---- Lagrangian space-time kriging (csrc/lagkrig.hip)
+# ---- Lagrangian space-time kriging (the velocity: csrc/lagkrig.hip; the rest: csrc/stkrig.hip with a velocity)
 LAGKRIG_MAX_VHALF = 16                                   # candidate velocities (i s, j s), |i|, |j| <= nhalf <= 16
 LAGKRIG_MAX_CANDIDATES = (2 * LAGKRIG_MAX_VHALF + 1) ** 2   # 33 x 33 = 1089: the largest grid the velocity kernels take
 LAGKRIG_VEL_CHUNKS = 32                                  # workgroups per (sample, candidate block) of the velocity pass (fixed: added in order)
 
 
 def _lag_vel(who, vel, dtype, B):
-    _krig_t(who, vel, dtype, (B, 2))
+    return _krig_t(who, vel, dtype, (B, 2))
 
 
 def lagkrig_velocity(pix, z, info, B, T, n_tlags, nhalf, vstep, bandwidth):
@@ -1840,67 +1859,21 @@ def lagkrig_velocity(pix, z, info, B, T, n_tlags, nhalf, vstep, bandwidth):
 
 
 def lagkrig_variogram(pix, z, info, vel, B, T, n_lags, n_tlags, lag_width, model):
-    """stkrig_variogram with the pairs of temporal lag u binned by the advected spatial distance |x_j - x_i - v u|, vel (B, 2) fp64; the
-    fit is p2i_stkrig_fit's, unchanged.  With vel = 0 the bins are stkrig_variogram's bit for bit."""
-    lib = _hip.load()
-    F = B * T
-    cap = pix.shape[1]
-    _krig_t("lagkrig_variogram", pix, torch.int32, (F, cap))
-    _krig_t("lagkrig_variogram", z, torch.float32, (F, cap))
-    _krig_t("lagkrig_variogram", info, torch.int32, (2 * F,))
-    _lag_vel("lagkrig_variogram", vel, torch.float64, B)
-    if not (1 <= n_lags <= KRIG_MAX_LAGS) or not lag_width > 0:
-        raise ValueError(f"lagkrig_variogram: n_lags must be 1..{KRIG_MAX_LAGS} and the lag width positive")
-    if not (0 <= n_tlags <= STKRIG_MAX_TLAGS and n_tlags < T):
-        raise ValueError(f"lagkrig_variogram: n_tlags must be 0..{STKRIG_MAX_TLAGS} and below T = {T} (got {n_tlags})")
-    dev = pix.device
-    part = torch.empty(B, n_tlags + 1, STKRIG_BIN_CHUNKS, n_lags, 3, device=dev, dtype=torch.float64)
-    bins = torch.empty(B, n_tlags + 1, n_lags, 3, device=dev, dtype=torch.float64)
-    fit = torch.empty(B, 5, device=dev, dtype=torch.float64)
-    cand = torch.empty(B, device=dev, dtype=torch.int32)
-    params = torch.empty(B, 4, device=dev, dtype=torch.float32)
-    _hip.check(lib.p2i_lagkrig_bins(_ptr(pix), _ptr(z), _ptr(info), _ptr(vel), B, T, cap, STKRIG_BIN_CHUNKS, n_lags, n_tlags,
-                                    float(lag_width), _ptr(part), _stream()), "p2i_lagkrig_bins")
-    _hip.check(lib.p2i_stkrig_fit(_ptr(part), B, STKRIG_BIN_CHUNKS, n_lags, n_tlags, float(lag_width), int(model), _ptr(bins), _ptr(fit),
-                                  _ptr(cand), _ptr(params), _stream()), "p2i_stkrig_fit")
-    return bins, fit, cand, params
+    """stkrig_variogram with a velocity that must be there: vel (B, 2) fp64."""
+    return stkrig_variogram(pix, z, info, B, T, n_lags, n_tlags, lag_width, model, _lag_vel("lagkrig_variogram", vel, torch.float64, B),
+                            "lagkrig_variogram")
 
 
 def lagkrig_factor(stpix, stt, stinfo, params, velf, model, s0, nsys, np_, L, status):
-    """stkrig_factor with the Lagrangian distance; velf (B, 2) fp32 = (v_y, v_x) per sample."""
-    lib = _hip.load()
-    B, cap = stpix.shape
-    _krig_t("lagkrig_factor", stpix, torch.int32)
-    _krig_t("lagkrig_factor", stt, torch.int32, (B, cap))
-    _krig_t("lagkrig_factor", stinfo, torch.int32, (2 * B,))
-    _krig_t("lagkrig_factor", params, torch.float32, (B, 4))
-    _lag_vel("lagkrig_factor", velf, torch.float32, B)
-    _krig_t("lagkrig_factor", L, torch.float32)
-    _krig_t("lagkrig_factor", status, torch.int32, (nsys,))
-    _krig_sys("lagkrig_factor", s0, 1, 1, nsys, B, np_, cap)
-    if L.numel() < nsys * np_ * np_:
-        raise RuntimeError("lagkrig_factor: factor workspace too small")
-    _hip.check(lib.p2i_lagkrig_factor(_ptr(stpix), _ptr(stt), _ptr(stinfo), _ptr(params), _ptr(velf), int(model), s0, nsys, np_, cap, _ptr(L),
-                                      _ptr(status), _stream()), "p2i_lagkrig_factor")
+    """stkrig_factor with a velocity that must be there: velf (B, 2) fp32 = (v_y, v_x) per sample."""
+    return stkrig_factor(stpix, stt, stinfo, params, model, s0, nsys, np_, L, status,
+                         _lag_vel("lagkrig_factor", velf, torch.float32, stpix.shape[0]), "lagkrig_factor")
 
 
 def lagkrig_predict(stpix, stt, alpha, mean, stinfo, params, velf, model, T, H, W):
-    """out (B, T, H*W) = mean_b + sum_i alpha_i c0((t, p), i) over the sample's space-time points, Lagrangian distance."""
-    lib = _hip.load()
-    B, cap = stpix.shape
-    _krig_t("lagkrig_predict", stpix, torch.int32)
-    _krig_t("lagkrig_predict", stt, torch.int32, (B, cap))
-    _krig_t("lagkrig_predict", alpha, torch.float32, (B, cap))
-    _krig_t("lagkrig_predict", mean, torch.float32, (B,))
-    _krig_t("lagkrig_predict", stinfo, torch.int32, (2 * B,))
-    _krig_t("lagkrig_predict", params, torch.float32, (B, 4))
-    _lag_vel("lagkrig_predict", velf, torch.float32, B)
-    if T < 1 or H < 1 or W < 1 or cap % KRIG_TILE or cap > KRIG_MAX_CAP:
-        raise RuntimeError(f"lagkrig_predict: bad shape T {T}, {H} x {W}, cap {cap}")
-    out = torch.empty(B, T, H * W, device=stpix.device, dtype=torch.float32)
-    _hip.check(lib.p2i_lagkrig_predict(_ptr(stpix), _ptr(stt), _ptr(alpha), _ptr(mean), _ptr(stinfo), _ptr(params), _ptr(velf), int(model), B,
-                                       T, H, W, cap, _ptr(out), _stream()), "p2i_lagkrig_predict")
-    return out
+    """stkrig_predict with a velocity that must be there: out (B, T, H*W), Lagrangian distance."""
+    return stkrig_predict(stpix, stt, alpha, mean, stinfo, params, model, T, H, W,
+                          _lag_vel("lagkrig_predict", velf, torch.float32, stpix.shape[0]), "lagkrig_predict")
 
 
 # ---- moving-neighbourhood space-time kriging (csrc/lkrig.hip, DESIGN.md section 20)
