@@ -249,12 +249,24 @@ int p2i_idw_fwd(const float* vals_src, const float* mask, const float* grid_x, c
  * Round 4: pass 2 first DECIDES a listed voxel from the points within its (now known) 4th distance D, met in index order -- the
  * reference's heap holds the four smallest values seen so far, so the first four points with d <= D stay unless a point with d < D
  * follows them (idw.hip, IDW_CONSIDER_FIXED) -- and only the voxels where one does (~7 %) take the full replay, from a second list.
+ * Those shares are a gauge mask's.  Whole-frame masks (the loader's nowcasting / fi / stin types) tie far more often -- the two
+ * in-frame neighbours of a voxel are equidistant -- and the same passes carry them; read from the device counters on an MI355X
+ * (tests/test_idw_regimes_gpu.py, shares of Q = T*H*W voxels as listed / left to the full replay): 16 x 32 x 32 nowcasting keep 4
+ * 0.497 / 0.127, fi stride 6 0.532 / 0.181, fi stride 3 0.506 / 0.139, stin keep 4 block 4 0.235 / 0.095; 16 x 48 x 48 fi stride 3
+ * 0.558 / 0.189.  The replay's grid covers Q / 8 voxels per sample and loops beyond that.
  *   amb int32 [B*(2Q+2+ceil(Q/256))]: per sample the number of listed voxels, the lists of pass 1's workgroups (256 slots each) and
  *       their lengths / prefix sums; behind the B samples' blocks the second list, per sample [count, voxels ...] (work buffer). */
 int p2i_idw_fwd_ws(const float* vals_src, const float* mask, const float* grid_x, const float* grid_y,
                    const float* grid_z, float* out, int32_t* pt_pos, int32_t* pt_count, int32_t* frame_count,
                    int32_t* row_start, float* pt_xyzn, int32_t* sel_idx, float* sel_w, int32_t* amb, int B, int T, int H, int W,
                    float tau, void* stream);
+/* Backward: dvals_src[pt_pos[j]] = sum over the voxels that selected point j of dout * sel_w, every other entry 0 (values enter the
+ * output linearly; the weights are data).  Float atomics by default; with a scratch registered through p2i_det_workspace the same
+ * scatter in 64-bit fixed point, scaled from the largest FINITE |dout| of the call: bit-equal from run to run and exact up to the
+ * conversion of each product and one final rounding.  In both modes a NaN / Inf in dout arrives as NaN / Inf at the four selected
+ * points of its voxel, as the reference's autograd gives it, and changes no other entry (in fixed point such products bypass the
+ * integer accumulators as float atomics; finite inputs are untouched by that path, bit for bit).
+ * Pinned by tests/test_idw_regimes_gpu.py. */
 int p2i_idw_bwd(const float* dout, const int32_t* pt_pos, const int32_t* pt_count, const int32_t* sel_idx,
                 const float* sel_w, float* dvals_src, int B, int T, int H, int W, void* stream);
 

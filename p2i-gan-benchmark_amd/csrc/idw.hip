@@ -666,12 +666,21 @@ __global__ __launch_bounds__(256) void idw_bwd_kernel(const float* __restrict__ 
 // is associative, so the order in which the atomics arrive no longer matters.  scale = 2^k with k chosen from max |dout| of the call
 // (idw_absmax_kernel: an integer max over the float bit patterns, order-free too) so that the sum of all 4 Q contributions of a
 // sample stays below 2^61: a contribution g * w (rounded to float as before) times 2^k is converted exactly unless it is smaller than
-// 2^-41 of the largest -- more accurate than the float atomics it replaces.  ctl[0] = bits of max |dout|, ctl[1] = ticket of the
-// last kernel.
+// 2^-41 of the largest -- more accurate than the float atomics it replaces.  ctl[0] = bits of max FINITE |dout|, ctl[1] = ticket of
+// the last kernel.
+// Non-finite gradients (NaN, +-Inf) have no fixed-point image (__float2ll_rn(NaN) is 0, and an Inf as the maximum would scale every
+// finite contribution of the batch to 0), and the reference's autograd hands them to the four selected points of their voxel.  They
+// stay out of the maximum, and their products g * w (the weights are finite, in (0, 1]) go as float atomics into the points' slots
+// of dvals, which the caller has zeroed; the finish kernel writes fixed + slot.  NaN and Inf absorb whatever is added to them in
+// whatever order, and a slot nobody touched holds +0, so finite inputs give the bits they gave without this path.
+__device__ __forceinline__ bool idw_non_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 __global__ __launch_bounds__(256) void idw_absmax_kernel(const float* __restrict__ dout, size_t n, unsigned* ctl) {
   __shared__ float red[16];
   float m = 0.f;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(dout[i]));
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float v = dout[i];
+    if (!idw_non_finite(v)) m = fmaxf(m, fabsf(v));
+  }
   m = block_max(m, red);
   if (threadIdx.x == 0 && m > 0.f) atomicMax(ctl, __float_as_uint(m));
 }
@@ -683,9 +692,10 @@ __device__ __forceinline__ int idw_fix_exp(unsigned maxbits, int Q) {
   int k = 61 - (e + 1) - lq;
   return k > 120 ? 120 : (k < -120 ? -120 : k);
 }
-__global__ __launch_bounds__(256) void idw_bwd_fix_kernel(const float* __restrict__ dout, const int32_t* __restrict__ pt_count,
-                                                         const int32_t* __restrict__ sel_idx, const float* __restrict__ sel_w,
-                                                         unsigned long long* acc64, const unsigned* __restrict__ ctl, int Q, int chunk) {
+__global__ __launch_bounds__(256) void idw_bwd_fix_kernel(const float* __restrict__ dout, const int32_t* __restrict__ pt_pos,
+                                                         const int32_t* __restrict__ pt_count, const int32_t* __restrict__ sel_idx,
+                                                         const float* __restrict__ sel_w, unsigned long long* acc64, float* dvals,
+                                                         const unsigned* __restrict__ ctl, int Q, int chunk) {
   extern __shared__ unsigned long long accl[];          // [IDW_LDS_PTS]
   const int b = blockIdx.y;
   const int N = pt_count[b];
@@ -704,6 +714,13 @@ __global__ __launch_bounds__(256) void idw_bwd_fix_kernel(const float* __restric
     if (g == 0.f) continue;
     const int4 id = *reinterpret_cast<const int4*>(sel_idx + i * 4);
     const float4 w = *reinterpret_cast<const float4*>(sel_w + i * 4);
+    if (idw_non_finite(g)) {                             // (rare: a diverging run) straight into the zeroed output slots, see above
+      const int32_t* pp = pt_pos + (size_t)b * Q;
+      float* dv = dvals + (size_t)b * Q;
+      atomicAdd(dv + pp[id.x], g * w.x); atomicAdd(dv + pp[id.y], g * w.y);
+      atomicAdd(dv + pp[id.z], g * w.z); atomicAdd(dv + pp[id.w], g * w.w);
+      continue;
+    }
     const unsigned long long c0 = (unsigned long long)__float2ll_rn(g * w.x * S), c1 = (unsigned long long)__float2ll_rn(g * w.y * S);
     const unsigned long long c2 = (unsigned long long)__float2ll_rn(g * w.z * S), c3 = (unsigned long long)__float2ll_rn(g * w.w * S);
     if (use_lds) {
@@ -720,7 +737,7 @@ __global__ __launch_bounds__(256) void idw_bwd_fix_kernel(const float* __restric
     }
   }
 }
-// d vals[pt_pos[j]] = fixed-point sum / scale
+// d vals[pt_pos[j]] = fixed-point sum / scale + what the slot holds: +0, or the point's non-finite contributions
 __global__ __launch_bounds__(256) void idw_bwd_fix_finish_kernel(const unsigned long long* __restrict__ acc64, const int32_t* __restrict__ pt_pos,
                                                                 const int32_t* __restrict__ pt_count, float* dvals, unsigned* ctl, int Q) {
   const int b = blockIdx.y;
@@ -730,7 +747,8 @@ __global__ __launch_bounds__(256) void idw_bwd_fix_finish_kernel(const unsigned 
     const int32_t* pp = pt_pos + (size_t)b * Q;
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < N; j += gridDim.x * blockDim.x) {
       const long long v = (long long)acc64[(size_t)b * Q + j];
-      dvals[(size_t)b * Q + pp[j]] = (float)ldexp((double)v, -k);
+      float* slot = dvals + (size_t)b * Q + pp[j];
+      *slot = __fadd_rn((float)ldexp((double)v, -k), *slot);
     }
   }
   (void)ctl;
@@ -823,8 +841,8 @@ extern "C" int p2i_idw_bwd(const float* dout, const int32_t* pt_pos, const int32
       attr_set = true;
     }
     P2I_LAUNCH(idw_absmax_kernel, dim3(256), dim3(256), 0, s, dout, total, ctl);
-    P2I_LAUNCH(idw_bwd_fix_kernel, dim3(ceil_div(Q, chunk), B), dim3(256), sizeof(unsigned long long) * IDW_LDS_PTS, s, dout, pt_count, sel_idx,
-               sel_w, acc64, ctl, Q, chunk);
+    P2I_LAUNCH(idw_bwd_fix_kernel, dim3(ceil_div(Q, chunk), B), dim3(256), sizeof(unsigned long long) * IDW_LDS_PTS, s, dout, pt_pos, pt_count,
+               sel_idx, sel_w, acc64, dvals_src, ctl, Q, chunk);
     P2I_LAUNCH(idw_bwd_fix_finish_kernel, dim3(16, B), dim3(256), 0, s, acc64, pt_pos, pt_count, dvals_src, ctl, Q);
     return launch_status();
   }
