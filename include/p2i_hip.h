@@ -309,7 +309,8 @@ int p2i_gan_loss(const float* logits_a, const float* logits_b, int n, int loss_t
 /* ---- the reference's other objectives (losses.py:51-162).  fp32, contiguous.  Scalar results (out1) are sums of
  * workgroup partials added in a fixed order: they need the scratch of p2i_det_workspace.  gout: DEVICE pointer to the upstream
  * gradient of a scalar result.  Every backward pass is a gather (no atomics); max-pool ties go to the first maximal element of
- * the window in raster order (torch's rule).
+ * the window in raster order, and a window that holds a NaN pools to NaN with its LAST NaN in raster order as the argmax (both
+ * torch's rules; the 5/4/2 pool and the shock loss's pool alike).
  * p2i_loss_transform_fwd / _bwd: y = 0.036 * 10^((x*255/3)*0.0625) (losses.py:51-53; NOT metric.py's transform); dx = dy * dy/dx.
  * p2i_fdiff_fwd / _bwd: out[b][t] = x[b][t+1] - x[b][t] over dim 1 of [B][T][inner] (losses.py:83-85); T >= 2.
  * p2i_wl1_fwd / _bwd: mean(w(target) * |pred - target|), w = 0.5 exp(5.14 min(target, 0.7)) + 0.12 (losses.py:56-65); sign(0) = 0.
@@ -327,7 +328,7 @@ int p2i_gan_loss(const float* logits_a, const float* logits_b, int n, int loss_t
  * p2i_shock_loss_fwd / _bwd: out [N][Hp - 2 border][Wp - 2 border] = relu(|s(P truth)| - |s(P pred)|) cropped by border, P =
  *   max_pool2d(pool, pool), Hp = H / pool (floor) (losses.py:140-162); one kernel, no map is written.  _bwd: dpred from dout in two
  *   kernels (map-gradient coefficients, then the transposed-stencil gather routed through the pool argmax); relu'(0) = 0,
- *   sign(0) = 0; scratch: 3 N Hp Wp floats. */
+ *   sign(0) = 0; a NaN difference stays NaN in out and passes the relu's gradient (torch); scratch: 3 N Hp Wp floats. */
 int p2i_loss_transform_fwd(const float* x, float* y, int64_t n, void* stream);
 int p2i_loss_transform_bwd(const float* x, const float* dy, float* dx, int64_t n, void* stream);
 int p2i_fdiff_fwd(const float* x, float* out, int B, int T, int64_t inner, void* stream);

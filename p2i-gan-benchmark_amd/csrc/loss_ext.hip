@@ -3,7 +3,8 @@
 // difference (:83-85), MaxPool2d(5, 4, 2) (:88-91), temporal-difference matching (:94-109), the shock map (:112-137) and the shock
 // loss (:140-162), each with its gradient.  All tensors fp32 and contiguous.  Every cross-workgroup sum is a set of workgroup
 // partials added in workgroup order by det_reduce (common.h); every backward pass is a gather with a fixed order of additions, so
-// two runs give the same bits.  Max-pool ties: the first maximal element of the window in raster order takes the gradient (torch).
+// two runs give the same bits.  Max-pool ties: the first maximal element of the window in raster order takes the gradient; a NaN
+// wins every scan (`v > m || v != v`), so a window that holds one pools to NaN and its last NaN in raster order is the argmax (torch).
 #include "common.h"
 
 namespace p2i {
@@ -166,7 +167,8 @@ __global__ __launch_bounds__(256) void kl_bwd_kernel(const float* __restrict__ p
 }
 
 // ---------------------------------------------------------------- MaxPool2d(5, stride 4, padding 2) (losses.py:88-91)
-// max over the valid part of the window (padding is -inf) and the plane index h*W + w of its first maximal element in raster order
+// max over the valid part of the window (padding is -inf) and the plane index h*W + w of its first maximal element in raster order;
+// a NaN replaces whatever the scan holds, so the window's last NaN wins
 __device__ __forceinline__ float spool_window(const float* __restrict__ plane, int H, int W, int oh, int ow, int& arg) {
   const int h0 = max(4 * oh - 2, 0), h1 = min(4 * oh + 2, H - 1), w0 = max(4 * ow - 2, 0), w1 = min(4 * ow + 2, W - 1);
   float m = plane[h0 * W + w0];
@@ -174,7 +176,7 @@ __device__ __forceinline__ float spool_window(const float* __restrict__ plane, i
   for (int h = h0; h <= h1; ++h)
     for (int w = w0; w <= w1; ++w) {
       const float v = plane[h * W + w];
-      if (v > m) { m = v; arg = h * W + w; }
+      if (v > m || v != v) { m = v; arg = h * W + w; }
     }
   return m;
 }
@@ -249,7 +251,10 @@ __device__ __forceinline__ float pooled_at(const float* __restrict__ plane, int 
   const float* p = plane + (size_t)(py * pool) * W + px * pool;
   float m = p[0];
   for (int i = 0; i < pool; ++i)
-    for (int j = 0; j < pool; ++j) m = fmaxf(m, p[i * W + j]);
+    for (int j = 0; j < pool; ++j) {
+      const float v = p[i * W + j];
+      if (v > m || v != v) m = v;                                              // fmaxf would drop a NaN
+    }
   return m;
 }
 // stage the (STH + 2) x (STW + 2) pooled, reflect-padded tile whose interior starts at map pixel (ty0, tx0)
@@ -304,10 +309,10 @@ __global__ __launch_bounds__(STW * STH) void shock_tile_kernel(const float* __re
     const bool inside = cy >= 0 && cy < Hc && cx >= 0 && cx < Wc;
     const size_t c = ((size_t)n * Hc + cy) * Wc + cx;
     if constexpr (MODE == 1) {
-      if (inside) out[c] = d > 0.f ? d : 0.f;                                  // relu
+      if (inside) out[c] = d <= 0.f ? 0.f : d;                                 // relu; a NaN difference stays NaN
       return;
     }
-    if (inside && d > 0.f) g = sx > 0.f ? -dout[c] : (sx < 0.f ? dout[c] : 0.f);     // relu'(0) = 0, sign(0) = 0
+    if (inside && !(d <= 0.f)) g = sx > 0.f ? -dout[c] : (sx < 0.f ? dout[c] : 0.f);  // relu'(0) = 0, relu'(NaN) = 1, sign(0) = 0
   } else {
     g = dout[q];
   }
@@ -318,7 +323,7 @@ __global__ __launch_bounds__(STW * STH) void shock_tile_kernel(const float* __re
   out[2 * np + q] = g * a.beta * (1.f - th * th) * gr;
 }
 
-// Backward gather, thread = one stored pixel (h, w).  When pooled, only the first maximal element of its pool window goes on (the
+// Backward gather, thread = one stored pixel (h, w).  When pooled, only the first maximal element (or last NaN) of its pool window goes on (the
 // others and the dropped trailing rows / columns get 0).  Its map pixel p then adds, over every padded position i that the reflect
 // padding maps to p (p itself, -1 for p == 1, n for p == n - 2) and every tap d, the coefficient of the output pixel i - d times the
 // tap's weight: the transposed stencils, border rows and columns counted as often as the padding repeats them.
@@ -337,7 +342,7 @@ __global__ __launch_bounds__(256) void shock_gather_kernel(const float* __restri
       for (int r = 0; r < a.pool; ++r)
         for (int c = 0; c < a.pool; ++c) {
           const float v = p[r * a.W + c];
-          if (v > m) { m = v; arg = r * a.pool + c; }
+          if (v > m || v != v) { m = v; arg = r * a.pool + c; }
         }
       mine = arg == (h - py * a.pool) * a.pool + (w - px * a.pool);
     }

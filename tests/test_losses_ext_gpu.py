@@ -133,8 +133,10 @@ def test_spatial_pool_three_dims_and_negative_planes(dev, L):
     ("compute_forward_difference", [(3, 5, 7, 4)]), ("kl_divergence", [(8, 15, 72, 64)] * 2), ("softmax_temperature", [(8, 15, 72, 64)]),
     ("spatial_pool", [(4, 5, 70, 66)]), ("temporal_difference_matching_loss", [(4, 5, 70, 66), (4, 5, 70, 66), (4, 6, 70, 66)])])
 def test_larger_shapes_match_the_restatement(dev, L, name, shapes):
-    """Sizes at which the vectorised path, more than one workgroup per reduction and the grid-stride loops run; the expected
-    values are the float64 restatement on the same float32 inputs."""
+    """Sizes at which the vectorised path and more than one workgroup per reduction run; the expected values are the float64
+    restatement on the same float32 inputs.  Only the reductions' loops, whose grids are sized for four trips, go round again
+    here: the largest tensor has 589,824 floats and one trip of the element-wise kernels covers 4,194,304 (1,048,576 on the
+    scalar path), of the pool kernels 2,097,152 and of tdm_fwd 131,072 positions.  test_loss_ext_edges_gpu.py has those sizes."""
     gen = torch.Generator().manual_seed(len(name))
     if name == "kl_divergence":
         inputs = [R.softmax_temperature(0.2 * torch.randn(s, generator=gen, dtype=torch.float64), R.TEMP).float().numpy() for s in shapes]
