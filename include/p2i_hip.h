@@ -159,6 +159,10 @@ int p2i_wgrad_last_plan(int* out4);
  *   adds the `+ x.repeat_interleave(rep, dim=1)` skip of p2igan.py:79 as a centre-tap identity; that skip exists for a 3x3
  *   layer with I * rep == O only, anything else is refused with P2I_EINVAL.
  * p2i_doconv_fold_bwd: dW, dD from the packed weight gradient produced by p2i_conv_wgrad.
+ * The library holds ONE kernel family per operation, the batched one (blockIdx.z = layer): every single-layer entry point of this
+ *   and the next section is a batch of one of the same kernels, so a layer gives the same bits alone as in a list -- except the
+ *   spectral-norm unpack's dot product, whose number of partial sums follows the largest layer of the batch.  3x3, groups 1, no
+ *   identity skip, O and I multiples of 32 take the tile kernels of the *_batched fold; every other layer the per-layer generic ones.
  * Every fold, pack, unpack and spectral-norm entry point of this and the next section, and the weight split p2i_x6_split /
  * p2i_x6_split_batched, are swept over their shapes -- exactly, on integer-valued inputs, wherever the operation allows it -- by
  * tests/test_weightprep_gpu.py (cases: tests/weightprep_cases.py).
@@ -204,12 +208,14 @@ int p2i_weight_unpack_grad_batched_acc(const float* const* dwp_f, const int* O, 
  * One power iteration of torch.nn.utils.spectral_norm (call sites layer.py:402-407,
  * p2igan.py:141): v <- normalize(W^T u), u <- normalize(W v), sigma = u^T W v, eps 1e-12.
  * training==0: sigma only from the stored u, v.  W is (O, K) row-major.  scratch >= O + K + 4 floats.
+ * A batch of one of p2i_spectral_norm_batched's kernels: no sum crosses a workgroup, nothing is atomic and nothing needs zeroing,
+ * so two calls on the same inputs give the same bits.
  */
 int p2i_spectral_norm(const float* w, int O, int K, float* u, float* v, int training, float* sigma,
                       float* scratch, void* stream);
 
 /* The same power iteration for n <= 16 layers at once (blockIdx.z = layer): 4 launches for the whole discriminator instead
- * of 4-5 per layer.  Arrays of n HOST entries holding device pointers / sizes; scratch[i] >= O[i] + K[i] + 4 floats. */
+ * of 4 per layer.  Arrays of n HOST entries holding device pointers / sizes; scratch[i] >= O[i] + K[i] + 4 floats. */
 int p2i_spectral_norm_batched(const float* const* w, const int* O, const int* K, float* const* u, float* const* v,
                               int training, float* const* sigma, float* const* scratch, float* const* u_snap,
                               float* const* v_snap, int n, void* stream);   /* u_snap / v_snap (may be NULL): copies of the

@@ -16,9 +16,10 @@ void set_error(const char* fmt, ...) {
 
 __device__ __forceinline__ int pad32(int v) { return (v + 31) & ~31; }
 
-// ---- DO-Conv fold.  One thread per flat pair q = o'*I + i of the (O/g, I, 9) view; a block owns a
-// 16 (o') x 16 (i) tile so that BOTH packed layouts are written in 64-B runs (wp_f: o contiguous,
-// wp_d: cin contiguous) via an LDS transpose.  groups == 1 only; grouped / 1x1 layers use the simple kernel.
+// ---- DO-Conv fold.  Every kernel family of this file exists ONCE, in its batched form (blockIdx.z = layer, pointer tables in
+// the kernel argument): the kernels are launch-latency bound, and a single-layer entry point is a batch of one.  The tile kernels
+// take 3x3, groups 1, no identity skip, O and I multiples of 32; grouped / 1x1 / padded / identity-skip layers use the simple
+// per-layer kernels (fold_fwd_kernel, fold_bwd_w_kernel, fold_bwd_d_kernel).
 constexpr int FOLD_MAX_LAYERS = 16;
 // same-shape layers of one launch (blockIdx.z = layer): the fold kernels are launch-latency bound (8-12 us each)
 struct FoldBatch {
@@ -30,45 +31,10 @@ struct FoldBatch {
   const float* g[FOLD_MAX_LAYERS];    // bwd: packed weight gradient
 };
 
-__device__ __forceinline__ void fold_fwd_tile_body(const float* __restrict__ W, const float* __restrict__ D,
-                                                   const float* __restrict__ Dd, int O, int I, float* wp_f, float* wp_d) {
-  __shared__ float tile[9][16][17];
-  const int ti = threadIdx.x & 15, to = threadIdx.x >> 4;     // thread computes (o' = o0+to, i = i0+ti): W reads 36-B runs
-  const int o0 = blockIdx.y * 16, i0 = blockIdx.x * 16;
-  const int o = o0 + to, i = i0 + ti;
-  if (o < O && i < I) {
-    float w[9];
-    const float* wq = W + ((size_t)o * I + i) * 9;
-#pragma unroll
-    for (int s2 = 0; s2 < 9; ++s2) w[s2] = wq[s2];
-    const float* d = D + (size_t)i * 81;
-    const float* dd = Dd + (size_t)i * 81;
-#pragma unroll
-    for (int m = 0; m < 9; ++m) {
-      float acc = 0.f;
-#pragma unroll
-      for (int s2 = 0; s2 < 9; ++s2) acc += (d[m * 9 + s2] + dd[m * 9 + s2]) * w[s2];
-      tile[m][to][ti] = acc;
-    }
-  }
-  __syncthreads();
-  const int a = threadIdx.x & 15, b = threadIdx.x >> 4;
-#pragma unroll
-  for (int m = 0; m < 9; ++m) {
-    // wp_f[m][i][o]: lanes along o
-    if (i0 + b < I && o0 + a < O) wp_f[((size_t)m * I + i0 + b) * O + o0 + a] = tile[m][a][b];
-    // wp_d[m][o][i]: lanes along i
-    if (wp_d && o0 + b < O && i0 + a < I) wp_d[((size_t)m * O + o0 + b) * I + i0 + a] = tile[m][b][a];
-  }
-}
-__global__ __launch_bounds__(256) void fold_fwd_tile_kernel(const float* __restrict__ W, const float* __restrict__ D,
-                                                           const float* __restrict__ Dd, int O, int I, float* wp_f, float* wp_d) {
-  fold_fwd_tile_body(W, D, Dd, O, I, wp_f, wp_d);
-}
-// 32 x 32 (o, i) tile for O, I multiples of 32 (the batched path).  The 16 x 16 body above reads D + D_diag (2 x 81 floats) from
-// global memory in EVERY (o, i) thread -- 162 of its 171 loads -- and stores 64-byte runs: 130 us for the eight 512-channel layers,
-// 1.7 TB/s.  Here D + D_diag of the tile's 32 input channels is summed once into LDS (conflict-free: 81 floats per channel, odd
-// pitch), a thread folds FOUR output channels against one read of it, and both packed layouts are written in full 128-byte lines.
+// 32 x 32 (o, i) tile for O, I multiples of 32.  D + D_diag of the tile's 32 input channels is summed once into LDS (conflict-free:
+// 81 floats per channel, odd pitch), a thread folds FOUR output channels against one read of it, and both packed layouts (wp_f: o
+// contiguous, wp_d: cin contiguous) are written in full 128-byte lines through an LDS transpose.  (A thread per (o, i) pair that
+// reads D + D_diag from global memory -- 162 of its 171 loads -- took 130 us for the eight 512-channel layers, 1.7 TB/s.)
 __global__ __launch_bounds__(256) void fold_fwd_tile_batched_kernel(const FoldBatch fb, int O, int I) {
   __shared__ float dsum[32][81];
   __shared__ float tile[9][32][33];
@@ -144,39 +110,9 @@ __global__ void fold_fwd_kernel(const float* __restrict__ W, const float* __rest
   }
 }
 
-// dW[o'][i][s] = sum_m dDoW[o',i,m] (D+Dd)[i][m][s] for groups == 1: dDoW tile gathered with o-contiguous reads
-__device__ __forceinline__ void fold_bwd_w_tile_body(const float* __restrict__ dwp, const float* __restrict__ D,
-                                                     const float* __restrict__ Dd, int O, int I, float* dW) {
-  __shared__ float tile[9][16][17];
-  const int o0 = blockIdx.y * 16, i0 = blockIdx.x * 16;
-  const int a = threadIdx.x & 15, b = threadIdx.x >> 4;
-#pragma unroll
-  for (int m = 0; m < 9; ++m)
-    tile[m][a][b] = (i0 + b < I && o0 + a < O) ? dwp[((size_t)m * I + i0 + b) * O + o0 + a] : 0.f;    // [m][o][i]
-  __syncthreads();
-  const int ti = threadIdx.x & 15, to = threadIdx.x >> 4;
-  const int o = o0 + to, i = i0 + ti;
-  if (o >= O || i >= I) return;
-  float g[9];
-#pragma unroll
-  for (int m = 0; m < 9; ++m) g[m] = tile[m][to][ti];
-  const float* d = D + (size_t)i * 81;
-  const float* dd = Dd + (size_t)i * 81;
-  float* out = dW + ((size_t)o * I + i) * 9;
-#pragma unroll
-  for (int s2 = 0; s2 < 9; ++s2) {
-    float acc = 0.f;
-#pragma unroll
-    for (int m = 0; m < 9; ++m) acc += g[m] * (d[m * 9 + s2] + dd[m * 9 + s2]);
-    out[s2] = acc;
-  }
-}
-__global__ __launch_bounds__(256) void fold_bwd_w_tile_kernel(const float* __restrict__ dwp, const float* __restrict__ D,
-                                                             const float* __restrict__ Dd, int O, int I, float* dW) {
-  fold_bwd_w_tile_body(dwp, D, Dd, O, I, dW);
-}
-// 32 x 32 (o, i) tile, D + D_diag of the tile's input channels summed once into LDS, four output channels per thread (same
-// restructuring as fold_fwd_tile_batched_kernel; O, I multiples of 32)
+// dW[o'][i][s] = sum_m dDoW[o',i,m] (D+Dd)[i][m][s] for groups == 1: 32 x 32 (o, i) tile gathered with o-contiguous reads, D + D_diag
+// of the tile's input channels summed once into LDS, four output channels per thread (the layout of fold_fwd_tile_batched_kernel;
+// O, I multiples of 32)
 __global__ __launch_bounds__(256) void fold_bwd_w_tile_batched_kernel(const FoldBatch fb, int O, int I) {
   __shared__ float dsum[32][81];
   __shared__ float tile[9][32][33];
@@ -242,8 +178,8 @@ __global__ void fold_bwd_w_kernel(const float* __restrict__ dwp, const float* __
 
 // dD[i][m][s] = sum_{o'} dDoW[o',i,m] * W[o',i,s]; block per i, threads stride over o' (coalesced dDoW reads),
 // 81 register accumulators per thread, wave shuffle + LDS combine
-__device__ __forceinline__ void fold_bwd_d_body(const float* __restrict__ dwp, const float* __restrict__ W, int O, int I,
-                                                int groups, float* dD) {
+__global__ __launch_bounds__(256) void fold_bwd_d_kernel(const float* __restrict__ dwp, const float* __restrict__ W, int O, int I,
+                                                        int groups, float* dD) {
   __shared__ float part[4][81];
   const int i = blockIdx.x;
   const int Ig = I / groups, Og = O / groups, Opad = pad32(O);
@@ -280,11 +216,7 @@ __device__ __forceinline__ void fold_bwd_d_body(const float* __restrict__ dwp, c
   __syncthreads();
   if (threadIdx.x < 81) dD[i * 81 + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
 }
-__global__ __launch_bounds__(256) void fold_bwd_d_kernel(const float* __restrict__ dwp, const float* __restrict__ W, int O, int I,
-                                                        int groups, float* dD) {
-  fold_bwd_d_body(dwp, W, O, I, groups, dD);
-}
-// dD for 32 input channels per block (O, I multiples of 32, groups 1).  The per-channel body above reads W in 36-byte pieces one
+// dD for 32 input channels per block (O, I multiples of 32, groups 1).  The per-channel kernel above reads W in 36-byte pieces one
 // cache line apart (104 us for the eight 512-channel layers).  Here dDoW tiles [9][32 i][32 o] are staged through LDS with lanes
 // along o, W is read with lanes along i (both coalesced), thread = (input channel, one of 8 output-channel slices) keeps the 81
 // sums in registers over all of O, and the 8 slices are combined through LDS at the end.
@@ -339,90 +271,62 @@ __global__ __launch_bounds__(256) void fold_bwd_d_batched_kernel(const FoldBatch
   }
 }
 
-// ---- plain (O, I, NT) <-> packed
-__global__ void pack_kernel(const float* __restrict__ w, int O, int I, int NT, const float* div_ptr, float* wp_f, float* wp_d) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= O * I * NT) return;
-  const int tap = idx % NT, i = (idx / NT) % I, o = idx / (NT * I);
-  float v = w[idx];
-  if (div_ptr) v = v / *div_ptr;
-  if (wp_f) wp_f[((size_t)tap * I + i) * pad32(O) + o] = v;
-  if (wp_d) wp_d[((size_t)tap * O + o) * pad32(I) + i] = v;
+// ---- plain (O, I, NT) <-> packed, up to 16 layers of DIFFERENT shapes in one launch each (blockIdx.z = layer): the discriminator's
+//      ten spectral-norm layers are packed once per forward and unpacked once per backward
+constexpr int PACK_MAX_LAYERS = 16;
+struct PackBatch {
+  const float* w[PACK_MAX_LAYERS];
+  const float* div[PACK_MAX_LAYERS];
+  float* f[PACK_MAX_LAYERS];
+  float* d[PACK_MAX_LAYERS];
+  const float* g[PACK_MAX_LAYERS];     // unpack: packed gradient
+  const float* u[PACK_MAX_LAYERS];
+  const float* v[PACK_MAX_LAYERS];
+  float* dot[PACK_MAX_LAYERS];
+  int O[PACK_MAX_LAYERS], I[PACK_MAX_LAYERS], NT[PACK_MAX_LAYERS];
+  int accumulate;                      // unpack: dw += instead of dw =
+};
+__global__ void pack_batched_kernel(const PackBatch b) {
+  const int L = blockIdx.z, O = b.O[L], I = b.I[L], NT = b.NT[L];
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < O * I * NT; idx += gridDim.x * blockDim.x) {
+    const int tap = idx % NT, i = (idx / NT) % I, o = idx / (NT * I);
+    float v = b.w[L][idx];
+    if (b.div[L]) v = v / *b.div[L];
+    if (b.f[L]) b.f[L][((size_t)tap * I + i) * pad32(O) + o] = v;
+    if (b.d[L]) b.d[L][((size_t)tap * O + o) * pad32(I) + i] = v;
+  }
 }
-
-__global__ void unpack_dot_kernel(const float* __restrict__ dwp, const float* __restrict__ w, int O, int I, int NT, float* dot, DetWs ws) {
+__global__ void unpack_dot_batched_kernel(const PackBatch b, DetWs ws) {
   __shared__ float red[16];
+  const int L = blockIdx.z, O = b.O[L], I = b.I[L], NT = b.NT[L];
+  if (!b.div[L]) return;                              // plain unpack: no sigma term
   float acc = 0.f;
   const int n = O * I * NT;
   for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += gridDim.x * blockDim.x) {
     const int tap = idx % NT, i = (idx / NT) % I, o = idx / (NT * I);
-    acc += dwp[((size_t)tap * I + i) * pad32(O) + o] * w[idx];
+    acc += b.g[L][((size_t)tap * I + i) * pad32(O) + o] * b.w[L][idx];
   }
   acc = block_sum(acc, red);
-  if (ws.part) {
-    if (threadIdx.x == 0) ws.part[blockIdx.x] = acc;
+  if (ws.part) {                                       // ws.part = [layers][gridDim.x]: added in workgroup order by det_reduce
+    if (threadIdx.x == 0) ws.part[(size_t)L * gridDim.x + blockIdx.x] = acc;
     return;
   }
-  if (threadIdx.x == 0) atomicAdd(dot, acc);
+  if (threadIdx.x == 0 && acc != 0.f) atomicAdd(b.dot[L], acc);
 }
-
-__global__ void unpack_kernel(const float* __restrict__ dwp, int O, int I, int NT, const float* sigma_ptr, const float* dot,
-                              const float* __restrict__ u, const float* __restrict__ v, float* dw) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= O * I * NT) return;
-  const int tap = idx % NT, i = (idx / NT) % I, o = idx / (NT * I);
-  float g = dwp[((size_t)tap * I + i) * pad32(O) + o];
-  if (sigma_ptr) {
-    const float sg = *sigma_ptr;
-    g = g / sg - (*dot / (sg * sg)) * u[o] * v[i * NT + tap];
-  }
-  dw[idx] = g;
-}
-
-// ---- spectral norm
-// t[k] += sum_{o in slab} W[o][k] u[o]; grid (K/64, O/32); block 256 = 64 columns x 4 row groups (t zeroed by caller)
-__global__ __launch_bounds__(256) void sn_wtu_kernel(const float* __restrict__ w, const float* __restrict__ u, int O, int K, float* t) {
-  __shared__ float part[4][64];
-  const int col = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int k = blockIdx.x * 64 + col, o0 = blockIdx.y * 32 + rg * 8;
-  float acc = 0.f;
-  if (k < K) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const int o = o0 + r;
-      if (o < O) acc += w[(size_t)o * K + k] * u[o];
+__global__ void unpack_batched_kernel(const PackBatch b) {
+  const int L = blockIdx.z, O = b.O[L], I = b.I[L], NT = b.NT[L];
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < O * I * NT; idx += gridDim.x * blockDim.x) {
+    const int tap = idx % NT, i = (idx / NT) % I, o = idx / (NT * I);
+    float g = b.g[L][((size_t)tap * I + i) * pad32(O) + o];
+    if (b.div[L]) {
+      const float sg = *b.div[L];
+      g = g / sg - (*b.dot[L] / (sg * sg)) * b.u[L][o] * b.v[L][i * NT + tap];
     }
-  }
-  part[rg][col] = acc;
-  __syncthreads();
-  if (rg == 0 && k < K) atomicAdd(t + k, part[0][col] + part[1][col] + part[2][col] + part[3][col]);
-}
-__global__ void sn_wv_kernel(const float* __restrict__ w, const float* __restrict__ v, int O, int K, float* s) {
-  const int o = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (o >= O) return;
-  float acc = 0.f;
-  for (int k = lane; k < K; k += 64) acc += w[(size_t)o * K + k] * v[k];
-  acc = wave_sum(acc);
-  if (lane == 0) s[o] = acc;
-}
-// out = in / max(||in||, eps); optionally sigma = sum(out * in) (= u^T W v with the NEW u)
-__global__ void sn_normalize_kernel(const float* __restrict__ in, int n, float* out, float* sigma) {
-  __shared__ float red[16];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) acc += in[i] * in[i];
-  const float nrm = fmaxf(sqrtf(block_sum(acc, red)), 1e-12f);
-  float dot = 0.f;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const float o = in[i] / nrm;
-    out[i] = o;
-    dot += o * in[i];
-  }
-  if (sigma) {
-    dot = block_sum(dot, red);
-    if (threadIdx.x == 0) *sigma = dot;
+    if (b.accumulate) b.f[L][idx] += g; else b.f[L][idx] = g;
   }
 }
-// ---- the same power iteration for ALL spectral-norm layers of a network in 4 launches (blockIdx.z = layer) instead of
+
+// ---- spectral norm: the power iteration for ALL spectral-norm layers of a network in 4 launches (blockIdx.z = layer) instead of
 //      4-5 launches per layer: these kernels are launch-latency bound (4-8 us each, 120 of them per training step)
 constexpr int SN_MAX_LAYERS = 16;
 struct SnBatch {
@@ -492,12 +396,53 @@ __global__ void sn_finish_batched_kernel(const SnBatch b, int phase) {
     if (threadIdx.x == 0) *b.sigma[L] = dot;
   }
 }
-__global__ void sn_dot_kernel(const float* __restrict__ a, const float* __restrict__ b, int n, float* out) {
-  __shared__ float red[16];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) acc += a[i] * b[i];
-  acc = block_sum(acc, red);
-  if (threadIdx.x == 0) *out = acc;
+
+// ---- one launch helper per operation: the *_batched entry points fill n slots of the table, the single-layer ones slot 0
+static int fold_fwd_launch(const FoldBatch& fb, int n, int O, int I, hipStream_t s) {
+  P2I_LAUNCH(fold_fwd_tile_batched_kernel, dim3(I / 32, O / 32, n), dim3(256), 0, s, fb, O, I);
+  return launch_status();
+}
+static int fold_bwd_launch(const FoldBatch& fb, int n, int O, int I, hipStream_t s) {
+  P2I_LAUNCH(fold_bwd_w_tile_batched_kernel, dim3(I / 32, O / 32, n), dim3(256), 0, s, fb, O, I);
+  P2I_LAUNCH(fold_bwd_d_batched_kernel, dim3(I / 32, 1, n), dim3(256), 0, s, fb, O, I);
+  return launch_status();
+}
+// maxn: the largest O * I * ntaps of the n layers
+static int pack_launch(const PackBatch& b, int n, int maxn, hipStream_t s) {
+  const int blocks = ceil_div(maxn, 256);
+  P2I_LAUNCH(pack_batched_kernel, dim3(blocks > 512 ? 512 : blocks, 1, n), dim3(256), 0, s, b);
+  return launch_status();
+}
+// dots: the n floats that b.dot[i] = dots + i point into.  Zeroed, summed into and read only when a layer has a sigma; without
+// one it may be null.
+static int unpack_launch(const PackBatch& b, int n, int maxn, float* dots, hipStream_t s) {
+  bool any_sigma = false;
+  for (int i = 0; i < n; ++i) any_sigma = any_sigma || b.div[i] != nullptr;
+  const int blocks = ceil_div(maxn, 256);
+  if (any_sigma) {
+    (void)p2i::memset_async(dots, 0, sizeof(float) * n, s);
+    const int nbd = blocks > 128 ? 128 : blocks;
+    const DetWs ws = det_take((size_t)nbd * n, 0);
+    if (ws.part) (void)p2i::memset_async(ws.part, 0, sizeof(float) * (size_t)nbd * n, s);     // (layers without sigma store nothing)
+    P2I_LAUNCH(unpack_dot_batched_kernel, dim3(nbd, 1, n), dim3(256), 0, s, b, ws);
+    if (ws.part)
+      if (int e = det_reduce(ws.part, n, nbd, nbd, 1, DetSegs{{dots, nullptr, nullptr, nullptr}, {n, 0, 0, 0}}, s)) return e;
+  }
+  P2I_LAUNCH(unpack_batched_kernel, dim3(blocks > 512 ? 512 : blocks, 1, n), dim3(256), 0, s, b);
+  return launch_status();
+}
+// maxO, maxK: the largest O and K of the n layers
+static int sn_launch(const SnBatch& b, int n, int maxO, int maxK, int training, hipStream_t s) {
+  if (training) {
+    P2I_LAUNCH(sn_wtu_batched_kernel, dim3(ceil_div(maxK, 64), 1, n), dim3(256), 0, s, b);
+    P2I_LAUNCH(sn_finish_batched_kernel, dim3(1, 1, n), dim3(1024), 0, s, b, 0);
+    P2I_LAUNCH(sn_wv_batched_kernel, dim3(ceil_div(maxO, 4), 1, n), dim3(256), 0, s, b);
+    P2I_LAUNCH(sn_finish_batched_kernel, dim3(1, 1, n), dim3(1024), 0, s, b, 1);
+  } else {
+    P2I_LAUNCH(sn_wv_batched_kernel, dim3(ceil_div(maxO, 4), 1, n), dim3(256), 0, s, b);
+    P2I_LAUNCH(sn_finish_batched_kernel, dim3(1, 1, n), dim3(1024), 0, s, b, 2);
+  }
+  return launch_status();
 }
 
 }  // namespace p2i
@@ -520,8 +465,9 @@ extern "C" int p2i_doconv_fold_fwd(const float* W, const float* D, const float* 
   if (groups > 1 || Opad != O) (void)p2i::memset_async(wp_f, 0, sizeof(float) * (size_t)nt * I * Opad, s);
   if (wp_d && (groups > 1 || Ipad != I)) (void)p2i::memset_async(wp_d, 0, sizeof(float) * (size_t)nt * O * Ipad, s);
   if (ksz == 3 && groups == 1 && identity_rep == 0 && Opad == O && Ipad == I) {
-    P2I_LAUNCH(fold_fwd_tile_kernel, dim3(ceil_div(I, 16), ceil_div(O, 16)), dim3(256), 0, s, W, D, D_diag, O, I, wp_f, wp_d);
-    return launch_status();
+    FoldBatch fb{};
+    fb.W[0] = W; fb.D[0] = D; fb.Dd[0] = D_diag; fb.a[0] = wp_f; fb.b[0] = wp_d;
+    return fold_fwd_launch(fb, 1, O, I, s);
   }
   const int n = (ksz == 1) ? O * (I / groups) : (O / groups) * I;
   P2I_LAUNCH(fold_fwd_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, W, D, D_diag, O, I, groups, ksz, identity_rep, wp_f, wp_d);
@@ -533,11 +479,13 @@ extern "C" int p2i_doconv_fold_bwd(const float* dwp_f, const float* W, const flo
   P2I_REQUIRE(dwp_f && W && dW, "null pointer");
   P2I_REQUIRE(ksz == 1 || (D && D_diag && dD), "3x3 DO-Conv needs D, D_diag, dD");
   hipStream_t s = (hipStream_t)stream;
+  if (ksz == 3 && groups == 1 && O % 32 == 0 && I % 32 == 0) {
+    FoldBatch fb{};
+    fb.g[0] = dwp_f; fb.W[0] = W; fb.D[0] = D; fb.Dd[0] = D_diag; fb.a[0] = dW; fb.b[0] = dD;
+    return fold_bwd_launch(fb, 1, O, I, s);
+  }
   const int n = (ksz == 1) ? O * (I / groups) : (O / groups) * I;
-  if (ksz == 3 && groups == 1 && O % 32 == 0)
-    P2I_LAUNCH(fold_bwd_w_tile_kernel, dim3(ceil_div(I, 16), ceil_div(O, 16)), dim3(256), 0, s, dwp_f, D, D_diag, O, I, dW);
-  else
-    P2I_LAUNCH(fold_bwd_w_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, dwp_f, D, D_diag, O, I, groups, ksz, dW);
+  P2I_LAUNCH(fold_bwd_w_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, dwp_f, D, D_diag, O, I, groups, ksz, dW);
   if (ksz == 3) P2I_LAUNCH(fold_bwd_d_kernel, dim3(I), dim3(256), 0, s, dwp_f, W, O, I, groups, dD);
   return launch_status();
 }
@@ -549,45 +497,28 @@ extern "C" int p2i_weight_pack(const float* w, int O, int I, int ntaps, const fl
   const int Opad = (O + 31) / 32 * 32, Ipad = (I + 31) / 32 * 32;
   if (wp_f && Opad != O) (void)p2i::memset_async(wp_f, 0, sizeof(float) * (size_t)ntaps * I * Opad, s);
   if (wp_d && Ipad != I) (void)p2i::memset_async(wp_d, 0, sizeof(float) * (size_t)ntaps * O * Ipad, s);
-  P2I_LAUNCH(pack_kernel, dim3(ceil_div(O * I * ntaps, 256)), dim3(256), 0, s, w, O, I, ntaps, inv_div_ptr, wp_f, wp_d);
-  return launch_status();
+  PackBatch b{};
+  b.w[0] = w; b.div[0] = inv_div_ptr; b.f[0] = wp_f; b.d[0] = wp_d; b.O[0] = O; b.I[0] = I; b.NT[0] = ntaps;
+  return pack_launch(b, 1, O * I * ntaps, s);
 }
 
 extern "C" int p2i_weight_unpack_grad(const float* dwp_f, int O, int I, int ntaps, const float* w_orig, const float* sigma_ptr,
                                       const float* u, const float* v, float* scratch, float* dw, void* stream) {
   P2I_REQUIRE(dwp_f && dw, "null pointer");
   P2I_REQUIRE(!sigma_ptr || (w_orig && u && v && scratch), "spectral-norm unpack needs w_orig, u, v, scratch");
-  hipStream_t s = (hipStream_t)stream;
-  const int n = O * I * ntaps;
-  if (sigma_ptr) {
-    (void)p2i::memset_async(scratch, 0, sizeof(float), s);
-    const int nbd = min(ceil_div(n, 256), 256);
-    const DetWs ws = det_take((size_t)nbd, 0);
-    P2I_LAUNCH(unpack_dot_kernel, dim3(nbd), dim3(256), 0, s, dwp_f, w_orig, O, I, ntaps, scratch, ws);
-    if (ws.part)
-      if (int e = det_reduce(ws.part, 1, nbd, 0, 1, DetSegs{{scratch, nullptr, nullptr, nullptr}, {1, 0, 0, 0}}, s)) return e;
-  }
-  P2I_LAUNCH(unpack_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, dwp_f, O, I, ntaps, sigma_ptr, scratch, u, v, dw);
-  return launch_status();
+  PackBatch b{};                     // scratch (one float: the dot product) is null without sigma, and then never touched
+  b.g[0] = dwp_f; b.f[0] = dw; b.div[0] = sigma_ptr; b.w[0] = w_orig; b.u[0] = u; b.v[0] = v; b.dot[0] = scratch;
+  b.O[0] = O; b.I[0] = I; b.NT[0] = ntaps;
+  return unpack_launch(b, 1, O * I * ntaps, scratch, (hipStream_t)stream);
 }
 
 extern "C" int p2i_spectral_norm(const float* w, int O, int K, float* u, float* v, int training, float* sigma, float* scratch,
                                  void* stream) {
   P2I_REQUIRE(w && u && v && sigma && scratch, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  float* t = scratch;        // K
-  float* sv = scratch + K;   // O
-  if (training) {
-    (void)p2i::memset_async(t, 0, sizeof(float) * K, s);
-    P2I_LAUNCH(sn_wtu_kernel, dim3(ceil_div(K, 64), ceil_div(O, 32)), dim3(256), 0, s, w, u, O, K, t);
-    P2I_LAUNCH(sn_normalize_kernel, dim3(1), dim3(1024), 0, s, t, K, v, (float*)nullptr);
-    P2I_LAUNCH(sn_wv_kernel, dim3(ceil_div(O, 4)), dim3(256), 0, s, w, v, O, K, sv);
-    P2I_LAUNCH(sn_normalize_kernel, dim3(1), dim3(1024), 0, s, sv, O, u, sigma);
-  } else {
-    P2I_LAUNCH(sn_wv_kernel, dim3(ceil_div(O, 4)), dim3(256), 0, s, w, v, O, K, sv);
-    P2I_LAUNCH(sn_dot_kernel, dim3(1), dim3(1024), 0, s, u, sv, O, sigma);
-  }
-  return launch_status();
+  SnBatch b{};                       // no snapshots: the caller reads u, v in place
+  b.w[0] = w; b.u[0] = u; b.v[0] = v; b.sigma[0] = sigma; b.scratch[0] = scratch; b.O[0] = O; b.K[0] = K;
+  b.n = 1;
+  return sn_launch(b, 1, O, K, training, (hipStream_t)stream);
 }
 
 extern "C" int p2i_spectral_norm_batched(const float* const* w, const int* O, const int* K, float* const* u, float* const* v,
@@ -605,17 +536,7 @@ extern "C" int p2i_spectral_norm_batched(const float* const* w, const int* O, co
     if (K[j] > maxK) maxK = K[j];
   }
   b.n = n;
-  hipStream_t s = (hipStream_t)stream;
-  if (training) {
-    P2I_LAUNCH(sn_wtu_batched_kernel, dim3(ceil_div(maxK, 64), 1, n), dim3(256), 0, s, b);
-    P2I_LAUNCH(sn_finish_batched_kernel, dim3(1, 1, n), dim3(1024), 0, s, b, 0);
-    P2I_LAUNCH(sn_wv_batched_kernel, dim3(ceil_div(maxO, 4), 1, n), dim3(256), 0, s, b);
-    P2I_LAUNCH(sn_finish_batched_kernel, dim3(1, 1, n), dim3(1024), 0, s, b, 1);
-  } else {
-    P2I_LAUNCH(sn_wv_batched_kernel, dim3(ceil_div(maxO, 4), 1, n), dim3(256), 0, s, b);
-    P2I_LAUNCH(sn_finish_batched_kernel, dim3(1, 1, n), dim3(1024), 0, s, b, 2);
-  }
-  return launch_status();
+  return sn_launch(b, n, maxO, maxK, training, (hipStream_t)stream);
 }
 
 // n <= 16 same-shape 3x3 DO-Conv layers (groups 1, O and I multiples of 32: the generator's residual stack) in ONE launch
@@ -628,8 +549,7 @@ extern "C" int p2i_doconv_fold_fwd_batched(const float* const* W, const float* c
     P2I_REQUIRE(W[i] && D[i] && D_diag[i] && wp_f[i], "null pointer (layer %d)", i);
     fb.W[i] = W[i]; fb.D[i] = D[i]; fb.Dd[i] = D_diag[i]; fb.a[i] = wp_f[i]; fb.b[i] = wp_d ? wp_d[i] : nullptr;
   }
-  P2I_LAUNCH(fold_fwd_tile_batched_kernel, dim3(I / 32, O / 32, n), dim3(256), 0, (hipStream_t)stream, fb, O, I);
-  return launch_status();
+  return fold_fwd_launch(fb, n, O, I, (hipStream_t)stream);
 }
 extern "C" int p2i_doconv_fold_bwd_batched(const float* const* dwp_f, const float* const* W, const float* const* D,
                                            const float* const* D_diag, int n, int O, int I, float* const* dW, float* const* dD,
@@ -641,68 +561,8 @@ extern "C" int p2i_doconv_fold_bwd_batched(const float* const* dwp_f, const floa
     P2I_REQUIRE(dwp_f[i] && W[i] && D[i] && D_diag[i] && dW[i] && dD[i], "null pointer (layer %d)", i);
     fb.g[i] = dwp_f[i]; fb.W[i] = W[i]; fb.D[i] = D[i]; fb.Dd[i] = D_diag[i]; fb.a[i] = dW[i]; fb.b[i] = dD[i];
   }
-  hipStream_t s = (hipStream_t)stream;
-  P2I_LAUNCH(fold_bwd_w_tile_batched_kernel, dim3(I / 32, O / 32, n), dim3(256), 0, s, fb, O, I);
-  P2I_LAUNCH(fold_bwd_d_batched_kernel, dim3(I / 32, 1, n), dim3(256), 0, s, fb, O, I);
-  return launch_status();
+  return fold_bwd_launch(fb, n, O, I, (hipStream_t)stream);
 }
-
-// ---- pack / unpack of up to 16 layers of DIFFERENT shapes in one launch each (blockIdx.z = layer): the discriminator's ten
-//      spectral-norm layers are packed once per forward and unpacked once per backward
-namespace p2i {
-constexpr int PACK_MAX_LAYERS = 16;
-struct PackBatch {
-  const float* w[PACK_MAX_LAYERS];
-  const float* div[PACK_MAX_LAYERS];
-  float* f[PACK_MAX_LAYERS];
-  float* d[PACK_MAX_LAYERS];
-  const float* g[PACK_MAX_LAYERS];     // unpack: packed gradient
-  const float* u[PACK_MAX_LAYERS];
-  const float* v[PACK_MAX_LAYERS];
-  float* dot[PACK_MAX_LAYERS];
-  int O[PACK_MAX_LAYERS], I[PACK_MAX_LAYERS], NT[PACK_MAX_LAYERS];
-  int accumulate;                      // unpack: dw += instead of dw =
-};
-__global__ void pack_batched_kernel(const PackBatch b) {
-  const int L = blockIdx.z, O = b.O[L], I = b.I[L], NT = b.NT[L];
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < O * I * NT; idx += gridDim.x * blockDim.x) {
-    const int tap = idx % NT, i = (idx / NT) % I, o = idx / (NT * I);
-    float v = b.w[L][idx];
-    if (b.div[L]) v = v / *b.div[L];
-    if (b.f[L]) b.f[L][((size_t)tap * I + i) * pad32(O) + o] = v;
-    if (b.d[L]) b.d[L][((size_t)tap * O + o) * pad32(I) + i] = v;
-  }
-}
-__global__ void unpack_dot_batched_kernel(const PackBatch b, DetWs ws) {
-  __shared__ float red[16];
-  const int L = blockIdx.z, O = b.O[L], I = b.I[L], NT = b.NT[L];
-  if (!b.div[L]) return;                              // plain unpack: no sigma term
-  float acc = 0.f;
-  const int n = O * I * NT;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += gridDim.x * blockDim.x) {
-    const int tap = idx % NT, i = (idx / NT) % I, o = idx / (NT * I);
-    acc += b.g[L][((size_t)tap * I + i) * pad32(O) + o] * b.w[L][idx];
-  }
-  acc = block_sum(acc, red);
-  if (ws.part) {                                       // ws.part = [layers][gridDim.x]: added in workgroup order by det_reduce
-    if (threadIdx.x == 0) ws.part[(size_t)L * gridDim.x + blockIdx.x] = acc;
-    return;
-  }
-  if (threadIdx.x == 0 && acc != 0.f) atomicAdd(b.dot[L], acc);
-}
-__global__ void unpack_batched_kernel(const PackBatch b) {
-  const int L = blockIdx.z, O = b.O[L], I = b.I[L], NT = b.NT[L];
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < O * I * NT; idx += gridDim.x * blockDim.x) {
-    const int tap = idx % NT, i = (idx / NT) % I, o = idx / (NT * I);
-    float g = b.g[L][((size_t)tap * I + i) * pad32(O) + o];
-    if (b.div[L]) {
-      const float sg = *b.div[L];
-      g = g / sg - (*b.dot[L] / (sg * sg)) * b.u[L][o] * b.v[L][i * NT + tap];
-    }
-    if (b.accumulate) b.f[L][idx] += g; else b.f[L][idx] = g;
-  }
-}
-}  // namespace p2i
 
 extern "C" int p2i_weight_pack_batched(const float* const* w, const int* O, const int* I, const int* ntaps, const float* const* inv_div,
                                        float* const* wp_f, float* const* wp_d, int n, void* stream) {
@@ -715,9 +575,7 @@ extern "C" int p2i_weight_pack_batched(const float* const* w, const int* O, cons
     b.O[i] = O[i]; b.I[i] = I[i]; b.NT[i] = ntaps[i];
     if (O[i] * I[i] * ntaps[i] > maxn) maxn = O[i] * I[i] * ntaps[i];
   }
-  const int blocks = ceil_div(maxn, 256);
-  P2I_LAUNCH(pack_batched_kernel, dim3(blocks > 512 ? 512 : blocks, 1, n), dim3(256), 0, (hipStream_t)stream, b);
-  return launch_status();
+  return pack_launch(b, n, maxn, (hipStream_t)stream);
 }
 
 extern "C" int p2i_weight_unpack_grad_batched_acc(const float* const* dwp_f, const int* O, const int* I, const int* ntaps,
@@ -728,7 +586,6 @@ extern "C" int p2i_weight_unpack_grad_batched_acc(const float* const* dwp_f, con
   PackBatch b{};
   b.accumulate = accumulate;
   int maxn = 0;
-  bool any_sigma = false;
   for (int i = 0; i < n; ++i) {
     P2I_REQUIRE(dwp_f[i] && dw[i] && O[i] > 0 && I[i] > 0 && ntaps[i] > 0, "bad layer %d", i);
     const bool sg = sigma && sigma[i];
@@ -736,22 +593,9 @@ extern "C" int p2i_weight_unpack_grad_batched_acc(const float* const* dwp_f, con
     b.g[i] = dwp_f[i]; b.f[i] = dw[i]; b.div[i] = sg ? sigma[i] : nullptr; b.w[i] = sg ? w_orig[i] : nullptr;
     b.u[i] = sg ? u[i] : nullptr; b.v[i] = sg ? v[i] : nullptr; b.dot[i] = dots + i;
     b.O[i] = O[i]; b.I[i] = I[i]; b.NT[i] = ntaps[i];
-    any_sigma = any_sigma || sg;
     if (O[i] * I[i] * ntaps[i] > maxn) maxn = O[i] * I[i] * ntaps[i];
   }
-  hipStream_t s = (hipStream_t)stream;
-  const int blocks = ceil_div(maxn, 256);
-  if (any_sigma) {
-    (void)p2i::memset_async(dots, 0, sizeof(float) * n, s);
-    const int nbd = blocks > 128 ? 128 : blocks;
-    const DetWs ws = det_take((size_t)nbd * n, 0);
-    if (ws.part) (void)p2i::memset_async(ws.part, 0, sizeof(float) * (size_t)nbd * n, s);     // (layers without sigma store nothing)
-    P2I_LAUNCH(unpack_dot_batched_kernel, dim3(nbd, 1, n), dim3(256), 0, s, b, ws);
-    if (ws.part)
-      if (int e = det_reduce(ws.part, n, nbd, nbd, 1, DetSegs{{dots, nullptr, nullptr, nullptr}, {n, 0, 0, 0}}, s)) return e;
-  }
-  P2I_LAUNCH(unpack_batched_kernel, dim3(blocks > 512 ? 512 : blocks, 1, n), dim3(256), 0, s, b);
-  return launch_status();
+  return unpack_launch(b, n, maxn, dots, (hipStream_t)stream);
 }
 
 extern "C" int p2i_weight_unpack_grad_batched(const float* const* dwp_f, const int* O, const int* I, const int* ntaps,

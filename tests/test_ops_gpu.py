@@ -685,7 +685,8 @@ def test_wgrad_slices_are_bit_reproducible_and_match_atomics(ops):
 
 
 def test_spectral_norm_batched_matches_per_layer(ops):
-    """p2i_spectral_norm_batched (all layers in 4 launches) == p2i_spectral_norm layer by layer, training and eval."""
+    """p2i_spectral_norm_batched (all layers in 4 launches) == p2i_spectral_norm layer by layer, training and eval: the single call
+    is a batch of one of the same kernels, and a layer's sums do not depend on the rest of the batch, so the bits are equal."""
     shapes = [(64, 16, 3, 3), (128, 64, 3, 3), (32, 1, 3, 3, 3), (1, 128, 1, 1, 1), (256, 256, 3, 3)]
     ws = [_rand(*sh, seed=10 + i, scale=0.1).cuda() for i, sh in enumerate(shapes)]
     for training in (True, False):
@@ -695,8 +696,8 @@ def test_spectral_norm_batched_matches_per_layer(ops):
         s1 = [ops.spectral_norm(w, u, v, training) for w, u, v in zip(ws, u1, v1)]
         sb = ops.spectral_norm_batched(ws, us, vs, training)
         for i in range(len(ws)):
-            assert abs(float(sb[i]) - float(s1[i])) <= 1e-5 * abs(float(s1[i])), (i, training)
-            assert rel_err(us[i].cpu().numpy(), u1[i].cpu().numpy()) < 1e-5 and rel_err(vs[i].cpu().numpy(), v1[i].cpu().numpy()) < 1e-5
+            assert torch.equal(sb[i], s1[i]), (i, training)
+            assert torch.equal(us[i], u1[i]) and torch.equal(vs[i], v1[i]), (i, training)
 
 
 def test_doconv_fold_batched_matches_per_layer(ops):

@@ -1,6 +1,6 @@
 """The case tables of tests/weightprep_cases.py have the properties that test_weightprep_gpu.py relies on: every fold / pack sum is
 an integer below 2^24 (so float32 results do not depend on the order of summation and the comparison can be torch.equal), every
-listed reason -- which kernel the planner picks, partial tiles, second trips, row slabs -- is true of its case, the restatements
+listed reason -- which kernel the planner picks, second trips, ragged column and row groups -- is true of its case, the restatements
 agree with the oracle's own fold, and the three-term bf16 split is exact on the case values."""
 import numpy as np
 import pytest
@@ -68,15 +68,17 @@ def test_fold_reasons_hold():
     assert {(32, 64), (64, 32), (96, 32), (32, 160), (288, 32)} == {c[:2] for c in tile_both}
     assert all(c[0] != c[1] for c in tile_both)                                   # O != I everywhere on the tile kernels
     assert any(c[5] == "int" for c in tile_both)
-    partial = [c for c in wc.FOLD_CASES if wc.fold_bwd_is_tile(c) and not wc.fold_fwd_is_tile(c) and c[4] == 0]
-    assert {(32, 24), (64, 40)} == {c[:2] for c in partial}
-    assert all(c[1] % 16 != 0 for c in partial)                                   # a partial 16-wide tile in I
+    assert all(wc.fold_bwd_is_tile(c) == wc.fold_fwd_is_tile(c) for c in wc.FOLD_CASES if c[4] == 0)      # one planner, both ways
     generic = [c for c in wc.FOLD_CASES if not wc.fold_bwd_is_tile(c) and c[2] == 1 and c[3] == 3]
     assert {(48, 16), (16, 48), (33, 65), (1, 8), (8, 1)} <= {c[:2] for c in generic}
     assert all(wc.pad32(c[0]) != c[0] or wc.pad32(c[1]) != c[1] for c in generic)
+    ragged_i = [c for c in generic if c[0] % 32 == 0 and c[4] == 0]               # whole tiles in O, none in I: generic all the same,
+    assert {(32, 24), (64, 40), (288, 24)} == {c[:2] for c in ragged_i}           # with an unpadded pitch (pad32(O) == O) in dwp
+    assert all(c[1] % 32 != 0 and c[1] % 16 != 0 for c in ragged_i)
     assert sum(c[2] > 1 for c in wc.FOLD_CASES) == 4 and {1, 3} == {c[3] for c in wc.FOLD_CASES if c[2] > 1}
     assert any(c[4] > 0 and c[2] == 1 and not wc.fold_fwd_is_tile(c) and c[0] % 32 == 0 for c in wc.FOLD_CASES)
-    assert any(c[0] // c[2] > 256 for c in wc.FOLD_CASES)                         # second trip of fold_bwd_d_kernel's 256 threads
+    assert any(c[0] // c[2] > 256 and c[3] == 3 and not wc.fold_bwd_is_tile(c) for c in wc.FOLD_CASES)      # second trip of fold_bwd_d_kernel's 256 threads
+    assert any(c[0] > 256 and wc.fold_bwd_is_tile(c) for c in wc.FOLD_CASES)
     for c in wc.FOLD_CASES:
         assert c[4] == 0 or (c[3] == 3 and c[1] * c[4] == c[0])
     for c in wc.FOLD_REFUSED:
@@ -178,10 +180,13 @@ def test_split_tables():
 
 # ------------------------------------------------------------------------------------------------ spectral norm
 def test_spectral_norm_reasons_hold():
-    slabs = {o: -(-o // wc.SN_SLAB) for o, _ in wc.SN_SHAPES}
-    assert slabs[33] == 2 and slabs[40] == 2 and slabs[70] == 3 and slabs[1030] == 33         # atomically added row slabs
-    assert all(o % wc.SN_SLAB != 0 for o in (33, 40, 70, 1030))                                 # the last one partial
-    assert any(k < 64 and o > 1 for o, k in wc.SN_SHAPES)
+    groups = {k: -(-k // wc.SN_WTU_COLS) for _, k in wc.SN_SHAPES}              # workgroups of W^T u per layer
+    assert groups[65] == 2 and groups[1030] == 17 and groups[4100] == 65           # more than one, the last one ragged
+    assert all(k % wc.SN_WTU_COLS != 0 for k in (65, 1030, 4100)) and any(k % wc.SN_WTU_COLS == 0 for _, k in wc.SN_SHAPES)
+    assert any(k < wc.SN_WTU_COLS and o > 1 for o, k in wc.SN_SHAPES)
+    # rows: the 4 row groups take unequal shares (O % 4 != 0), some take none (O < 4), and O = 1030 gives each more than 256 trips
+    assert {1, 2, 3} <= {o % wc.SN_WTU_ROW_GROUPS for o, _ in wc.SN_SHAPES} and any(o < wc.SN_WTU_ROW_GROUPS for o, _ in wc.SN_SHAPES)
+    assert all(o in {o for o, _ in wc.SN_SHAPES} for o in (33, 40, 70, 1030))                  # the row counts of the earlier sweep stay
     assert any(o > wc.SN_NORM_THREADS for o, _ in wc.SN_SHAPES) and any(k > wc.SN_NORM_THREADS for _, k in wc.SN_SHAPES)
     assert any(k > 4 * wc.SN_NORM_THREADS for _, k in wc.SN_SHAPES)
     assert 2 * len(wc.SN_SHAPES) == wc.SN_MAX_LAYERS

@@ -221,6 +221,17 @@ def test_plain_unpack_exact_and_blind_to_the_padding(ops, shape):
     assert ops.weight_unpack_grad(g7.cuda(), like, out=tgt) is tgt and _eq(tgt, want)
 
 
+def test_plain_unpack_of_one_layer_needs_no_dot_product_scratch(ops, reduce):
+    """without sigma the single-layer call hands the launch helper a NULL dot-product slot: nothing is zeroed, summed or read there,
+    with the fixed-order scratch registered or not, and the caller's target gets exactly the expected integers"""
+    shape = (65, 33, 4)
+    g = wc.packed_grad(shape, 1, 7)
+    tgt = torch.full(shape, POISON, device="cuda")
+    assert ops.weight_unpack_grad(g.cuda(), torch.empty(shape, device="cuda"), out=tgt) is tgt
+    torch.cuda.synchronize()
+    assert _eq(tgt, wc.unpack_expected(g, shape[0]))
+
+
 def test_plain_unpack_batched_and_accumulate_exact(ops, reduce):
     shapes = wc.PACK_SHAPES
     likes = [torch.empty(sh, device="cuda") for sh in shapes]
@@ -407,16 +418,34 @@ def _sn_close(got, ref, what):
 
 @pytest.mark.parametrize("shape", wc.SN_SHAPES, ids=wc.case_id)
 def test_spectral_norm_matches_float64(ops, shape):
-    """p2i_spectral_norm reads no scratch of the fixed-order sums: its one cross-workgroup sum (sn_wtu_kernel's row slabs) is always
-    atomic, so there is a single ending to run; O = 33, 40, 70, 1030 have two or more slabs."""
+    """p2i_spectral_norm is a batch of one of the batched kernels: no sum crosses a workgroup (a column of W^T u is summed by the four
+    row groups of ONE workgroup, whatever O is; K > 64 only adds workgroups with columns of their own), nothing is atomic and no
+    scratch of the fixed-order sums is read -- a single ending, and a second run from the same inputs gives the same bits."""
     (w, u, v), (un, vn, sn), (_, _, se) = _sn_ref(shape)
     wg, ug, vg = _cuda(w, u, v)
     sigma = ops.spectral_norm(wg, ug, vg, True)
     _sn_close(ug, un, "u"), _sn_close(vg, vn, "v"), _sn_close(sigma, sn.reshape(1), "sigma")
+    u2, v2 = u.cuda(), v.cuda()
+    assert torch.equal(ops.spectral_norm(wg, u2, v2, True), sigma) and torch.equal(u2, ug) and torch.equal(v2, vg)
     ue, ve = u.cuda(), v.cuda()
     s2 = ops.spectral_norm(wg, ue, ve, False)
     assert _eq(ue, u) and _eq(ve, v)                 # eval: u, v untouched
     _sn_close(s2, se.reshape(1), "sigma (eval)")
+    assert torch.equal(ops.spectral_norm(wg, ue, ve, False), s2)
+
+
+@pytest.mark.parametrize("training", [True, False], ids=["train", "eval"])
+def test_spectral_norm_single_call_is_the_batched_call(ops, training):
+    """a layer's arithmetic does not depend on what else is in the batch: every SN_SHAPES layer alone == the whole list at once,
+    bit for bit"""
+    refs = [_sn_ref(sh) for sh in wc.SN_SHAPES]
+    ws = [r[0][0].cuda() for r in refs]
+    u1, v1 = [r[0][1].cuda() for r in refs], [r[0][2].cuda() for r in refs]
+    ub, vb = [r[0][1].cuda() for r in refs], [r[0][2].cuda() for r in refs]
+    s1 = [ops.spectral_norm(w, u, v, training) for w, u, v in zip(ws, u1, v1)]
+    sb = ops.spectral_norm_batched(ws, ub, vb, training)
+    for i, sh in enumerate(wc.SN_SHAPES):
+        assert torch.equal(s1[i], sb[i]) and torch.equal(u1[i], ub[i]) and torch.equal(v1[i], vb[i]), sh
 
 
 def test_spectral_norm_of_a_zero_weight(ops):

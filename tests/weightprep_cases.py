@@ -1,7 +1,7 @@
 """Case tables, seeded input builders and exact restatements for the shape sweep of the weight-preparation kernels (csrc/weights.hip)
 and of the bf16 weight split (wsplit_kernel / wsplit_batched_kernel of csrc/conv_x6c.hip): test_weightprep_gpu.py runs them on the
 GPU, test_weightprep_cpu.py checks on the CPU that the tables have the properties the comparisons rely on (every sum an integer
-below 2^24, every listed reason -- tile or generic kernel, partial tile, second trip, number of row slabs -- true of its case, the
+below 2^24, every listed reason -- tile or generic kernel, second trip, ragged column and row groups -- true of its case, the
 split exact on the case values).  Everything here is torch / numpy on the CPU and a function of the case alone; the restatements
 follow the formulas of include/p2i_hip.h and oracle/p2i_oracle.py."""
 import numpy as np
@@ -38,14 +38,16 @@ FOLD_CASES = [
     # tile kernels forward and backward (3x3, groups 1, O and I multiples of 32) with O != I: an O <-> I swap in a pitch shows
     (32, 64, 1, 3, 0, "eye"), (64, 32, 1, 3, 0, "eye"), (96, 32, 1, 3, 0, "eye"), (32, 160, 1, 3, 0, "eye"),
     (64, 32, 1, 3, 0, "int"),                      # an integer D_diag that is not the identity: D and D_diag are really ADDED
-    # O % 32 == 0, I % 16 != 0: the forward goes generic (padded I), the backward takes the tile kernel with a partial tile in I
+    # O % 32 == 0, I % 32 != 0: the tile kernels want whole 32 x 32 tiles, so forward (padded I) and backward both go generic --
+    # fold_bwd_w_kernel reads a packed gradient whose pitch pad32(O) is O itself
     (32, 24, 1, 3, 0, "eye"), (64, 40, 1, 3, 0, "eye"),
     # generic kernels, groups 1, padded O and / or I
     (48, 16, 1, 3, 0, "eye"), (16, 48, 1, 3, 0, "eye"), (33, 65, 1, 3, 0, "eye"), (1, 8, 1, 3, 0, "eye"), (8, 1, 1, 3, 0, "eye"),
     # groups: the model's input layer (identity skip) and output layer (1x1), three groups, two groups 1x1
     (64, 16, 4, 3, 4, "eye"), (16, 64, 4, 1, 0, "eye"), (24, 12, 3, 3, 0, "eye"), (40, 8, 2, 1, 0, "eye"),
     (32, 8, 1, 3, 4, "eye"),                       # identity skip with groups 1: generic path although O % 32 == 0
-    (288, 32, 1, 3, 0, "eye"),                     # O/g > 256: the thread-stride loop of fold_bwd_d_kernel takes a second trip
+    (288, 32, 1, 3, 0, "eye"),                     # nine 32-row trips of fold_bwd_d_batched_kernel's loop over O
+    (288, 24, 1, 3, 0, "eye"),                     # O/g > 256, generic: the thread-stride loop of fold_bwd_d_kernel takes a second trip
 ]
 # identity_rep asks for `+ x.repeat_interleave(rep, dim=1)`, which exists for I * rep == O and 3x3 only: anything else is refused
 FOLD_REFUSED = [(12, 24, 3, 3, 1, "eye"), (16, 64, 4, 1, 4, "eye")]
@@ -65,7 +67,7 @@ def fold_fwd_is_tile(c):
 def fold_bwd_is_tile(c):
     """the planner of p2i_doconv_fold_bwd, restated"""
     O, I, g, ksz, _, _ = c
-    return ksz == 3 and g == 1 and O % 32 == 0
+    return ksz == 3 and g == 1 and O % 32 == 0 and I % 32 == 0
 
 
 def fold_inputs(c, seed=0):
@@ -233,8 +235,9 @@ def split_image(a):
 SN_SHAPES = [(1, 1), (5, 3), (33, 27), (40, 65), (70, 64), (1030, 8), (8, 1030), (3, 4100)]     # (O, K)
 SN_ZERO_SHAPE = (16, 27)
 SN_MAX_LAYERS = 16
-SN_SLAB = 32               # rows per workgroup of sn_wtu_kernel: ceil(O / 32) workgroups add into t[k] atomically
-SN_NORM_THREADS = 1024     # sn_normalize_kernel: one workgroup of 1024 threads strides over the vector
+SN_WTU_COLS = 64           # sn_wtu_batched_kernel: a workgroup owns 64 columns of W^T u (ceil(K / 64) workgroups per layer) ...
+SN_WTU_ROW_GROUPS = 4      # ... and its 4 row groups stride over ALL rows o = rg, rg + 4, ...: one fixed order, nothing atomic
+SN_NORM_THREADS = 1024     # sn_finish_batched_kernel: one workgroup of 1024 threads per layer strides over the vector
 
 
 def sn_inputs(shape, seed=0):
