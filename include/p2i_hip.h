@@ -628,6 +628,39 @@ int p2i_idw_loo(const int* pix, const float* z, const int* counts, int F, int ca
 int p2i_loo_scores(const float* z, const float* pred, const float* var, const int* counts, int F, int cap, double* part, double* out,
                    void* stream);
 
+/* ---- conditional simulation of ordinary kriging (no counterpart in the reference): M ensemble members per
+ * frame that carry the variogram's texture and equal z at every gauge.  Symbols, systems (f0, R, T, nsys, np, cap) and the frame
+ * rules are those of the two blocks above.  The unconditional fields live on the torus Sy x Sx = (e H) x (e W), both <= 512.
+ * p2i_krig_cs_spectrum: per sample b, in fp64 from the fp32 params: base[j][k] = C(sqrt(dj^2 + dk^2)) + nugget [dj = dk = 0], dj =
+ *   min(j, Sy - j), dk = min(k, Sx - k); lambda = Re DFT2(base) as two cosine products over twiddle [Sy + Sx] fp64 (DEVICE, computed
+ *   on the host: cos(2 pi m / Sy), m < Sy, then cos(2 pi m / Sx), m < Sx); amp [B][Sy][Sx] fp32 = sqrt(max(lambda, 0) (sum lambda /
+ *   sum max(lambda, 0)) / (Sy Sx)); clip [B] fp64 = sum max(-lambda, 0) / sum |lambda|.  work: 2 B Sy Sx fp64 of scratch.  A
+ *   degenerate sample (cand[b] < 0; cand may be NULL) gets amp = 0 and clip = NaN.
+ * p2i_krig_cs_noise: xi [npairs][Sy][Sx][2] fp32, the complex standard normal of torus cell j Sx + k and member pair q0 + q: with
+ *   (r0, r1, ., .) = Philox4x32-10 of counter (j Sx + k, q0 + q, stream_id low, high) under key (seed low, high): rho^2 = -2 ln((r0 +
+ *   1) 2^-32), taken as -2 log1p(-(2^32 - 1 - r0) 2^-32) for r0 >= 2^31; xi = rho (cos, sin)(2 pi r1 2^-32).
+ * p2i_krig_cs_fields: for the frames f0 .. f0 + nframes - 1 and every pair q < (M + 1) / 2: Y = DFT2(amp[f / T] xi)[:H, :W] with
+ *   xi of (seed, streams[f], q) drawn in the loader, as two products on v_mfma_f32_32x32x2_f32 over tx [2][Sx][W] and ty [2][Sy][H]
+ *   fp32 (cos, then sin, of 2 pi k w / Sx and 2 pi j h / Sy; DEVICE, rounded from fp64 on the host); ens [F][M][H W]: member 2q = Re
+ *   Y, member 2q + 1 = Im Y (dropped past M).  P: nframes ((M + 1) / 2) 2 Sy W fp32 of scratch.  streams [F] int64.
+ * p2i_krig_cs_weights: for column c = t M + m of system s (frame fs + t, member m; ens holds U there): r = z - U(gauges), v = Winv^T
+ *   (Winv r), mu [nsys][R M] = u^T r / s, alpha [nsys][R M][cap] = v - mu u (0 past the count), sums in fp64.  sol, status, Winv as
+ *   left by p2i_krig_solve / p2i_krig_factor / p2i_krig_invert for the same (f0, R, nsys, np).  No model: alpha = 0, mu = 0.
+ * p2i_krig_cs_predict: ens[fs + t][m][p] = U + mu + sum_i alpha_i c0(p, i), in place, as an MFMA product of alpha with c0 evaluated
+ *   once per (pixel, gauge) for all columns of the system; a gauge pixel is written as the frame's z there; NaN everywhere for a
+ *   system without gauges, with status != 0 or of a degenerate sample.  1 <= M <= 64. */
+int p2i_krig_cs_spectrum(const float* params, const int* cand, int model, int B, int Sy, int Sx, const double* twiddle, double* work,
+                         float* amp, double* clip, void* stream);
+int p2i_krig_cs_noise(uint64_t seed, int64_t stream_id, int q0, int npairs, int Sy, int Sx, float* xi, void* stream);
+int p2i_krig_cs_fields(const float* amp, const int64_t* streams, const float* tx, const float* ty, uint64_t seed, int f0, int nframes,
+                       int T, int M, int H, int W, int Sy, int Sx, float* P, float* ens, void* stream);
+int p2i_krig_cs_weights(const float* Winv, const double* sol, const int* pix, const float* z, const int* counts, const int* status,
+                        const int* cand, const float* ens, int f0, int R, int T, int nsys, int np, int M, int H, int W, int cap,
+                        float* alpha, float* mu, void* stream);
+int p2i_krig_cs_predict(const float* alpha, const float* mu, const int* pix, const float* z, const int* counts, const int* status,
+                        const int* cand, const float* params, int model, int f0, int R, int T, int nsys, int np, int M, int H, int W,
+                        int cap, float* ens, void* stream);
+
 /* ---- space-time ordinary kriging (no counterpart in the reference): every pixel of every frame of a sample
  * from all gauges of all frames of that sample, one system per sample.  Point i of a sample has pixel (y_i, x_i), frame t_i and value
  * z_i; the points are the frames' gauges as p2i_krig_compact leaves them, frame-major.  Distance d = sqrt(dy^2 + dx^2 + kappa^2

@@ -140,6 +140,11 @@ SIGNATURES = {
     "p2i_krig_invert": [_P, _I, _I, _P, _P],
     "p2i_krig_variance": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "p2i_krig_loo": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "p2i_krig_cs_spectrum": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "p2i_krig_cs_noise": [C.c_uint64, _L, _I, _I, _I, _I, _P, _P],
+    "p2i_krig_cs_fields": [_P, _P, _P, _P, C.c_uint64, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "p2i_krig_cs_weights": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "p2i_krig_cs_predict": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "p2i_stkrig_gather": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "p2i_stkrig_bins": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F64, _P, _P],
     "p2i_stkrig_fit": [_P, _I, _I, _I, _I, _F64, _I, _P, _P, _P, _P, _P],

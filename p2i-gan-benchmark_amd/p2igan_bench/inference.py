@@ -60,3 +60,22 @@ def infer_event_variance(generator, masked: torch.Tensor, masks: torch.Tensor, s
     L = masked.shape[1]
     parts = [generator.forward_uq(masked[:, s:s + stride].contiguous(), masks[:, s:s + stride].contiguous())[1][0] for s in range(0, L, stride)]
     return torch.cat(parts, dim=0) * float(output_scale) ** 2
+
+
+@torch.no_grad()
+def infer_event_ensemble(generator, masked: torch.Tensor, masks: torch.Tensor, members: int, seed: int = 0, event_index: int = 0,
+                         stride: int = 16, output_scale: float = 255.0) -> torch.Tensor:
+    """The conditional-simulation members of infer_event_chunks' predictions, chunk by chunk (the same chunks, so the same fits):
+    (L, members, H, W) float32 = member x output_scale, unclipped (NaN over a frame without a model).  The stream id of frame l of the
+    event is (event_index << 32) | l, so the chunk length changes the fit but not the noise.  generator.last_ensemble["clip"] holds the
+    clip shares of all the event's chunks afterwards."""
+    L = masked.shape[1]
+    parts, clips = [], []
+    for s in range(0, L, stride):
+        n = min(stride, L - s)
+        streams = (int(event_index) << 32) + torch.arange(s, s + n, dtype=torch.int64).view(1, n)
+        parts.append(generator.forward_ensemble(masked[:, s:s + stride].contiguous(), masks[:, s:s + stride].contiguous(), members,
+                                                seed=seed, streams=streams)[1][0])
+        clips.append(generator.last_ensemble["clip"])
+    generator.last_ensemble = dict(generator.last_ensemble, clip=torch.cat(clips))
+    return torch.cat(parts, dim=0) * float(output_scale)

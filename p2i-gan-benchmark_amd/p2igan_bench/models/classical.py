@@ -8,6 +8,10 @@ Neither has parameters (state_dict() is empty) and both are deterministic from r
 Uncertainty and validation (csrc/krig_uq.hip): KrigingGenerator.forward_uq adds the kriging variance map, and
 cross_validate of either model predicts every gauge from the frame's other gauges (leave-one-out) and scores the residuals.
 
+Conditional simulation (csrc/krig_cs.hip): KrigingGenerator.forward_ensemble adds ensemble members, fields that
+carry the fitted variogram's texture and equal the gauge values at the gauge pixels; their mean and variance at a pixel are the
+kriging mean and variance.
+
 Space-time kriging (csrc/stkrig.hip): SpaceTimeKrigingGenerator kriges every pixel of every frame of a sample
 from all gauges of all frames of that sample, one system per sample, with a metric space-time covariance.  Its truth-free score is
 leave-one-site-out (csrc/stkrig_loso.hip): cross_validate_sites of all models predicts every point of a
@@ -117,7 +121,8 @@ class _ClassicalBase(nn.Module):
 class KrigingGenerator(_ClassicalBase):
     """Ordinary kriging with a global neighbourhood in its dual form, one system per frame (or per sample when its frames share
     their mask).  model.variogram = {"model": "exponential" | "spherical", "fit": true, "n_lags": 16} fits (nugget, psill, range)
-    per sample on the device; {"model", "fit": false, "nugget", "psill", "range"} takes them as given."""
+    per sample on the device; {"model", "fit": false, "nugget", "psill", "range"} takes them as given.  model.ensemble = {"embed": 2}
+    (2 to 4) sets the side of forward_ensemble's embedding torus in frame sides."""
 
     def __init__(self, config: Dict[str, Any]):
         super().__init__(config)
@@ -140,12 +145,44 @@ class KrigingGenerator(_ClassicalBase):
             if not (self.fixed[0] >= 0 and self.fixed[1] > 0 and self.fixed[2] > 0):
                 raise ValueError("model.variogram: nugget >= 0, psill > 0 and range > 0 are required")
         self.share_sets = bool(mc.get("share_sets", True))   # false: one factorisation per frame even where a sample shares its mask
+        ens = mc.get("ensemble")
+        if ens is not None and not isinstance(ens, dict):
+            raise ValueError(f"model.ensemble must be a mapping such as {{\"embed\": 2}} (got {ens!r})")
+        self.embed = (ens or {}).get("embed", 2)             # forward_ensemble: the torus is embed times the frame on a side
+        if isinstance(self.embed, bool) or not isinstance(self.embed, int) or self.embed not in ops.KRIG_CS_EMBEDS:
+            raise ValueError(f"model.ensemble.embed must be an integer in {list(ops.KRIG_CS_EMBEDS)} (got {self.embed!r})")
         self.last_fit = None         # {"bins", "fit", "cand"} device tensors of the last call (fit=true)
         self.last_status = None      # per-system int32 of the last call: 1 where the factorisation met a non-positive pivot
+        self.last_ensemble = None    # {"clip": (B,) fp64 clip share of each sample's spectrum, "embed"} of the last forward_ensemble
 
     @torch.no_grad()
     def forward(self, masked_frames, masks):
         return self._krige(masked_frames, masks)["pred"]
+
+    @torch.no_grad()
+    def forward_ensemble(self, masked_frames, masks, members, seed=0, streams=None):
+        """(prediction (B, T, 1, H, W), ensemble (B, T, members, H, W)) by conditional simulation.  The prediction
+        is forward()'s.  Every member carries the variogram's texture and equals the gauge values at the gauge pixels; the members'
+        mean and variance at a pixel are the kriging mean and variance.  Member m of a frame is a function of (seed, the frame's
+        stream id, m, the variogram, the gauges) only; streams (B, T) int64 defaults to b T + t.  Members are raw Gaussian (they can be
+        negative) and NaN over a frame without a model, as the variance is.  1 <= members <= 64."""
+        if isinstance(members, bool) or not isinstance(members, int) or not 1 <= members <= ops.KRIG_CS_MAX_MEMBERS:
+            raise ValueError(f"forward_ensemble: members must be an integer in [1, {ops.KRIG_CS_MAX_MEMBERS}] (got {members!r})")
+        if masked_frames.dim() != 5:
+            raise RuntimeError(f"{type(self).__name__}.forward_ensemble takes (B, T, 1, H, W) frames")
+        b, t, _, h, w = masked_frames.shape
+        ops.krig_cs_torus(h, w, self.embed)                  # ValueError before any launch
+        if not (masked_frames.is_cuda and masks.is_cuda):
+            raise RuntimeError(f"{type(self).__name__}.forward_ensemble runs on the HIP path only (CUDA tensors)")
+        if streams is None:
+            streams = torch.arange(b * t, dtype=torch.int64)
+        else:
+            streams = torch.as_tensor(streams)
+            if streams.dtype != torch.int64 or tuple(streams.shape) != (b, t):
+                raise ValueError(f"forward_ensemble: streams must be an int64 ({b}, {t}) tensor")
+        streams = streams.reshape(b * t).contiguous().to(masked_frames.device)
+        out = self._krige(masked_frames, masks, ensemble=(members, int(seed), streams))
+        return out["pred"], out["ens"]
 
     @torch.no_grad()
     def forward_uq(self, masked_frames, masks):
@@ -164,7 +201,7 @@ class KrigingGenerator(_ClassicalBase):
         """cross_validate's result with its site field filled: the systems are per frame, so leaving a site out is leaving a gauge out."""
         return _sites_of_frames(self.cross_validate(masked_frames, masks), masks)
 
-    def _krige(self, masked_frames, masks, predict=True, variance=False, loo=False):
+    def _krige(self, masked_frames, masks, predict=True, variance=False, loo=False, ensemble=None):
         b, t, _, h, w = masked_frames.shape
         pix, z, info, counts, shared = self._compact(masked_frames, masks)
         f, dev = b * t, masked_frames.device
@@ -178,8 +215,15 @@ class KrigingGenerator(_ClassicalBase):
         r = t if (shared and self.share_sets) else 1
         nsys = f // r
         np_ = max(ops.KRIG_TILE, _round_up(int(counts.max()), ops.KRIG_TILE))
-        inverse = variance or loo            # these also hold the factor's inverse: two workspaces per system
+        inverse = variance or loo or ensemble is not None    # these also hold the factor's inverse: two workspaces per system
         per = max(1, min(nsys, _FACTOR_BYTES // (np_ * np_ * 4 * (2 if inverse else 1))))
+        if ensemble is not None:             # the members' dual coefficients of one chunk of systems stay under the same bound
+            members, seed, streams = ensemble
+            per = max(1, min(per, _FACTOR_BYTES // (r * members * pix.shape[1] * 4)))
+            amp, clip = ops.krig_cs_spectrum(params, cand, self.variogram_model, h, w, self.embed)
+            self.last_ensemble = {"clip": clip, "embed": self.embed}
+            ens = torch.empty(f, members, h * w, device=dev, dtype=torch.float32)
+            ops.krig_cs_fields(amp, streams, seed, t, members, h, w, self.embed, ens)
         work = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
         winv = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32) if inverse else None
         status = torch.zeros(nsys, device=dev, dtype=torch.int32)
@@ -198,6 +242,9 @@ class KrigingGenerator(_ClassicalBase):
                 ops.krig_variance(winv, sol, pix, info, st, cand, params, self.variogram_model, s0 * r, r, t, ns, np_, h, w, var)
             if loo:
                 ops.krig_loo(winv, sol, alpha, z, info, st, cand, s0 * r, r, t, ns, np_, loo_pred, loo_var)
+            if ensemble is not None:
+                ca, cm = ops.krig_cs_weights(winv, sol, pix, z, info, st, cand, ens, s0 * r, r, t, ns, np_, members, h, w)
+                ops.krig_cs_predict(ca, cm, pix, z, info, st, cand, params, self.variogram_model, s0 * r, r, t, ns, np_, members, h, w, ens)
         out = {}
         if predict:
             out["pred"] = ops.krig_predict(pix, alpha, mean, info, params, self.variogram_model, r, t, h, w).view(b, t, 1, h, w)
@@ -209,6 +256,8 @@ class KrigingGenerator(_ClassicalBase):
             out["var"] = var.view(b, t, 1, h, w)
         if loo:
             out["loo"] = LOOResult(pix, z, loo_pred, loo_var, info[:f], status)
+        if ensemble is not None:
+            out["ens"] = ens.view(b, t, members, h, w)
         return out
 
 

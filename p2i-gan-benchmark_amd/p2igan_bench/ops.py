@@ -7,6 +7,7 @@ raises RuntimeError on failure.  No CPU path exists here by design.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -2004,6 +2005,141 @@ def krig_loo(Winv, sol, alpha, z, info, status, cand, f0, R, T, nsys, np_, pred,
     colsq = torch.empty(nsys, np_, device=z.device, dtype=torch.float64)
     _hip.check(lib.p2i_krig_loo(_ptr(Winv), _ptr(sol), _ptr(alpha), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), f0, R, T, nsys, np_, cap,
                                 _ptr(colsq), _ptr(pred), _ptr(var), _stream()), "p2i_krig_loo")
+
+
+# ---- conditional simulation of ordinary kriging (csrc/krig_cs.hip)
+KRIG_CS_MAX_SIDE = 512       # side of the embedding torus
+KRIG_CS_MAX_MEMBERS = 64
+KRIG_CS_EMBEDS = (2, 3, 4)
+_KRIG_CS_P_BYTES = 1 << 28   # the stage-1 workspace of one p2i_krig_cs_fields call stays under this
+_KRIG_CS_TABLES = {}
+
+
+def krig_cs_torus(H, W, embed):
+    """(Sy, Sx) = (embed H, embed W) of the embedding torus; ValueError for an embed outside 2..4 or a side past 512."""
+    if isinstance(embed, bool) or not isinstance(embed, int) or embed not in KRIG_CS_EMBEDS:
+        raise ValueError(f"model.ensemble.embed must be an integer in {list(KRIG_CS_EMBEDS)} (got {embed!r})")
+    Sy, Sx = embed * H, embed * W
+    if max(Sy, Sx) > KRIG_CS_MAX_SIDE:
+        raise ValueError(f"conditional simulation: the embedding torus {Sy} x {Sx} (embed {embed} of {H} x {W} frames) exceeds "
+                         f"{KRIG_CS_MAX_SIDE} on a side")
+    return Sy, Sx
+
+
+def _krig_cs_members(who, M):
+    if isinstance(M, bool) or not isinstance(M, int) or not 1 <= M <= KRIG_CS_MAX_MEMBERS:
+        raise ValueError(f"{who}: members must be an integer in [1, {KRIG_CS_MAX_MEMBERS}] (got {M!r})")
+
+
+def krig_cs_tables(H, W, embed, device):
+    """The host-built fp64 twiddles of one (H, W, embed), on `device` (kept): tw (Sy + Sx,) fp64 = cos(2 pi m / Sy), cos(2 pi m / Sx)
+    for the spectrum; tx (2, Sx, W) and ty (2, Sy, H) fp32 = cos, sin of 2 pi k w / Sx and 2 pi j h / Sy for the fields."""
+    key = (H, W, embed, str(device))
+    if key not in _KRIG_CS_TABLES:
+        Sy, Sx = krig_cs_torus(H, W, embed)
+
+        def pair(S, n):
+            ang = (torch.arange(S, dtype=torch.int64)[:, None] * torch.arange(n, dtype=torch.int64)[None, :]) % S
+            ang = ang.double() * (2.0 * math.pi / S)
+            return torch.stack([torch.cos(ang), torch.sin(ang)]).float().contiguous().to(device)
+
+        tw = torch.cat([torch.cos(torch.arange(S, dtype=torch.float64) * (2.0 * math.pi / S)) for S in (Sy, Sx)])
+        _KRIG_CS_TABLES[key] = {"Sy": Sy, "Sx": Sx, "tw": tw.contiguous().to(device), "tx": pair(Sx, W), "ty": pair(Sy, H)}
+    return _KRIG_CS_TABLES[key]
+
+
+def krig_cs_spectrum(params, cand, model, H, W, embed):
+    """amp (B, Sy, Sx) fp32, the amplitude of the circulant embedding of every sample's covariance, and clip (B,) fp64, the share of
+    the spectrum that was negative and clipped (0 where the embedding is exact; NaN for a degenerate sample)."""
+    lib = _hip.load()
+    _krig_t("krig_cs_spectrum", params, torch.float32)
+    B = params.shape[0]
+    if tuple(params.shape) != (B, 4):
+        raise RuntimeError("krig_cs_spectrum: params (B, 4) expected")
+    if cand is not None:
+        _krig_t("krig_cs_spectrum", cand, torch.int32, (B,))
+    tab = krig_cs_tables(H, W, embed, params.device)
+    Sy, Sx = tab["Sy"], tab["Sx"]
+    work = torch.empty(2, B, Sy, Sx, device=params.device, dtype=torch.float64)
+    amp = torch.empty(B, Sy, Sx, device=params.device, dtype=torch.float32)
+    clip = torch.empty(B, device=params.device, dtype=torch.float64)
+    _hip.check(lib.p2i_krig_cs_spectrum(_ptr(params), _ptr(cand), int(model), B, Sy, Sx, _ptr(tab["tw"]), _ptr(work), _ptr(amp), _ptr(clip),
+                                        _stream()), "p2i_krig_cs_spectrum")
+    return amp, clip
+
+
+def krig_cs_noise(seed, stream_id, q0, npairs, Sy, Sx, device):
+    """xi (npairs, Sy, Sx, 2) fp32: the complex standard normal of the member pairs q0 .. q0 + npairs - 1 of frame id stream_id."""
+    lib = _hip.load()
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("krig_cs_noise runs on the HIP path only (a CUDA device)")
+    if not (1 <= Sy <= KRIG_CS_MAX_SIDE and 1 <= Sx <= KRIG_CS_MAX_SIDE) or q0 < 0 or npairs < 1:
+        raise ValueError(f"krig_cs_noise: bad torus {Sy} x {Sx} or pairs {q0} + {npairs}")
+    xi = torch.empty(npairs, Sy, Sx, 2, device=device, dtype=torch.float32)
+    _hip.check(lib.p2i_krig_cs_noise(int(seed) & (2 ** 64 - 1), int(stream_id), int(q0), int(npairs), Sy, Sx, _ptr(xi), _stream()),
+               "p2i_krig_cs_noise")
+    return xi
+
+
+def krig_cs_fields(amp, streams, seed, T, M, H, W, embed, ens):
+    """The unconditional members U of every frame into ens (F, M, H*W), in place: pair q of frame f is DFT2(amp[f // T] xi)[:H, :W]
+    with xi of (seed, streams[f], q); member 2q is its real part, member 2q + 1 its imaginary part."""
+    lib = _hip.load()
+    _krig_cs_members("krig_cs_fields", M)
+    tab = krig_cs_tables(H, W, embed, ens.device)
+    Sy, Sx = tab["Sy"], tab["Sx"]
+    F = ens.shape[0]
+    _krig_t("krig_cs_fields", ens, torch.float32, (F, M, H * W))
+    _krig_t("krig_cs_fields", amp, torch.float32, (F // T, Sy, Sx))
+    _krig_t("krig_cs_fields", streams, torch.int64, (F,))
+    npairs = (M + 1) // 2
+    per = max(1, min(F, _KRIG_CS_P_BYTES // (npairs * 2 * Sy * W * 4)))
+    P = torch.empty(per * npairs * 2 * Sy * W, device=ens.device, dtype=torch.float32)
+    for f0 in range(0, F, per):
+        _hip.check(lib.p2i_krig_cs_fields(_ptr(amp), _ptr(streams), _ptr(tab["tx"]), _ptr(tab["ty"]), int(seed) & (2 ** 64 - 1), f0,
+                                          min(per, F - f0), T, M, H, W, Sy, Sx, _ptr(P), _ptr(ens), _stream()), "p2i_krig_cs_fields")
+
+
+def _krig_cs_sys(who, Winv_or_alpha, pix, z, info, status, cand, ens, f0, R, T, nsys, np_, M, H, W):
+    F, cap = pix.shape
+    _krig_cs_members(who, M)
+    _krig_t(who, pix, torch.int32)
+    _krig_t(who, z, torch.float32, (F, cap))
+    _krig_t(who, info, torch.int32, (2 * F,))
+    _krig_t(who, status, torch.int32, (nsys,))
+    if cand is not None:
+        _krig_t(who, cand, torch.int32, (F // T,))
+    _krig_t(who, ens, torch.float32, (F, M, H * W))
+    _krig_t(who, Winv_or_alpha, torch.float32)
+    _krig_sys(who, f0, R, T, nsys, F, np_, cap)
+    return cap
+
+
+def krig_cs_weights(Winv, sol, pix, z, info, status, cand, ens, f0, R, T, nsys, np_, M, H, W):
+    """(alpha (nsys, R*M, cap), mu (nsys, R*M)): the kriging of the residuals z - U(gauges) of every member of the systems' frames,
+    ens holding U; column t*M + m of a system is member m of its frame t."""
+    lib = _hip.load()
+    cap = _krig_cs_sys("krig_cs_weights", Winv, pix, z, info, status, cand, ens, f0, R, T, nsys, np_, M, H, W)
+    _krig_t("krig_cs_weights", sol, torch.float64, (nsys, R + 1, np_))
+    if Winv.numel() < nsys * np_ * np_:
+        raise RuntimeError("krig_cs_weights: inverse workspace too small")
+    alpha = torch.empty(nsys, R * M, cap, device=z.device, dtype=torch.float32)
+    mu = torch.empty(nsys, R * M, device=z.device, dtype=torch.float32)
+    _hip.check(lib.p2i_krig_cs_weights(_ptr(Winv), _ptr(sol), _ptr(pix), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), _ptr(ens), f0, R, T,
+                                       nsys, np_, M, H, W, cap, _ptr(alpha), _ptr(mu), _stream()), "p2i_krig_cs_weights")
+    return alpha, mu
+
+
+def krig_cs_predict(alpha, mu, pix, z, info, status, cand, params, model, f0, R, T, nsys, np_, M, H, W, ens):
+    """ens[f][m] = U + mu + sum_i alpha_i c0(p, x_i) for the members of the systems' frames, in place; z on a gauge pixel; NaN for a
+    system without a model."""
+    lib = _hip.load()
+    cap = _krig_cs_sys("krig_cs_predict", alpha, pix, z, info, status, cand, ens, f0, R, T, nsys, np_, M, H, W)
+    _krig_t("krig_cs_predict", alpha, torch.float32, (nsys, R * M, cap))
+    _krig_t("krig_cs_predict", mu, torch.float32, (nsys, R * M))
+    _krig_t("krig_cs_predict", params, torch.float32, (pix.shape[0] // T, 4))
+    _hip.check(lib.p2i_krig_cs_predict(_ptr(alpha), _ptr(mu), _ptr(pix), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), _ptr(params),
+                                       int(model), f0, R, T, nsys, np_, M, H, W, cap, _ptr(ens), _stream()), "p2i_krig_cs_predict")
 
 
 def idw_loo(pix, z, info, power=2.0):

@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 from p2igan_bench.data import zarr_lite  # noqa: E402
 from p2igan_bench.data.dataloader import P2IDataModule  # noqa: E402
-from p2igan_bench.inference import infer_event, infer_event_chunks, infer_event_variance  # noqa: E402
+from p2igan_bench.inference import infer_event, infer_event_chunks, infer_event_ensemble, infer_event_variance  # noqa: E402
 from p2igan_bench.models import CLASSICAL, build_generator  # noqa: E402
 from p2igan_bench.models.classical import LOCAL  # noqa: E402
 
@@ -42,6 +42,10 @@ def parse_args(argv=None):
     p.add_argument("--overwrite", action="store_true")
     p.add_argument("--variance-output", type=Path, default=None,
                    help="kriging, localkriging and locallagkriging only: a second zarr with the kriging variance x output-scale^2 under the same event keys")
+    p.add_argument("--ensemble-output", type=Path, default=None,
+                   help="kriging only: a directory of member_%%03d.zarr, the conditional-simulation members laid out as --output is")
+    p.add_argument("--members", type=int, default=None, help="ensemble members per frame (1..64), with --ensemble-output")
+    p.add_argument("--ensemble-seed", type=int, default=0)
     p.add_argument("--log-level", type=str, default="INFO")
     return p.parse_args(argv)
 
@@ -67,6 +71,14 @@ def main(argv=None):
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.INFO), format="%(asctime)s | %(levelname)s | %(message)s")
     with args.config.open() as f:
         cfg = json.load(f)
+    if args.ensemble_output is not None:         # refused before the device, the data or a checkpoint is touched
+        asked = cfg.get("model", {}).get("name", "model")
+        if str(asked).lower() != "kriging":
+            raise RuntimeError(f"--ensemble-output needs model.name 'kriging', the model with a forward_ensemble (got '{asked}')")
+        if args.members is None or not 1 <= args.members <= 64:
+            raise ValueError(f"--ensemble-output needs --members in 1..64 (got {args.members})")
+    elif args.members is not None:
+        raise ValueError("--members needs --ensemble-output")
     torch.manual_seed(cfg.get("seed", 42))
     np.random.seed(cfg.get("seed", 42))
     if args.data_root is not None:
@@ -92,6 +104,10 @@ def main(argv=None):
         if not args.overwrite:
             raise FileExistsError(f"Output already exists: {args.variance_output}")
         shutil.rmtree(args.variance_output)
+    if args.ensemble_output is not None and args.ensemble_output.exists():
+        if not args.overwrite:
+            raise FileExistsError(f"Output already exists: {args.ensemble_output}")
+        shutil.rmtree(args.ensemble_output)
     group = zarr_lite.Group(str(out), "w")
     group.attrs.update({"config_path": str(args.config), "checkpoint": None if ckpt is None else str(ckpt), "model_name": name,
                         "data_root": cfg.get("data", {}).get("test", {}).get("data_root"), "passes": int(args.passes),
@@ -101,7 +117,7 @@ def main(argv=None):
         state = torch.load(ckpt, map_location=dev, weights_only=True)
         G.load_state_dict(state["generator"] if isinstance(state, dict) and "generator" in state else state)
     G.eval()
-    results, variances = {}, {}
+    results, variances, ensembles, clip_max = {}, {}, {}, 0.0
     for p in range(max(1, args.passes)):
         t0 = time.time()
         for i, batch in enumerate(loader):
@@ -113,6 +129,11 @@ def main(argv=None):
             key = f"event_{i + 1:02d}"
             if args.variance_output is not None and p == 0:       # a function of gauge positions and variogram: the same every pass
                 variances[key] = infer_event_variance(G, masked, masks, max(1, args.stride), args.output_scale).cpu().numpy()
+            if args.ensemble_output is not None and p == 0:       # a function of (seed, event, frame, member): the same every pass
+                ens = infer_event_ensemble(G, masked, masks, args.members, args.ensemble_seed, i, max(1, args.stride), args.output_scale)
+                ensembles[key] = ens.clamp(min=0.0).cpu().numpy()
+                clip = G.last_ensemble["clip"]
+                clip_max = max(clip_max, float(clip[~clip.isnan()].max()) if bool((~clip.isnan()).any()) else 0.0)
             results[key] = comp if p == 0 else results[key] + (comp - results[key]) / float(p + 1)
             if (i + 1) % max(1, args.log_every) == 0:
                 logging.info("Pass %d | %d samples | %.2f samples/sec", p + 1, i + 1, (i + 1) / max(time.time() - t0, 1e-6))
@@ -125,6 +146,15 @@ def main(argv=None):
         for key, v in variances.items():
             vgroup.create_dataset(key, v.astype(np.float32), chunks=v.shape)
         logging.info("Kriging variance saved to %s", args.variance_output)
+    if args.ensemble_output is not None:
+        for m in range(args.members):
+            mgroup = zarr_lite.Group(str(args.ensemble_output / f"member_{m:03d}.zarr"), "w")
+            mgroup.attrs.update(dict(group.attrs, member=m, members=int(args.members), seed=int(args.ensemble_seed), embed=int(G.embed),
+                                     clip_share_max=clip_max))
+            for key, ens in ensembles.items():
+                comp = np.ascontiguousarray(ens[:, m:m + 1])
+                mgroup.create_dataset(key, comp.astype(np.float32), chunks=comp.shape)
+        logging.info("%d ensemble members saved to %s", args.members, args.ensemble_output)
     logging.info("Inference completed. Output saved to %s", out)
 
 
