@@ -12,8 +12,9 @@
 namespace p2i {
 namespace {
 
-constexpr int N_CAND = 25;        // range candidates a_c = w 2^((c - 6) / 3)
-constexpr int RC = 8;             // right-hand sides fed from one covariance evaluation
+constexpr int N_RANGE = 25;       // range candidates a_c = w 2^((c - 6) / 3)
+constexpr int N_KAPPA = 17;       // anisotropy candidates kappa_q = 2^((q - 6) / 2) px / frame (space-time fit)
+constexpr int RC = 8;            // right-hand sides fed from one covariance evaluation
 
 // ---- compaction: one workgroup per frame.  pix / z [F][cap] (entries past the count are zero), info[f] = count (may exceed cap:
 // the host refuses), info[F + f] = 1 if the frame's mask pattern differs from that of frame 0 of its sample
@@ -85,66 +86,81 @@ __global__ __launch_bounds__(BIN_THREADS) void krig_bins_kernel(const int* __res
   bins.reduce(n_lags, part, (size_t)f * nch + ch);
 }
 
-// ---- fit: one workgroup per sample.  Adds the sample's partial bins in order, then thread c < 25 fits (nugget, psill) for the range
-// candidate a_c by count-weighted least squares; thread 0 keeps the smallest SSE (lowest c on a tie).
-// bins [B][n_lags][3] (raw sums), fit [B][4] = (nugget, psill, range, sse), cand [B] (-1: degenerate), params [B][4] fp32 for the
-// kriging kernels (a harmless (0, 1, w) when degenerate)
-__global__ __launch_bounds__(64) void krig_fit_kernel(const double* __restrict__ part, int nparts, int n_lags, double lagw, int model,
-                                                      double* __restrict__ bins, double* __restrict__ fit, int* __restrict__ cand,
-                                                      float* __restrict__ params) {
-  __shared__ double sn[MAX_LAGS], sgam[MAX_LAGS], shb[MAX_LAGS];
-  __shared__ double c_sse[N_CAND], c_nug[N_CAND], c_ps[N_CAND];
-  __shared__ int c_ok[N_CAND];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  for (int k = tid; k < n_lags; k += 64) {
+// ---- fit, spatial (ST = false) and space-time (ST = true): one workgroup per sample.  Adds the chunks' partial bins in order, then
+// candidate q 25 + c fits (nugget, psill) of gamma = nugget + psill g(sqrt(hbar^2 + (kappa_q u)^2) / a_c) by the count-weighted normal
+// equations and fallbacks of krig_common.h; thread 0 keeps the smallest SSE (lowest q 25 + c on a tie, so that bins of u = 0 alone
+// give the spatial fit with q = 0).  The spatial fit has the temporal lag u = 0 only (nu = 1, nch = its frames' chunks in order) and
+// the 25 candidates of q = 0, in which kappa does not appear.
+// part [B][nu][nch][n_lags][3], bins [B][nu][n_lags][3] (raw sums), cand [B] = q 25 + c (-1: degenerate), params [B][4] fp32 for the
+// kriging kernels.  ST: fit [B][5] = (nugget, psill, range, kappa, sse), params = (nugget, psill, range, kappa), a harmless (0, 1, w, 1)
+// when degenerate; spatial: fit [B][4] = (nugget, psill, range, sse), params = (nugget, psill, range, 0), (0, 1, w, 0) when degenerate
+template <bool ST>
+__global__ __launch_bounds__(ST ? 256 : 64) void krig_fit_kernel(const double* __restrict__ part, int nu, int nch, int n_lags, double lagw,
+                                                                 int model, double* __restrict__ bins, double* __restrict__ fit,
+                                                                 int* __restrict__ cand, float* __restrict__ params) {
+  constexpr int NT = ST ? 256 : 64, NB = (ST ? MAX_TLAGS + 1 : 1) * MAX_LAGS, NC = (ST ? N_KAPPA : 1) * N_RANGE, NF = ST ? 5 : 4;
+  __shared__ double sn[NB], sgam[NB], shb[NB];
+  __shared__ double c_sse[NC], c_nug[NC], c_ps[NC];
+  __shared__ int c_ok[NC];
+  const int b = blockIdx.x, tid = threadIdx.x, nb = nu * n_lags;
+  for (int e = tid; e < nb; e += NT) {
+    const int u = ST ? e / n_lags : 0, k = ST ? e % n_lags : e;
     double c = 0.0, g = 0.0, h = 0.0;
-    for (int p = 0; p < nparts; ++p) {
-      const double* q = part + (((size_t)b * nparts + p) * n_lags + k) * 3;
+    for (int p = 0; p < nch; ++p) {
+      const double* q = part + ((((size_t)b * nu + u) * nch + p) * n_lags + k) * 3;
       c += q[0];
       g += q[1];
       h += q[2];
     }
-    double* o = bins + ((size_t)b * n_lags + k) * 3;
+    double* o = bins + ((size_t)b * nb + e) * 3;
     o[0] = c;
     o[1] = g;
     o[2] = h;
-    sn[k] = c;
-    sgam[k] = c > 0.0 ? g / c : 0.0;
-    shb[k] = c > 0.0 ? h / c : 0.0;
+    sn[e] = c;
+    sgam[e] = c > 0.0 ? g / c : 0.0;
+    shb[e] = c > 0.0 ? h / c : 0.0;
   }
   __syncthreads();
-  if (tid < N_CAND) {
-    const double a = lagw * exp2((double)(tid - 6) / 3.0);
-    const FitCand r = vario_fit_candidate(sn, sgam, n_lags, [&](int k) { return g_d(shb[k] / a, model); });
-    c_ok[tid] = r.ok;
-    c_sse[tid] = r.sse;
-    c_nug[tid] = r.nug;
-    c_ps[tid] = r.ps;
+  for (int cd = tid; cd < NC; cd += NT) {
+    const double kap = exp2((double)(cd / N_RANGE - 6) * 0.5);
+    const double a = lagw * exp2((double)(cd % N_RANGE - 6) / 3.0);
+    const FitCand r = vario_fit_candidate(sn, sgam, nb, [&](int e) {
+      if constexpr (!ST) return g_d(shb[e] / a, model);
+      const double ku = kap * (double)(e / n_lags);
+      const double d = e < n_lags ? shb[e] : sqrt(shb[e] * shb[e] + ku * ku);
+      return g_d(d / a, model);
+    });
+    c_ok[cd] = r.ok;
+    c_sse[cd] = r.sse;
+    c_nug[cd] = r.nug;
+    c_ps[cd] = r.ps;
   }
   __syncthreads();
   if (tid == 0) {
     int best = -1;
-    for (int c = 0; c < N_CAND; ++c)
+    for (int c = 0; c < NC; ++c)
       if (c_ok[c] && (best < 0 || c_sse[c] < c_sse[best])) best = c;
-    double* o = fit + (size_t)b * 4;
+    double* o = fit + (size_t)b * NF;
     float* pf = params + (size_t)b * 4;
     cand[b] = best;
     if (best >= 0) {
-      const double a = lagw * exp2((double)(best - 6) / 3.0);
+      const double kap = exp2((double)(best / N_RANGE - 6) * 0.5);
+      const double a = lagw * exp2((double)(best % N_RANGE - 6) / 3.0);
       o[0] = c_nug[best];
       o[1] = c_ps[best];
       o[2] = a;
-      o[3] = c_sse[best];
+      if constexpr (ST) o[3] = kap;
+      o[NF - 1] = c_sse[best];
       pf[0] = (float)c_nug[best];
       pf[1] = (float)c_ps[best];
       pf[2] = (float)a;
-      pf[3] = 0.f;
+      pf[3] = ST ? (float)kap : 0.f;
     } else {
-      o[0] = o[1] = o[2] = o[3] = 0.0;
+      for (int k = 0; k < NF; ++k) o[k] = 0.0;
       pf[0] = 0.f;
       pf[1] = 1.f;
       pf[2] = (float)lagw;
-      pf[3] = 0.f;
+      pf[3] = ST ? 1.f : 0.f;
     }
   }
 }
@@ -332,14 +348,13 @@ __global__ __launch_bounds__(256) void krig_dual_kernel(const double* __restrict
   const double* v = u + (size_t)(t + 1) * np;
   const float* zf = z + (size_t)f * cap;
   float* af = alpha + (size_t)f * cap;
-  const bool fallback = n == 0 || status[s] != 0 || (cand != nullptr && cand[f / T] < 0);
-  double su = 0.0, sv = 0.0, sz = 0.0;
+  const bool fallback = n == 0 || no_model(status[s], cand, f / T);
+  const double su = sum_u(u, n, red);
+  double sv = 0.0, sz = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) {
-    su += u[i];
     sv += v[i];
     sz += (double)zf[i];
   }
-  su = block_sum_d(su, red);
   sv = block_sum_d(sv, red);
   sz = block_sum_d(sz, red);
   const double m = fallback ? (n > 0 ? sz / (double)n : 0.0) : sv / su;
@@ -445,6 +460,15 @@ void p2i::krig_factor_tiles(float* L, int nsys, int np, int* status, hipStream_t
   }
 }
 
+// the one variogram fit (krig_common.h): p2i_krig_fit here and p2i_stkrig_fit of stkrig.hip
+void p2i::krig_fit_launch(bool st, const double* part, int B, int nu, int nch, int n_lags, double lagw, int model, double* bins,
+                          double* fit, int* cand, float* params, hipStream_t s) {
+  if (st)
+    P2I_LAUNCH(krig_fit_kernel<true>, dim3(B), dim3(256), 0, s, part, nu, nch, n_lags, lagw, model, bins, fit, cand, params);
+  else
+    P2I_LAUNCH(krig_fit_kernel<false>, dim3(B), dim3(64), 0, s, part, nu, nch, n_lags, lagw, model, bins, fit, cand, params);
+}
+
 extern "C" int p2i_krig_compact(const float* masked, const float* mask, int B, int T, int H, int W, int cap, int* pix, float* z, int* info,
                                 void* stream) {
   P2I_REQUIRE(masked && mask && pix && z && info, "null pointer");
@@ -467,9 +491,10 @@ extern "C" int p2i_krig_bins(const int* pix, const float* z, const int* counts, 
 extern "C" int p2i_krig_fit(const double* part, int B, int nparts, int n_lags, double lag_width, int model, double* bins, double* fit,
                             int* cand, float* params, void* stream) {
   P2I_REQUIRE(part && bins && fit && cand && params, "null pointer");
-  P2I_REQUIRE(B > 0 && nparts > 0 && n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "bad fit shape");
+  P2I_REQUIRE(B > 0 && nparts > 0, "bad fit shape");
+  if (int rc = krig_lags_check(n_lags, lag_width)) return rc;
   if (int rc = krig_model_check(model)) return rc;
-  P2I_LAUNCH(krig_fit_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, part, nparts, n_lags, lag_width, model, bins, fit, cand, params);
+  krig_fit_launch(false, part, B, 1, nparts, n_lags, lag_width, model, bins, fit, cand, params, (hipStream_t)stream);
   return launch_status();
 }
 

@@ -1,6 +1,6 @@
-// What the kriging files (classical.hip, krig_uq.hip, stkrig.hip, stkrig_loso.hip, lagkrig.hip, lkrig.hip) share: the tile and size
-// limits, the covariance function and the space-time distances, the fixed-tree fp64 block sum, the variogram's bin image and fit
-// candidate, the covariance tile writer and the host-side checks.
+// What the kriging files (classical.hip, krig_uq.hip, krig_cs.hip, stkrig.hip, stkrig_loso.hip, lagkrig.hip, lkrig.hip) share: the tile
+// and size limits, the covariance function and the space-time distances, the fixed-tree fp64 block sum, the "no model" rule, the
+// variogram's bin image and fit candidate, the covariance tile writer and the host-side checks.  krig_mfma.h adds the c0 slab core.
 #pragma once
 #include "common.h"
 
@@ -26,6 +26,19 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {   // red:
   const double r = red[0];
   __syncthreads();
   return r;
+}
+
+// u^T 1 over the n gauges of a system (u = K^-1 1, row 0 of its solutions), in every thread of the 256
+__device__ __forceinline__ double sum_u(const double* __restrict__ u, int n, double* red) {
+  double su = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) su += u[i];
+  return block_sum_d(su, red);
+}
+
+// a system has no model: its factorisation met a non-positive pivot (status), or the fit of its sample b is degenerate (cand, null
+// with fixed parameters).  Each caller joins its own count condition (no gauges, fewer than 2, one site only).
+__device__ __forceinline__ bool no_model(int status, const int* __restrict__ cand, int b) {
+  return status != 0 || (cand != nullptr && cand[b] < 0);
 }
 
 // C(h) = psill (1 - g(h / a)): exponential g(r) = 1 - exp(-r); spherical g(r) = 1.5 r - 0.5 r^3 below 1, 1 beyond
@@ -188,6 +201,12 @@ static inline int krig_sys_check(int f0, int R, int T, int nsys, int np, int cap
   P2I_REQUIRE(np > 0 && np % TS == 0 && np <= cap && cap <= MAX_NP, "padded size %d must be a multiple of %d within cap %d", np, TS, cap);
   return P2I_OK;
 }
+
+// classical.hip: the variogram fit of B samples from part [B][nu][nch][n_lags][3] (the fit kernel's comment has the outputs).
+// st = false: range candidates only, nu = 1, fit [B][4]; st = true: (kappa, range) candidates, fit [B][5].  The caller has checked
+// the arguments and checks launch_status().
+void krig_fit_launch(bool st, const double* part, int B, int nu, int nch, int n_lags, double lagw, int model, double* bins, double* fit,
+                     int* cand, float* params, hipStream_t s);
 
 // classical.hip: the right-looking tiled Cholesky (panel, trailing update per 32 columns) over nsys systems whose lower tiles are
 // already built in L [nsys][np][np]; status[s] is set where a pivot is not > 0.  The caller checks launch_status().

@@ -7,23 +7,15 @@
 // Number formats: the spectrum is fp64; the noise, both DFT products and the predictor run in fp32 on v_mfma_f32_32x32x2_f32 (a k-ordered
 // fmaf chain per output); W is fp32 and the conditioning sums (W r, W^T y, u^T r) are fp64.  Every sum has a fixed order and there are
 // no atomics: results are identical from run to run.
-#include "krig_common.h"
+#include "krig_mfma.h"
 
 namespace p2i {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CS_MAX_S = 512;      // side of the embedding torus: a row of it in LDS as fp64
 constexpr int CS_MAX_M = 64;       // members per frame
 constexpr int WU = 8;              // loads of W a thread of the weights kernel keeps in flight
 constexpr int CB = 4;             // 32-column tiles of alpha per workgroup of the predictor (section 16's row-block balance)
-constexpr int PT = 128;            // pixels per workgroup: one 32-pixel MFMA column tile per wave
-constexpr int SLAB_LD = PT + 32;   // row stride of the c0 slab (krig_uq.hip)
-constexpr int A_LD = TS + 1;       // row stride of a staged 32 x 32 operand tile: lanes walk rows, so an odd stride
-
-// row of accumulator register e of a 32 x 32 MFMA result in lane half lhi; the column is lane & 31
-__device__ __forceinline__ int acc_row(int e, int lhi) { return (e & 3) + 8 * (e >> 2) + 4 * lhi; }
 
 // ---- Philox4x32-10 (Salmon et al. 2011): the first two output words of counter (c0, c1, c2, c3) under key (k0, k1)
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned& r0,
@@ -264,7 +256,7 @@ __global__ __launch_bounds__(256) void cs_weights_kernel(const float* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float* al = alpha + (size_t)s * ncols * cap;
   float* ms = mu + (size_t)s * ncols;
-  if (n == 0 || status[s] != 0 || (cand != nullptr && cand[fs / T] < 0)) {
+  if (n == 0 || no_model(status[s], cand, fs / T)) {
     for (int c = 0; c < nc && c0 + c < ncols; ++c) {
       for (int i = tid; i < cap; i += 256) al[(size_t)(c0 + c) * cap + i] = 0.f;
       if (tid == 0) ms[c0 + c] = 0.f;
@@ -274,9 +266,7 @@ __global__ __launch_bounds__(256) void cs_weights_kernel(const float* __restrict
   const double* u = sol + (size_t)s * (R + 1) * np;
   const float* Ws = Wi + (size_t)s * np * np;
   const int* gp = pix + (size_t)fs * cap;
-  double su = 0.0;
-  for (int i = tid; i < n; i += 256) su += u[i];
-  su = block_sum_d(su, red);
+  const double su = sum_u(u, n, red);
   double muc[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -360,11 +350,11 @@ __global__ __launch_bounds__(256) void cs_weights_kernel(const float* __restrict
   }
 }
 
-// ---- conditional members of system s on a tile of PT pixels: D = alpha c0 on v_mfma_f32_32x32x2_f32 with A = alpha (m = column: frame
-// t = col / M, member col % M of the system), B = c0 (n = pixel), K = gauge; wave w owns pixels 32 w .. 32 w + 31 and CB column tiles.
-// Per 32-gauge slab all threads evaluate c0 [32][PT] into LDS exactly as krig_variance_kernel does (k(p) never touches HBM) next to
-// the group's alpha tiles; c0 is evaluated once per (pixel, gauge) for up to 32 CB outputs.  The epilogue adds U (read from the
-// buffer it writes) and mu; a gauge pixel is written as the frame's z there; a system without a model is written as NaN.
+// ---- conditional members of system s on a tile of PT pixels: D = alpha c0 on the slab core of krig_mfma.h with A = alpha (m = column:
+// frame t = col / M, member col % M of the system), K = gauge; a wave holds CB column tiles, blockIdx.z walks the column groups.  Per
+// 32-gauge slab the c0 slab is filled next to the group's alpha tiles (zeros past the columns); c0 is evaluated once per (pixel,
+// gauge) for up to 32 CB outputs.  The epilogue adds U (read from the buffer it writes) and mu; a gauge pixel is written as the
+// frame's z there; a system without a model is written as NaN.
 __global__ __launch_bounds__(256, 2) void cs_predict_kernel(const float* __restrict__ alpha, const float* __restrict__ mu,
                                                             const int* __restrict__ pix, const float* __restrict__ z,
                                                             const int* __restrict__ counts, const int* __restrict__ status,
@@ -378,7 +368,7 @@ __global__ __launch_bounds__(256, 2) void cs_predict_kernel(const float* __restr
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
   const int p0 = blockIdx.x * PT;
   float* out = ens + (size_t)fs * M * HW;
-  if (n == 0 || status[s] != 0 || (cand != nullptr && cand[b] < 0)) {       // no model: NaN
+  if (n == 0 || no_model(status[s], cand, b)) {       // NaN
     if (tid < PT && p0 + tid < HW)
       for (int c = cg; c < min(cg + CB * TS, ncols); ++c) out[(size_t)c * HW + p0 + tid] = __builtin_nanf("");
     return;
@@ -387,10 +377,9 @@ __global__ __launch_bounds__(256, 2) void cs_predict_kernel(const float* __restr
   const float* al = alpha + (size_t)s * ncols * cap;
   const float* ms = mu + (size_t)s * ncols;
   const int* gp = pix + (size_t)fs * cap;
-  const int bp = tid & (PT - 1), bg = tid >> 7;
+  const int bp = tid & (PT - 1);
   const int p = min(p0 + bp, HW - 1);
   const int py = p / W, px = p % W;
-  const int ar = tid >> 3, ac = (tid & 7) * 4;     // this thread's float4 of a staged alpha tile
   if (tid < PT) hit[tid] = -1;
   f32x16 acc[CB];
 #pragma unroll
@@ -400,38 +389,15 @@ __global__ __launch_bounds__(256, 2) void cs_predict_kernel(const float* __restr
   const int nt = (n + TS - 1) / TS;
   for (int sb = 0; sb < nt; ++sb) {
     __syncthreads();
-#pragma unroll 1
-    for (int j = 0; j < TS / 2; ++j) {
-      const int g = bg * (TS / 2) + j, i = sb * TS + g;
-      float c0 = 0.f;
-      if (i < n) {
-        const int gq = gp[i];
-        const int dy = py - (gq >> 16), dx = px - (gq & 0xffff);
-        const int d2 = dy * dy + dx * dx;
-        c0 = cov_f(sqrtf((float)d2), psill, a, model) + (d2 == 0 ? nug : 0.f);
-        if (d2 == 0) hit[bp] = i;                  // gauge pixels are distinct: one writer per pixel
-      }
-      slab[g][bp] = c0;
-    }
+    slab_fill(slab, gp, n, sb, py, px, nug, psill, a, model, [&](int i, float, bool at) {
+      if (at) hit[bp] = i;                         // gauge pixels are distinct: one writer per pixel
+    });
 #pragma unroll
-    for (int r = 0; r < CB; ++r) {
-      const int col = cg + r * TS + ar;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (col < ncols) v = *reinterpret_cast<const float4*>(al + (size_t)col * cap + sb * TS + ac);
-      At[r][ar][ac] = v.x;
-      At[r][ar][ac + 1] = v.y;
-      At[r][ar][ac + 2] = v.z;
-      At[r][ar][ac + 3] = v.w;
-    }
+    for (int r = 0; r < CB; ++r) tile_stage(At[r], al + (size_t)(cg + r * TS) * cap + sb * TS, cap, ncols - (cg + r * TS));
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < CB; ++r) {
-      if (cg + r * TS < ncols) {
-#pragma unroll
-        for (int kk = 0; kk < TS / 2; ++kk)
-          acc[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(At[r][l31][2 * kk + lhi], slab[2 * kk + lhi][wave * 32 + l31], acc[r], 0, 0, 0);
-      }
-    }
+    for (int r = 0; r < CB; ++r)
+      if (cg + r * TS < ncols) acc[r] = tile_mfma(At[r], slab, acc[r]);
   }
   const int pi = wave * 32 + l31;
   if (p0 + pi < HW) {

@@ -6,17 +6,12 @@
 // Number formats: W is fp32 (fmaf tile products); the variance GEMM runs on the f32 matrix pipe with fp32 accumulators down the
 // gauge axis, and everything after it (the squares, u^T k, the formula) is fp64; column square-sums, LOO and scores are fp64.  Every
 // sum has a fixed order and there are no atomics: results are identical from run to run.
-#include "krig_common.h"
+#include "krig_mfma.h"
 
 namespace p2i {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int RB = 4;              // row tiles of W per row block of the variance GEMM (section 16: exponentials against MFMA cycles)
-constexpr int PT = 128;            // pixels per workgroup: one 32-pixel MFMA column tile per wave
-constexpr int SLAB_LD = PT + 32;   // row stride of the c0 slab: the two k rows a wave reads fall into different halves of the 64 banks
-constexpr int A_LD = TS + 1;       // row stride of a staged W tile: lanes walk rows, so an odd stride
 
 // ---- W tile (i, i) = inverse of the factor's diagonal tile, and zeros in the tiles right of it.  Thread c < 32 solves T x = e_c by
 // forward substitution with x in registers and T read as LDS broadcasts.  Identity padding inverts to identity exactly.
@@ -111,12 +106,10 @@ __global__ __launch_bounds__(256) void krig_invcol_kernel(const float* __restric
   }
 }
 
-// ---- variance map of system s (gauges of frame fs = f0 + s R) on a tile of PT pixels.  D = W k on v_mfma_f32_32x32x2_f32: A = W
-// (m = gauge row), B = c0 (n = pixel), K = gauge column; wave w owns pixels 32 w .. 32 w + 31 and RB row tiles at a time.  Per
-// 32-gauge slab all threads evaluate c0 [32][PT] into LDS (thread -> pixel tid & 127, gauges 16 (tid >> 7) ..+15) next to the row
-// block's W tiles (one float4 per thread and tile), and the waves feed both to the MFMAs; tiles right of the diagonal are skipped.  When a row block's last slab is
-// done its accumulators are squared and added down the gauge axis in fp64.  The last row block's sweep sees every slab once: u^T k
-// and the gauge-pixel flag ride on it.
+// ---- variance map of system s (gauges of frame fs = f0 + s R) on a tile of PT pixels.  D = W k on the slab core of krig_mfma.h: A =
+// W (m = gauge row), K = gauge column; a wave holds RB row tiles at a time.  Per 32-gauge slab the c0 slab is filled next to the row
+// block's W tiles; tiles right of the diagonal are skipped.  When a row block's last slab is done its accumulators are squared and
+// added down the gauge axis in fp64.  The last row block's sweep sees every slab once: u^T k and the gauge-pixel flag ride on it.
 __global__ __launch_bounds__(256, 4) void krig_variance_kernel(const float* __restrict__ Wi, const double* __restrict__ sol,
                                                             const int* __restrict__ pix, const int* __restrict__ counts,
                                                             const int* __restrict__ status, const int* __restrict__ cand,
@@ -130,7 +123,7 @@ __global__ __launch_bounds__(256, 4) void krig_variance_kernel(const float* __re
   const int n = min(counts[fs], np);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
   const int p0 = blockIdx.x * PT;
-  if (n == 0 || status[s] != 0 || (cand != nullptr && cand[b] < 0)) {       // no model: NaN
+  if (n == 0 || no_model(status[s], cand, b)) {       // NaN
     if (tid < PT && p0 + tid < HW)
       for (int t = 0; t < R; ++t) var[(size_t)(fs + t) * HW + p0 + tid] = __builtin_nanf("");
     return;
@@ -139,13 +132,9 @@ __global__ __launch_bounds__(256, 4) void krig_variance_kernel(const float* __re
   const double* u = sol + (size_t)s * (R + 1) * np;
   const float* Ws = Wi + (size_t)s * np * np;
   const int* gp = pix + (size_t)fs * cap;
-  double su = 0.0;
-  for (int i = tid; i < n; i += 256) su += u[i];
-  su = block_sum_d(su, red);
-  const int bp = tid & (PT - 1), bg = tid >> 7;
-  const int p = min(p0 + bp, HW - 1);
+  const double su = sum_u(u, n, red);
+  const int p = min(p0 + (tid & (PT - 1)), HW - 1);
   const int py = p / W, px = p % W;
-  const int ar = tid >> 3, ac = (tid & 7) * 4;     // this thread's float4 of a staged W tile
   const int nt = (n + TS - 1) / TS;          // rows and columns past the gauges are identity against k = 0
   double q = 0.0, uk = 0.0;
   int hit = 0;
@@ -159,41 +148,19 @@ __global__ __launch_bounds__(256, 4) void krig_variance_kernel(const float* __re
       for (int e = 0; e < 16; ++e) acc[r][e] = 0.f;
     for (int sb = 0; sb < rb0 + rbn; ++sb) {
       __syncthreads();
-#pragma unroll 1
-      for (int j = 0; j < TS / 2; ++j) {
-        const int g = bg * (TS / 2) + j, i = sb * TS + g;
-        float c0 = 0.f;
-        if (i < n) {
-          const int gq = gp[i];
-          const int dy = py - (gq >> 16), dx = px - (gq & 0xffff);
-          const int d2 = dy * dy + dx * dx;
-          c0 = cov_f(sqrtf((float)d2), psill, a, model) + (d2 == 0 ? nug : 0.f);
-          if (last) {
-            uk = fma(u[i], (double)c0, uk);
-            hit |= d2 == 0;
-          }
+      slab_fill(slab, gp, n, sb, py, px, nug, psill, a, model, [&](int i, float c0, bool at) {
+        if (last) {
+          uk = fma(u[i], (double)c0, uk);
+          hit |= at;
         }
-        slab[g][bp] = c0;
-      }
+      });
 #pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        if (r < rbn && rb0 + r >= sb) {
-          const float4 v = *reinterpret_cast<const float4*>(Ws + (size_t)((rb0 + r) * TS + ar) * np + sb * TS + ac);
-          At[r][ar][ac] = v.x;
-          At[r][ar][ac + 1] = v.y;
-          At[r][ar][ac + 2] = v.z;
-          At[r][ar][ac + 3] = v.w;
-        }
-      }
+      for (int r = 0; r < RB; ++r)
+        if (r < rbn && rb0 + r >= sb) tile_stage(At[r], Ws + (size_t)(rb0 + r) * TS * np + sb * TS, np, TS);
       __syncthreads();
 #pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        if (r < rbn && rb0 + r >= sb) {
-#pragma unroll
-          for (int kk = 0; kk < TS / 2; ++kk)
-            acc[r] = __builtin_amdgcn_mfma_f32_32x32x2f32(At[r][l31][2 * kk + lhi], slab[2 * kk + lhi][wave * 32 + l31], acc[r], 0, 0, 0);
-        }
-      }
+      for (int r = 0; r < RB; ++r)
+        if (r < rbn && rb0 + r >= sb) acc[r] = tile_mfma(At[r], slab, acc[r]);
     }
 #pragma unroll
     for (int r = 0; r < RB; ++r)
@@ -249,10 +216,8 @@ __global__ __launch_bounds__(256) void krig_loo_kernel(const double* __restrict_
   const int n = min(counts[fs], np);
   const double* u = sol + (size_t)s * (R + 1) * np;
   const double* cs = colsq + (size_t)s * np;
-  const bool none = n < 2 || status[s] != 0 || (cand != nullptr && cand[f / T] < 0);
-  double su = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) su += u[i];
-  su = block_sum_d(su, red);
+  const bool none = n < 2 || no_model(status[s], cand, f / T);
+  const double su = sum_u(u, n, red);
   for (int i = threadIdx.x; i < cap; i += 256) {
     float pv = 0.f, vv = 0.f;
     if (i < n) {
@@ -360,8 +325,7 @@ extern "C" int p2i_krig_variance(const float* Winv, const double* sol, const int
                                  const int* cand, const float* params, int model, int f0, int R, int T, int nsys, int np, int H, int W,
                                  int cap, float* var, void* stream) {
   P2I_REQUIRE(Winv && sol && pix && counts && status && params && var, "null pointer");
-  P2I_REQUIRE(model == 0 || model == 1, "variogram model must be 0 (exponential) or 1 (spherical)");
-  P2I_REQUIRE(H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE, "bad frame shape");
+  if (int rc = krig_frame_check(model, H, W)) return rc;
   if (int rc = krig_sys_check(f0, R, T, nsys, np, cap)) return rc;
   const int HW = H * W;
   P2I_LAUNCH(krig_variance_kernel, dim3(ceil_div(HW, PT), nsys), dim3(256), 0, (hipStream_t)stream, Winv, sol, pix, counts, status, cand,

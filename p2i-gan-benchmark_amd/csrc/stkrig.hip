@@ -1,7 +1,8 @@
 // Space-time ordinary kriging: every pixel of every frame of a sample from ALL gauges of ALL frames of that
 // sample, one system per sample, with the metric space-time distance d = sqrt(dy^2 + dx^2 + kappa^2 dt^2) (kappa in pixels per frame)
 // inside the covariance of krig_common.h.  Stages: per-frame compaction (classical.hip) -> gather into per-sample point sets ->
-// [space-time variogram bins -> (kappa, range) candidate fit] -> covariance build + the shared tiled Cholesky (classical.hip) ->
+// [space-time variogram bins -> (kappa, range) candidate fit (classical.hip's one fit kernel, ST = true)] -> covariance build + the
+// shared tiled Cholesky (classical.hip) ->
 // p2i_krig_solve with the samples standing in for frames -> predictor.
 //
 // LAG: the bins, build and predictor kernels in the frame that moves with the rain, one velocity v = (v_y, v_x)
@@ -15,10 +16,6 @@
 
 namespace p2i {
 namespace {
-
-constexpr int N_RANGE = 25;       // range candidates a_c = w 2^((c - 6) / 3)
-constexpr int N_KAPPA = 17;       // anisotropy candidates kappa_q = 2^((q - 6) / 2) px / frame
-constexpr int N_CAND = N_RANGE * N_KAPPA;
 
 // ---- gather: one workgroup per sample walks its T frames in order (the running offset is the exclusive scan of their counts) and
 // appends each frame's gauges; stpix / stt / stz [B][cap] are zero past the count, stcounts[b] = the sum (it may exceed cap: the host
@@ -94,79 +91,6 @@ __global__ __launch_bounds__(BIN_THREADS) void stkrig_bins_kernel(const int* __r
     }
   }
   bins.reduce(n_lags, part, ((size_t)b * nu + u) * nch + ch);
-}
-
-// ---- fit: one workgroup per sample.  Adds the chunks' partial bins in order, then candidate q 25 + c fits (nugget, psill) of
-// gamma = nugget + psill g(sqrt(hbar^2 + (kappa_q u)^2) / a_c) by the count-weighted normal equations and fallbacks of krig_common.h;
-// thread 0 keeps the smallest SSE (lowest q 25 + c on a tie, so that bins of u = 0 alone give the spatial fit with q = 0).
-// bins [B][nu][n_lags][3], fit [B][5] = (nugget, psill, range, kappa, sse), cand [B] = q 25 + c (-1: degenerate), params [B][4] fp32 =
-// (nugget, psill, range, kappa) (a harmless (0, 1, w, 1) when degenerate)
-__global__ __launch_bounds__(256) void stkrig_fit_kernel(const double* __restrict__ part, int nu, int nch, int n_lags, double lagw,
-                                                         int model, double* __restrict__ bins, double* __restrict__ fit,
-                                                         int* __restrict__ cand, float* __restrict__ params) {
-  __shared__ double sn[(MAX_TLAGS + 1) * MAX_LAGS], sgam[(MAX_TLAGS + 1) * MAX_LAGS], shb[(MAX_TLAGS + 1) * MAX_LAGS];
-  __shared__ double c_sse[N_CAND], c_nug[N_CAND], c_ps[N_CAND];
-  __shared__ int c_ok[N_CAND];
-  const int b = blockIdx.x, tid = threadIdx.x, nb = nu * n_lags;
-  for (int e = tid; e < nb; e += 256) {
-    const int u = e / n_lags, k = e % n_lags;
-    double c = 0.0, g = 0.0, h = 0.0;
-    for (int p = 0; p < nch; ++p) {
-      const double* q = part + ((((size_t)b * nu + u) * nch + p) * n_lags + k) * 3;
-      c += q[0];
-      g += q[1];
-      h += q[2];
-    }
-    double* o = bins + ((size_t)b * nb + e) * 3;
-    o[0] = c;
-    o[1] = g;
-    o[2] = h;
-    sn[e] = c;
-    sgam[e] = c > 0.0 ? g / c : 0.0;
-    shb[e] = c > 0.0 ? h / c : 0.0;
-  }
-  __syncthreads();
-  for (int cd = tid; cd < N_CAND; cd += 256) {
-    const double kap = exp2((double)(cd / N_RANGE - 6) * 0.5);
-    const double a = lagw * exp2((double)(cd % N_RANGE - 6) / 3.0);
-    const FitCand r = vario_fit_candidate(sn, sgam, nb, [&](int e) {
-      const double ku = kap * (double)(e / n_lags);
-      const double d = e < n_lags ? shb[e] : sqrt(shb[e] * shb[e] + ku * ku);
-      return g_d(d / a, model);
-    });
-    c_ok[cd] = r.ok;
-    c_sse[cd] = r.sse;
-    c_nug[cd] = r.nug;
-    c_ps[cd] = r.ps;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int best = -1;
-    for (int c = 0; c < N_CAND; ++c)
-      if (c_ok[c] && (best < 0 || c_sse[c] < c_sse[best])) best = c;
-    double* o = fit + (size_t)b * 5;
-    float* pf = params + (size_t)b * 4;
-    cand[b] = best;
-    if (best >= 0) {
-      const double kap = exp2((double)(best / N_RANGE - 6) * 0.5);
-      const double a = lagw * exp2((double)(best % N_RANGE - 6) / 3.0);
-      o[0] = c_nug[best];
-      o[1] = c_ps[best];
-      o[2] = a;
-      o[3] = kap;
-      o[4] = c_sse[best];
-      pf[0] = (float)c_nug[best];
-      pf[1] = (float)c_ps[best];
-      pf[2] = (float)a;
-      pf[3] = (float)kap;
-    } else {
-      o[0] = o[1] = o[2] = o[3] = o[4] = 0.0;
-      pf[0] = 0.f;
-      pf[1] = 1.f;
-      pf[2] = (float)lagw;
-      pf[3] = 1.f;
-    }
-  }
 }
 
 // ---- covariance matrix of the point set of sample s0 + s (the tile writer of krig_common.h); LAG: lag_dist with velf [B][2] fp32
@@ -281,7 +205,8 @@ extern "C" int p2i_stkrig_gather(const int* pix, const float* z, const int* coun
                                  int* stt, float* stz, int* stcounts, void* stream) {
   P2I_REQUIRE(pix && z && counts && stpix && stt && stz && stcounts, "null pointer");
   P2I_REQUIRE(B > 0 && T > 0 && (long long)B * T <= 65535, "bad sample shape %d x %d", B, T);
-  P2I_REQUIRE(fcap > 0 && cap > 0 && cap % TS == 0 && cap <= MAX_NP, "cap must be a multiple of %d, at most %d (got %d)", TS, MAX_NP, cap);
+  P2I_REQUIRE(fcap > 0, "bad frame row length %d", fcap);
+  if (int rc = krig_cap_check(cap)) return rc;
   P2I_LAUNCH(stkrig_gather_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, pix, z, counts, T, fcap, cap, stpix, stt, stz, stcounts);
   return launch_status();
 }
@@ -342,11 +267,11 @@ extern "C" int p2i_lagkrig_bins(const int* pix, const float* z, const int* count
 extern "C" int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags, int n_tlags, double lag_width, int model, double* bins,
                               double* fit, int* cand, float* params, void* stream) {
   P2I_REQUIRE(part && bins && fit && cand && params, "null pointer");
-  P2I_REQUIRE(B > 0 && chunks > 0 && n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "bad fit shape");
+  P2I_REQUIRE(B > 0 && chunks > 0, "bad fit shape");
+  if (int rc = krig_lags_check(n_lags, lag_width)) return rc;
   P2I_REQUIRE(n_tlags >= 0 && n_tlags <= MAX_TLAGS, "n_tlags must be 0..%d", MAX_TLAGS);
   if (int rc = krig_model_check(model)) return rc;
-  P2I_LAUNCH(stkrig_fit_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, part, n_tlags + 1, chunks, n_lags, lag_width, model, bins, fit,
-             cand, params);
+  krig_fit_launch(true, part, B, n_tlags + 1, chunks, n_lags, lag_width, model, bins, fit, cand, params, (hipStream_t)stream);
   return launch_status();
 }
 

@@ -185,14 +185,12 @@ __global__ __launch_bounds__(256) void stkrig_loso_kernel(const double* __restri
   const int* bk = back + (size_t)b * cap + p0;
   float* po = pred + (size_t)b * T * fcap;
   float* vo = var + (size_t)b * T * fcap;
-  if (ns < 2 || m > TS || status[s] != 0 || (cand != nullptr && cand[b] < 0)) {
+  if (ns < 2 || m > TS || no_model(status[s], cand, b)) {
     for (int i = tid; i < m; i += 256) po[bk[i]] = vo[bk[i]] = __builtin_nanf("");
     return;
   }
   const double* u = sol + (size_t)s * 2 * np;
-  double su = 0.0;
-  for (int i = tid; i < n; i += 256) su += u[i];
-  su = block_sum_d(su, red);
+  const double su = sum_u(u, n, red);
   const int nt = np / TS;
   for (int e = tid; e < m * m; e += 256) {
     const int i = e / m, j = e % m;
@@ -261,8 +259,8 @@ extern "C" int p2i_stkrig_gather_sites(const int* pix, const float* z, const int
                                        int* fsite, void* stream) {
   P2I_REQUIRE(pix && z && counts && stpix && stt && stz && stcounts && site_start && nsites && psite && back && fsite, "null pointer");
   P2I_REQUIRE(B > 0 && T > 0 && (long long)B * T <= 65535, "bad sample shape %d x %d", B, T);
-  P2I_REQUIRE(fcap > 0 && fcap <= MAX_NP && cap > 0 && cap % TS == 0 && cap <= MAX_NP,
-              "cap must be a multiple of %d, at most %d (got %d; frame rows of %d)", TS, MAX_NP, cap, fcap);
+  P2I_REQUIRE(fcap > 0 && fcap <= MAX_NP, "bad frame row length %d", fcap);
+  if (int rc = krig_cap_check(cap)) return rc;
   P2I_LAUNCH(stkrig_gather_sites_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, pix, z, counts, T, fcap, cap, stpix, stt, stz, stcounts,
              site_start, nsites, psite, back, fsite);
   return launch_status();

@@ -95,6 +95,64 @@ def _sites_of_frames(res: LOOResult, masks) -> LOOResult:
     return res
 
 
+class _Systems:
+    """The workspace of one call's nsys kriging systems of padded size np_, factored `per` at a time so that the factors (and, with
+    inverse, their inverses: two workspaces per system) of one chunk stay under _FACTOR_BYTES; `limit` bounds the chunk further.
+    work / winv: the chunk's factors / inverses; status (nsys,), alpha (rows, cap) and mean (rows,) span the whole call."""
+
+    def __init__(self, nsys, np_, rows, cap, dev, inverse=False, limit=None):
+        per = max(1, min(nsys, _FACTOR_BYTES // (np_ * np_ * 4 * (2 if inverse else 1))))
+        if limit is not None:
+            per = max(1, min(per, limit))
+        self.nsys, self.per = nsys, per
+        self.work = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
+        self.winv = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32) if inverse else None
+        self.status = torch.zeros(nsys, device=dev, dtype=torch.int32)
+        self.alpha = torch.empty(rows, cap, device=dev, dtype=torch.float32)
+        self.mean = torch.empty(rows, device=dev, dtype=torch.float32)
+
+    def chunks(self):
+        """(first system, systems, their slice of status) of every chunk."""
+        for s0 in range(0, self.nsys, self.per):
+            ns = min(self.per, self.nsys - s0)
+            yield s0, ns, self.status[s0:s0 + ns]
+
+    def finish(self, model, warning, each=1):
+        """Leaves status in model.last_status and logs `warning` with the failed systems times `each` (a host read)."""
+        model.last_status = self.status
+        failed = int(self.status.sum()) * each
+        if failed:
+            logging.warning(warning, failed)
+
+
+def _variogram_config(self, mc, space_time=False):
+    """model.variogram on `self`: variogram_model, fit, n_lags and, with fit=false, fixed = (nugget, psill, range); the space-time
+    models add n_tlags and, to fixed, time_scale."""
+    vg = dict(mc.get("variogram") or {})
+    name = str(vg.get("model", "exponential")).lower()
+    if name not in ops.KRIG_MODELS:
+        raise ValueError(f"model.variogram.model must be one of {sorted(ops.KRIG_MODELS)} (got '{name}')")
+    self.variogram_model = ops.KRIG_MODELS[name]
+    self.fit = bool(vg.get("fit", True))
+    self.n_lags = int(vg.get("n_lags", 16))
+    if space_time:
+        self.n_tlags = int(vg.get("n_tlags", 3))
+    if self.fit:
+        if not 1 <= self.n_lags <= ops.KRIG_MAX_LAGS:
+            raise ValueError(f"model.variogram.n_lags must be in [1, {ops.KRIG_MAX_LAGS}] (got {self.n_lags})")
+        if space_time and not 0 <= self.n_tlags <= ops.STKRIG_MAX_TLAGS:
+            raise ValueError(f"model.variogram.n_tlags must be in [0, {ops.STKRIG_MAX_TLAGS}] (got {self.n_tlags})")
+        return
+    keys = ("nugget", "psill", "range") + (("time_scale",) if space_time else ())
+    bounds = ["nugget >= 0"] + [f"{k} > 0" for k in keys[1:]]
+    try:
+        self.fixed = tuple(float(vg[k]) for k in keys)
+    except KeyError as e:
+        raise ValueError(f"model.variogram with fit=false needs {', '.join(keys[:-1])} and {keys[-1]} (missing {e})") from None
+    if not (self.fixed[0] >= 0 and all(v > 0 for v in self.fixed[1:])):
+        raise ValueError(f"model.variogram: {', '.join(bounds[:-1])} and {bounds[-1]} are required")
+
+
 class _ClassicalBase(nn.Module):
     DEFAULT_MAX_POINTS = 1024
 
@@ -127,23 +185,7 @@ class KrigingGenerator(_ClassicalBase):
     def __init__(self, config: Dict[str, Any]):
         super().__init__(config)
         mc = config.get("model", {})
-        vg = dict(mc.get("variogram") or {})
-        name = str(vg.get("model", "exponential")).lower()
-        if name not in ops.KRIG_MODELS:
-            raise ValueError(f"model.variogram.model must be one of {sorted(ops.KRIG_MODELS)} (got '{name}')")
-        self.variogram_model = ops.KRIG_MODELS[name]
-        self.fit = bool(vg.get("fit", True))
-        self.n_lags = int(vg.get("n_lags", 16))
-        if self.fit:
-            if not 1 <= self.n_lags <= ops.KRIG_MAX_LAGS:
-                raise ValueError(f"model.variogram.n_lags must be in [1, {ops.KRIG_MAX_LAGS}] (got {self.n_lags})")
-        else:
-            try:
-                self.fixed = (float(vg["nugget"]), float(vg["psill"]), float(vg["range"]))
-            except KeyError as e:
-                raise ValueError(f"model.variogram with fit=false needs nugget, psill and range (missing {e})") from None
-            if not (self.fixed[0] >= 0 and self.fixed[1] > 0 and self.fixed[2] > 0):
-                raise ValueError("model.variogram: nugget >= 0, psill > 0 and range > 0 are required")
+        _variogram_config(self, mc)
         self.share_sets = bool(mc.get("share_sets", True))   # false: one factorisation per frame even where a sample shares its mask
         ens = mc.get("ensemble")
         if ens is not None and not isinstance(ens, dict):
@@ -215,25 +257,20 @@ class KrigingGenerator(_ClassicalBase):
         r = t if (shared and self.share_sets) else 1
         nsys = f // r
         np_ = max(ops.KRIG_TILE, _round_up(int(counts.max()), ops.KRIG_TILE))
-        inverse = variance or loo or ensemble is not None    # these also hold the factor's inverse: two workspaces per system
-        per = max(1, min(nsys, _FACTOR_BYTES // (np_ * np_ * 4 * (2 if inverse else 1))))
+        inverse = variance or loo or ensemble is not None    # these also hold the factor's inverse
+        limit = None
         if ensemble is not None:             # the members' dual coefficients of one chunk of systems stay under the same bound
             members, seed, streams = ensemble
-            per = max(1, min(per, _FACTOR_BYTES // (r * members * pix.shape[1] * 4)))
+            limit = _FACTOR_BYTES // (r * members * pix.shape[1] * 4)
             amp, clip = ops.krig_cs_spectrum(params, cand, self.variogram_model, h, w, self.embed)
             self.last_ensemble = {"clip": clip, "embed": self.embed}
             ens = torch.empty(f, members, h * w, device=dev, dtype=torch.float32)
             ops.krig_cs_fields(amp, streams, seed, t, members, h, w, self.embed, ens)
-        work = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
-        winv = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32) if inverse else None
-        status = torch.zeros(nsys, device=dev, dtype=torch.int32)
-        alpha = torch.empty(f, pix.shape[1], device=dev, dtype=torch.float32)
-        mean = torch.empty(f, device=dev, dtype=torch.float32)
+        sy = _Systems(nsys, np_, f, pix.shape[1], dev, inverse, limit)
+        work, winv, alpha, mean = sy.work, sy.winv, sy.alpha, sy.mean
         var = torch.empty(f, h * w, device=dev, dtype=torch.float32) if variance else None
         loo_pred, loo_var = (torch.empty_like(z), torch.empty_like(z)) if loo else (None, None)
-        for s0 in range(0, nsys, per):
-            ns = min(per, nsys - s0)
-            st = status[s0:s0 + ns]
+        for s0, ns, st in sy.chunks():
             ops.krig_factor(pix, info, params, self.variogram_model, s0 * r, r, t, ns, np_, work, st)
             sol = ops.krig_solve(work, z, info, st, cand, s0 * r, r, t, ns, np_, alpha, mean)
             if inverse:
@@ -248,14 +285,11 @@ class KrigingGenerator(_ClassicalBase):
         out = {}
         if predict:
             out["pred"] = ops.krig_predict(pix, alpha, mean, info, params, self.variogram_model, r, t, h, w).view(b, t, 1, h, w)
-        self.last_status = status
-        failed = int(status.sum()) * r
-        if failed:
-            logging.warning("kriging: %d frame(s) met a non-positive pivot and predict their gauge mean", failed)
+        sy.finish(self, "kriging: %d frame(s) met a non-positive pivot and predict their gauge mean", r)
         if variance:
             out["var"] = var.view(b, t, 1, h, w)
         if loo:
-            out["loo"] = LOOResult(pix, z, loo_pred, loo_var, info[:f], status)
+            out["loo"] = LOOResult(pix, z, loo_pred, loo_var, info[:f], sy.status)
         if ensemble is not None:
             out["ens"] = ens.view(b, t, members, h, w)
         return out
@@ -288,32 +322,8 @@ class IDWGenerator(_ClassicalBase):
         return _sites_of_frames(self.cross_validate(masked_frames, masks), masks)
 
 
-def _st_variogram_config(self, mc):
-    """model.variogram of the space-time models on `self`: variogram_model, fit, n_lags, n_tlags and, with fit=false, fixed."""
-    vg = dict(mc.get("variogram") or {})
-    name = str(vg.get("model", "exponential")).lower()
-    if name not in ops.KRIG_MODELS:
-        raise ValueError(f"model.variogram.model must be one of {sorted(ops.KRIG_MODELS)} (got '{name}')")
-    self.variogram_model = ops.KRIG_MODELS[name]
-    self.fit = bool(vg.get("fit", True))
-    self.n_lags = int(vg.get("n_lags", 16))
-    self.n_tlags = int(vg.get("n_tlags", 3))
-    if self.fit:
-        if not 1 <= self.n_lags <= ops.KRIG_MAX_LAGS:
-            raise ValueError(f"model.variogram.n_lags must be in [1, {ops.KRIG_MAX_LAGS}] (got {self.n_lags})")
-        if not 0 <= self.n_tlags <= ops.STKRIG_MAX_TLAGS:
-            raise ValueError(f"model.variogram.n_tlags must be in [0, {ops.STKRIG_MAX_TLAGS}] (got {self.n_tlags})")
-    else:
-        try:
-            self.fixed = (float(vg["nugget"]), float(vg["psill"]), float(vg["range"]), float(vg["time_scale"]))
-        except KeyError as e:
-            raise ValueError(f"model.variogram with fit=false needs nugget, psill, range and time_scale (missing {e})") from None
-        if not (self.fixed[0] >= 0 and self.fixed[1] > 0 and self.fixed[2] > 0 and self.fixed[3] > 0):
-            raise ValueError("model.variogram: nugget >= 0, psill > 0, range > 0 and time_scale > 0 are required")
-
-
 def _advection_config(self, mc):
-    """model.advection of the Lagrangian models on `self` (after _st_variogram_config): fit_velocity and, fitted, vmax, vstep, nhalf,
+    """model.advection of the Lagrangian models on `self` (after _variogram_config): fit_velocity and, fitted, vmax, vstep, nhalf,
     adv_tlags and bandwidth; with fit=false, fixed_v."""
     adv = dict(mc.get("advection") or {})
     self.fit_velocity = bool(adv.get("fit", True))
@@ -355,7 +365,7 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
 
     def __init__(self, config: Dict[str, Any]):
         super().__init__(config)
-        _st_variogram_config(self, config.get("model", {}))
+        _variogram_config(self, config.get("model", {}), space_time=True)
         self.last_fit = None         # {"bins", "fit", "cand", "q", "c"} device tensors of the last call (fit=true)
         self.last_status = None      # per-sample int32 of the last call: 1 where the factorisation met a non-positive pivot
         self._velf = None            # (B, 2) fp32 of the last call's velocities where _variogram fits them (LagrangianKrigingGenerator)
@@ -391,21 +401,12 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         dev = masked_frames.device
         stpix, stt, stz, stinfo = ops.stkrig_gather(pix, z, info, b, t, np_)
         cand, params = self._variogram(pix, z, info, b, t, h, w)
-        per = max(1, min(b, _FACTOR_BYTES // (np_ * np_ * 4)))
-        work = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
-        status = torch.zeros(b, device=dev, dtype=torch.int32)
-        alpha = torch.empty(b, np_, device=dev, dtype=torch.float32)
-        mean = torch.empty(b, device=dev, dtype=torch.float32)
-        for s0 in range(0, b, per):
-            ns = min(per, b - s0)
-            st = status[s0:s0 + ns]
-            ops.stkrig_factor(stpix, stt, stinfo, params, self.variogram_model, s0, ns, np_, work, st, self._velf)
-            ops.krig_solve(work, stz, stinfo, st, cand, s0, 1, 1, ns, np_, alpha, mean)      # the samples stand in for frames
-        out = ops.stkrig_predict(stpix, stt, alpha, mean, stinfo, params, self.variogram_model, t, h, w, self._velf)
-        self.last_status = status
-        failed = int(status.sum())
-        if failed:
-            logging.warning("space-time kriging: %d sample(s) met a non-positive pivot and predict their gauge mean", failed)
+        sy = _Systems(b, np_, b, np_, dev)
+        for s0, ns, st in sy.chunks():
+            ops.stkrig_factor(stpix, stt, stinfo, params, self.variogram_model, s0, ns, np_, sy.work, st, self._velf)
+            ops.krig_solve(sy.work, stz, stinfo, st, cand, s0, 1, 1, ns, np_, sy.alpha, sy.mean)      # the samples stand in for frames
+        out = ops.stkrig_predict(stpix, stt, sy.alpha, sy.mean, stinfo, params, self.variogram_model, t, h, w, self._velf)
+        sy.finish(self, "space-time kriging: %d sample(s) met a non-positive pivot and predict their gauge mean")
         return out.view(b, t, 1, h, w)
 
     @torch.no_grad()
@@ -421,26 +422,16 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         dev = masked_frames.device
         sites = ops.stkrig_gather_sites(pix, z, info, b, t, np_)
         cand, params = self._variogram(pix, z, info, b, t, h, w)
-        per = max(1, min(b, _FACTOR_BYTES // (np_ * np_ * 4 * 2)))      # the factor and its inverse: two workspaces per sample
-        work = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
-        winv = torch.empty(per * np_ * np_, device=dev, dtype=torch.float32)
-        status = torch.zeros(b, device=dev, dtype=torch.int32)
-        alpha = torch.empty(b, np_, device=dev, dtype=torch.float32)
-        mean = torch.empty(b, device=dev, dtype=torch.float32)
+        sy = _Systems(b, np_, b, np_, dev, inverse=True)
         pred, var = torch.zeros_like(z), torch.zeros_like(z)
-        for s0 in range(0, b, per):
-            ns = min(per, b - s0)
-            st = status[s0:s0 + ns]
-            ops.stkrig_factor(sites["stpix"], sites["stt"], sites["stinfo"], params, self.variogram_model, s0, ns, np_, work, st, self._velf)
-            sol = ops.krig_solve(work, sites["stz"], sites["stinfo"], st, cand, s0, 1, 1, ns, np_, alpha, mean)
-            ops.krig_invert(work, ns, np_, winv)
-            gram = ops.stkrig_site_gram(winv, ns, np_)
-            ops.stkrig_loso(gram, sol, alpha, sites, st, cand, s0, t, ns, np_, pred, var)
-        self.last_status = status
-        failed = int(status.sum())
-        if failed:
-            logging.warning("space-time kriging: %d sample(s) met a non-positive pivot and have no leave-one-site-out scores", failed)
-        return LOOResult(pix, z, pred, var, info[:b * t], status, sites["fsite"])
+        for s0, ns, st in sy.chunks():
+            ops.stkrig_factor(sites["stpix"], sites["stt"], sites["stinfo"], params, self.variogram_model, s0, ns, np_, sy.work, st, self._velf)
+            sol = ops.krig_solve(sy.work, sites["stz"], sites["stinfo"], st, cand, s0, 1, 1, ns, np_, sy.alpha, sy.mean)
+            ops.krig_invert(sy.work, ns, np_, sy.winv)
+            gram = ops.stkrig_site_gram(sy.winv, ns, np_)
+            ops.stkrig_loso(gram, sol, sy.alpha, sites, st, cand, s0, t, ns, np_, pred, var)
+        sy.finish(self, "space-time kriging: %d sample(s) met a non-positive pivot and have no leave-one-site-out scores")
+        return LOOResult(pix, z, pred, var, info[:b * t], sy.status, sites["fsite"])
 
 
 class LagrangianKrigingGenerator(SpaceTimeKrigingGenerator):
@@ -498,7 +489,7 @@ class LocalKrigingGenerator(_ClassicalBase):
     def __init__(self, config: Dict[str, Any]):
         super().__init__(config)
         mc = config.get("model", {})
-        _st_variogram_config(self, mc)
+        _variogram_config(self, mc, space_time=True)
         nb = dict(mc.get("neighbourhood") or {})
         k, frames = nb.get("k", 32), nb.get("frames", 2)
         if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= ops.LKRIG_MAX_K:

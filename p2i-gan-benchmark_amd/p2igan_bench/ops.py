@@ -1517,6 +1517,16 @@ def _krig_sys(what, f0, R, T, nsys, F, np_, cap):
         raise RuntimeError(f"{what}: padded size {np_} must be a multiple of {KRIG_TILE} within cap {cap}")
 
 
+def _krig_cap(what, cap, ok=True):
+    if not ok or cap < KRIG_TILE or cap % KRIG_TILE or cap > KRIG_MAX_CAP:
+        raise ValueError(f"{what}: cap must be a multiple of {KRIG_TILE} in [{KRIG_TILE}, {KRIG_MAX_CAP}] (got {cap})")
+
+
+def _krig_ws(what, ws, nsys, np_, kind="factor"):
+    if ws.numel() < nsys * np_ * np_:
+        raise RuntimeError(f"{what}: {kind} workspace too small")
+
+
 def krig_compact(masked, mask, cap):
     """masked, mask: (B, T, H, W) fp32.  Returns pix (B*T, cap) int32 ((y << 16) | x of the frame's mask != 0 pixels in raster order),
     z (B*T, cap) (masked there; both zero past the count) and info (2*B*T,) int32: counts, then 'mask differs from the sample's
@@ -1526,8 +1536,7 @@ def krig_compact(masked, mask, cap):
     _krig_t("krig_compact", mask, torch.float32, masked.shape)
     if masked.dim() != 4:
         raise RuntimeError("krig_compact: (B, T, H, W) expected")
-    if cap < KRIG_TILE or cap % KRIG_TILE or cap > KRIG_MAX_CAP:
-        raise ValueError(f"krig_compact: cap must be a multiple of {KRIG_TILE} in [{KRIG_TILE}, {KRIG_MAX_CAP}] (got {cap})")
+    _krig_cap("krig_compact", cap)
     B, T, H, W = masked.shape
     F = B * T
     pix = torch.empty(F, cap, device=masked.device, dtype=torch.int32)
@@ -1574,8 +1583,7 @@ def krig_factor(pix, info, params, model, f0, R, T, nsys, np_, L, status):
     _krig_t("krig_factor", L, torch.float32)
     _krig_t("krig_factor", status, torch.int32, (nsys,))
     _krig_sys("krig_factor", f0, R, T, nsys, F, np_, cap)
-    if L.numel() < nsys * np_ * np_:
-        raise RuntimeError("krig_factor: factor workspace too small")
+    _krig_ws("krig_factor", L, nsys, np_)
     _hip.check(lib.p2i_krig_factor(_ptr(pix), _ptr(info), _ptr(params), int(model), f0, R, T, nsys, np_, cap, _ptr(L), _ptr(status),
                                    _stream()), "p2i_krig_factor")
 
@@ -1594,8 +1602,7 @@ def krig_solve(L, z, info, status, cand, f0, R, T, nsys, np_, alpha, mean):
     _krig_t("krig_solve", alpha, torch.float32, (F, cap))
     _krig_t("krig_solve", mean, torch.float32, (F,))
     _krig_sys("krig_solve", f0, R, T, nsys, F, np_, cap)
-    if L.numel() < nsys * np_ * np_:
-        raise RuntimeError("krig_solve: factor workspace too small")
+    _krig_ws("krig_solve", L, nsys, np_)
     sol = torch.empty(nsys, R + 1, np_, device=z.device, dtype=torch.float64)
     _hip.check(lib.p2i_krig_solve(_ptr(L), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), f0, R, T, nsys, np_, cap, _ptr(sol), _ptr(alpha),
                                   _ptr(mean), _stream()), "p2i_krig_solve")
@@ -1648,8 +1655,7 @@ def stkrig_gather(pix, z, info, B, T, cap):
     _krig_t("stkrig_gather", pix, torch.int32, (F, fcap))
     _krig_t("stkrig_gather", z, torch.float32, (F, fcap))
     _krig_t("stkrig_gather", info, torch.int32, (2 * F,))
-    if cap < KRIG_TILE or cap % KRIG_TILE or cap > KRIG_MAX_CAP:
-        raise ValueError(f"stkrig_gather: cap must be a multiple of {KRIG_TILE} in [{KRIG_TILE}, {KRIG_MAX_CAP}] (got {cap})")
+    _krig_cap("stkrig_gather", cap)
     dev = pix.device
     stpix = torch.empty(B, cap, device=dev, dtype=torch.int32)
     stt = torch.empty(B, cap, device=dev, dtype=torch.int32)
@@ -1708,8 +1714,7 @@ def stkrig_factor(stpix, stt, stinfo, params, model, s0, nsys, np_, L, status, v
     _krig_t(who, L, torch.float32)
     _krig_t(who, status, torch.int32, (nsys,))
     _krig_sys(who, s0, 1, 1, nsys, B, np_, cap)
-    if L.numel() < nsys * np_ * np_:
-        raise RuntimeError(f"{who}: factor workspace too small")
+    _krig_ws(who, L, nsys, np_)
     if velf is not None:
         _lag_vel(who, velf, torch.float32, B)
         _hip.check(lib.p2i_lagkrig_factor(_ptr(stpix), _ptr(stt), _ptr(stinfo), _ptr(params), _ptr(velf), int(model), s0, nsys, np_, cap,
@@ -1755,8 +1760,7 @@ def stkrig_gather_sites(pix, z, info, B, T, cap):
     _krig_t("stkrig_gather_sites", pix, torch.int32, (F, fcap))
     _krig_t("stkrig_gather_sites", z, torch.float32, (F, fcap))
     _krig_t("stkrig_gather_sites", info, torch.int32, (2 * F,))
-    if cap < KRIG_TILE or cap % KRIG_TILE or cap > KRIG_MAX_CAP or fcap > KRIG_MAX_CAP:
-        raise ValueError(f"stkrig_gather_sites: cap must be a multiple of {KRIG_TILE} in [{KRIG_TILE}, {KRIG_MAX_CAP}] (got {cap})")
+    _krig_cap("stkrig_gather_sites", cap, fcap <= KRIG_MAX_CAP)
     dev = pix.device
     out = {k: torch.empty(B, cap, device=dev, dtype=torch.int32) for k in ("stpix", "stt", "psite", "back")}
     out["stz"] = torch.empty(B, cap, device=dev, dtype=torch.float32)
@@ -1777,8 +1781,7 @@ def stkrig_site_gram(Winv, nsys, np_):
     _krig_t("stkrig_site_gram", Winv, torch.float32)
     if nsys < 1 or np_ < KRIG_TILE or np_ % KRIG_TILE or np_ > KRIG_MAX_CAP:
         raise RuntimeError(f"stkrig_site_gram: bad system shape {nsys} x {np_}")
-    if Winv.numel() < nsys * np_ * np_:
-        raise RuntimeError("stkrig_site_gram: inverse workspace too small")
+    _krig_ws("stkrig_site_gram", Winv, nsys, np_, "inverse")
     gram = torch.empty(nsys, np_ // KRIG_TILE, 2, KRIG_TILE, KRIG_TILE, device=Winv.device, dtype=torch.float64)
     _hip.check(lib.p2i_stkrig_site_gram(_ptr(Winv), nsys, np_, _ptr(gram), _stream()), "p2i_stkrig_site_gram")
     return gram
@@ -1979,8 +1982,7 @@ def krig_variance(Winv, sol, pix, info, status, cand, params, model, f0, R, T, n
     _krig_t("krig_variance", params, torch.float32, (F // T, 4))
     _krig_t("krig_variance", var, torch.float32, (F, H * W))
     _krig_sys("krig_variance", f0, R, T, nsys, F, np_, cap)
-    if Winv.numel() < nsys * np_ * np_:
-        raise RuntimeError("krig_variance: inverse workspace too small")
+    _krig_ws("krig_variance", Winv, nsys, np_, "inverse")
     _hip.check(lib.p2i_krig_variance(_ptr(Winv), _ptr(sol), _ptr(pix), _ptr(info), _ptr(status), _ptr(cand), _ptr(params), int(model), f0,
                                      R, T, nsys, np_, H, W, cap, _ptr(var), _stream()), "p2i_krig_variance")
 
@@ -2000,8 +2002,7 @@ def krig_loo(Winv, sol, alpha, z, info, status, cand, f0, R, T, nsys, np_, pred,
     _krig_t("krig_loo", pred, torch.float32, (F, cap))
     _krig_t("krig_loo", var, torch.float32, (F, cap))
     _krig_sys("krig_loo", f0, R, T, nsys, F, np_, cap)
-    if Winv.numel() < nsys * np_ * np_:
-        raise RuntimeError("krig_loo: inverse workspace too small")
+    _krig_ws("krig_loo", Winv, nsys, np_, "inverse")
     colsq = torch.empty(nsys, np_, device=z.device, dtype=torch.float64)
     _hip.check(lib.p2i_krig_loo(_ptr(Winv), _ptr(sol), _ptr(alpha), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), f0, R, T, nsys, np_, cap,
                                 _ptr(colsq), _ptr(pred), _ptr(var), _stream()), "p2i_krig_loo")
@@ -2121,8 +2122,7 @@ def krig_cs_weights(Winv, sol, pix, z, info, status, cand, ens, f0, R, T, nsys, 
     lib = _hip.load()
     cap = _krig_cs_sys("krig_cs_weights", Winv, pix, z, info, status, cand, ens, f0, R, T, nsys, np_, M, H, W)
     _krig_t("krig_cs_weights", sol, torch.float64, (nsys, R + 1, np_))
-    if Winv.numel() < nsys * np_ * np_:
-        raise RuntimeError("krig_cs_weights: inverse workspace too small")
+    _krig_ws("krig_cs_weights", Winv, nsys, np_, "inverse")
     alpha = torch.empty(nsys, R * M, cap, device=z.device, dtype=torch.float32)
     mu = torch.empty(nsys, R * M, device=z.device, dtype=torch.float32)
     _hip.check(lib.p2i_krig_cs_weights(_ptr(Winv), _ptr(sol), _ptr(pix), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), _ptr(ens), f0, R, T,

@@ -38,6 +38,8 @@ CASES = {
     "24x40-sph-nug-n65-m1": (24, 40, 2, (65,), "sph-nug", True, 1, 2),
     "16-sph-nug-n33-e3-m5": (16, 16, 2, (33,), "sph-nug", True, 5, 3),
     "17x23-exp-nug-n2-31-perframe-m5": (17, 23, 2, (2, 31), "exp-nug", True, 5, 2),
+    # T M = 165 columns of one shared system: the predictor's second column group (one full 32-column tile and one of 5)
+    "16-exp-nug-n33-m33-t5": (16, 16, 5, (33,), "exp-nug", True, 33, 2),
 }
 SEED = (3 << 32) | 11
 
