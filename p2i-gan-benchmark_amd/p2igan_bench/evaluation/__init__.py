@@ -32,7 +32,8 @@ objects (``objects.py``, section 23; no counterpart in the reference): ``run_obj
 frame at the absolute thresholds and at one relative level and returns per method and level SAL (structure, amplitude, location)
 against the truth and the object population of both sides.  ``ObjectEvaluator`` is the streaming form (one host read per launch).
 
-``_common.py`` holds what the units share."""
+``_common.py`` holds what the units share: the input and event-dict rules and ``Streaming``, the base of the exp1, scale, prob and
+objects evaluators (section 10a)."""
 from ._common import crop_mask, crop_origin, ensure_thw_shape, selection, transform_mmhr, truth_lut  # noqa: F401
 from .exp1 import DEFAULT_THRESHOLDS, PSS_BINS, PSS_MIN_VALUE, Exp1Evaluator, pss_bin, pss_edges, run_exp1  # noqa: F401
 from .exp2 import (EXP2_MAX_EVENTS, EXP2_MAX_FRAMES, Exp2Event, Exp2Result, compute_exp2, default_zoom, exp2_canvases,  # noqa: F401

@@ -2,13 +2,14 @@
 restatement of np.histogram's PSS bin edges.  The rules it reproduces, the reference's quirks included: DESIGN.md section 10."""
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Dict, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .. import ops
-from ._common import _pieces, _thw, _to_device, crop_origin, device_tables, eval_device, selection
+from ._common import Streaming, cat, eval_device, event_lists, selection
 
 DEFAULT_THRESHOLDS = (0.5, 2.0, 4.0, 8.0)
 PSS_BINS = 50
@@ -36,21 +37,17 @@ def pss_bin(x, edges: np.ndarray) -> np.ndarray:
     return np.minimum(np.searchsorted(edges, x, side="right") - 1, len(edges) - 2)
 
 
-class _Method:
-    def __init__(self):
-        self.parts, self.pool_p, self.pool_g, self.sel_p, self.sel_g = [], [], [], [], []
-        self.T = 0
-
-
-class Exp1Evaluator:
+class Exp1Evaluator(Streaming):
     """Streaming exp1 scores.  ``update(method, pred, truth)`` adds one piece whose frames pair one for one (the longer side is
     truncated, as align_length does); the pieces of a method form its stack in the order given, and dTSSIM pairs frames across
     piece boundaries, as the reference does on its concatenated stack.  ``mask`` is the crop_size x crop_size mask (already
     cropped, as main.py passes it).  ``compute()`` syncs once and returns ``{method: {...}}`` in the reference's layout."""
 
+    what = "exp1 scoring runs"
+
     def __init__(self, mask, mode: str, crop_size: int, thresholds: Sequence[float] = DEFAULT_THRESHOLDS, use_pool8: bool = True,
                  divide_by_3: bool = True, device=None):
-        self.device = eval_device(device, "exp1 scoring runs")
+        device = eval_device(device, self.what)          # here the GPU check comes ahead of the arguments'
         self.size = int(crop_size)
         self.pool = 8 if use_pool8 else 1
         if self.size // self.pool == 0:
@@ -58,28 +55,22 @@ class Exp1Evaluator:
         self.thresholds = tuple(float(t) for t in thresholds)
         if len(self.thresholds) > ops.EXP1_MAX_THR:
             raise ValueError(f"at most {ops.EXP1_MAX_THR} thresholds")
-        self.mode, self.divide_by_3 = mode, bool(divide_by_3)
+        self.mode = mode
         self._sel = selection(mask, mode, self.size)
         self.nsel = int(self._sel.sum())
-        self._lut, self._rank = device_tables(self.device, self.divide_by_3, self._sel)
-        self._methods: Dict[str, _Method] = {}
+        self._start(device, divide_by_3, self._sel)
 
-    def reset(self):
-        self._methods = {}
+    def _new_state(self):
+        return SimpleNamespace(parts=[], pool_p=[], pool_g=[], sel_p=[], sel_g=[], T=0)
+
+    def _launch_frames(self):
+        return _MAX_FRAMES
 
     def update(self, method: str, pred_event, truth_event):
         with torch.cuda.device(self.device):
-            truth = _to_device(_thw(truth_event), self.device)
-            pred = _to_device(_thw(pred_event), self.device)
-            gtl = crop_origin(truth.shape[1], truth.shape[2], self.size)     # the truth is cropped first, as in run_exp1
-            n = min(pred.shape[0], truth.shape[0])
-            ptl = crop_origin(pred.shape[1], pred.shape[2], self.size)
-            st = self._methods.get(method)
-            if st is None:
-                st = self._methods[method] = _Method()
+            pred, truth, ptl, gtl, n, st = self._open(method, pred_event, truth_event)
             S, ps = self.size, self.size // self.pool
-            for t0 in range(0, n, _MAX_FRAMES):
-                tn = min(_MAX_FRAMES, n - t0)
+            for t0, tn in self._cuts(n):
                 part = torch.empty(ops.exp1_workspace(tn, S, self.pool), device=self.device, dtype=torch.float64)
                 pp = torch.empty(tn, ps, ps, device=self.device, dtype=torch.float32)
                 pg = torch.empty_like(pp)
@@ -106,7 +97,7 @@ class Exp1Evaluator:
                     raise ValueError(f"method {name!r} has no frames to score")
                 # the partials of all pieces in frame order, folded in one fixed order: where pieces were cut does not matter
                 acc = torch.zeros(ops.EXP1_NSTAT, device=self.device, dtype=torch.float64)
-                ops.exp1_merge(torch.cat(st.parts) if len(st.parts) > 1 else st.parts[0], acc)
+                ops.exp1_merge(cat(st.parts), acc)
                 score = torch.empty(st.T, device=self.device, dtype=torch.float64)
                 flag = torch.empty(st.T, device=self.device, dtype=torch.int32)
                 edges = torch.empty(PSS_BINS + 2, device=self.device, dtype=torch.float32)
@@ -114,9 +105,7 @@ class Exp1Evaluator:
                 for sp, sg in zip(st.sel_p, st.sel_g):
                     ops.exp1_hist(sp, sg, acc, score[t0:t0 + sp.shape[0]], flag[t0:t0 + sp.shape[0]], edges)
                     t0 += sp.shape[0]
-                pp = torch.cat(st.pool_p).reshape(st.T, -1) if len(st.pool_p) > 1 else st.pool_p[0].reshape(st.T, -1)
-                pg = torch.cat(st.pool_g).reshape(st.T, -1) if len(st.pool_g) > 1 else st.pool_g[0].reshape(st.T, -1)
-                ssim3 = ops.exp1_ssim(pp, pg)
+                ssim3 = ops.exp1_ssim(cat(st.pool_p).reshape(st.T, -1), cat(st.pool_g).reshape(st.T, -1))
                 outs.append(ops.exp1_finalize(acc, self.thresholds, score, flag, edges, ssim3))
             host = torch.stack(outs).cpu().numpy()         # the one host sync
         res = {}
@@ -135,33 +124,11 @@ def run_exp1(preds, truth, mask, mode: str, crop_size: int, thresholds: Tuple[fl
              divide_by_3: bool = True, device=None) -> Dict[str, Dict[str, object]]:
     """The reference's run_exp1 (experiments/exp1.py) on the device.  With a dict ``truth``, every method's events are taken in
     the truth's key order; an event a method lacks is skipped for that method (its stack then shifts against the truth's, as in
-    the reference), and a method that is not a dict is left out."""
-    if isinstance(truth, dict):
-        keys = list(truth.keys())
-        if not keys:
-            return {}
-        truth_events = [truth[k] for k in keys if truth.get(k) is not None]
-        methods = {}
-        for name, src in preds.items():
-            if isinstance(src, dict):
-                methods[name] = [src[k] for k in keys if src.get(k) is not None]
-    else:
-        truth_events = [truth]
-        methods = {}
-        for name, src in preds.items():
-            if isinstance(src, dict):
-                raise TypeError(f"method {name!r}: per-event predictions need a per-event truth")
-            methods[name] = [src]
+    the reference), and a method that is not a dict is left out (``event_lists``)."""
+    truth_events, methods = event_lists(preds, truth)
     if not truth_events:
-        raise ValueError("Expected [T,H,W], got shape (0,)")
+        return {}
     ev = Exp1Evaluator(mask, mode, crop_size, thresholds, use_pool8, divide_by_3, device=device)
-    truth_dev = [_to_device(_thw(e), ev.device) for e in truth_events]
-    for t in truth_dev:
-        crop_origin(t.shape[1], t.shape[2], ev.size)
-    for name, events in methods.items():
-        if not events:
-            raise ValueError("Expected [T,H,W], got shape (0,)")
-        pred_dev = [_to_device(_thw(e), ev.device) for e in events]
-        for p, g in _pieces(pred_dev, truth_dev):
-            ev.update(name, p, g)
+    for name, p, g, _ in ev.pieces(truth_events, methods):
+        ev.update(name, p, g)
     return ev.compute()

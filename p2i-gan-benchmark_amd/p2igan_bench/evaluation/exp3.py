@@ -13,13 +13,12 @@ import numpy as np
 import torch
 
 from .. import ops
-from ._common import _pieces, _thw, _to_device, crop_origin, device_tables, eval_device, selection
+from ._common import NO_EVENTS, _pieces, _thw, _to_device, crop_origin, device_tables, eval_device, selection
 
 EXP3_MAX_POINTS = 2000      # the scatter / residual panels' sample size
 EXP3_SEED = 42              # np.random.default_rng(42), once per figure, advanced across methods
 EXP3_MIN_VALUE = 0.1        # the pool keeps observations >= 0.1 mm/h
 LOGFREQ_EDGES = np.linspace(0.0, 32.0, ops.EXP3_BINS + 1)
-_SHAPE_ERROR = "Expected [T,H,W], got shape (0,)"
 
 
 def linregress(x, y) -> Tuple[float, float, float]:
@@ -175,7 +174,7 @@ class Exp3Evaluator:
 
     def compute(self) -> Exp3Result:
         if not self._truth:
-            raise ValueError(_SHAPE_ERROR)
+            raise ValueError(NO_EVENTS)
         if not self.methods:
             raise ValueError("Number of columns must be a positive integer, not 0")     # the reference's empty figure row
         S, dev = self.size, self.device
@@ -184,7 +183,7 @@ class Exp3Evaluator:
             for name in self.methods:
                 st = self._m[name]
                 if not st.pieces:
-                    raise ValueError(_SHAPE_ERROR)
+                    raise ValueError(NO_EVENTS)
                 if self.per_event and st.full:
                     pairs = [(p, po, t, to) for (p, po), (t, to) in zip(st.pieces, self._truth)]
                     srec = torch.cat(st.rec)
@@ -280,7 +279,7 @@ def compute_exp3(preds, truth, mask, mode: str, crop_size: int, divide_by_3: boo
     if isinstance(truth, dict):
         names = list(preds.keys())
         if any(not isinstance(src, dict) for src in preds.values()):
-            raise ValueError(_SHAPE_ERROR)              # the reference stacks nothing for it, then fails on the empty stack
+            raise ValueError(NO_EVENTS)              # the reference stacks nothing for it, then fails on the empty stack
         ev = Exp3Evaluator(mask, mode, crop_size, names, per_event=True, divide_by_3=divide_by_3, device=device)
         for k in truth.keys():
             if truth.get(k) is None:

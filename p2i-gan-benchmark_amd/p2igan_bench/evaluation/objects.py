@@ -7,13 +7,14 @@ from __future__ import annotations
 
 import os
 import warnings
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from .. import ops
-from ._common import _frames, _pieces, _thw, _to_device, crop_origin, device_tables, eval_device
+from ._common import Streaming, bounded_crop, event_lists, radar_thresholds
 from .exp1 import DEFAULT_THRESHOLDS
 
 DEFAULT_SAL_FACTOR = 1.0 / 15.0      # Wernli et al. 2008: R* = Rmax / 15
@@ -29,15 +30,7 @@ def level_keys(thresholds: Sequence[float]) -> List[str]:
     return [f"thr_{q:g}" for q in thresholds] + [RELATIVE_LEVEL]
 
 
-def _check_args(mode, thresholds, connectivity, sal_factor, sal_floor, crop_size):
-    if mode == "gauge":
-        raise ValueError("object verification labels connected pixels of the whole crop: mode 'gauge' (isolated gauge pixels) has no "
-                         "meaning")
-    if mode != "radar":
-        raise ValueError(f"Unknown mode: {mode}")
-    thresholds = tuple(float(t) for t in thresholds)
-    if not 0 < len(thresholds) <= ops.EXP1_MAX_THR:
-        raise ValueError(f"1 to {ops.EXP1_MAX_THR} thresholds")
+def _check_sal(connectivity, sal_factor, sal_floor):
     if connectivity not in (4, 8):
         raise ValueError(f"connectivity is 4 or 8, got {connectivity!r}")
     sal_factor, sal_floor = float(sal_factor), float(sal_floor)
@@ -45,10 +38,7 @@ def _check_args(mode, thresholds, connectivity, sal_factor, sal_floor, crop_size
         raise ValueError(f"the SAL factor lies in (0, 1], got {sal_factor}")
     if not sal_floor >= 0.0:
         raise ValueError(f"the SAL floor is a rain rate >= 0, got {sal_floor}")
-    size = int(crop_size)
-    if not 0 < size <= ops.SCALE_MAX_CROP:
-        raise ValueError(f"crop size {size}: 1 to {ops.SCALE_MAX_CROP}")
-    return thresholds, int(connectivity), sal_factor, sal_floor, size
+    return int(connectivity), sal_factor, sal_floor
 
 
 class _Segments:
@@ -144,56 +134,38 @@ def sal_summary(frames: Dict[str, np.ndarray], keys: Sequence[str]) -> Dict[str,
     return res
 
 
-class _Method:
-    def __init__(self):
-        self.rec, self.lev, self.offsets, self.table, self.origin, self.T = [], [], [], [], [], 0
-
-
-class ObjectEvaluator:
+class ObjectEvaluator(Streaming):
     """Streaming object verification.  ``update(method, pred, truth)`` adds one piece whose frames pair one for one (the longer side is
     truncated, as align_length does), syncs once per launch to size the object table and sends the launch's results to pinned host
     memory; ``compute()`` waits for those copies and returns ``{method: {...}}`` (see
     ``run_objects``)."""
 
+    what = "object verification runs"
+
     def __init__(self, crop_size: int, thresholds: Sequence[float] = DEFAULT_THRESHOLDS, connectivity: int = 8,
                  sal_factor: float = DEFAULT_SAL_FACTOR, sal_floor: float = DEFAULT_SAL_FLOOR, divide_by_3: bool = True, device=None,
                  mode: str = "radar"):
-        self.thresholds, self.connectivity, self.sal_factor, self.sal_floor, self.size = _check_args(
-            mode, thresholds, connectivity, sal_factor, sal_floor, crop_size)
-        self.device = eval_device(device, "object verification runs")
-        self.divide_by_3 = bool(divide_by_3)
+        self.thresholds = radar_thresholds(mode, thresholds, "object verification labels connected pixels")
+        self.connectivity, self.sal_factor, self.sal_floor = _check_sal(connectivity, sal_factor, sal_floor)
+        self.size = bounded_crop(crop_size)
+        self._start(device, divide_by_3)
         self.keys = level_keys(self.thresholds)
         self.use_workspace = self.size > ops.OBJECTS_LDS_CROP      # tests set it to run a small crop through the large-crop path
-        self._lut, _ = device_tables(self.device, self.divide_by_3)
-        self._work: Dict[str, torch.Tensor] = {}
-        self._methods: Dict[str, _Method] = {}
 
-    def reset(self):
-        self._methods = {}
+    def _new_state(self):
+        return SimpleNamespace(rec=[], lev=[], offsets=[], table=[], origin=[], T=0)
 
-    def _buf(self, name: str, n: int, dtype) -> torch.Tensor:
-        b = self._work.get(name)
-        if b is None or b.numel() < n or b.dtype != dtype:
-            b = self._work[name] = torch.empty(n, device=self.device, dtype=dtype)
-        return b[:n]
+    def _launch_frames(self):
+        return _WORK_BYTES // (2 * len(self.keys) * self.size * self.size * (4 if self.use_workspace else 2))
 
     def update(self, method: str, pred_event, truth_event, origin=(0, 0)):
         """``origin`` = (event index, first frame) of the piece in the truth, recorded with its frames."""
         S, L = self.size, len(self.keys)
         with torch.cuda.device(self.device):
-            truth = _to_device(_thw(truth_event), self.device)
-            pred = _to_device(_thw(pred_event), self.device)
-            gtl = crop_origin(truth.shape[1], truth.shape[2], S)
-            n = min(pred.shape[0], truth.shape[0])
-            ptl = crop_origin(pred.shape[1], pred.shape[2], S)
-            st = self._methods.get(method)
-            if st is None:
-                st = self._methods[method] = _Method()
+            pred, truth, ptl, gtl, n, st = self._open(method, pred_event, truth_event)
             wide = bool(self.use_workspace)
             ldt = torch.int32 if wide else torch.int16
-            step = max(1, _WORK_BYTES // (2 * L * S * S * (4 if wide else 2)))
-            for t0 in range(0, n, step):
-                tn = min(step, n - t0)
+            for t0, tn in self._cuts(n):
                 q = self._buf("q", tn * 2 * S * S, torch.int32)
                 bits = self._buf("bits", tn * 2 * S * S, torch.int16)
                 labels = self._buf("labels", tn * 2 * L * S * S, ldt)
@@ -278,38 +250,12 @@ def run_objects(preds, truth, crop_size: int, thresholds: Sequence[float] = DEFA
     ``{"levels": {"thr_<q:g>" | "rel": {"S_mean", "S_median", ... "L2_median", "S_abs_mean", "A_abs_mean", "frames_scored",
     "frames_pred_only", "frames_truth_only", "frames_no_object", "pred": {...}, "truth": {...}}}, "frames": T, "frames_skipped": k,
     "connectivity", "sal_factor", "sal_floor"}`` (see ``sal_summary``); ``frames_out`` receives the per-frame arrays."""
-    if isinstance(truth, dict):
-        keys = list(truth.keys())
-        if not keys:
-            return {}
-        truth_events = [truth[k] for k in keys if truth.get(k) is not None]
-        methods = {}
-        for name, src in preds.items():
-            if isinstance(src, dict):
-                methods[name] = [src[k] for k in keys if src.get(k) is not None]
-    else:
-        truth_events = [truth]
-        methods = {}
-        for name, src in preds.items():
-            if isinstance(src, dict):
-                raise TypeError(f"method {name!r}: per-event predictions need a per-event truth")
-            methods[name] = [src]
+    truth_events, methods = event_lists(preds, truth)
     if not truth_events:
-        raise ValueError("Expected [T,H,W], got shape (0,)")
+        return {}
     ev = ObjectEvaluator(crop_size, thresholds, connectivity, sal_factor, sal_floor, divide_by_3, device=device, mode=mode)
-    truth_dev = [_to_device(_thw(e), ev.device) for e in truth_events]
-    for t in truth_dev:
-        crop_origin(t.shape[1], t.shape[2], ev.size)
-    ends = np.cumsum([_frames(t) for t in truth_dev])
-    for name, events in methods.items():
-        if not events:
-            raise ValueError("Expected [T,H,W], got shape (0,)")
-        pred_dev = [_to_device(_thw(e), ev.device) for e in events]
-        at = 0
-        for p, g in _pieces(pred_dev, truth_dev):
-            e = int(np.searchsorted(ends, at, side="right"))
-            ev.update(name, p, g, origin=(e, at - (int(ends[e - 1]) if e else 0)))
-            at += _frames(g)
+    for name, p, g, origin in ev.pieces(truth_events, methods):
+        ev.update(name, p, g, origin=origin)
     return ev.compute(frames_out)
 
 

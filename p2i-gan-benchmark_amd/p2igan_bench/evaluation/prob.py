@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ._common import _pieces, _thw, _to_device, device_tables, eval_device, transform_mmhr
+from ._common import Streaming, _pieces, _thw, _to_device, crop_origin, eval_device, selection, transform_mmhr, upload_events
 from .exp1 import DEFAULT_THRESHOLDS
 
 DEFAULT_LEVELS = (0.5, 0.8, 0.9, 0.95)
@@ -132,17 +132,13 @@ def _crop_shape(crop_size):
     return rows, cols
 
 
-def _origin(h: int, w: int, rows: int, cols: int):
-    if rows > h or cols > w:
-        raise ValueError(f"crop {rows}x{cols} exceeds input {h}x{w}")
-    return (h - rows) // 2, (w - cols) // 2
-
-
-class ProbEvaluator:
+class ProbEvaluator(Streaming):
     """Streaming probabilistic scores.  ``update(method, pred, truth, var)`` adds one piece whose frames pair one for one (the
     longer side is truncated); ``var`` is an array aligned with ``pred`` or a float (one variance for every pixel).  ``crop_size`` is
     an int or (rows, cols): the centre crop of every input.  ``mask`` [rows, cols] with ``mode`` selects exp1's pixels (radar: mask
     False, gauge: mask True); without a mask every pixel counts.  ``compute()`` syncs once and returns ``{method: scores}``."""
+
+    what = "probabilistic verification runs"
 
     def __init__(self, crop_size, mask=None, mode: str = "radar", thresholds: Sequence[float] = DEFAULT_THRESHOLDS,
                  levels: Sequence[float] = DEFAULT_LEVELS, sigma_edges: Sequence[float] = DEFAULT_SIGMA_EDGES,
@@ -150,7 +146,7 @@ class ProbEvaluator:
                  device=None):
         if mode not in ("radar", "gauge"):
             raise ValueError(f"Unknown mode: {mode}")
-        self.rows, self.cols = _crop_shape(crop_size)
+        self.size = self.rows, self.cols = _crop_shape(crop_size)
         self.divide_by_3, self.censor = bool(divide_by_3), bool(censor)
         self.thresholds = tuple(float(q) for q in thresholds)
         self.levels = tuple(float(v) for v in levels)
@@ -166,43 +162,35 @@ class ProbEvaluator:
             raise ValueError(f"pit_bins in 1..{ops.PROB_MAX_PIT_BINS}, rel_bins in 1..{ops.PROB_MAX_REL_BINS}")
         self.xq = tuple(pixel_threshold(q, self.divide_by_3) for q in self.thresholds)
         self.halfwidths = tuple(half_width(v) for v in self.levels)
-        sel = None
-        if mask is not None:
-            m = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask).astype(bool)
-            if m.shape != (self.rows, self.cols):
-                raise ValueError(f"Mask shape {m.shape} != data shape {(self.rows, self.cols)}")
-            sel = ~m if mode == "radar" else m
-        self.device = eval_device(device, "probabilistic verification runs")
-        self._lut, self._rank = device_tables(self.device, self.divide_by_3, sel)
+        self._start(device, divide_by_3, None if mask is None else selection(mask, mode, self.size))
         self.layout = _Layout(len(self.thresholds), len(self.levels), len(self.sigma_edges), self.pit_bins, self.rel_bins)
         if ops.prob_record(len(self.thresholds), len(self.levels), len(self.sigma_edges), self.pit_bins, self.rel_bins) != \
                 (self.layout.nf, self.layout.ni):
             raise RuntimeError("the record layout of prob.py and csrc/eval_prob.hip differ")
-        self._acc: Dict[object, torch.Tensor] = {}
 
-    def reset(self):
-        self._acc = {}
+    def _new_state(self):
+        """The method's accumulator: one record."""
+        return torch.zeros(self.layout.nf + self.layout.ni, device=self.device, dtype=torch.float64)
+
+    def _launch_frames(self):
+        return (_PART_WORDS // (self.layout.nf + self.layout.ni)) * ops.PROB_WG_PIXELS // (self.rows * self.cols)
 
     def update(self, method, pred_event, truth_event, var):
         rows, cols, lay = self.rows, self.cols, self.layout
         nw = lay.nf + lay.ni
         with torch.cuda.device(self.device):
-            truth = _to_device(_thw(truth_event), self.device)
-            pred = _to_device(_thw(pred_event), self.device)
+            # its own opening: the variance rides along, and here the prediction's crop is checked ahead of the truth's
+            pred, truth = self._upload(pred_event, truth_event)
             scalar = not (isinstance(var, (torch.Tensor, np.ndarray)) and getattr(var, "ndim", 0) > 0)
             v = float(var) if scalar else _to_device(_thw(var), self.device)
             if not scalar and v.shape[0] != pred.shape[0]:
                 raise ValueError(f"the variance has {v.shape[0]} frames, the prediction {pred.shape[0]}")
             n = min(pred.shape[0], truth.shape[0])
-            ptl = _origin(pred.shape[1], pred.shape[2], rows, cols)
-            gtl = _origin(truth.shape[1], truth.shape[2], rows, cols)
-            vtl = None if scalar else _origin(v.shape[1], v.shape[2], rows, cols)
-            acc = self._acc.get(method)
-            if acc is None:
-                acc = self._acc[method] = torch.zeros(nw, device=self.device, dtype=torch.float64)
-            step = max(1, (_PART_WORDS // nw) * ops.PROB_WG_PIXELS // (rows * cols))
-            for t0 in range(0, n, step):
-                tn = min(step, n - t0)
+            ptl = crop_origin(pred.shape[1], pred.shape[2], self.size)
+            gtl = crop_origin(truth.shape[1], truth.shape[2], self.size)
+            vtl = None if scalar else crop_origin(v.shape[1], v.shape[2], self.size)
+            acc = self._state(method)
+            for t0, tn in self._cuts(n):
                 nwg = -(-tn * rows * cols // ops.PROB_WG_PIXELS)
                 part = torch.empty(nwg * nw, device=self.device, dtype=torch.float64)
                 ops.prob_accumulate(pred[t0:t0 + tn], v if scalar else v[t0:t0 + tn], truth[t0:t0 + tn], ptl, vtl, gtl, rows, cols,
@@ -212,19 +200,19 @@ class ProbEvaluator:
 
     def raw(self, method) -> torch.Tensor:
         """The method's accumulator on the device: nf fp64 words, then ni int64 words as their bits."""
-        return self._acc[method]
+        return self._methods[method]
 
     def sums(self, method) -> Dict[str, object]:
         """The method's sums so far by name (``unpack_record``); syncs.  For checks: ``compute`` is the product path."""
-        row = self._acc[method].cpu().numpy()
+        row = self._methods[method].cpu().numpy()
         return unpack_record(row[:self.layout.nf], np.ascontiguousarray(row[self.layout.nf:]).view(np.int64), self.layout)
 
     def compute(self) -> Dict[object, Dict[str, object]]:
-        names = list(self._acc)
+        names = list(self._methods)
         if not names:
             return {}
         with torch.cuda.device(self.device):
-            host = torch.stack([self._acc[k] for k in names]).cpu().numpy()         # the one host sync
+            host = torch.stack([self._methods[k] for k in names]).cpu().numpy()         # the one host sync
         nf = self.layout.nf
         return {name: prob_scores(unpack_record(row[:nf], np.ascontiguousarray(row[nf:]).view(np.int64), self.layout),
                                   self.thresholds, self.levels, self.sigma_edges) for name, row in zip(names, host)}
@@ -295,16 +283,16 @@ def run_prob(preds, variances, truth, mask=None, mode: str = "radar", crop_size=
         events = {name: ([src], [variances[name]] if name in variances else None) for name, src in preds.items()}
     if not truth_events:
         return {}
-    truth_dev = [_to_device(_thw(e), dev) for e in truth_events]
+    truth_dev = upload_events(truth_events, dev)
 
     def pieces_of(name):
         pe, ve = events[name]
-        pd = [_to_device(_thw(e), dev) for e in pe]
+        pd = upload_events(pe, dev)
         if ve is None:
             for p, g in _pieces(pd, truth_dev):
                 yield p, g, None
             return
-        vd = [_to_device(_thw(e), dev) for e in ve]
+        vd = upload_events(ve, dev)
         for p, v in zip(pd, vd):
             if p.shape[0] != v.shape[0]:
                 raise ValueError(f"method {name!r}: a variance event has {v.shape[0]} frames, its prediction {p.shape[0]}")

@@ -6,13 +6,14 @@ from __future__ import annotations
 
 import os
 import warnings
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .. import ops
-from ._common import _pieces, _thw, _to_device, crop_origin, device_tables, eval_device
+from ._common import Streaming, bounded_crop, cat, event_lists, radar_thresholds
 from .exp1 import DEFAULT_THRESHOLDS
 
 DEFAULT_SCALES = (1, 3, 5, 9, 17, 33, 65)
@@ -86,73 +87,49 @@ def spectrum_scores(pm: np.ndarray, pt: np.ndarray, S: int) -> Tuple[float, floa
     return lsd, hfr
 
 
-def _check_args(mode, thresholds, scales):
-    if mode == "gauge":
-        raise ValueError("scale verification scores neighbourhoods of the whole crop: mode 'gauge' (isolated gauge pixels) has no meaning")
-    if mode != "radar":
-        raise ValueError(f"Unknown mode: {mode}")
-    thresholds = tuple(float(t) for t in thresholds)
-    if not 0 < len(thresholds) <= ops.EXP1_MAX_THR:
-        raise ValueError(f"1 to {ops.EXP1_MAX_THR} thresholds")
+def _check_scales(scales):
     scales = tuple(int(n) for n in scales)
     if not 0 < len(scales) <= MAX_SCALES:
         raise ValueError(f"1 to {MAX_SCALES} scales")
     if any(n < 1 for n in scales) or len(set(scales)) != len(scales):
         raise ValueError(f"scales are distinct window sizes >= 1, got {scales}")
-    return thresholds, scales
+    return scales
 
 
-class _Method:
-    def __init__(self, acc):
-        self.acc, self.P, self.flag, self.T = acc, [], [], 0
-
-
-class ScaleEvaluator:
+class ScaleEvaluator(Streaming):
     """Streaming FSS and spectra.  ``update(method, pred, truth)`` adds one piece whose frames pair one for one (the longer side is
     truncated, as align_length does); ``compute()`` syncs once and returns ``{method: {...}}`` (see ``run_scale``)."""
 
+    what = "scale verification runs"
+
     def __init__(self, crop_size: int, thresholds: Sequence[float] = DEFAULT_THRESHOLDS, scales: Sequence[int] = DEFAULT_SCALES,
                  divide_by_3: bool = True, device=None, mode: str = "radar"):
-        self.thresholds, self.scales = _check_args(mode, thresholds, scales)
-        self.size = int(crop_size)
-        if not 0 < self.size <= ops.SCALE_MAX_CROP:
-            raise ValueError(f"crop size {self.size}: 1 to {ops.SCALE_MAX_CROP}")
-        self.device = eval_device(device, "scale verification runs")
-        self.divide_by_3 = bool(divide_by_3)
+        self.thresholds = radar_thresholds(mode, thresholds, "scale verification scores neighbourhoods")
+        self.scales = _check_scales(scales)
+        self.size = bounded_crop(crop_size)
+        self._start(device, divide_by_3)
         self.use_workspace = self.size > ops.SCALE_LDS_CROP      # tests set it to run a small crop through the large-crop path
-        self._lut, _ = device_tables(self.device, self.divide_by_3)
         with torch.cuda.device(self.device):
             self._tw = torch.from_numpy(twiddle(self.size)).to(self.device)
             self._rings = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in ring_list(self.size))
-        self._work: Dict[str, torch.Tensor] = {}
-        self._methods: Dict[str, _Method] = {}
 
-    def reset(self):
-        self._methods = {}
+    def _new_state(self):
+        words = len(self.thresholds) * (3 * len(self.scales) + 1)
+        return SimpleNamespace(acc=torch.zeros(words, device=self.device, dtype=torch.int64), P=[], flag=[], T=0)
 
-    def _buf(self, name: str, n: int, dtype) -> torch.Tensor:
-        b = self._work.get(name)
-        if b is None or b.numel() < n:
-            b = self._work[name] = torch.empty(n, device=self.device, dtype=dtype)
-        return b[:n]
+    def _launch_frames(self):
+        S, R = self.size, self.size // 2 + 1
+        step = max(1, _WORK_DOUBLES // (4 * S * R))
+        if self.use_workspace:
+            step = min(step, max(1, _WORK_COUNTS // (len(self.thresholds) * 2 * S * S)))
+        return step
 
     def update(self, method: str, pred_event, truth_event):
         S, R, K, N = self.size, self.size // 2 + 1, len(self.thresholds), len(self.scales)
         with torch.cuda.device(self.device):
-            truth = _to_device(_thw(truth_event), self.device)
-            pred = _to_device(_thw(pred_event), self.device)
-            gtl = crop_origin(truth.shape[1], truth.shape[2], S)
-            n = min(pred.shape[0], truth.shape[0])
-            ptl = crop_origin(pred.shape[1], pred.shape[2], S)
-            st = self._methods.get(method)
-            if st is None:
-                st = self._methods[method] = _Method(torch.zeros(K * (3 * N + 1), device=self.device, dtype=torch.int64))
+            pred, truth, ptl, gtl, n, st = self._open(method, pred_event, truth_event)
             check_overflow(st.T + n, S, self.scales)
-            step = max(1, _WORK_DOUBLES // (4 * S * R))
-            if self.use_workspace:
-                step = min(step, max(1, _WORK_COUNTS // (K * 2 * S * S)))
-            for t0 in range(0, n, step):
-                tn = min(step, n - t0)
+            for t0, tn in self._cuts(n):
                 p, g = pred[t0:t0 + tn], truth[t0:t0 + tn]
                 part = torch.empty(tn, K, 3 * N + 1, device=self.device, dtype=torch.int64)
                 ws = self._buf("tables", tn * K * 2 * S * S, torch.int32) if self.use_workspace else None
@@ -178,8 +155,7 @@ class ScaleEvaluator:
                 if st.T == 0:
                     raise ValueError(f"method {name!r} has no frames to score")
                 # the frames' ring means of all pieces in frame order, folded in that order: where pieces were cut does not matter
-                spec = ops.scale_spectrum_merge(torch.cat(st.P) if len(st.P) > 1 else st.P[0],
-                                                torch.cat(st.flag) if len(st.flag) > 1 else st.flag[0])
+                spec = ops.scale_spectrum_merge(cat(st.P), cat(st.flag))
                 rows.append(torch.cat([spec, st.acc.view(torch.float64)]))       # the integers travel as their bits
             host = torch.stack(rows).cpu().numpy()         # the one host sync
         res = {}
@@ -211,34 +187,12 @@ def run_scale(preds, truth, crop_size: int, thresholds: Sequence[float] = DEFAUL
     event a method lacks is skipped for that method, a method that is not a dict is left out).  Returns per method
     ``{"FSS": {"thr_<q:g>": {"n_<n>": v}}, "useful_scale": {"thr_<q:g>": n or None}, "LSD": dB, "HF_ratio": v, "spectrum": [...],
     "truth_spectrum": [...], "wavelength_px": [...], "frames": T, "frames_skipped": k}``."""
-    if isinstance(truth, dict):
-        keys = list(truth.keys())
-        if not keys:
-            return {}
-        truth_events = [truth[k] for k in keys if truth.get(k) is not None]
-        methods = {}
-        for name, src in preds.items():
-            if isinstance(src, dict):
-                methods[name] = [src[k] for k in keys if src.get(k) is not None]
-    else:
-        truth_events = [truth]
-        methods = {}
-        for name, src in preds.items():
-            if isinstance(src, dict):
-                raise TypeError(f"method {name!r}: per-event predictions need a per-event truth")
-            methods[name] = [src]
+    truth_events, methods = event_lists(preds, truth)
     if not truth_events:
-        raise ValueError("Expected [T,H,W], got shape (0,)")
+        return {}
     ev = ScaleEvaluator(crop_size, thresholds, scales, divide_by_3, device=device, mode=mode)
-    truth_dev = [_to_device(_thw(e), ev.device) for e in truth_events]
-    for t in truth_dev:
-        crop_origin(t.shape[1], t.shape[2], ev.size)
-    for name, events in methods.items():
-        if not events:
-            raise ValueError("Expected [T,H,W], got shape (0,)")
-        pred_dev = [_to_device(_thw(e), ev.device) for e in events]
-        for p, g in _pieces(pred_dev, truth_dev):
-            ev.update(name, p, g)
+    for name, p, g, _ in ev.pieces(truth_events, methods):
+        ev.update(name, p, g)
     return ev.compute()
 
 

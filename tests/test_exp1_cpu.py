@@ -158,6 +158,28 @@ def test_selection_rules():
         crop_origin(30, 40, 32)
 
 
+def test_event_lists_rules():
+    """run_exp1's reading of (preds, truth), which run_scale and run_objects share."""
+    from p2igan_bench.evaluation._common import event_lists
+    a, b, c = (np.full((2, 4, 4), v, np.uint8) for v in (1, 2, 3))
+    truth = {"z": a, "m": None, "k": b, "a": c}                      # not sorted: the truth's own key order counts
+    preds = {"full": {"a": c + 10, "k": b + 10, "z": a + 10}, "lacks_k": {"z": a + 20, "k": None, "a": c + 20, "extra": a},
+             "array": a + 30, "none": {}}
+    events, methods = event_lists(preds, truth)
+    assert [int(e[0, 0, 0]) for e in events] == [1, 2, 3]           # the None-valued event is dropped
+    assert list(methods) == ["full", "lacks_k", "none"]              # a method that is not a dict is left out
+    assert [int(e[0, 0, 0]) for e in methods["full"]] == [11, 12, 13]
+    assert [int(e[0, 0, 0]) for e in methods["lacks_k"]] == [21, 23]         # skipped for this method only
+    assert methods["none"] == []
+    events, methods = event_lists({"m": a + 1, "n": b}, a)
+    assert len(events) == 1 and events[0] is a and list(methods) == ["m", "n"] and methods["n"][0] is b
+    with pytest.raises(TypeError, match="method 'd': per-event predictions need a per-event truth"):
+        event_lists({"m": a, "d": {"z": a}}, a)
+    assert event_lists(preds, {}) == ([], {})
+    with pytest.raises(ValueError, match=r"Expected \[T,H,W\], got shape \(0,\)"):
+        event_lists(preds, {"z": None})
+
+
 def _evaluate_module():
     sys.path.insert(0, os.path.join(ROOT, "p2i-gan-benchmark_amd", "scripts"))
     try:

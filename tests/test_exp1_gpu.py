@@ -105,6 +105,48 @@ def test_input_forms_and_streaming_agree_bit_for_bit():
             assert np.float64(fa[k]).tobytes() == np.float64(fo[k]).tobytes(), k
 
 
+def _cut_case():
+    """crop 16 with 8x8 pooling, T = 5: a float32 prediction [5, 1, 20, 24] (crop origin (2, 4)) that follows a uint8 truth
+    [5, 1, 23, 19] (crop origin (3, 1)) inside the crop and holds unrelated values around it, and a mask with both classes."""
+    from p2igan_bench.utils import seeded
+    S, T = 16, 5
+    truth = seeded.exp1_truth(610, T, 23, 19)
+    pred = seeded.exp1_pred(611, seeded.exp1_truth(612, T, 20, 24), 30.0)
+    pred[:, :, 2:2 + S, 4:4 + S] = seeded.exp1_pred(613, truth[:, :, 3:3 + S, 1:1 + S], 10.0, 0.02, 0.01)
+    mask = seeded.exp1_mask(614, S, S, 0.3)
+    assert pred.dtype == np.float32 and truth.dtype == np.uint8 and mask.any() and not mask.all()
+    return pred, truth, mask
+
+
+@pytest.mark.parametrize("mode", ["radar", "gauge"])
+def test_launch_cuts_inside_one_update_agree_bit_for_bit(monkeypatch, mode):
+    """``max_frames`` cuts the five frames of one update into launches of 1 and of 2 frames (2 + 2 + 1).  Where the launches are cut
+    does not matter: every value is bit-identical to the single launch's, dTSSIM (which pairs frames across the cuts) included."""
+    from p2igan_bench import ops
+    from p2igan_bench.evaluation import Exp1Evaluator
+    pred, truth, mask = _cut_case()
+    kw = {"mode": mode, "crop_size": 16, "thresholds": (0.5, 2.0, 4.0, 8.0), "use_pool8": True}
+    launches, real = [], ops.exp1_accumulate
+    monkeypatch.setattr(ops, "exp1_accumulate", lambda *a, **k: (launches.append(a[0].shape[0]), real(*a, **k))[1])
+
+    def run(max_frames):
+        ev = Exp1Evaluator(mask, **kw)
+        ev.max_frames = max_frames
+        del launches[:]
+        ev.update("m", pred, truth)
+        return exp1_ref.flatten(ev.compute()), list(launches)
+    whole, n_whole = run(None)
+    assert n_whole == [5]
+    assert_device_matches(whole, _ref({"m": pred}, truth, mask, kw))        # the input says something: it scores as restated
+    assert not any(math.isnan(v) for k, v in whole.items() if k.split("/")[1] in FLOAT32_KEYS + ("PSS",))
+    for max_frames, want in ((1, [1] * 5), (2, [2, 2, 1])):
+        cut, n_cut = run(max_frames)
+        assert n_cut == want
+        assert cut.keys() == whole.keys()
+        for k in whole:
+            assert np.float64(cut[k]).tobytes() == np.float64(whole[k]).tobytes(), (max_frames, k)
+
+
 def test_two_runs_are_bit_identical():
     from p2igan_bench.evaluation import run_exp1
     preds, truth, mask = _big("gauge")

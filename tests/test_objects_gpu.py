@@ -126,6 +126,37 @@ def test_paths_pieces_and_reruns_agree():
     assert ev.compute() == {}
 
 
+@pytest.mark.parametrize("workspace", [False, True])
+def test_launch_cuts_inside_one_update_agree(monkeypatch, workspace):
+    """``max_frames`` cuts the five frames of one update into launches of 1 and of 2 frames (2 + 2 + 1), on both labelling paths.
+    Frames are labelled and scored on their own, so the integers, the frames' positions and the result do not depend on the cuts;
+    a launch's frames follow on the piece's ``origin``."""
+    from p2igan_bench import ops
+    S, T = 33, 5
+    pred, truth = ref.exact_inputs(S, T)
+    p, g = pred.astype(np.float32), ref.as_dtype(truth, np.uint8)
+    launches, real = [], ops.objects_label
+    monkeypatch.setattr(ops, "objects_label", lambda *a, **k: (launches.append(a[1]), real(*a, **k))[1])
+
+    def run(max_frames, **kw):
+        ev = evaluator(S, 8, workspace=workspace)
+        ev.max_frames = max_frames
+        del launches[:]
+        ev.update("m", p, g, **kw)
+        return ev.records("m"), json.dumps(ev.compute(), sort_keys=True), list(launches)
+    whole = run(None)
+    assert whole[2] == [T] and whole[0]["frame"].tolist() == list(range(T)) and whole[0]["event"].tolist() == [0] * T
+    for max_frames, want in ((1, [1] * 5), (2, [2, 2, 1])):
+        rec, res, n = run(max_frames)
+        assert n == want
+        assert_ints_equal(rec, whole[0], ("cuts", max_frames, workspace))
+        assert rec["frame"].tolist() == list(range(T)) and rec["event"].tolist() == [0] * T
+        assert res == whole[1], max_frames
+    rec, _, n = run(2, origin=(2, 7))
+    assert n == [2, 2, 1] and rec["frame"].tolist() == list(range(7, 7 + T)) and rec["event"].tolist() == [2] * T
+    assert_ints_equal(rec, whole[0], ("cuts at an origin", workspace))
+
+
 @pytest.mark.parametrize("conn", [4, 8])
 def test_large_crop_through_the_workspace_path(conn):
     """S = 160: 3 x 3 tiles with a ragged last row and column; patterns that straddle every border and corner, and a float field."""

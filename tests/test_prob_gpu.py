@@ -239,6 +239,37 @@ def test_two_pieces_equal_one(dev):
     assert_sums("two pieces vs reference", two.sums("m"), ref)
 
 
+@pytest.mark.parametrize("scalar", [False, True])
+def test_launch_cuts_inside_one_update(dev, monkeypatch, scalar):
+    """``max_frames`` cuts the three frames of one update into launches of 1 and of 2 frames (2 + 1), with the variance map (cut
+    along with the prediction) and with one variance for every pixel.  The workgroups' boundaries move with the cuts, so the fp64
+    sums hold at the bounds of two pieces against one, not bit for bit; a cut run repeats itself bit for bit."""
+    from p2igan_bench import ops
+    (p, v, g), kw, (cp, _, cg), sel, ref = build("u8_f32_f32_radar_3wg")
+    if scalar:
+        v = 37.5
+        ref = pr.prob_sums(cp, v, cg, sel, **{k: x for k, x in kw.items() if k not in ("crop_size", "mask", "mode")})
+        assert ref["edge_count"] == 0
+    launches, real = [], ops.prob_accumulate
+    monkeypatch.setattr(ops, "prob_accumulate", lambda *a, **k: (launches.append(a[0].shape[0]), real(*a, **k))[1])
+
+    def run(max_frames):
+        ev = _evaluator(dev, kw)
+        ev.max_frames = max_frames
+        del launches[:]
+        ev.update("m", p, g, v)
+        return ev.sums("m"), ev.raw("m").clone(), list(launches)
+    whole = run(None)
+    assert whole[2] == [3]
+    assert_sums(f"one launch (scalar {scalar}) vs reference", whole[0], ref)
+    for max_frames, want in ((1, [1, 1, 1]), (2, [2, 1])):
+        sums, raw, n = run(max_frames)
+        assert n == want
+        assert_sums(f"launches of {max_frames} (scalar {scalar})", sums, whole[0])
+        assert_sums(f"launches of {max_frames} (scalar {scalar}) vs reference", sums, ref)
+        assert torch.equal(raw.view(torch.int64), run(max_frames)[1].view(torch.int64))
+
+
 def test_krig_uq_end_to_end(dev, tmp_path):
     """KrigingGenerator.forward_uq and cross_validate on a 16 x 16, 4-frame synthetic event with 24 gauges, through run_prob /
     write_prob_outputs and run_prob_points: the files exist, the JSON equals prob_ref on the same arrays, `map` is there for kriging

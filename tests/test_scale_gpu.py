@@ -157,6 +157,33 @@ def test_streaming_and_reruns_are_bit_identical():
     assert ev.compute() == {}
 
 
+@pytest.mark.parametrize("workspace", [False, True])
+def test_launch_cuts_inside_one_update_are_bit_identical(monkeypatch, workspace):
+    """``max_frames`` cuts the six frames of one update into launches of 1, 2 and 4 frames (4 + 2); with ``use_workspace`` the
+    large-crop path's table workspace is cut as well.  The sums are integers and the spectra are folded per frame in frame order, so
+    where the launches are cut does not matter."""
+    from p2igan_bench import ops
+    S, T = 27, 6
+    pred, truth = inputs(S, T)
+    p, g = pred.astype(np.float32), scale_ref.as_dtype(truth, np.uint8)
+    launches, real = [], ops.scale_fss
+    monkeypatch.setattr(ops, "scale_fss", lambda *a, **k: (launches.append(a[0].shape[0]), real(*a, **k))[1])
+
+    def run(max_frames):
+        ev = evaluator(S, (1, 2, 5, 27, 55), (0.5, 2.0))
+        ev.use_workspace, ev.max_frames = workspace, max_frames
+        del launches[:]
+        ev.update("m", p, g)
+        return json.dumps(ev.compute()), ev.sums("m").tolist(), list(launches)
+    whole = run(None)
+    assert whole[2] == [T] and json.loads(whole[0])["m"]["frames"] == T
+    for max_frames, want in ((1, [1] * 6), (2, [2, 2, 2]), (4, [4, 2])):
+        res, sums, n = run(max_frames)
+        assert n == want
+        assert sums == whole[1], max_frames
+        assert res == whole[0], max_frames
+
+
 def test_large_crop_path_equals_lds_path_and_restatement():
     S, T = 128, 2
     pred, truth = inputs(S, T)
