@@ -481,8 +481,12 @@ int p2i_stdk_layer1_bwd(const float* phi_s, const float* phi_t, const float* z, 
                         int Ks, int Kt, int Kz, float* dqt, float* dqb, float* part, int splits, float* dw1, float* db1, void* stream);
 
 /* ---- exp1 scoring (reference experiments/exp1.py run_exp1 + experiments/io.py).  Inputs are DEVICE arrays
- * of dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W]; every statistic is fp64.  transform_mmhr(x) = clip(10^min(max(x,
+ * of dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][h][w]; every statistic is fp64.  transform_mmhr(x) = clip(10^min(max(x,
  * 0.001) [/3] / 16, 38) * 0.036, 0, 200) (exp1.py:151-159); uint8 values go through lut[256] (computed on the host by numpy).
+ * An input travels as ONE descriptor, p2i_eval_input (a HOST struct, read during the call only): the array, its dtype code, its
+ * frame extent h x w and the origin (top, left) of the crop the call reads from every frame; each input has its own extent and
+ * origin, the crop's size is the call's (S x S, or rows x cols).  A NULL descriptor or NULL data is refused like a NULL array.  This
+ * and every later evaluation unit take their inputs this way.
  * p2i_exp1_transform: out[i] = transform_mmhr(x[i]) (fp64; the check of the device pow).
  * p2i_exp1_workspace: doubles of `part` that p2i_exp1_accumulate needs for T frames of an S x S crop.
  * p2i_exp1_accumulate: one aligned piece of T frames; the crop is [top, top + S) x [left, left + S) of each input; rank[S*S]
@@ -504,12 +508,12 @@ int p2i_stdk_layer1_bwd(const float* phi_s, const float* phi_t, const float* z, 
 #define P2I_EXP1_MAX_THR 8
 #define P2I_EXP1_NSTAT (8 + 3 * P2I_EXP1_MAX_THR)
 #define P2I_EXP1_NOUT(nthr) (8 + 4 * (nthr))
+typedef struct { const void* data; int dtype, h, w, top, left; } p2i_eval_input;   /* [T][h][w] of P2I_EXP1_U8/_F32/_F64, crop origin (top, left) */
 int p2i_exp1_transform(const void* x, int dtype, int64_t n, int divide_by_3, double* out, void* stream);
 int p2i_exp1_workspace(int T, int S, int pool, int64_t* part_doubles);
-int p2i_exp1_accumulate(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth, int truth_dtype,
-                        int gh, int gw, int gtop, int gleft, int T, int S, int pool, const int* rank, int nsel, const double* lut,
-                        const double* thresholds_host, int nthr, int divide_by_3, float* pool_pred, float* pool_truth, float* sel_pred,
-                        float* sel_truth, double* part, void* stream);
+int p2i_exp1_accumulate(const p2i_eval_input* pred, const p2i_eval_input* truth, int T, int S, int pool, const int* rank, int nsel,
+                        const double* lut, const double* thresholds_host, int nthr, int divide_by_3, float* pool_pred, float* pool_truth,
+                        float* sel_pred, float* sel_truth, double* part, void* stream);
 int p2i_exp1_merge(const double* part, int64_t nparts, double* acc, void* stream);
 int p2i_exp1_hist(const float* sel_pred, const float* sel_truth, int T, int nsel, const double* acc, double* score, int* flag,
                   float* edges, void* stream);
@@ -518,8 +522,7 @@ int p2i_exp1_finalize(const double* acc, const double* thresholds_host, int nthr
                       const float* edges, const double* ssim, const double* d1, const double* d2, double* out, void* stream);
 
 /* ---- exp3 analysis (reference experiments/exp3.py run_exp3 + experiments/io.py).  Inputs are DEVICE arrays
- * as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform and uint8 table); statistics are fp64,
- * counts are integers.
+ * as for exp1 (p2i_eval_input descriptors, the same transform and uint8 table); statistics are fp64, counts are integers.
  * p2i_exp3_accumulate: one aligned piece of T frames, crops [top, top + S) x [left, left + S); rank[S*S] >= 0 marks the mode's
  *   selection.  Writes rec[T][P2I_EXP3_NREC] = per frame (n, sum (p-g)^2, truth mean, truth M2) over the selection's finite
  *   pairs; rows[T][S] (int32) = per crop row the scatter pool: pixels of the whole crop with p and g finite and g >= 0.1; and, when
@@ -535,21 +538,17 @@ int p2i_exp1_finalize(const double* acc, const double* thresholds_host, int nthr
 #define P2I_EXP3_NREC 4
 #define P2I_EXP3_BINS 64
 #define P2I_EXP3_NHIST (P2I_EXP3_BINS + 1)
-int p2i_exp3_accumulate(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth, int truth_dtype,
-                        int gh, int gw, int gtop, int gleft, int T, int S, const int* rank, const double* lut, int divide_by_3,
-                        double* rec, int* rows, uint64_t* hist, void* stream);
-int p2i_exp3_truth_hist(const void* truth, int truth_dtype, int gh, int gw, int gtop, int gleft, int T, int S, const double* lut,
-                        int divide_by_3, uint64_t* hist, void* stream);
+int p2i_exp3_accumulate(const p2i_eval_input* pred, const p2i_eval_input* truth, int T, int S, const int* rank, const double* lut,
+                        int divide_by_3, double* rec, int* rows, uint64_t* hist, void* stream);
+int p2i_exp3_truth_hist(const p2i_eval_input* truth, int T, int S, const double* lut, int divide_by_3, uint64_t* hist, void* stream);
 int p2i_exp3_scan(const int* rows, int64_t n, int64_t* prefix, void* stream);
-int p2i_exp3_gather(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth, int truth_dtype, int gh,
-                    int gw, int gtop, int gleft, int T, int S, const double* lut, int divide_by_3, const int64_t* prefix, int64_t row0,
-                    const int64_t* ords, int K, double* out_g, double* out_p, void* stream);
+int p2i_exp3_gather(const p2i_eval_input* pred, const p2i_eval_input* truth, int T, int S, const double* lut, int divide_by_3,
+                    const int64_t* prefix, int64_t row0, const int64_t* ords, int K, double* out_g, double* out_p, void* stream);
 int p2i_exp3_nse(const double* event_rec, const int* event_off, int E, const double* stack_rec, int T, double* out, void* stream);
 
 /* ---- exp2 comparison renders (reference experiments/exp2.py run_exp2 / _save_combo_gif / run_exp2_paper_zarr; DESIGN.md section
- * 12).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform and uint8
- * table).
- * p2i_exp2_index: out[n][S][S] (uint8, any alignment) = the colour index of the first n frames' crop [top, top + S) x [left,
+ * 12).  Inputs are DEVICE arrays as for exp1 (p2i_eval_input descriptors, the same transform and uint8 table).
+ * p2i_exp2_index: out[n][S][S] (uint8, any alignment) = the colour index of the first n of the input's T frames' crop [top, top + S) x [left,
  *   left + S): clip(searchsorted_right(bounds, transform_mmhr(x)) - 1, 0, 140) over the P2I_EXP2_NBOUNDS fp64 bounds (DEVICE,
  *   ascending), decided by fp64 >= compares; NaN -> P2I_EXP2_BAD.
  * p2i_exp2_compose: out[n][Hc][pitch] (uint8; pitch a multiple of 16, out and chrome 16-byte aligned) = chrome[Hc][pitch] with
@@ -560,8 +559,8 @@ int p2i_exp3_nse(const double* event_rec, const int* event_off, int E, const dou
  *   own index at the point (bg where that is P2I_EXP2_BAD), (R - 2)^2 < d2 <= R^2 takes the index edge. */
 #define P2I_EXP2_NBOUNDS 142
 #define P2I_EXP2_BAD 141
-int p2i_exp2_index(const void* x, int dtype, int T, int H, int W, int top, int left, int S, int n, const double* bounds,
-                   const double* lut, int divide_by_3, uint8_t* out, void* stream);
+int p2i_exp2_index(const p2i_eval_input* in, int T, int S, int n, const double* bounds, const double* lut, int divide_by_3,
+                   uint8_t* out, void* stream);
 int p2i_exp2_compose(const uint8_t* panels, int P, int n, int S, int zoom, unsigned gauge_bits, const int* points, int K,
                      const uint8_t* chrome, int Hc, int pitch, int oy, int ox, int step, int bg, int edge, uint8_t* out, void* stream);
 
@@ -667,7 +666,7 @@ int p2i_krig_cs_predict(const float* alpha, const float* mu, const int* pix, con
  * dt^2), kappa > 0 in pixels per frame, inside the covariance of the classical block; params [B][4] fp32 = (nugget, psill, range a,
  * kappa) per sample.  pix / z / counts are p2i_krig_compact's per-frame arrays with row length fcap; cap (a multiple of 32, <= 4096)
  * is the row length of the per-sample arrays; systems are padded to np (a multiple of 32, <= cap).  All sums run in a fixed order.
- * The solve is p2i_krig_solve with the samples standing in for frames (F = B, R = T = 1, z = stz, counts = stcounts): a sample
+ * vel / velf: NULL here; the sample velocities of the Lagrangian block below otherwise.  The solve is p2i_krig_solve with the samples standing in for frames (F = B, R = T = 1, z = stz, counts = stcounts): a sample
  * without gauges gets (0, 0), a degenerate or failed one its gauge mean over all its frames.
  * p2i_stkrig_gather: stpix [B][cap] ((y << 16) | x), stt [B][cap] (frame index), stz [B][cap] (all zero past the count), stcounts [B]
  *   = the sum of the sample's frame counts (it may exceed cap: only the first cap points are stored, the caller refuses).
@@ -683,14 +682,14 @@ int p2i_krig_cs_predict(const float* alpha, const float* mu, const int* pix, con
  * p2i_stkrig_predict: out [B][T][H W] = mean[b] + sum_i alpha[b][i] (C(d((t, p), i)) + nugget [p = x_i and t = t_i]). */
 int p2i_stkrig_gather(const int* pix, const float* z, const int* counts, int B, int T, int fcap, int cap, int* stpix, int* stt,
                       float* stz, int* stcounts, void* stream);
-int p2i_stkrig_bins(const int* pix, const float* z, const int* counts, int B, int T, int cap, int chunks, int n_lags, int n_tlags,
-                    double lag_width, double* part, void* stream);
+int p2i_stkrig_bins(const int* pix, const float* z, const int* counts, const double* vel, int B, int T, int cap, int chunks, int n_lags,
+                    int n_tlags, double lag_width, double* part, void* stream);
 int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags, int n_tlags, double lag_width, int model, double* bins,
                    double* fit, int* cand, float* params, void* stream);
-int p2i_stkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, int model, int s0, int nsys, int np,
-                      int cap, float* L, int* status, void* stream);
+int p2i_stkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, const float* velf, int model, int s0,
+                      int nsys, int np, int cap, float* L, int* status, void* stream);
 int p2i_stkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
-                       const float* params, int model, int B, int T, int H, int W, int cap, float* out, void* stream);
+                       const float* params, const float* velf, int model, int B, int T, int H, int W, int cap, float* out, void* stream);
 
 /* ---- leave-one-site-out (LOSO) cross-validation of space-time kriging (no counterpart in the reference).  A
  * site is the set of a sample's points that share a pixel (at most one per frame).  With W = L^-1, u = K^-1 1, s = 1^T u and alpha the
@@ -728,20 +727,17 @@ int p2i_stkrig_loso(const double* gram, const double* sol, const float* alpha, c
  *   distinct pixels and score [B][n n] = (sum w (z_a - z_b)^2 / 2) / W(v) (+inf where W(v) = 0), and takes the candidate of the
  *   smallest score among those with N(v) >= N(0) / 2; ties go to the smaller i^2 + j^2, then to the lower c (no pair, or zero
  *   variance: v = 0).  vel, velf [B][2] = (i, j) vstep, vcand [B] = c.
- * p2i_lagkrig_bins: p2i_stkrig_bins with h = |x_j - x_i - v u| for a pair (i in frame t, j in frame t + u); the same part layout, to
- *   be fitted by p2i_stkrig_fit.  With vel = 0 the bins are p2i_stkrig_bins' bit for bit.
- * p2i_lagkrig_factor, p2i_lagkrig_predict: p2i_stkrig_factor and p2i_stkrig_predict with the distance above (one device function
- *   serves both and is symmetric in its two points bit for bit, so a gauge is reproduced in its own frame at nugget 0). */
+ * The three stages that see the distance are the space-time block's entry points with a velocity in place of NULL; a NULL velocity
+ * IS the plain space-time model, so the library cannot tell a forgotten one: the caller checks that it has one (the Python binding's
+ * lagkrig_* wrappers do, and that is the only such guard).
+ * p2i_stkrig_bins with vel: h = |x_j - x_i - v u| for a pair (i in frame t, j in frame t + u); the same part layout, to be fitted by
+ *   p2i_stkrig_fit.  With vel = 0 the bins are the NULL call's bit for bit.
+ * p2i_stkrig_factor, p2i_stkrig_predict with velf: the distance above (one device function serves both and is symmetric in its two
+ *   points bit for bit, so a gauge is reproduced in its own frame at nugget 0). */
 int p2i_lagkrig_velocity(const int* pix, const float* z, const int* counts, int B, int T, int cap, int chunks, int n_tlags, int nhalf,
                          double vstep, double bandwidth, double* part, void* stream);
 int p2i_lagkrig_pick(const double* part, int B, int chunks, int nhalf, double vstep, double* score, double* weight, double* support,
                      double* vel, float* velf, int* vcand, void* stream);
-int p2i_lagkrig_bins(const int* pix, const float* z, const int* counts, const double* vel, int B, int T, int cap, int chunks, int n_lags,
-                     int n_tlags, double lag_width, double* part, void* stream);
-int p2i_lagkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, const float* velf, int model, int s0,
-                       int nsys, int np, int cap, float* L, int* status, void* stream);
-int p2i_lagkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
-                        const float* params, const float* velf, int model, int B, int T, int H, int W, int cap, float* out, void* stream);
 
 /* ---- moving-neighbourhood space-time ordinary kriging (no counterpart in the reference): every target is
  * predicted from its k nearest points in the space-time metric, from a k x k system of its own.  pix / z / counts are
@@ -759,28 +755,21 @@ int p2i_lagkrig_predict(const int* stpix, const int* stt, const float* alpha, co
  * p2i_lkrig_predict: out, var (nullable) [B][T][H W]; nbr (nullable) [B][T][H W][k] int32 = the selection of the kernel itself, point
  *   index t' fcap + slot in selection order, -1 past m.
  * p2i_lkrig_loso: the points as targets, each without the candidates at its own pixel (leave-one-site-out); pred, var [B T][fcap], 0
- *   past the frame's count, NaN where no candidate is left or the sample is degenerate. */
+ *   past the frame's count, NaN where no candidate is left or the sample is degenerate.
+ * velf: NULL for all of the above.  Otherwise the same two in the Lagrangian frame: velf [B][2] fp32 = (v_y, v_x)
+ * in pixels per frame, one velocity per sample.  Key, fp64, every operation rounded once and none fused: with fdt = t - t' (target minus
+ * point), e_y = (t_y - g_y) - v_y fdt and e_x likewise (one product, one sum each), key = ((e_y e_y + e_x e_x) + (kappa kappa) dt^2); the
+ * order is (key, point index).  d in K and c0 is the fp32 Lagrangian distance of the block above (sqrt((dy - v_y dt)^2 + (dx - v_x dt)^2
+ * + kappa^2 dt^2)); the nugget stays on the same pixel and frame, leave-one-site-out leaves out the target's pixel in every frame, and
+ * everything else is as above.  With v = 0 the key and the selection are those of the NULL call bit for bit. */
 int p2i_lkrig_predict(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
                       int frames, int B, int T, int H, int W, int fcap, double* stat, float* out, float* var, int* status, int* nbr,
-                      void* stream);
+                      const float* velf, void* stream);
 int p2i_lkrig_loso(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k, int frames,
-                   int B, int T, int fcap, double* stat, float* pred, float* var, int* status, void* stream);
-/* The same two in the Lagrangian frame: velf [B][2] fp32 = (v_y, v_x) in pixels per frame, one velocity per
- * sample.  Key, fp64, every operation rounded once and none fused: with fdt = t - t' (target minus point), e_y = (t_y - g_y) - v_y fdt
- * and e_x likewise (one product, one sum each), key = ((e_y e_y + e_x e_x) + (kappa kappa) dt^2); the order is (key, point index).  d
- * in K and c0 is the fp32 Lagrangian distance of the block above (sqrt((dy - v_y dt)^2 + (dx - v_x dt)^2 + kappa^2 dt^2)); the nugget
- * stays on the same pixel and frame, leave-one-site-out leaves out the target's pixel in every frame, and everything else is as
- * above.  With v = 0 the key and the selection are those of p2i_lkrig_predict / _loso bit for bit. */
-int p2i_lkrig_predict_lag(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
-                          int frames, int B, int T, int H, int W, int fcap, double* stat, float* out, float* var, int* status, int* nbr,
-                          const float* velf, void* stream);
-int p2i_lkrig_loso_lag(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
-                       int frames, int B, int T, int fcap, double* stat, float* pred, float* var, int* status, const float* velf,
-                       void* stream);
+                   int B, int T, int fcap, double* stat, float* pred, float* var, int* status, const float* velf, void* stream);
 
 /* ---- scale-aware verification: fractions skill score and radially averaged power spectra (no counterpart in
- * the reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], the same transform
- * and uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <= P2I_SCALE_MAX_CROP.
+ * the reference).  Inputs are DEVICE arrays as for exp1 (p2i_eval_input descriptors, the same transform and uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <= P2I_SCALE_MAX_CROP.
  * p2i_scale_fss: one aligned piece of T frames.  For threshold q (HOST array, <= P2I_EXP1_MAX_THR) and window size n >= 1 (HOST
  *   array, <= P2I_SCALE_MAX_SCALES), with I_p = (pred >= q), I_g = (truth >= q) (NaN compares false) and c(y, x) = the number of set
  *   pixels in rows y - n/2 .. y - n/2 + n - 1 and the same range of columns (outside the crop: 0): part[T][nthr][3 nscales + 1]
@@ -798,21 +787,20 @@ int p2i_lkrig_loso_lag(const int* pix, const float* z, const int* counts, const 
 #define P2I_SCALE_MAX_SCALES 16
 #define P2I_SCALE_LDS_CROP 128
 #define P2I_SCALE_MAX_CROP 1024
-int p2i_scale_fss(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth, int truth_dtype, int gh,
-                  int gw, int gtop, int gleft, int T, int S, const double* lut, const double* thresholds_host, int nthr,
-                  const int* scales_host, int nscales, int divide_by_3, void* workspace, int64_t* part, void* stream);
+int p2i_scale_fss(const p2i_eval_input* pred, const p2i_eval_input* truth, int T, int S, const double* lut,
+                  const double* thresholds_host, int nthr, const int* scales_host, int nscales, int divide_by_3, void* workspace,
+                  int64_t* part, void* stream);
 int p2i_scale_fss_merge(const int64_t* part, int64_t T, int n, int64_t* acc, void* stream);
-int p2i_scale_dft_rows(const void* x, int dtype, int h, int w, int top, int left, int T, int S, int field, const double* lut,
-                       int divide_by_3, const double* twiddle, double* G, int* nanflag, void* stream);
+int p2i_scale_dft_rows(const p2i_eval_input* in, int T, int S, int field, const double* lut, int divide_by_3, const double* twiddle,
+                       double* G, int* nanflag, void* stream);
 int p2i_scale_dft_cols(const double* G, int T, int S, const double* twiddle, double* psd, void* stream);
 int p2i_scale_rings(const double* psd, int T, int S, const int* order, const double* weight, const int* offsets, const double* count,
                     int R, double* P, void* stream);
 int p2i_scale_spectrum_merge(const double* P, const int* nanflag, int64_t T, int R, double* out, void* stream);
 
 /* ---- probabilistic verification of a prediction and its variance against the truth (no counterpart in the
- * reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous [T][H][W], each with its own
- * extent and crop origin); the crop is rows x cols.  Scored on the inputs' own 0-255 scale in fp64: per pixel mu = pred, s2 = var
- * (var == NULL: var_scalar for every pixel), y = truth, sigma = sqrt(s2), Phi / phi the standard normal cdf / pdf, predictive
+ * reference).  Inputs are DEVICE arrays as for exp1 (p2i_eval_input descriptors); the crop is rows x cols.  Scored on the inputs'
+ * own 0-255 scale in fp64: per pixel mu = pred, s2 = var (a NULL var descriptor, or one with NULL data: var_scalar for every pixel), y = truth, sigma = sqrt(s2), Phi / phi the standard normal cdf / pdf, predictive
  * distribution N(mu, s2), left-censored at 0 when `censor`; mu' = max(mu, 0) under censoring, mu otherwise; e = y - mu';
  * z = (y - mu) / sigma, l = -mu / sigma.  rank[rows * cols] (int32; NULL: every pixel) selects the pixels with rank >= 0.  A
  * selected pixel is SKIPPED when mu, s2 or y is NaN, s2 < 0, or (censor and y < 0); every other selected pixel is scored.
@@ -851,17 +839,15 @@ int p2i_scale_spectrum_merge(const double* P, const int* nanflag, int64_t T, int
 #define P2I_PROB_MAX_REL_BINS 32
 #define P2I_PROB_WG_PIXELS 1024
 int p2i_prob_record(int nthr, int nlevels, int nedges, int pit_bins, int rel_bins, int* nf, int* ni);
-int p2i_prob_accumulate(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* var, int var_dtype, int vh,
-                        int vw, int vtop, int vleft, double var_scalar, const void* truth, int truth_dtype, int gh, int gw, int gtop,
-                        int gleft, int64_t T, int rows, int cols, const int* rank, const double* lut, const double* thresholds_host,
-                        const double* xq_host, int nthr, const double* halfwidths_host, int nlevels, const double* edges_host,
-                        int nedges, int pit_bins, int rel_bins, int censor, int divide_by_3, double* part, int64_t part_words,
-                        void* stream);
+int p2i_prob_accumulate(const p2i_eval_input* pred, const p2i_eval_input* var, double var_scalar, const p2i_eval_input* truth, int64_t T,
+                        int rows, int cols, const int* rank, const double* lut, const double* thresholds_host, const double* xq_host,
+                        int nthr, const double* halfwidths_host, int nlevels, const double* edges_host, int nedges, int pit_bins,
+                        int rel_bins, int censor, int divide_by_3, double* part, int64_t part_words, void* stream);
 int p2i_prob_merge(const double* part, int64_t nparts, int nf, int ni, double* acc, void* stream);
 
 /* ---- object-based verification: connected rain objects and their integer moments, for SAL and the object population (DESIGN.md
- * section 23; no counterpart in the reference).  Inputs are DEVICE arrays as for exp1 (dtype P2I_EXP1_U8 / _F32 / _F64, contiguous
- * [T][h][w], the transform and uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <=
+ * section 23; no counterpart in the reference).  Inputs are DEVICE arrays as for exp1 (p2i_eval_input descriptors, the transform and
+ * uint8 table); every pixel of the crop [top, top + S) x [left, left + S) counts, S <=
  * P2I_OBJECTS_MAX_CROP.  R = the transformed pixel (mm/h) and Q = rint(R 2^24) (half-even; 0 for a NaN), Q < 2^32.  Levels: nthr
  * absolute thresholds (HOST array, <= P2I_EXP1_MAX_THR) give the mask R >= q, and one relative level, the last, R >= max(sal_factor
  * Rmax, sal_floor) with Rmax the maximum of the field's own crop in that frame; NaN compares false.  nlev = nthr + 1.  An object is
@@ -881,9 +867,8 @@ int p2i_prob_merge(const double* part, int64_t nparts, int nf, int ni, double* a
 #define P2I_OBJECTS_LDS_CROP 128
 #define P2I_OBJECTS_TILE 64
 #define P2I_OBJECTS_MAX_CROP 1024
-int p2i_objects_quantize(const void* x, int dtype, int h, int w, int top, int left, int T, int S, int field, const double* lut,
-                         const double* thresholds_host, int nthr, double sal_factor, double sal_floor, int divide_by_3, uint32_t* q,
-                         uint16_t* bits, int64_t* rec, void* stream);
+int p2i_objects_quantize(const p2i_eval_input* in, int T, int S, int field, const double* lut, const double* thresholds_host, int nthr,
+                         double sal_factor, double sal_floor, int divide_by_3, uint32_t* q, uint16_t* bits, int64_t* rec, void* stream);
 int p2i_objects_label(const uint16_t* bits, int T, int S, int nlev, int connectivity, int wide, void* labels, void* stream);
 int p2i_objects_count(const void* labels, int wide, const uint32_t* q, int T, int S, int nlev, int64_t* lev, int64_t* counts,
                       void* stream);

@@ -5,6 +5,8 @@
 // separate operations do.
 #pragma once
 #include "common.h"
+#include <stddef.h>
+#include <type_traits>
 
 namespace p2i {
 
@@ -73,17 +75,30 @@ template <int N, typename R> __device__ __forceinline__ void block_tree(R& r, do
   }
 }
 
-static inline bool eval_dtype_ok(int d) { return d == P2I_EXP1_U8 || d == P2I_EXP1_F32 || d == P2I_EXP1_F64; }
-static inline bool crop_ok(int h, int w, int top, int left, int S) { return top >= 0 && left >= 0 && top + S <= h && left + S <= w; }
+// ---- host side: the entry points' input descriptor (p2i_eval_input of p2i_hip.h), its checks and its dtype dispatch
+static_assert(sizeof(p2i_eval_input) == 32 && offsetof(p2i_eval_input, data) == 0 && offsetof(p2i_eval_input, dtype) == 8 &&
+                  offsetof(p2i_eval_input, h) == 12 && offsetof(p2i_eval_input, w) == 16 && offsetof(p2i_eval_input, top) == 20 &&
+                  offsetof(p2i_eval_input, left) == 24,
+              "p2i_eval_input is mirrored field by field by the ctypes binding");
 
-// dtype dispatch of the entry points (after eval_dtype_ok): f(T{}) for an input's dtype, f(PT{}, GT{}) for a pair's
-template <typename F> static void dispatch1(int dt, F&& f) {
-  if (dt == P2I_EXP1_U8) f(uint8_t{});
-  else if (dt == P2I_EXP1_F32) f(float{});
-  else f(double{});
+static inline bool eval_dtype_ok(int d) { return d == P2I_EXP1_U8 || d == P2I_EXP1_F32 || d == P2I_EXP1_F64; }
+// a descriptor that names an array (a NULL descriptor or NULL data names none) / whose rows x cols crop lies inside its h x w
+static inline bool input_set(const p2i_eval_input* in) { return in && in->data; }
+static inline bool crop_ok(const p2i_eval_input* in, int rows, int cols) {
+  return in->top >= 0 && in->left >= 0 && in->top + rows <= in->h && in->left + cols <= in->w;
 }
-template <typename F> static void dispatch2(int pdt, int gdt, F&& f) {
-  dispatch1(pdt, [&](auto pz) { dispatch1(gdt, [&](auto gz) { f(pz, gz); }); });
+
+// dtype dispatch of the entry points (after eval_dtype_ok): f(Crop<T>) with the input's typed view, f(Crop<PT>, Crop<GT>) for a pair.
+// Elem<decltype(view)> is T, to name the kernel's instantiation.
+template <typename T> static Crop<T> view(const p2i_eval_input* in) { return Crop<T>{(const T*)in->data, in->h, in->w, in->top, in->left}; }
+template <typename V> using Elem = std::remove_cv_t<std::remove_pointer_t<decltype(V::p)>>;
+template <typename F> static void dispatch1(const p2i_eval_input* in, F&& f) {
+  if (in->dtype == P2I_EXP1_U8) f(view<uint8_t>(in));
+  else if (in->dtype == P2I_EXP1_F32) f(view<float>(in));
+  else f(view<double>(in));
+}
+template <typename F> static void dispatch2(const p2i_eval_input* pin, const p2i_eval_input* gin, F&& f) {
+  dispatch1(pin, [&](auto p) { dispatch1(gin, [&](auto g) { f(p, g); }); });
 }
 
 }  // namespace p2i

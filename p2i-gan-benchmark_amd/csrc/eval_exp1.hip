@@ -380,16 +380,15 @@ extern "C" int p2i_exp1_workspace(int T, int S, int pool, int64_t* part_doubles)
   return P2I_OK;
 }
 
-extern "C" int p2i_exp1_accumulate(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth,
-                                   int truth_dtype, int gh, int gw, int gtop, int gleft, int T, int S, int pool, const int* rank,
+extern "C" int p2i_exp1_accumulate(const p2i_eval_input* pred, const p2i_eval_input* truth, int T, int S, int pool, const int* rank,
                                    int nsel, const double* lut, const double* thresholds_host, int nthr, int divide_by_3,
                                    float* pool_pred, float* pool_truth, float* sel_pred, float* sel_truth, double* part,
                                    void* stream) {
-  P2I_REQUIRE(pred && truth && rank && lut && part && pool_pred && pool_truth, "bad arguments");
-  P2I_REQUIRE(eval_dtype_ok(pred_dtype) && eval_dtype_ok(truth_dtype), "unsupported dtype");
+  P2I_REQUIRE(input_set(pred) && input_set(truth) && rank && lut && part && pool_pred && pool_truth, "bad arguments");
+  P2I_REQUIRE(eval_dtype_ok(pred->dtype) && eval_dtype_ok(truth->dtype), "unsupported dtype");
   P2I_REQUIRE(T > 0 && T <= 65535 && S > 0 && (pool == 1 || pool == 8) && S / pool > 0, "bad frame count / crop / pool");
-  P2I_REQUIRE(crop_ok(ph, pw, ptop, pleft, S), "crop outside the prediction");
-  P2I_REQUIRE(crop_ok(gh, gw, gtop, gleft, S), "crop outside the truth");
+  P2I_REQUIRE(crop_ok(pred, S, S), "crop outside the prediction");
+  P2I_REQUIRE(crop_ok(truth, S, S), "crop outside the truth");
   P2I_REQUIRE(nsel >= 0 && nsel <= S * S && (nsel == 0 || (sel_pred && sel_truth)), "bad selection");
   P2I_REQUIRE(nthr >= 0 && nthr <= XK && (nthr == 0 || thresholds_host), "at most %d thresholds", XK);
   Thr thr;
@@ -398,11 +397,9 @@ extern "C" int p2i_exp1_accumulate(const void* pred, int pred_dtype, int ph, int
   const int cdim = (S + pool - 1) / pool;
   const dim3 grid((unsigned)ceil_div(cdim * cdim, 64), (unsigned)T);
   const hipStream_t s = (hipStream_t)stream;
-  dispatch2(pred_dtype, truth_dtype, [&](auto pz, auto gz) {
-    using PT = decltype(pz);
-    using GT = decltype(gz);
-    P2I_LAUNCH((exp1_accumulate_kernel<PT, GT>), grid, dim3(64), 0, s, (const PT*)pred, ph, pw, ptop, pleft, (const GT*)truth, gh, gw,
-               gtop, gleft, S, pool, rank, nsel, lut, thr, divide_by_3, pool_pred, pool_truth, sel_pred, sel_truth, part);
+  dispatch2(pred, truth, [&](auto p, auto g) {
+    P2I_LAUNCH((exp1_accumulate_kernel<Elem<decltype(p)>, Elem<decltype(g)>>), grid, dim3(64), 0, s, p.p, p.h, p.w, p.top, p.left, g.p,
+               g.h, g.w, g.top, g.left, S, pool, rank, nsel, lut, thr, divide_by_3, pool_pred, pool_truth, sel_pred, sel_truth, part);
   });
   return launch_status();
 }

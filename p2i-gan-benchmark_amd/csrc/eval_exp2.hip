@@ -166,19 +166,17 @@ __global__ __launch_bounds__(64) void exp2_compose_kernel(const uint8_t* __restr
 
 using namespace p2i;
 
-extern "C" int p2i_exp2_index(const void* x, int dtype, int T, int H, int W, int top, int left, int S, int n, const double* bounds,
-                              const double* lut, int divide_by_3, uint8_t* out, void* stream) {
-  P2I_REQUIRE(x && bounds && lut && out && eval_dtype_ok(dtype), "bad arguments");
+extern "C" int p2i_exp2_index(const p2i_eval_input* in, int T, int S, int n, const double* bounds, const double* lut, int divide_by_3,
+                              uint8_t* out, void* stream) {
+  P2I_REQUIRE(input_set(in) && bounds && lut && out && eval_dtype_ok(in->dtype), "bad arguments");
   P2I_REQUIRE(S > 0 && n > 0 && n <= T, "bad frame count / crop");
-  P2I_REQUIRE(crop_ok(H, W, top, left, S), "crop outside the input");
+  P2I_REQUIRE(crop_ok(in, S, S), "crop outside the input");
   const long long total = (long long)n * S * S;
   const long long blocks = (total + (long long)((uintptr_t)out & 3u) + 1023) / 1024;
   P2I_REQUIRE(blocks <= 0x7fffffffLL, "too many pixels for one launch");
   const hipStream_t s = (hipStream_t)stream;
-  dispatch1(dtype, [&](auto z) {
-    using XT = decltype(z);
-    P2I_LAUNCH(exp2_index_kernel<XT>, dim3((unsigned)blocks), dim3(256), 0, s, Crop<XT>{(const XT*)x, H, W, top, left}, S, total, bounds,
-               lut, divide_by_3, out);
+  dispatch1(in, [&](auto x) {
+    P2I_LAUNCH(exp2_index_kernel<Elem<decltype(x)>>, dim3((unsigned)blocks), dim3(256), 0, s, x, S, total, bounds, lut, divide_by_3, out);
   });
   return launch_status();
 }

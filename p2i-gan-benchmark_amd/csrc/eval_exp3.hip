@@ -195,33 +195,29 @@ __global__ __launch_bounds__(256) void exp3_nse_kernel(const double* __restrict_
 
 using namespace p2i;
 
-extern "C" int p2i_exp3_accumulate(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth,
-                                   int truth_dtype, int gh, int gw, int gtop, int gleft, int T, int S, const int* rank,
+extern "C" int p2i_exp3_accumulate(const p2i_eval_input* pred, const p2i_eval_input* truth, int T, int S, const int* rank,
                                    const double* lut, int divide_by_3, double* rec, int* rows, uint64_t* hist, void* stream) {
-  P2I_REQUIRE(pred && truth && rank && lut && rec && rows, "bad arguments");
-  P2I_REQUIRE(eval_dtype_ok(pred_dtype) && eval_dtype_ok(truth_dtype), "unsupported dtype");
+  P2I_REQUIRE(input_set(pred) && input_set(truth) && rank && lut && rec && rows, "bad arguments");
+  P2I_REQUIRE(eval_dtype_ok(pred->dtype) && eval_dtype_ok(truth->dtype), "unsupported dtype");
   P2I_REQUIRE(T > 0 && S > 0, "bad frame count / crop");
-  P2I_REQUIRE(crop_ok(ph, pw, ptop, pleft, S), "crop outside the prediction");
-  P2I_REQUIRE(crop_ok(gh, gw, gtop, gleft, S), "crop outside the truth");
+  P2I_REQUIRE(crop_ok(pred, S, S), "crop outside the prediction");
+  P2I_REQUIRE(crop_ok(truth, S, S), "crop outside the truth");
   const hipStream_t s = (hipStream_t)stream;
-  dispatch2(pred_dtype, truth_dtype, [&](auto pz, auto gz) {
-    using PT = decltype(pz);
-    using GT = decltype(gz);
-    P2I_LAUNCH((exp3_accumulate_kernel<PT, GT>), dim3((unsigned)T), dim3(256), 0, s, Crop<PT>{(const PT*)pred, ph, pw, ptop, pleft},
-               Crop<GT>{(const GT*)truth, gh, gw, gtop, gleft}, S, rank, lut, divide_by_3, rec, rows, (unsigned long long*)hist);
+  dispatch2(pred, truth, [&](auto p, auto g) {
+    P2I_LAUNCH((exp3_accumulate_kernel<Elem<decltype(p)>, Elem<decltype(g)>>), dim3((unsigned)T), dim3(256), 0, s, p, g, S, rank, lut,
+               divide_by_3, rec, rows, (unsigned long long*)hist);
   });
   return launch_status();
 }
 
-extern "C" int p2i_exp3_truth_hist(const void* truth, int truth_dtype, int gh, int gw, int gtop, int gleft, int T, int S,
-                                   const double* lut, int divide_by_3, uint64_t* hist, void* stream) {
-  P2I_REQUIRE(truth && lut && hist && eval_dtype_ok(truth_dtype) && T > 0 && S > 0, "bad arguments");
-  P2I_REQUIRE(crop_ok(gh, gw, gtop, gleft, S), "crop outside the truth");
+extern "C" int p2i_exp3_truth_hist(const p2i_eval_input* truth, int T, int S, const double* lut, int divide_by_3, uint64_t* hist,
+                                   void* stream) {
+  P2I_REQUIRE(input_set(truth) && lut && hist && eval_dtype_ok(truth->dtype) && T > 0 && S > 0, "bad arguments");
+  P2I_REQUIRE(crop_ok(truth, S, S), "crop outside the truth");
   const hipStream_t s = (hipStream_t)stream;
-  dispatch1(truth_dtype, [&](auto gz) {
-    using GT = decltype(gz);
-    P2I_LAUNCH(exp3_truth_hist_kernel<GT>, dim3((unsigned)T), dim3(256), 0, s, Crop<GT>{(const GT*)truth, gh, gw, gtop, gleft}, S, lut,
-               divide_by_3, (unsigned long long*)hist);
+  dispatch1(truth, [&](auto g) {
+    P2I_LAUNCH(exp3_truth_hist_kernel<Elem<decltype(g)>>, dim3((unsigned)T), dim3(256), 0, s, g, S, lut, divide_by_3,
+               (unsigned long long*)hist);
   });
   return launch_status();
 }
@@ -232,22 +228,18 @@ extern "C" int p2i_exp3_scan(const int* rows, int64_t n, int64_t* prefix, void* 
   return launch_status();
 }
 
-extern "C" int p2i_exp3_gather(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth, int truth_dtype,
-                               int gh, int gw, int gtop, int gleft, int T, int S, const double* lut, int divide_by_3,
+extern "C" int p2i_exp3_gather(const p2i_eval_input* pred, const p2i_eval_input* truth, int T, int S, const double* lut, int divide_by_3,
                                const int64_t* prefix, int64_t row0, const int64_t* ords, int K, double* out_g, double* out_p,
                                void* stream) {
-  P2I_REQUIRE(pred && truth && lut && prefix && ords && out_g && out_p && K > 0 && row0 >= 0, "bad arguments");
-  P2I_REQUIRE(eval_dtype_ok(pred_dtype) && eval_dtype_ok(truth_dtype), "unsupported dtype");
+  P2I_REQUIRE(input_set(pred) && input_set(truth) && lut && prefix && ords && out_g && out_p && K > 0 && row0 >= 0, "bad arguments");
+  P2I_REQUIRE(eval_dtype_ok(pred->dtype) && eval_dtype_ok(truth->dtype), "unsupported dtype");
   P2I_REQUIRE(T > 0 && S > 0, "bad frame count / crop");
-  P2I_REQUIRE(crop_ok(ph, pw, ptop, pleft, S), "crop outside the prediction");
-  P2I_REQUIRE(crop_ok(gh, gw, gtop, gleft, S), "crop outside the truth");
+  P2I_REQUIRE(crop_ok(pred, S, S), "crop outside the prediction");
+  P2I_REQUIRE(crop_ok(truth, S, S), "crop outside the truth");
   const hipStream_t s = (hipStream_t)stream;
-  dispatch2(pred_dtype, truth_dtype, [&](auto pz, auto gz) {
-    using PT = decltype(pz);
-    using GT = decltype(gz);
-    P2I_LAUNCH((exp3_gather_kernel<PT, GT>), dim3((unsigned)ceil_div(K, 256)), dim3(256), 0, s,
-               Crop<PT>{(const PT*)pred, ph, pw, ptop, pleft}, Crop<GT>{(const GT*)truth, gh, gw, gtop, gleft}, T, S, lut, divide_by_3,
-               (const long long*)prefix, (long long)row0, (const long long*)ords, K, out_g, out_p);
+  dispatch2(pred, truth, [&](auto p, auto g) {
+    P2I_LAUNCH((exp3_gather_kernel<Elem<decltype(p)>, Elem<decltype(g)>>), dim3((unsigned)ceil_div(K, 256)), dim3(256), 0, s, p, g, T, S,
+               lut, divide_by_3, (const long long*)prefix, (long long)row0, (const long long*)ords, K, out_g, out_p);
   });
   return launch_status();
 }

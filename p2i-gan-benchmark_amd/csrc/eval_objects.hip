@@ -414,22 +414,20 @@ static inline bool objects_sizes_ok(int T, int S, int nlev) {
 
 using namespace p2i;
 
-extern "C" int p2i_objects_quantize(const void* x, int dtype, int h, int w, int top, int left, int T, int S, int field, const double* lut,
-                                    const double* thresholds_host, int nthr, double sal_factor, double sal_floor, int divide_by_3,
-                                    uint32_t* q, uint16_t* bits, int64_t* rec, void* stream) {
-  P2I_REQUIRE(x && lut && thresholds_host && q && bits && rec && eval_dtype_ok(dtype), "bad arguments");
+extern "C" int p2i_objects_quantize(const p2i_eval_input* in, int T, int S, int field, const double* lut, const double* thresholds_host,
+                                    int nthr, double sal_factor, double sal_floor, int divide_by_3, uint32_t* q, uint16_t* bits,
+                                    int64_t* rec, void* stream) {
+  P2I_REQUIRE(input_set(in) && lut && thresholds_host && q && bits && rec && eval_dtype_ok(in->dtype), "bad arguments");
   P2I_REQUIRE(T > 0 && S > 0 && S <= P2I_OBJECTS_MAX_CROP && (field == 0 || field == 1), "bad frame count / crop / field");
-  P2I_REQUIRE(crop_ok(h, w, top, left, S), "crop outside the input");
+  P2I_REQUIRE(crop_ok(in, S, S), "crop outside the input");
   P2I_REQUIRE(nthr > 0 && nthr <= OXK, "1 to %d thresholds", OXK);
   P2I_REQUIRE(sal_factor > 0.0 && sal_factor <= 1.0 && sal_floor >= 0.0, "the relative level takes a factor in (0, 1] and a floor >= 0");
   OThr thr;
   thr.k = nthr;
   for (int i = 0; i < OXK; ++i) thr.v[i] = i < nthr ? thresholds_host[i] : 0.0;
-  dispatch1(dtype, [&](auto z) {
-    using XT = decltype(z);
-    const Crop<XT> in{(const XT*)x, h, w, top, left};
-    P2I_LAUNCH((objects_quantize_kernel<XT>), dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, in, S, field, lut, thr, sal_factor,
-               sal_floor, divide_by_3, q, bits, (long long*)rec);
+  dispatch1(in, [&](auto x) {
+    P2I_LAUNCH((objects_quantize_kernel<Elem<decltype(x)>>), dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, x, S, field, lut, thr,
+               sal_factor, sal_floor, divide_by_3, q, bits, (long long*)rec);
   });
   return launch_status();
 }

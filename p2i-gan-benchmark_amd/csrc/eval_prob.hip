@@ -291,10 +291,6 @@ __global__ __launch_bounds__(64) void prob_merge_kernel(const double* __restrict
   }
 }
 
-static inline bool prob_crop_ok(int h, int w, int top, int left, int rows, int cols) {
-  return h > 0 && w > 0 && top >= 0 && left >= 0 && top + rows <= h && left + cols <= w;
-}
-
 static inline bool prob_layout(int nthr, int nlev, int nedges, int pit_bins, int rel_bins, PLayout* lay) {
   if (nthr < 0 || nthr > PK || nlev < 0 || nlev > PL || nedges < 0 || nedges > PE) return false;
   if (pit_bins < 1 || pit_bins > PNB || rel_bins < 1 || rel_bins > PRB) return false;
@@ -314,18 +310,19 @@ extern "C" int p2i_prob_record(int nthr, int nlevels, int nedges, int pit_bins, 
   return P2I_OK;
 }
 
-extern "C" int p2i_prob_accumulate(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* var, int var_dtype,
-                                   int vh, int vw, int vtop, int vleft, double var_scalar, const void* truth, int truth_dtype, int gh,
-                                   int gw, int gtop, int gleft, int64_t T, int rows, int cols, const int* rank, const double* lut,
-                                   const double* thresholds_host, const double* xq_host, int nthr, const double* halfwidths_host,
-                                   int nlevels, const double* edges_host, int nedges, int pit_bins, int rel_bins, int censor,
-                                   int divide_by_3, double* part, int64_t part_words, void* stream) {
-  P2I_REQUIRE(pred && truth && lut && part, "bad arguments");
-  P2I_REQUIRE(eval_dtype_ok(pred_dtype) && eval_dtype_ok(truth_dtype) && (!var || eval_dtype_ok(var_dtype)), "unsupported dtype");
+extern "C" int p2i_prob_accumulate(const p2i_eval_input* pred, const p2i_eval_input* var, double var_scalar, const p2i_eval_input* truth,
+                                   int64_t T, int rows, int cols, const int* rank, const double* lut, const double* thresholds_host,
+                                   const double* xq_host, int nthr, const double* halfwidths_host, int nlevels, const double* edges_host,
+                                   int nedges, int pit_bins, int rel_bins, int censor, int divide_by_3, double* part,
+                                   int64_t part_words, void* stream) {
+  P2I_REQUIRE(input_set(pred) && input_set(truth) && lut && part, "bad arguments");
+  static const p2i_eval_input no_array{};
+  if (!var) var = &no_array;      // as NULL data: var_scalar for every pixel
+  P2I_REQUIRE(eval_dtype_ok(pred->dtype) && eval_dtype_ok(truth->dtype) && (!var->data || eval_dtype_ok(var->dtype)), "unsupported dtype");
   P2I_REQUIRE(T > 0 && rows > 0 && cols > 0 && (int64_t)rows * cols <= (int64_t)1 << 30, "bad frame count / crop");
-  P2I_REQUIRE(prob_crop_ok(ph, pw, ptop, pleft, rows, cols), "crop outside the prediction");
-  P2I_REQUIRE(prob_crop_ok(gh, gw, gtop, gleft, rows, cols), "crop outside the truth");
-  P2I_REQUIRE(!var || prob_crop_ok(vh, vw, vtop, vleft, rows, cols), "crop outside the variance");
+  P2I_REQUIRE(crop_ok(pred, rows, cols), "crop outside the prediction");
+  P2I_REQUIRE(crop_ok(truth, rows, cols), "crop outside the truth");
+  P2I_REQUIRE(!var->data || crop_ok(var, rows, cols), "crop outside the variance");
   PArgs a;
   P2I_REQUIRE(prob_layout(nthr, nlevels, nedges, pit_bins, rel_bins, &a.lay), "at most %d thresholds, %d levels, %d edges, %d PIT bins, %d reliability bins",
               PK, PL, PE, PNB, PRB);
@@ -349,14 +346,10 @@ extern "C" int p2i_prob_accumulate(const void* pred, int pred_dtype, int ph, int
   const long long total = (long long)T * rows * cols;
   const long long nwg = (total + P2I_PROB_WG_PIXELS - 1) / P2I_PROB_WG_PIXELS;
   P2I_REQUIRE(nwg <= 0x7fffffffLL && part_words >= nwg * (a.lay.nf() + a.lay.ni()), "partial buffer too small");
-  const PVar v{var, var_dtype, vh, vw, vtop, vleft, var_scalar};
-  dispatch2(pred_dtype, truth_dtype, [&](auto pz, auto gz) {
-    using PT = decltype(pz);
-    using GT = decltype(gz);
-    const Crop<PT> p{(const PT*)pred, ph, pw, ptop, pleft};
-    const Crop<GT> g{(const GT*)truth, gh, gw, gtop, gleft};
-    P2I_LAUNCH((prob_accumulate_kernel<PT, GT>), dim3((unsigned)nwg), dim3(PTH), 0, (hipStream_t)stream, p, g, v, total, rows, cols, rank,
-               lut, a, part);
+  const PVar v{var->data, var->dtype, var->h, var->w, var->top, var->left, var_scalar};
+  dispatch2(pred, truth, [&](auto p, auto g) {
+    P2I_LAUNCH((prob_accumulate_kernel<Elem<decltype(p)>, Elem<decltype(g)>>), dim3((unsigned)nwg), dim3(PTH), 0, (hipStream_t)stream, p,
+               g, v, total, rows, cols, rank, lut, a, part);
   });
   return launch_status();
 }

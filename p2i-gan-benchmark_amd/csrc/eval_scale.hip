@@ -276,16 +276,15 @@ __global__ __launch_bounds__(128) void scale_spectrum_merge_kernel(const double*
 
 using namespace p2i;
 
-extern "C" int p2i_scale_fss(const void* pred, int pred_dtype, int ph, int pw, int ptop, int pleft, const void* truth, int truth_dtype,
-                             int gh, int gw, int gtop, int gleft, int T, int S, const double* lut, const double* thresholds_host,
-                             int nthr, const int* scales_host, int nscales, int divide_by_3, void* workspace, int64_t* part,
-                             void* stream) {
-  P2I_REQUIRE(pred && truth && lut && part && thresholds_host && scales_host, "bad arguments");
-  P2I_REQUIRE(eval_dtype_ok(pred_dtype) && eval_dtype_ok(truth_dtype), "unsupported dtype");
+extern "C" int p2i_scale_fss(const p2i_eval_input* pred, const p2i_eval_input* truth, int T, int S, const double* lut,
+                             const double* thresholds_host, int nthr, const int* scales_host, int nscales, int divide_by_3,
+                             void* workspace, int64_t* part, void* stream) {
+  P2I_REQUIRE(input_set(pred) && input_set(truth) && lut && part && thresholds_host && scales_host, "bad arguments");
+  P2I_REQUIRE(eval_dtype_ok(pred->dtype) && eval_dtype_ok(truth->dtype), "unsupported dtype");
   P2I_REQUIRE(T > 0 && S > 0 && S <= P2I_SCALE_MAX_CROP, "bad frame count / crop (at most %d)", P2I_SCALE_MAX_CROP);
   P2I_REQUIRE(workspace || S <= LS, "a crop above %d needs the table workspace", LS);
-  P2I_REQUIRE(crop_ok(ph, pw, ptop, pleft, S), "crop outside the prediction");
-  P2I_REQUIRE(crop_ok(gh, gw, gtop, gleft, S), "crop outside the truth");
+  P2I_REQUIRE(crop_ok(pred, S, S), "crop outside the prediction");
+  P2I_REQUIRE(crop_ok(truth, S, S), "crop outside the truth");
   P2I_REQUIRE(nthr > 0 && nthr <= XK, "1 to %d thresholds", XK);
   P2I_REQUIRE(nscales > 0 && nscales <= XN, "1 to %d scales", XN);
   SThr thr;
@@ -300,11 +299,9 @@ extern "C" int p2i_scale_fss(const void* pred, int pred_dtype, int ph, int pw, i
   }
   const dim3 grid((unsigned)T, (unsigned)nthr);
   const hipStream_t s = (hipStream_t)stream;
-  dispatch2(pred_dtype, truth_dtype, [&](auto pz, auto gz) {
-    using PT = decltype(pz);
-    using GT = decltype(gz);
-    const Crop<PT> p{(const PT*)pred, ph, pw, ptop, pleft};
-    const Crop<GT> g{(const GT*)truth, gh, gw, gtop, gleft};
+  dispatch2(pred, truth, [&](auto p, auto g) {
+    using PT = Elem<decltype(p)>;
+    using GT = Elem<decltype(g)>;
     if (workspace)
       P2I_LAUNCH((scale_fss_kernel<PT, GT, uint32_t, false>), grid, dim3(256), 0, s, p, g, S, lut, thr, sc, divide_by_3,
                  (uint32_t*)workspace, (long long*)part);
@@ -329,18 +326,16 @@ extern "C" int p2i_scale_fss_merge(const int64_t* part, int64_t T, int n, int64_
   return launch_status();
 }
 
-extern "C" int p2i_scale_dft_rows(const void* x, int dtype, int h, int w, int top, int left, int T, int S, int field, const double* lut,
-                                  int divide_by_3, const double* twiddle, double* G, int* nanflag, void* stream) {
-  P2I_REQUIRE(x && lut && twiddle && G && nanflag && eval_dtype_ok(dtype), "bad arguments");
+extern "C" int p2i_scale_dft_rows(const p2i_eval_input* in, int T, int S, int field, const double* lut, int divide_by_3,
+                                  const double* twiddle, double* G, int* nanflag, void* stream) {
+  P2I_REQUIRE(input_set(in) && lut && twiddle && G && nanflag && eval_dtype_ok(in->dtype), "bad arguments");
   P2I_REQUIRE(T > 0 && S > 0 && S <= P2I_SCALE_MAX_CROP && (field == 0 || field == 1), "bad frame count / crop / field");
-  P2I_REQUIRE(crop_ok(h, w, top, left, S), "crop outside the input");
+  P2I_REQUIRE(crop_ok(in, S, S), "crop outside the input");
   const dim3 grid((unsigned)T, (unsigned)ceil_div(S, RB));
   const size_t lds = (size_t)(RB + 2) * S * sizeof(double);
-  dispatch1(dtype, [&](auto z) {
-    using XT = decltype(z);
-    const Crop<XT> in{(const XT*)x, h, w, top, left};
-    P2I_LAUNCH((scale_dft_rows_kernel<XT>), grid, dim3(128), lds, (hipStream_t)stream, in, S, S / 2 + 1, field, lut, divide_by_3,
-               twiddle, G, nanflag);
+  dispatch1(in, [&](auto x) {
+    P2I_LAUNCH((scale_dft_rows_kernel<Elem<decltype(x)>>), grid, dim3(128), lds, (hipStream_t)stream, x, S, S / 2 + 1, field, lut,
+               divide_by_3, twiddle, G, nanflag);
   });
   return launch_status();
 }

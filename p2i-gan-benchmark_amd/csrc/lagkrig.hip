@@ -2,8 +2,8 @@
 // with the rain, d = sqrt((dy - v_y dt)^2 + (dx - v_x dt)^2 + kappa^2 dt^2), v = (v_y, v_x) in pixels per frame, one velocity per
 // sample.  This file holds what is new in it: the velocity estimate from the gauges alone (a weighted cross-variogram score over a
 // grid of candidate velocities) and the choice among the candidates.  Everything after the velocity is stkrig.hip's: its bins, build
-// and predictor kernels are templates whose LAG = true instantiations take the velocity (p2i_lagkrig_bins / _factor / _predict are
-// defined there), and p2i_stkrig_fit, krig_factor_tiles, p2i_krig_solve / _invert and the leave-one-site-out kernels of
+// and predictor kernels are templates whose LAG = true instantiations take the velocity (p2i_stkrig_bins / _factor / _predict run
+// them when they are given one), and p2i_stkrig_fit, krig_factor_tiles, p2i_krig_solve / _invert and the leave-one-site-out kernels of
 // stkrig_loso.hip are reused as they are.
 //
 // Number formats: the velocity estimate is fp64 throughout; velf is its fp32 copy for K and c0.  Every sum has a fixed order (no

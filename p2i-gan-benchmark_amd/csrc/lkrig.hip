@@ -353,62 +353,33 @@ int lk_check(const LkArgs& A, int B) {
 
 using namespace p2i;
 
-namespace {
-
-template <bool LAG>
-int lk_predict(const LkArgs& A, int B, int H, int W, double* stat, float* out, float* var, int* status, int* nbr, void* stream) {
+// velf [B][2] fp32 = (v_y, v_x) per sample runs the LAG = true kernels, NULL the LAG = false ones
+extern "C" int p2i_lkrig_predict(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
+                                 int frames, int B, int T, int H, int W, int fcap, double* stat, float* out, float* var, int* status,
+                                 int* nbr, const float* velf, void* stream) {
+  const LkArgs A{pix, z, counts, params, cand, stat, velf, model, k, frames, T, fcap, HUGE_VAL};
   if (int rc = lk_check(A, B)) return rc;
-  P2I_REQUIRE(out && status && (!LAG || A.velf), "null pointer");
+  P2I_REQUIRE(out && status, "null pointer");
   P2I_REQUIRE(H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE, "bad frame shape");
   hipStream_t s = (hipStream_t)stream;
   const int HW = H * W;
-  P2I_LAUNCH(lkrig_stat_kernel, dim3(B), dim3(256), 0, s, A.z, A.counts, A.T, A.fcap, stat);
-  const dim3 grid(ceil_div(HW, LK_TPB), A.T, B);
-  if (A.k <= 32)
-    P2I_LAUNCH((lkrig_predict_kernel<32, LAG>), grid, dim3(64), 0, s, A, W, HW, out, var, status, nbr);
-  else
-    P2I_LAUNCH((lkrig_predict_kernel<64, LAG>), grid, dim3(64), 0, s, A, W, HW, out, var, status, nbr);
+  P2I_LAUNCH(lkrig_stat_kernel, dim3(B), dim3(256), 0, s, z, counts, T, fcap, stat);
+  const auto kernel = k <= 32 ? (velf ? lkrig_predict_kernel<32, true> : lkrig_predict_kernel<32, false>)
+                              : (velf ? lkrig_predict_kernel<64, true> : lkrig_predict_kernel<64, false>);
+  P2I_LAUNCH(kernel, dim3(ceil_div(HW, LK_TPB), T, B), dim3(64), 0, s, A, W, HW, out, var, status, nbr);
   return launch_status();
-}
-
-template <bool LAG>
-int lk_loso(const LkArgs& A, int B, double* stat, float* pred, float* var, int* status, void* stream) {
-  if (int rc = lk_check(A, B)) return rc;
-  P2I_REQUIRE(pred && var && status && (!LAG || A.velf), "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  P2I_LAUNCH(lkrig_stat_kernel, dim3(B), dim3(256), 0, s, A.z, A.counts, A.T, A.fcap, stat);
-  const dim3 grid(ceil_div(A.fcap, LK_TPB), A.T, B);
-  if (A.k <= 32)
-    P2I_LAUNCH((lkrig_loso_kernel<32, LAG>), grid, dim3(64), 0, s, A, pred, var, status);
-  else
-    P2I_LAUNCH((lkrig_loso_kernel<64, LAG>), grid, dim3(64), 0, s, A, pred, var, status);
-  return launch_status();
-}
-
-}  // namespace
-
-extern "C" int p2i_lkrig_predict(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
-                                 int frames, int B, int T, int H, int W, int fcap, double* stat, float* out, float* var, int* status,
-                                 int* nbr, void* stream) {
-  return lk_predict<false>(LkArgs{pix, z, counts, params, cand, stat, nullptr, model, k, frames, T, fcap, HUGE_VAL}, B, H, W, stat, out, var, status,
-                           nbr, stream);
 }
 
 extern "C" int p2i_lkrig_loso(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
-                              int frames, int B, int T, int fcap, double* stat, float* pred, float* var, int* status, void* stream) {
-  return lk_loso<false>(LkArgs{pix, z, counts, params, cand, stat, nullptr, model, k, frames, T, fcap, HUGE_VAL}, B, stat, pred, var, status, stream);
-}
-
-// the same two in the Lagrangian frame: velf [B][2] fp32 = (v_y, v_x) per sample
-extern "C" int p2i_lkrig_predict_lag(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model,
-                                     int k, int frames, int B, int T, int H, int W, int fcap, double* stat, float* out, float* var,
-                                     int* status, int* nbr, const float* velf, void* stream) {
-  return lk_predict<true>(LkArgs{pix, z, counts, params, cand, stat, velf, model, k, frames, T, fcap, HUGE_VAL}, B, H, W, stat, out, var, status,
-                          nbr, stream);
-}
-
-extern "C" int p2i_lkrig_loso_lag(const int* pix, const float* z, const int* counts, const float* params, const int* cand, int model, int k,
-                                  int frames, int B, int T, int fcap, double* stat, float* pred, float* var, int* status, const float* velf,
-                                  void* stream) {
-  return lk_loso<true>(LkArgs{pix, z, counts, params, cand, stat, velf, model, k, frames, T, fcap, HUGE_VAL}, B, stat, pred, var, status, stream);
+                              int frames, int B, int T, int fcap, double* stat, float* pred, float* var, int* status, const float* velf,
+                              void* stream) {
+  const LkArgs A{pix, z, counts, params, cand, stat, velf, model, k, frames, T, fcap, HUGE_VAL};
+  if (int rc = lk_check(A, B)) return rc;
+  P2I_REQUIRE(pred && var && status, "null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  P2I_LAUNCH(lkrig_stat_kernel, dim3(B), dim3(256), 0, s, z, counts, T, fcap, stat);
+  const auto kernel = k <= 32 ? (velf ? lkrig_loso_kernel<32, true> : lkrig_loso_kernel<32, false>)
+                              : (velf ? lkrig_loso_kernel<64, true> : lkrig_loso_kernel<64, false>);
+  P2I_LAUNCH(kernel, dim3(ceil_div(fcap, LK_TPB), T, B), dim3(64), 0, s, A, pred, var, status);
+  return launch_status();
 }

@@ -7,8 +7,8 @@
 //
 // LAG: the bins, build and predictor kernels in the frame that moves with the rain, one velocity v = (v_y, v_x)
 // in pixels per frame per sample (lagkrig.hip estimates it): d = sqrt((dy - v_y dt)^2 + (dx - v_x dt)^2 + kappa^2 dt^2).  The
-// p2i_lagkrig_bins / _factor / _predict entry points are the LAG = true instantiations; the gather, the fit, the Cholesky and the solve
-// do not see the distance and serve both.
+// entry points run the LAG = true instantiations when they are given a velocity; the gather, the fit, the Cholesky and the solve do not
+// see the distance and serve both.
 //
 // Number formats as in classical.hip: K, its factor and c0 are fp32 (the velocity enters them as an fp32 copy); the predictor's sum
 // over the points is fp64; the variogram is fp64 throughout.  Every sum has a fixed order (no atomics).
@@ -211,57 +211,17 @@ extern "C" int p2i_stkrig_gather(const int* pix, const float* z, const int* coun
   return launch_status();
 }
 
-namespace {
-
-// the three stages that see the distance: LAG = true takes the sample velocities (vel fp64 for the bins, velf fp32 for K and c0)
-template <bool LAG>
-int st_bins(const int* pix, const float* z, const int* counts, const double* vel, int B, int T, int cap, int chunks, int n_lags, int n_tlags,
-            double lag_width, double* part, void* stream) {
-  P2I_REQUIRE(pix && z && counts && part && (!LAG || vel), "null pointer");
+// The three stages that see the distance take the sample velocities (vel fp64 for the bins, velf fp32 for K and c0): NULL runs the
+// LAG = false kernel, anything else the LAG = true one.
+extern "C" int p2i_stkrig_bins(const int* pix, const float* z, const int* counts, const double* vel, int B, int T, int cap, int chunks,
+                               int n_lags, int n_tlags, double lag_width, double* part, void* stream) {
+  P2I_REQUIRE(pix && z && counts && part, "null pointer");
   P2I_REQUIRE(B > 0 && B <= 65535 && T > 0 && (long long)B * T <= 65535 && cap > 0 && chunks > 0 && chunks <= 1024, "bad variogram shape");
   if (int rc = krig_lags_check(n_lags, lag_width)) return rc;
   P2I_REQUIRE(n_tlags >= 0 && n_tlags <= MAX_TLAGS && n_tlags < T, "n_tlags must be 0..%d and below T", MAX_TLAGS);
-  P2I_LAUNCH(stkrig_bins_kernel<LAG>, dim3(chunks, n_tlags + 1, B), dim3(BIN_THREADS), 0, (hipStream_t)stream, pix, z, counts, vel, T, cap,
-             n_lags, lag_width, part);
+  P2I_LAUNCH(vel ? stkrig_bins_kernel<true> : stkrig_bins_kernel<false>, dim3(chunks, n_tlags + 1, B), dim3(BIN_THREADS), 0,
+             (hipStream_t)stream, pix, z, counts, vel, T, cap, n_lags, lag_width, part);
   return launch_status();
-}
-
-template <bool LAG>
-int st_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, const float* velf, int model, int s0, int nsys,
-              int np, int cap, float* L, int* status, void* stream) {
-  P2I_REQUIRE(stpix && stt && stcounts && params && L && status && (!LAG || velf), "null pointer");
-  if (int rc = krig_model_check(model)) return rc;
-  if (int rc = krig_sys_check(s0, 1, 1, nsys, np, cap)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int nt = np / TS;
-  P2I_LAUNCH(stkrig_build_kernel<LAG>, dim3(nt, nt, nsys), dim3(256), 0, s, stpix, stt, stcounts, params, velf, model, s0, cap, np, L);
-  krig_factor_tiles(L, nsys, np, status, s);
-  return launch_status();
-}
-
-template <bool LAG>
-int st_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts, const float* params,
-               const float* velf, int model, int B, int T, int H, int W, int cap, float* out, void* stream) {
-  P2I_REQUIRE(stpix && stt && alpha && mean && stcounts && params && out && (!LAG || velf), "null pointer");
-  if (int rc = krig_frame_check(model, H, W)) return rc;
-  P2I_REQUIRE(B > 0 && B <= 65535 && T > 0 && ceil_div(T, FG) <= 65535, "bad sample shape %d x %d", B, T);
-  if (int rc = krig_cap_check(cap)) return rc;
-  const int HW = H * W;
-  P2I_LAUNCH(stkrig_predict_kernel<LAG>, dim3(ceil_div(HW, 256), B, ceil_div(T, FG)), dim3(256), 0, (hipStream_t)stream, stpix, stt, alpha,
-             mean, stcounts, params, velf, model, T, W, HW, cap, out);
-  return launch_status();
-}
-
-}  // namespace
-
-extern "C" int p2i_stkrig_bins(const int* pix, const float* z, const int* counts, int B, int T, int cap, int chunks, int n_lags,
-                               int n_tlags, double lag_width, double* part, void* stream) {
-  return st_bins<false>(pix, z, counts, nullptr, B, T, cap, chunks, n_lags, n_tlags, lag_width, part, stream);
-}
-
-extern "C" int p2i_lagkrig_bins(const int* pix, const float* z, const int* counts, const double* vel, int B, int T, int cap, int chunks,
-                                int n_lags, int n_tlags, double lag_width, double* part, void* stream) {
-  return st_bins<true>(pix, z, counts, vel, B, T, cap, chunks, n_lags, n_tlags, lag_width, part, stream);
 }
 
 extern "C" int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags, int n_tlags, double lag_width, int model, double* bins,
@@ -275,23 +235,28 @@ extern "C" int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags,
   return launch_status();
 }
 
-extern "C" int p2i_stkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, int model, int s0, int nsys,
-                                 int np, int cap, float* L, int* status, void* stream) {
-  return st_factor<false>(stpix, stt, stcounts, params, nullptr, model, s0, nsys, np, cap, L, status, stream);
-}
-
-extern "C" int p2i_lagkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, const float* velf, int model,
-                                  int s0, int nsys, int np, int cap, float* L, int* status, void* stream) {
-  return st_factor<true>(stpix, stt, stcounts, params, velf, model, s0, nsys, np, cap, L, status, stream);
+extern "C" int p2i_stkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, const float* velf, int model,
+                                 int s0, int nsys, int np, int cap, float* L, int* status, void* stream) {
+  P2I_REQUIRE(stpix && stt && stcounts && params && L && status, "null pointer");
+  if (int rc = krig_model_check(model)) return rc;
+  if (int rc = krig_sys_check(s0, 1, 1, nsys, np, cap)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int nt = np / TS;
+  P2I_LAUNCH(velf ? stkrig_build_kernel<true> : stkrig_build_kernel<false>, dim3(nt, nt, nsys), dim3(256), 0, s, stpix, stt, stcounts,
+             params, velf, model, s0, cap, np, L);
+  krig_factor_tiles(L, nsys, np, status, s);
+  return launch_status();
 }
 
 extern "C" int p2i_stkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
-                                  const float* params, int model, int B, int T, int H, int W, int cap, float* out, void* stream) {
-  return st_predict<false>(stpix, stt, alpha, mean, stcounts, params, nullptr, model, B, T, H, W, cap, out, stream);
-}
-
-extern "C" int p2i_lagkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
-                                   const float* params, const float* velf, int model, int B, int T, int H, int W, int cap, float* out,
-                                   void* stream) {
-  return st_predict<true>(stpix, stt, alpha, mean, stcounts, params, velf, model, B, T, H, W, cap, out, stream);
+                                  const float* params, const float* velf, int model, int B, int T, int H, int W, int cap, float* out,
+                                  void* stream) {
+  P2I_REQUIRE(stpix && stt && alpha && mean && stcounts && params && out, "null pointer");
+  if (int rc = krig_frame_check(model, H, W)) return rc;
+  P2I_REQUIRE(B > 0 && B <= 65535 && T > 0 && ceil_div(T, FG) <= 65535, "bad sample shape %d x %d", B, T);
+  if (int rc = krig_cap_check(cap)) return rc;
+  const int HW = H * W;
+  P2I_LAUNCH(velf ? stkrig_predict_kernel<true> : stkrig_predict_kernel<false>, dim3(ceil_div(HW, 256), B, ceil_div(T, FG)), dim3(256), 0,
+             (hipStream_t)stream, stpix, stt, alpha, mean, stcounts, params, velf, model, T, W, HW, cap, out);
+  return launch_status();
 }

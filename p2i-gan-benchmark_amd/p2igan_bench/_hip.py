@@ -20,12 +20,18 @@ class ConvDesc(C.Structure):
                  "st", "sh", "sw", "pt", "ph", "pw")]
 
 
+class EvalInput(C.Structure):
+    """p2i_eval_input: one evaluation input [T][h][w] of dtype code ``dtype`` and the origin (top, left) of the crop read from it"""
+    _fields_ = [("data", C.c_void_p)] + [(n, C.c_int) for n in ("dtype", "h", "w", "top", "left")]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
 _L = C.c_int64
 _F64 = C.c_double
 _D = C.POINTER(ConvDesc)
+_E = C.POINTER(EvalInput)
 
 # name -> argtypes (every entry point returns int); must list EVERY symbol of include/p2i_hip.h
 SIGNATURES = {
@@ -117,18 +123,17 @@ SIGNATURES = {
     "p2i_stdk_layer1_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P],
     "p2i_exp1_transform": [_P, _I, _L, _I, _P, _P],
     "p2i_exp1_workspace": [_I, _I, _I, C.POINTER(C.c_int64)],
-    "p2i_exp1_accumulate": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P,
-                            C.POINTER(C.c_double), _I, _I, _P, _P, _P, _P, _P, _P],
+    "p2i_exp1_accumulate": [_E, _E, _I, _I, _I, _P, _I, _P, C.POINTER(C.c_double), _I, _I, _P, _P, _P, _P, _P, _P],
     "p2i_exp1_merge": [_P, _L, _P, _P],
     "p2i_exp1_hist": [_P, _P, _I, _I, _P, _P, _P, _P, _P],
     "p2i_exp1_ssim": [_P, _P, _I, _I, _P, _P, _P, _P],
     "p2i_exp1_finalize": [_P, C.POINTER(C.c_double), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
-    "p2i_exp3_accumulate": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P],
-    "p2i_exp3_truth_hist": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P],
+    "p2i_exp3_accumulate": [_E, _E, _I, _I, _P, _P, _I, _P, _P, _P, _P],
+    "p2i_exp3_truth_hist": [_E, _I, _I, _P, _I, _P, _P],
     "p2i_exp3_scan": [_P, _L, _P, _P],
-    "p2i_exp3_gather": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _L, _P, _I, _P, _P, _P],
+    "p2i_exp3_gather": [_E, _E, _I, _I, _P, _I, _P, _L, _P, _I, _P, _P, _P],
     "p2i_exp3_nse": [_P, _P, _I, _P, _I, _P, _P],
-    "p2i_exp2_index": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P],
+    "p2i_exp2_index": [_E, _I, _I, _I, _P, _P, _I, _P, _P],
     "p2i_exp2_compose": [_P, _I, _I, _I, _I, C.c_uint, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "p2i_krig_compact": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "p2i_krig_bins": [_P, _P, _P, _I, _I, _I, _I, _F64, _P, _P],
@@ -146,37 +151,30 @@ SIGNATURES = {
     "p2i_krig_cs_weights": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "p2i_krig_cs_predict": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "p2i_stkrig_gather": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "p2i_stkrig_bins": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F64, _P, _P],
+    "p2i_stkrig_bins": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F64, _P, _P],
     "p2i_stkrig_fit": [_P, _I, _I, _I, _I, _F64, _I, _P, _P, _P, _P, _P],
-    "p2i_stkrig_factor": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
-    "p2i_stkrig_predict": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "p2i_stkrig_factor": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "p2i_stkrig_predict": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "p2i_stkrig_gather_sites": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "p2i_stkrig_site_gram": [_P, _I, _I, _P, _P],
     "p2i_stkrig_loso": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "p2i_lagkrig_velocity": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F64, _F64, _P, _P],
     "p2i_lagkrig_pick": [_P, _I, _I, _I, _F64, _P, _P, _P, _P, _P, _P, _P],
-    "p2i_lagkrig_bins": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F64, _P, _P],
-    "p2i_lagkrig_factor": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
-    "p2i_lagkrig_predict": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
-    "p2i_lkrig_predict": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "p2i_lkrig_loso": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "p2i_lkrig_predict_lag": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "p2i_lkrig_loso_lag": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "p2i_lkrig_predict": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "p2i_lkrig_loso": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "p2i_idw_loo": [_P, _P, _P, _I, _I, _F, _P, _P],
     "p2i_loo_scores": [_P, _P, _P, _P, _I, _I, _P, _P, _P],
-    "p2i_scale_fss": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(C.c_double), _I, C.POINTER(C.c_int), _I, _I,
-                      _P, _P, _P],
+    "p2i_scale_fss": [_E, _E, _I, _I, _P, C.POINTER(C.c_double), _I, C.POINTER(C.c_int), _I, _I, _P, _P, _P],
     "p2i_scale_fss_merge": [_P, _L, _I, _P, _P],
-    "p2i_scale_dft_rows": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
+    "p2i_scale_dft_rows": [_E, _I, _I, _I, _P, _I, _P, _P, _P, _P],
     "p2i_scale_dft_cols": [_P, _I, _I, _P, _P, _P],
     "p2i_scale_rings": [_P, _I, _I, _P, _P, _P, _P, _I, _P, _P],
     "p2i_scale_spectrum_merge": [_P, _P, _L, _I, _P, _P],
     "p2i_prob_record": [_I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)],
-    "p2i_prob_accumulate": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F64, _P, _I, _I, _I, _I, _I, _L, _I, _I, _P, _P,
-                            C.POINTER(C.c_double), C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I,
-                            _I, _I, _I, _I, _P, _L, _P],
+    "p2i_prob_accumulate": [_E, _E, _F64, _E, _L, _I, _I, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _I,
+                            C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, _I, _I, _I, _I, _P, _L, _P],
     "p2i_prob_merge": [_P, _L, _I, _I, _P, _P],
-    "p2i_objects_quantize": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(C.c_double), _I, _F64, _F64, _I, _P, _P, _P, _P],
+    "p2i_objects_quantize": [_E, _I, _I, _I, _P, C.POINTER(C.c_double), _I, _F64, _F64, _I, _P, _P, _P, _P],
     "p2i_objects_label": [_P, _I, _I, _I, _I, _I, _P, _P],
     "p2i_objects_count": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
     "p2i_objects_scan": [_P, _L, _P, _P],

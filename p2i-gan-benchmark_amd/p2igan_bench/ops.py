@@ -1690,12 +1690,8 @@ def stkrig_variogram(pix, z, info, B, T, n_lags, n_tlags, lag_width, model, vel=
     fit = torch.empty(B, 5, device=dev, dtype=torch.float64)
     cand = torch.empty(B, device=dev, dtype=torch.int32)
     params = torch.empty(B, 4, device=dev, dtype=torch.float32)
-    if vel is not None:
-        _hip.check(lib.p2i_lagkrig_bins(_ptr(pix), _ptr(z), _ptr(info), _ptr(vel), B, T, cap, STKRIG_BIN_CHUNKS, n_lags, n_tlags,
-                                        float(lag_width), _ptr(part), _stream()), "p2i_lagkrig_bins")
-    else:
-        _hip.check(lib.p2i_stkrig_bins(_ptr(pix), _ptr(z), _ptr(info), B, T, cap, STKRIG_BIN_CHUNKS, n_lags, n_tlags, float(lag_width),
-                                       _ptr(part), _stream()), "p2i_stkrig_bins")
+    _hip.check(lib.p2i_stkrig_bins(_ptr(pix), _ptr(z), _ptr(info), _ptr(vel), B, T, cap, STKRIG_BIN_CHUNKS, n_lags, n_tlags,
+                                   float(lag_width), _ptr(part), _stream()), "p2i_stkrig_bins")
     _hip.check(lib.p2i_stkrig_fit(_ptr(part), B, STKRIG_BIN_CHUNKS, n_lags, n_tlags, float(lag_width), int(model), _ptr(bins), _ptr(fit),
                                   _ptr(cand), _ptr(params), _stream()), "p2i_stkrig_fit")
     return bins, fit, cand, params
@@ -1717,11 +1713,8 @@ def stkrig_factor(stpix, stt, stinfo, params, model, s0, nsys, np_, L, status, v
     _krig_ws(who, L, nsys, np_)
     if velf is not None:
         _lag_vel(who, velf, torch.float32, B)
-        _hip.check(lib.p2i_lagkrig_factor(_ptr(stpix), _ptr(stt), _ptr(stinfo), _ptr(params), _ptr(velf), int(model), s0, nsys, np_, cap,
-                                          _ptr(L), _ptr(status), _stream()), "p2i_lagkrig_factor")
-        return
-    _hip.check(lib.p2i_stkrig_factor(_ptr(stpix), _ptr(stt), _ptr(stinfo), _ptr(params), int(model), s0, nsys, np_, cap, _ptr(L),
-                                     _ptr(status), _stream()), "p2i_stkrig_factor")
+    _hip.check(lib.p2i_stkrig_factor(_ptr(stpix), _ptr(stt), _ptr(stinfo), _ptr(params), _ptr(velf), int(model), s0, nsys, np_, cap,
+                                     _ptr(L), _ptr(status), _stream()), "p2i_stkrig_factor")
 
 
 def stkrig_predict(stpix, stt, alpha, mean, stinfo, params, model, T, H, W, velf=None, who="stkrig_predict"):
@@ -1739,11 +1732,8 @@ def stkrig_predict(stpix, stt, alpha, mean, stinfo, params, model, T, H, W, velf
     out = torch.empty(B, T, H * W, device=stpix.device, dtype=torch.float32)
     if velf is not None:
         _lag_vel(who, velf, torch.float32, B)
-        _hip.check(lib.p2i_lagkrig_predict(_ptr(stpix), _ptr(stt), _ptr(alpha), _ptr(mean), _ptr(stinfo), _ptr(params), _ptr(velf),
-                                           int(model), B, T, H, W, cap, _ptr(out), _stream()), "p2i_lagkrig_predict")
-        return out
-    _hip.check(lib.p2i_stkrig_predict(_ptr(stpix), _ptr(stt), _ptr(alpha), _ptr(mean), _ptr(stinfo), _ptr(params), int(model), B, T, H, W,
-                                      cap, _ptr(out), _stream()), "p2i_stkrig_predict")
+    _hip.check(lib.p2i_stkrig_predict(_ptr(stpix), _ptr(stt), _ptr(alpha), _ptr(mean), _ptr(stinfo), _ptr(params), _ptr(velf), int(model),
+                                      B, T, H, W, cap, _ptr(out), _stream()), "p2i_stkrig_predict")
     return out
 
 
@@ -1920,13 +1910,8 @@ def lkrig_predict(pix, z, info, params, cand, model, k, frames, B, T, H, W, vari
     var = torch.empty(B, T, H * W, device=dev, dtype=torch.float32) if variance else None
     nbr = torch.empty(B, T, H * W, k, device=dev, dtype=torch.int32) if neighbours else None
     status = torch.zeros(B, device=dev, dtype=torch.int32)
-    if velf is not None:
-        _hip.check(lib.p2i_lkrig_predict_lag(_ptr(pix), _ptr(z), _ptr(info), _ptr(params), _ptr(cand), int(model), k, frames, B, T, H, W, fcap,
-                                             _ptr(stat), _ptr(out), _ptr(var), _ptr(status), _ptr(nbr), _ptr(velf), _stream()),
-                   "p2i_lkrig_predict_lag")
-        return out, var, status, nbr
     _hip.check(lib.p2i_lkrig_predict(_ptr(pix), _ptr(z), _ptr(info), _ptr(params), _ptr(cand), int(model), k, frames, B, T, H, W, fcap,
-                                     _ptr(stat), _ptr(out), _ptr(var), _ptr(status), _ptr(nbr), _stream()), "p2i_lkrig_predict")
+                                     _ptr(stat), _ptr(out), _ptr(var), _ptr(status), _ptr(nbr), _ptr(velf), _stream()), "p2i_lkrig_predict")
     return out, var, status, nbr
 
 
@@ -1942,12 +1927,8 @@ def lkrig_loso(pix, z, info, params, cand, model, k, frames, B, T, velf=None):
     stat = torch.empty(B, 2, device=dev, dtype=torch.float64)
     pred, var = torch.empty_like(z), torch.empty_like(z)
     status = torch.zeros(B, device=dev, dtype=torch.int32)
-    if velf is not None:
-        _hip.check(lib.p2i_lkrig_loso_lag(_ptr(pix), _ptr(z), _ptr(info), _ptr(params), _ptr(cand), int(model), k, frames, B, T, fcap,
-                                          _ptr(stat), _ptr(pred), _ptr(var), _ptr(status), _ptr(velf), _stream()), "p2i_lkrig_loso_lag")
-        return pred, var, status
     _hip.check(lib.p2i_lkrig_loso(_ptr(pix), _ptr(z), _ptr(info), _ptr(params), _ptr(cand), int(model), k, frames, B, T, fcap, _ptr(stat),
-                                  _ptr(pred), _ptr(var), _ptr(status), _stream()), "p2i_lkrig_loso")
+                                  _ptr(pred), _ptr(var), _ptr(status), _ptr(velf), _stream()), "p2i_lkrig_loso")
     return pred, var, status
 
 
@@ -2195,10 +2176,11 @@ def _eval_code(t: torch.Tensor) -> int:
 
 
 def _eval_input(t: torch.Tensor, tl):
-    """An input [T, H, W] (uint8 / f32 / f64) and its crop origin (top, left) as the ABI's group ptr, dtype, H, W, top, left."""
+    """An input [T, H, W] (uint8 / f32 / f64) and its crop origin (top, left) as the ABI's descriptor p2i_eval_input; an entry point
+    takes it by reference, and the caller's name or argument list keeps it alive across the call."""
     if t.dim() != 3:
         raise RuntimeError(f"evaluation ops: expected [T, H, W], got {tuple(t.shape)}")
-    return _ptr(t), _eval_code(t), t.shape[1], t.shape[2], int(tl[0]), int(tl[1])
+    return _hip.EvalInput(_ptr(t), _eval_code(t), t.shape[1], t.shape[2], int(tl[0]), int(tl[1]))
 
 
 def _eval_bufs(what, *bufs):
@@ -2243,7 +2225,7 @@ def exp1_accumulate(pred, truth, ptl, gtl, S, pool, rank, nsel, lut, thresholds,
                (pool_g, torch.float32, npool), (sel_p, torch.float32, T * nsel), (sel_g, torch.float32, T * nsel),
                (part, torch.float64, part.numel()))
     _hip.check(_hip.load().p2i_exp1_accumulate(
-        *pin, *gin, T, S, pool, _ptr(rank), nsel, _ptr(lut), _f64s(thresholds), len(thresholds), int(divide_by_3), _ptr(pool_p),
+        pin, gin, T, S, pool, _ptr(rank), nsel, _ptr(lut), _f64s(thresholds), len(thresholds), int(divide_by_3), _ptr(pool_p),
         _ptr(pool_g), _ptr(sel_p) if nsel else None, _ptr(sel_g) if nsel else None, _ptr(part), _stream()), "p2i_exp1_accumulate")
 
 
@@ -2295,7 +2277,7 @@ def exp3_accumulate(pred, truth, ptl, gtl, S, rank, lut, divide_by_3, rec, rows,
     pin, gin = _eval_input(pred, ptl), _eval_input(truth, gtl)
     _eval_bufs("exp3_accumulate", (rank, torch.int32, S * S), (lut, torch.float64, 256), (rec, torch.float64, T * EXP3_NREC),
                (rows, torch.int32, T * S), *([(hist, torch.int64, EXP3_NHIST)] if hist is not None else []))
-    _hip.check(_hip.load().p2i_exp3_accumulate(*pin, *gin, T, S, _ptr(rank), _ptr(lut), int(divide_by_3), _ptr(rec), _ptr(rows),
+    _hip.check(_hip.load().p2i_exp3_accumulate(pin, gin, T, S, _ptr(rank), _ptr(lut), int(divide_by_3), _ptr(rec), _ptr(rows),
                                                _ptr(hist), _stream()), "p2i_exp3_accumulate")
 
 
@@ -2303,7 +2285,7 @@ def exp3_truth_hist(truth, gtl, S, lut, divide_by_3, hist):
     """Adds the log-frequency counts of every cropped frame of truth [T, H, W] to hist [EXP3_NHIST] (int64)."""
     gin = _eval_input(truth, gtl)
     _eval_bufs("exp3_truth_hist", (lut, torch.float64, 256), (hist, torch.int64, EXP3_NHIST))
-    _hip.check(_hip.load().p2i_exp3_truth_hist(*gin, truth.shape[0], S, _ptr(lut), int(divide_by_3), _ptr(hist), _stream()),
+    _hip.check(_hip.load().p2i_exp3_truth_hist(gin, truth.shape[0], S, _ptr(lut), int(divide_by_3), _ptr(hist), _stream()),
                "p2i_exp3_truth_hist")
 
 
@@ -2327,7 +2309,7 @@ def exp3_gather(pred, truth, ptl, gtl, S, lut, divide_by_3, prefix, row0, ords, 
                (out_g, torch.float64, K), (out_p, torch.float64, K))
     if K == 0 or T == 0:
         return
-    _hip.check(_hip.load().p2i_exp3_gather(*pin, *gin, T, S, _ptr(lut), int(divide_by_3), _ptr(prefix), int(row0), _ptr(ords), K,
+    _hip.check(_hip.load().p2i_exp3_gather(pin, gin, T, S, _ptr(lut), int(divide_by_3), _ptr(prefix), int(row0), _ptr(ords), K,
                                            _ptr(out_g), _ptr(out_p), _stream()), "p2i_exp3_gather")
 
 
@@ -2348,12 +2330,12 @@ def exp3_nse(event_rec, event_off, stack_rec) -> torch.Tensor:
 def exp2_index(x, tl, S, n, bounds, lut, divide_by_3, out):
     """The colour indices of the first n frames of x [T, H, W] (uint8 / f32 / f64), cropped to S x S at tl = (top, left), into out
     [n, S, S] (uint8): see include/p2i_hip.h.  bounds [EXP2_NBOUNDS] and lut [256] are f64 on the device."""
-    ptr, code, *crop = _eval_input(x, tl)
+    xin = _eval_input(x, tl)
     _eval_bufs("exp2_index", (bounds, torch.float64, EXP2_NBOUNDS), (lut, torch.float64, 256), (out, torch.uint8, n * S * S))
     if n == 0:
         return
-    _hip.check(_hip.load().p2i_exp2_index(ptr, code, x.shape[0], *crop, S, n, _ptr(bounds), _ptr(lut), int(divide_by_3), _ptr(out),
-                                          _stream()), "p2i_exp2_index")
+    _hip.check(_hip.load().p2i_exp2_index(xin, x.shape[0], S, n, _ptr(bounds), _ptr(lut), int(divide_by_3), _ptr(out), _stream()),
+               "p2i_exp2_index")
 
 
 def exp2_pitch(width: int) -> int:
@@ -2393,7 +2375,7 @@ def scale_fss(pred, truth, ptl, gtl, S, lut, thresholds, scales, divide_by_3, pa
     _eval_bufs("scale_fss", (lut, torch.float64, 256), (part, torch.int64, T * K * (3 * N + 1)),
                *([(workspace, torch.int32, T * K * 2 * S * S)] if workspace is not None else []))
     sc = (C.c_int * N)(*[min(int(n), 2 ** 31 - 1) for n in scales])
-    _hip.check(_hip.load().p2i_scale_fss(*pin, *gin, T, S, _ptr(lut), _f64s(thresholds), K, sc, N, int(divide_by_3),
+    _hip.check(_hip.load().p2i_scale_fss(pin, gin, T, S, _ptr(lut), _f64s(thresholds), K, sc, N, int(divide_by_3),
                                          _ptr(workspace) if workspace is not None else None, _ptr(part), _stream()), "p2i_scale_fss")
 
 
@@ -2421,7 +2403,7 @@ def scale_spectra(pred, truth, ptl, gtl, S, lut, divide_by_3, tw, rings, G, psd,
     nanflag.zero_()
     lib = _hip.load()
     for field, (x, tl) in enumerate(((pred, ptl), (truth, gtl))):
-        _hip.check(lib.p2i_scale_dft_rows(*_eval_input(x, tl), T, S, field, _ptr(lut), int(divide_by_3), _ptr(tw), _ptr(G), _ptr(nanflag),
+        _hip.check(lib.p2i_scale_dft_rows(_eval_input(x, tl), T, S, field, _ptr(lut), int(divide_by_3), _ptr(tw), _ptr(G), _ptr(nanflag),
                                           _stream()), "p2i_scale_dft_rows")
     _hip.check(lib.p2i_scale_dft_cols(_ptr(G), T, S, _ptr(tw), _ptr(psd), _stream()), "p2i_scale_dft_cols")
     _hip.check(lib.p2i_scale_rings(_ptr(psd), T, S, _ptr(order), _ptr(weight), _ptr(offsets), _ptr(count), R, _ptr(P), _stream()),
@@ -2456,7 +2438,7 @@ def objects_quantize(x, tl, field, S, lut, thresholds, sal_factor, sal_floor, di
         raise RuntimeError("objects_quantize: field / thresholds / crop")
     _eval_bufs("objects_quantize", (lut, torch.float64, 256), (q, torch.int32, T * 2 * S * S), (bits, torch.int16, T * 2 * S * S),
                (rec, torch.int64, T * 2 * 5))
-    _hip.check(_hip.load().p2i_objects_quantize(*_eval_input(x, tl), T, S, field, _ptr(lut), _f64s(thresholds), K, float(sal_factor),
+    _hip.check(_hip.load().p2i_objects_quantize(_eval_input(x, tl), T, S, field, _ptr(lut), _f64s(thresholds), K, float(sal_factor),
                                                 float(sal_floor), int(divide_by_3), _ptr(q), _ptr(bits), _ptr(rec), _stream()),
                "p2i_objects_quantize")
 
@@ -2524,7 +2506,7 @@ def prob_accumulate(pred, var, truth, ptl, vtl, gtl, rows, cols, rank, lut, thre
             raise RuntimeError("prob_accumulate: the variance's frame count")
         vin, v0 = _eval_input(var, vtl), 0.0
     else:
-        vin, v0 = (None, 0, 0, 0, 0, 0), float(var)
+        vin, v0 = None, float(var)
     nf, ni = prob_record(len(thresholds), len(halfwidths), len(edges), pit_bins, rel_bins)
     nwg = -(-T * rows * cols // PROB_WG_PIXELS)
     bufs = [(lut, torch.float64, 256), (part, torch.float64, nwg * (nf + ni))]
@@ -2532,7 +2514,7 @@ def prob_accumulate(pred, var, truth, ptl, vtl, gtl, rows, cols, rank, lut, thre
         bufs.append((rank, torch.int32, rows * cols))
     _eval_bufs("prob_accumulate", *bufs)
     _hip.check(_hip.load().p2i_prob_accumulate(
-        *pin, *vin, v0, *gin, T, rows, cols, _ptr(rank) if rank is not None else None, _ptr(lut), _f64s(thresholds), _f64s(xq),
+        pin, vin, v0, gin, T, rows, cols, _ptr(rank) if rank is not None else None, _ptr(lut), _f64s(thresholds), _f64s(xq),
         len(thresholds), _f64s(halfwidths), len(halfwidths), _f64s(edges), len(edges), pit_bins, rel_bins, int(bool(censor)),
         int(divide_by_3), _ptr(part), part.numel(), _stream()), "p2i_prob_accumulate")
 

@@ -254,6 +254,9 @@ def test_surface(tmp_path):
     assert inspect.signature(ops.lkrig_loso).parameters["velf"].default is None
     header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p2i_hip.h")).read(), flags=re.S)
     lib = _hip.load()
-    for name, base in (("p2i_lkrig_predict_lag", "p2i_lkrig_predict"), ("p2i_lkrig_loso_lag", "p2i_lkrig_loso")):
-        assert re.search(rf"\b{name}\s*\(", header) and hasattr(lib, name)
-        assert len(_hip.SIGNATURES[name]) == len(_hip.SIGNATURES[base]) + 1            # the existing list plus velf
+    for name, nargs in (("p2i_lkrig_predict", 20), ("p2i_lkrig_loso", 17)):           # the lists without a velocity (19, 16) plus velf
+        proto = re.search(rf"\bint {name}\s*\(([^;]*)\);", header)
+        assert proto and re.search(r"\bconst float\s*\*\s*velf\b", proto.group(1)) and hasattr(lib, name)
+        assert len(proto.group(1).split(",")) == nargs == len(_hip.SIGNATURES[name])
+        gone = name + "_lag"                                                          # one entry point per stage, no Lagrangian twin
+        assert not re.search(rf"\b{gone}\b", header) and not hasattr(lib, gone) and gone not in _hip.SIGNATURES

@@ -81,7 +81,7 @@ def main():
 
     def rows(p, g):
         for field, x in enumerate((p, g)):
-            ops._hip.check(lib.p2i_scale_dft_rows(*ops._eval_input(x, tl), T, S, field, ops._ptr(ev._lut), 1, ops._ptr(ev._tw), ops._ptr(G),
+            ops._hip.check(lib.p2i_scale_dft_rows(ops._eval_input(x, tl), T, S, field, ops._ptr(ev._lut), 1, ops._ptr(ev._tw), ops._ptr(G),
                                                   ops._ptr(flag), st()), "rows")
 
     stages = {
