@@ -586,20 +586,33 @@ int p2i_exp2_compose(const uint8_t* panels, int P, int n, int S, int zoom, unsig
  * p2i_krig_solve: K u = 1 and K v = z_f for the R frames of each system (sol [nsys][R + 1][np] fp64 scratch), then mean[f] = 1^T v /
  *   1^T u and alpha [F][cap] = v - mean u (zero past the count).  A frame without gauges gets (0, 0); a frame of a degenerate sample
  *   (cand[b] < 0; cand may be NULL) or of a system with status != 0 gets its gauge mean and alpha = 0.
- * p2i_krig_predict: out [F][H W] = mean[f] + sum_i alpha[f][i] (C(|p - x_i|) + nugget [p = x_i]) for the frames f0 .. f0 + nsets R.
+ * p2i_krig_predict: out [F][H W] = mean[f] + sum_i alpha[f][i] (C(|p - x_i|) + nugget [p = x_i]) for the frames f0 .. f0 + nsys R.
  * p2i_idw_all: out [F][H W] = sum_i w_i z_i / sum_i w_i, w_i = |p - x_i|^-power; z_i on a gauge pixel; 0 for a frame without gauges. */
 int p2i_krig_compact(const float* masked, const float* mask, int B, int T, int H, int W, int cap, int* pix, float* z, int* info,
                      void* stream);
+/* A chunk of nsys systems of one call, stated once for the nine dense stages below (ABI v3).  A stage refuses a NULL field among those
+ * it reads ("null pointer"); one it does not read may be NULL, and so may cand wherever it is read.  Reads, besides f0, R, T, nsys, cap
+ * (all nine) and np (all but p2i_krig_predict, whose nsys is its number of sets):
+ *   p2i_krig_factor, p2i_stkrig_factor: pix, counts, params, model, status     p2i_krig_predict: pix, counts, params, model
+ *   p2i_krig_solve, p2i_krig_loo, p2i_stkrig_loso: z, counts, status, cand     p2i_krig_variance: pix, counts, params, model, status, cand
+ *   p2i_krig_cs_weights: pix, z, counts, status, cand                          p2i_krig_cs_predict: every field
+ * The space-time stages take samples for frames: pix = stpix, z = stz, counts = stcounts, R = T = 1, f0 = the first sample. */
+typedef struct p2i_krig_systems {
+  const int* pix;      /* [rows][cap] (y << 16) | x */
+  const float* z;      /* [rows][cap] */
+  const int* counts;   /* p2i_krig_compact's info / p2i_stkrig_gather's stcounts */
+  const float* params; /* [samples][4] */
+  const int* cand;     /* [samples] or NULL (fixed parameters) */
+  int* status;         /* [nsys] of THIS chunk */
+  int model, f0, R, T, nsys, np, cap;
+} p2i_krig_systems;
 int p2i_krig_bins(const int* pix, const float* z, const int* counts, int F, int cap, int chunks, int n_lags, double lag_width,
                   double* part, void* stream);
 int p2i_krig_fit(const double* part, int B, int nparts, int n_lags, double lag_width, int model, double* bins, double* fit, int* cand,
                  float* params, void* stream);
-int p2i_krig_factor(const int* pix, const int* counts, const float* params, int model, int f0, int R, int T, int nsys, int np, int cap,
-                    float* L, int* status, void* stream);
-int p2i_krig_solve(const float* L, const float* z, const int* counts, const int* status, const int* cand, int f0, int R, int T, int nsys,
-                   int np, int cap, double* sol, float* alpha, float* mean, void* stream);
-int p2i_krig_predict(const int* pix, const float* alpha, const float* mean, const int* counts, const float* params, int model, int f0,
-                     int R, int T, int nsets, int H, int W, int cap, float* out, void* stream);
+int p2i_krig_factor(const p2i_krig_systems* sys, float* L, void* stream);
+int p2i_krig_solve(const p2i_krig_systems* sys, const float* L, double* sol, float* alpha, float* mean, void* stream);
+int p2i_krig_predict(const p2i_krig_systems* sys, const float* alpha, const float* mean, int H, int W, float* out, void* stream);
 int p2i_idw_all(const int* pix, const float* z, const int* counts, int F, int H, int W, int cap, float power, float* out, void* stream);
 
 /* ---- kriging variance and leave-one-out (LOO) cross-validation of the classical baselines (no counterpart in
@@ -618,11 +631,9 @@ int p2i_idw_all(const int* pix, const float* z, const int* counts, int F, int H,
  * p2i_loo_scores: out [5] fp64 = (n, sum e, sum |e|, sum e^2, sum e^2 / var) with e = z - pred over the entries i < counts[f] whose
  *   pred (and var, unless var is NULL: then out[4] = 0) is not NaN; part [F][5] fp64 is scratch.  Fixed order. */
 int p2i_krig_invert(const float* L, int nsys, int np, float* Winv, void* stream);
-int p2i_krig_variance(const float* Winv, const double* sol, const int* pix, const int* counts, const int* status, const int* cand,
-                      const float* params, int model, int f0, int R, int T, int nsys, int np, int H, int W, int cap, float* var,
-                      void* stream);
-int p2i_krig_loo(const float* Winv, const double* sol, const float* alpha, const float* z, const int* counts, const int* status,
-                 const int* cand, int f0, int R, int T, int nsys, int np, int cap, double* colsq, float* pred, float* var, void* stream);
+int p2i_krig_variance(const p2i_krig_systems* sys, const float* Winv, const double* sol, int H, int W, float* var, void* stream);
+int p2i_krig_loo(const p2i_krig_systems* sys, const float* Winv, const double* sol, const float* alpha, double* colsq, float* pred,
+                 float* var, void* stream);
 int p2i_idw_loo(const int* pix, const float* z, const int* counts, int F, int cap, float power, float* pred, void* stream);
 int p2i_loo_scores(const float* z, const float* pred, const float* var, const int* counts, int F, int cap, double* part, double* out,
                    void* stream);
@@ -653,12 +664,9 @@ int p2i_krig_cs_spectrum(const float* params, const int* cand, int model, int B,
 int p2i_krig_cs_noise(uint64_t seed, int64_t stream_id, int q0, int npairs, int Sy, int Sx, float* xi, void* stream);
 int p2i_krig_cs_fields(const float* amp, const int64_t* streams, const float* tx, const float* ty, uint64_t seed, int f0, int nframes,
                        int T, int M, int H, int W, int Sy, int Sx, float* P, float* ens, void* stream);
-int p2i_krig_cs_weights(const float* Winv, const double* sol, const int* pix, const float* z, const int* counts, const int* status,
-                        const int* cand, const float* ens, int f0, int R, int T, int nsys, int np, int M, int H, int W, int cap,
+int p2i_krig_cs_weights(const p2i_krig_systems* sys, const float* Winv, const double* sol, const float* ens, int M, int H, int W,
                         float* alpha, float* mu, void* stream);
-int p2i_krig_cs_predict(const float* alpha, const float* mu, const int* pix, const float* z, const int* counts, const int* status,
-                        const int* cand, const float* params, int model, int f0, int R, int T, int nsys, int np, int M, int H, int W,
-                        int cap, float* ens, void* stream);
+int p2i_krig_cs_predict(const p2i_krig_systems* sys, const float* alpha, const float* mu, int M, int H, int W, float* ens, void* stream);
 
 /* ---- space-time ordinary kriging (no counterpart in the reference): every pixel of every frame of a sample
  * from all gauges of all frames of that sample, one system per sample.  Point i of a sample has pixel (y_i, x_i), frame t_i and value
@@ -686,8 +694,7 @@ int p2i_stkrig_bins(const int* pix, const float* z, const int* counts, const dou
                     int n_tlags, double lag_width, double* part, void* stream);
 int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags, int n_tlags, double lag_width, int model, double* bins,
                    double* fit, int* cand, float* params, void* stream);
-int p2i_stkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, const float* velf, int model, int s0,
-                      int nsys, int np, int cap, float* L, int* status, void* stream);
+int p2i_stkrig_factor(const p2i_krig_systems* sys, const int* stt, const float* velf, float* L, void* stream);
 int p2i_stkrig_predict(const int* stpix, const int* stt, const float* alpha, const float* mean, const int* stcounts,
                        const float* params, const float* velf, int model, int B, int T, int H, int W, int cap, float* out, void* stream);
 
@@ -708,9 +715,8 @@ int p2i_stkrig_predict(const int* stpix, const int* stt, const float* alpha, con
 int p2i_stkrig_gather_sites(const int* pix, const float* z, const int* counts, int B, int T, int fcap, int cap, int* stpix, int* stt,
                             float* stz, int* stcounts, int* site_start, int* nsites, int* psite, int* back, int* fsite, void* stream);
 int p2i_stkrig_site_gram(const float* Winv, int nsys, int np, double* gram, void* stream);
-int p2i_stkrig_loso(const double* gram, const double* sol, const float* alpha, const float* stz, const int* stcounts,
-                    const int* site_start, const int* nsites, const int* back, const int* status, const int* cand, int s0, int T,
-                    int nsys, int np, int fcap, int cap, float* pred, float* var, void* stream);
+int p2i_stkrig_loso(const p2i_krig_systems* sys, const double* gram, const double* sol, const float* alpha, const int* site_start,
+                    const int* nsites, const int* back, int T, int fcap, float* pred, float* var, void* stream);
 
 /* ---- Lagrangian space-time ordinary kriging (no counterpart in the reference): the space-time block above with
  * its distance measured in the frame that moves with the rain, d = sqrt((dy - v_y dt)^2 + (dx - v_x dt)^2 + kappa^2 dt^2), dy, dx, dt

@@ -498,38 +498,34 @@ extern "C" int p2i_krig_fit(const double* part, int B, int nparts, int n_lags, d
   return launch_status();
 }
 
-extern "C" int p2i_krig_factor(const int* pix, const int* counts, const float* params, int model, int f0, int R, int T, int nsys, int np,
-                               int cap, float* L, int* status, void* stream) {
-  P2I_REQUIRE(pix && counts && params && L && status, "null pointer");
-  if (int rc = krig_model_check(model)) return rc;
-  if (int rc = krig_sys_check(f0, R, T, nsys, np, cap)) return rc;
+extern "C" int p2i_krig_factor(const p2i_krig_systems* k, float* L, void* stream) {
+  if (int rc = krig_sys_check(k, KS_PIX | KS_COUNTS | KS_PARAMS | KS_STATUS | KS_MODEL | KS_NP, L)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int nt = np / TS;
-  P2I_LAUNCH(krig_build_kernel, dim3(nt, nt, nsys), dim3(256), 0, s, pix, counts, params, model, f0, R, T, cap, np, L);
-  krig_factor_tiles(L, nsys, np, status, s);
+  const int nt = k->np / TS;
+  P2I_LAUNCH(krig_build_kernel, dim3(nt, nt, k->nsys), dim3(256), 0, s, k->pix, k->counts, k->params, k->model, k->f0, k->R, k->T, k->cap,
+             k->np, L);
+  krig_factor_tiles(L, k->nsys, k->np, k->status, s);
   return launch_status();
 }
 
-extern "C" int p2i_krig_solve(const float* L, const float* z, const int* counts, const int* status, const int* cand, int f0, int R, int T,
-                              int nsys, int np, int cap, double* sol, float* alpha, float* mean, void* stream) {
-  P2I_REQUIRE(L && z && counts && status && sol && alpha && mean, "null pointer");
-  if (int rc = krig_sys_check(f0, R, T, nsys, np, cap)) return rc;
+extern "C" int p2i_krig_solve(const p2i_krig_systems* k, const float* L, double* sol, float* alpha, float* mean, void* stream) {
+  if (int rc = krig_sys_check(k, KS_Z | KS_COUNTS | KS_STATUS | KS_NP, L && sol && alpha && mean)) return rc;
+  const int R = k->R;
   P2I_REQUIRE(R + 1 <= 65535, "too many right-hand sides");
   hipStream_t s = (hipStream_t)stream;
-  P2I_LAUNCH(krig_solve_kernel, dim3(R + 1, nsys), dim3(256), (size_t)np * sizeof(double), s, L, z, counts, f0, R, cap, np, sol);
-  P2I_LAUNCH(krig_dual_kernel, dim3(R, nsys), dim3(256), 0, s, sol, z, counts, status, cand, f0, R, T, cap, np, alpha, mean);
+  P2I_LAUNCH(krig_solve_kernel, dim3(R + 1, k->nsys), dim3(256), (size_t)k->np * sizeof(double), s, L, k->z, k->counts, k->f0, R, k->cap,
+             k->np, sol);
+  P2I_LAUNCH(krig_dual_kernel, dim3(R, k->nsys), dim3(256), 0, s, sol, k->z, k->counts, (const int*)k->status, k->cand, k->f0, R, k->T,
+             k->cap, k->np, alpha, mean);
   return launch_status();
 }
 
-extern "C" int p2i_krig_predict(const int* pix, const float* alpha, const float* mean, const int* counts, const float* params, int model,
-                                int f0, int R, int T, int nsets, int H, int W, int cap, float* out, void* stream) {
-  P2I_REQUIRE(pix && alpha && mean && counts && params && out, "null pointer");
-  if (int rc = krig_frame_check(model, H, W)) return rc;
-  if (int rc = krig_sys_check(f0, R, T, nsets, TS, cap)) return rc;
-  const int HW = H * W;
+extern "C" int p2i_krig_predict(const p2i_krig_systems* k, const float* alpha, const float* mean, int H, int W, float* out, void* stream) {
+  if (int rc = krig_sys_check(k, KS_PIX | KS_COUNTS | KS_PARAMS | KS_MODEL, alpha && mean && out, H, W)) return rc;
+  const int HW = H * W, R = k->R;
   P2I_REQUIRE(ceil_div(R, RC) <= 65535, "too many frames per set");
-  P2I_LAUNCH(krig_predict_kernel, dim3(ceil_div(HW, 256), nsets, ceil_div(R, RC)), dim3(256), 0, (hipStream_t)stream, pix, alpha, mean,
-             counts, params, model, f0, R, T, W, HW, cap, out);
+  P2I_LAUNCH(krig_predict_kernel, dim3(ceil_div(HW, 256), k->nsys, ceil_div(R, RC)), dim3(256), 0, (hipStream_t)stream, k->pix, alpha, mean,
+             k->counts, k->params, k->model, k->f0, R, k->T, W, HW, k->cap, out);
   return launch_status();
 }
 

@@ -195,11 +195,35 @@ static inline int krig_lags_check(int n_lags, double lag_width) {
   P2I_REQUIRE(n_lags > 0 && n_lags <= MAX_LAGS && lag_width > 0.0, "n_lags must be 1..%d with a positive lag width", MAX_LAGS);
   return P2I_OK;
 }
-static inline int krig_sys_check(int f0, int R, int T, int nsys, int np, int cap) {
-  P2I_REQUIRE(R > 0 && T > 0 && f0 >= 0 && nsys > 0 && nsys <= 65535, "bad system range");
-  P2I_REQUIRE(R == 1 || (R == T && f0 % T == 0), "a system spans one frame or one whole sample");
-  P2I_REQUIRE(np > 0 && np % TS == 0 && np <= cap && cap <= MAX_NP, "padded size %d must be a multiple of %d within cap %d", np, TS, cap);
+
+// ---- a chunk of systems (p2i_krig_systems of p2i_hip.h).  `reads`: the fields an entry point reads; a pointer field it does not read
+// may be NULL (cand wherever it is read), model is checked with KS_MODEL only, np stands at one tile without KS_NP.  `own`: its other
+// pointers are there.  krig_sys_check: null pointers, model and frame, range and sizes; p2i_stkrig_loso calls the halves around its own.
+using ks_t = p2i_krig_systems;
+static_assert(sizeof(p2i_krig_systems) == 80 && offsetof(ks_t, pix) == 0 && offsetof(ks_t, z) == 8 && offsetof(ks_t, counts) == 16 &&
+                  offsetof(ks_t, params) == 24 && offsetof(ks_t, cand) == 32 && offsetof(ks_t, status) == 40 && offsetof(ks_t, model) == 48 &&
+                  offsetof(ks_t, f0) == 52 && offsetof(ks_t, R) == 56 && offsetof(ks_t, T) == 60 && offsetof(ks_t, nsys) == 64 &&
+                  offsetof(ks_t, np) == 68 && offsetof(ks_t, cap) == 72,
+              "p2i_krig_systems is mirrored field by field by the ctypes binding");
+enum : unsigned { KS_PIX = 1, KS_Z = 2, KS_COUNTS = 4, KS_PARAMS = 8, KS_STATUS = 16, KS_MODEL = 32, KS_NP = 64 };
+static inline int krig_sys_ptrs(const p2i_krig_systems* k, unsigned reads, bool own) {
+  P2I_REQUIRE(k && own && (!(reads & KS_PIX) || k->pix) && (!(reads & KS_Z) || k->z) && (!(reads & KS_COUNTS) || k->counts) &&
+                  (!(reads & KS_PARAMS) || k->params) && (!(reads & KS_STATUS) || k->status),
+              "null pointer");
   return P2I_OK;
+}
+static inline int krig_sys_range(const p2i_krig_systems* k, unsigned reads) {
+  const int np = (reads & KS_NP) ? k->np : TS;
+  P2I_REQUIRE(k->R > 0 && k->T > 0 && k->f0 >= 0 && k->nsys > 0 && k->nsys <= 65535, "bad system range");
+  P2I_REQUIRE(k->R == 1 || (k->R == k->T && k->f0 % k->T == 0), "a system spans one frame or one whole sample");
+  P2I_REQUIRE(np > 0 && np % TS == 0 && np <= k->cap && k->cap <= MAX_NP, "padded size %d must be a multiple of %d within cap %d", np, TS,
+              k->cap);
+  return P2I_OK;
+}
+static inline int krig_sys_check(const p2i_krig_systems* k, unsigned reads, bool own, int H = 1, int W = 1) {
+  if (int rc = krig_sys_ptrs(k, reads, own)) return rc;
+  if (int rc = (reads & KS_MODEL) ? krig_frame_check(k->model, H, W) : P2I_OK) return rc;
+  return krig_sys_range(k, reads);
 }
 
 // classical.hip: the variogram fit of B samples from part [B][nu][nch][n_lags][3] (the fit kernel's comment has the outputs).

@@ -473,12 +473,11 @@ static inline int cs_members_check(int M, int H, int W) {
   return P2I_OK;
 }
 
-extern "C" int p2i_krig_cs_weights(const float* Winv, const double* sol, const int* pix, const float* z, const int* counts,
-                                   const int* status, const int* cand, const float* ens, int f0, int R, int T, int nsys, int np, int M,
-                                   int H, int W, int cap, float* alpha, float* mu, void* stream) {
-  P2I_REQUIRE(Winv && sol && pix && z && counts && status && ens && alpha && mu, "null pointer");
-  if (int rc = krig_sys_check(f0, R, T, nsys, np, cap)) return rc;
+extern "C" int p2i_krig_cs_weights(const p2i_krig_systems* k, const float* Winv, const double* sol, const float* ens, int M, int H, int W,
+                                   float* alpha, float* mu, void* stream) {
+  if (int rc = krig_sys_check(k, KS_PIX | KS_Z | KS_COUNTS | KS_STATUS | KS_NP, Winv && sol && ens && alpha && mu)) return rc;
   if (int rc = cs_members_check(M, H, W)) return rc;
+  const int np = k->np;
   const int nc = np <= 1024 ? 4 : (np <= 2048 ? 2 : 1);
   const size_t lds = (size_t)2 * nc * np * sizeof(double);      // at most 64 KiB
   static bool raised = false;
@@ -486,20 +485,17 @@ extern "C" int p2i_krig_cs_weights(const float* Winv, const double* sol, const i
     (void)hipFuncSetAttribute((const void*)cs_weights_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     raised = true;
   }
-  P2I_LAUNCH(cs_weights_kernel, dim3(ceil_div(R * M, nc), nsys), dim3(256), lds, (hipStream_t)stream, Winv, sol, pix, z, counts, status,
-             cand, ens, f0, R, T, M, W, H * W, cap, np, nc, alpha, mu);
+  P2I_LAUNCH(cs_weights_kernel, dim3(ceil_div(k->R * M, nc), k->nsys), dim3(256), lds, (hipStream_t)stream, Winv, sol, k->pix, k->z,
+             k->counts, (const int*)k->status, k->cand, ens, k->f0, k->R, k->T, M, W, H * W, k->cap, np, nc, alpha, mu);
   return launch_status();
 }
 
-extern "C" int p2i_krig_cs_predict(const float* alpha, const float* mu, const int* pix, const float* z, const int* counts,
-                                   const int* status, const int* cand, const float* params, int model, int f0, int R, int T, int nsys,
-                                   int np, int M, int H, int W, int cap, float* ens, void* stream) {
-  P2I_REQUIRE(alpha && mu && pix && z && counts && status && params && ens, "null pointer");
-  if (int rc = krig_model_check(model)) return rc;
-  if (int rc = krig_sys_check(f0, R, T, nsys, np, cap)) return rc;
+extern "C" int p2i_krig_cs_predict(const p2i_krig_systems* k, const float* alpha, const float* mu, int M, int H, int W, float* ens,
+                                   void* stream) {
+  if (int rc = krig_sys_check(k, KS_PIX | KS_Z | KS_COUNTS | KS_STATUS | KS_PARAMS | KS_MODEL | KS_NP, alpha && mu && ens)) return rc;
   if (int rc = cs_members_check(M, H, W)) return rc;
   const int HW = H * W;
-  P2I_LAUNCH(cs_predict_kernel, dim3(ceil_div(HW, PT), nsys, ceil_div(R * M, CB * TS)), dim3(256), 0, (hipStream_t)stream, alpha, mu, pix, z,
-             counts, status, cand, params, model, f0, R, T, M, W, HW, cap, np, ens);
+  P2I_LAUNCH(cs_predict_kernel, dim3(ceil_div(HW, PT), k->nsys, ceil_div(k->R * M, CB * TS)), dim3(256), 0, (hipStream_t)stream, alpha, mu,
+             k->pix, k->z, k->counts, (const int*)k->status, k->cand, k->params, k->model, k->f0, k->R, k->T, M, W, HW, k->cap, k->np, ens);
   return launch_status();
 }

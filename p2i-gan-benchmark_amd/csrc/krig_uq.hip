@@ -321,27 +321,21 @@ extern "C" int p2i_krig_invert(const float* L, int nsys, int np, float* Winv, vo
   return launch_status();
 }
 
-extern "C" int p2i_krig_variance(const float* Winv, const double* sol, const int* pix, const int* counts, const int* status,
-                                 const int* cand, const float* params, int model, int f0, int R, int T, int nsys, int np, int H, int W,
-                                 int cap, float* var, void* stream) {
-  P2I_REQUIRE(Winv && sol && pix && counts && status && params && var, "null pointer");
-  if (int rc = krig_frame_check(model, H, W)) return rc;
-  if (int rc = krig_sys_check(f0, R, T, nsys, np, cap)) return rc;
+extern "C" int p2i_krig_variance(const p2i_krig_systems* k, const float* Winv, const double* sol, int H, int W, float* var, void* stream) {
+  if (int rc = krig_sys_check(k, KS_PIX | KS_COUNTS | KS_STATUS | KS_PARAMS | KS_MODEL | KS_NP, Winv && sol && var, H, W)) return rc;
   const int HW = H * W;
-  P2I_LAUNCH(krig_variance_kernel, dim3(ceil_div(HW, PT), nsys), dim3(256), 0, (hipStream_t)stream, Winv, sol, pix, counts, status, cand,
-             params, model, f0, R, T, W, HW, cap, np, var);
+  P2I_LAUNCH(krig_variance_kernel, dim3(ceil_div(HW, PT), k->nsys), dim3(256), 0, (hipStream_t)stream, Winv, sol, k->pix, k->counts,
+             (const int*)k->status, k->cand, k->params, k->model, k->f0, k->R, k->T, W, HW, k->cap, k->np, var);
   return launch_status();
 }
 
-extern "C" int p2i_krig_loo(const float* Winv, const double* sol, const float* alpha, const float* z, const int* counts, const int* status,
-                            const int* cand, int f0, int R, int T, int nsys, int np, int cap, double* colsq, float* pred, float* var,
-                            void* stream) {
-  P2I_REQUIRE(Winv && sol && alpha && z && counts && status && colsq && pred && var, "null pointer");
-  if (int rc = krig_sys_check(f0, R, T, nsys, np, cap)) return rc;
+extern "C" int p2i_krig_loo(const p2i_krig_systems* k, const float* Winv, const double* sol, const float* alpha, double* colsq, float* pred,
+                            float* var, void* stream) {
+  if (int rc = krig_sys_check(k, KS_Z | KS_COUNTS | KS_STATUS | KS_NP, Winv && sol && alpha && colsq && pred && var)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  P2I_LAUNCH(krig_colsq_kernel, dim3(np / TS, nsys), dim3(256), 0, s, Winv, np, colsq);
-  P2I_LAUNCH(krig_loo_kernel, dim3(R, nsys), dim3(256), 0, s, (const double*)colsq, sol, alpha, z, counts, status, cand, f0, R, T, cap, np,
-             pred, var);
+  P2I_LAUNCH(krig_colsq_kernel, dim3(k->np / TS, k->nsys), dim3(256), 0, s, Winv, k->np, colsq);
+  P2I_LAUNCH(krig_loo_kernel, dim3(k->R, k->nsys), dim3(256), 0, s, (const double*)colsq, sol, alpha, k->z, k->counts,
+             (const int*)k->status, k->cand, k->f0, k->R, k->T, k->cap, k->np, pred, var);
   return launch_status();
 }
 

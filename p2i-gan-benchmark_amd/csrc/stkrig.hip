@@ -235,16 +235,14 @@ extern "C" int p2i_stkrig_fit(const double* part, int B, int chunks, int n_lags,
   return launch_status();
 }
 
-extern "C" int p2i_stkrig_factor(const int* stpix, const int* stt, const int* stcounts, const float* params, const float* velf, int model,
-                                 int s0, int nsys, int np, int cap, float* L, int* status, void* stream) {
-  P2I_REQUIRE(stpix && stt && stcounts && params && L && status, "null pointer");
-  if (int rc = krig_model_check(model)) return rc;
-  if (int rc = krig_sys_check(s0, 1, 1, nsys, np, cap)) return rc;
+extern "C" int p2i_stkrig_factor(const p2i_krig_systems* k, const int* stt, const float* velf, float* L, void* stream) {
+  if (int rc = krig_sys_check(k, KS_PIX | KS_COUNTS | KS_PARAMS | KS_STATUS | KS_MODEL | KS_NP, stt && L)) return rc;
+  P2I_REQUIRE(k->R == 1 && k->T == 1, "a space-time system is one sample: R = T = 1");
   hipStream_t s = (hipStream_t)stream;
-  const int nt = np / TS;
-  P2I_LAUNCH(velf ? stkrig_build_kernel<true> : stkrig_build_kernel<false>, dim3(nt, nt, nsys), dim3(256), 0, s, stpix, stt, stcounts,
-             params, velf, model, s0, cap, np, L);
-  krig_factor_tiles(L, nsys, np, status, s);
+  const int nt = k->np / TS;
+  P2I_LAUNCH(velf ? stkrig_build_kernel<true> : stkrig_build_kernel<false>, dim3(nt, nt, k->nsys), dim3(256), 0, s, k->pix, stt, k->counts,
+             k->params, velf, k->model, k->f0, k->cap, k->np, L);
+  krig_factor_tiles(L, k->nsys, k->np, k->status, s);
   return launch_status();
 }
 

@@ -273,14 +273,15 @@ extern "C" int p2i_stkrig_site_gram(const float* Winv, int nsys, int np, double*
   return launch_status();
 }
 
-extern "C" int p2i_stkrig_loso(const double* gram, const double* sol, const float* alpha, const float* stz, const int* stcounts,
-                               const int* site_start, const int* nsites, const int* back, const int* status, const int* cand, int s0,
-                               int T, int nsys, int np, int fcap, int cap, float* pred, float* var, void* stream) {
-  P2I_REQUIRE(gram && sol && alpha && stz && stcounts && site_start && nsites && back && status && pred && var, "null pointer");
+extern "C" int p2i_stkrig_loso(const p2i_krig_systems* k, const double* gram, const double* sol, const float* alpha, const int* site_start,
+                               const int* nsites, const int* back, int T, int fcap, float* pred, float* var, void* stream) {
+  const unsigned reads = KS_Z | KS_COUNTS | KS_STATUS | KS_NP;
+  if (int rc = krig_sys_ptrs(k, reads, gram && sol && alpha && site_start && nsites && back && pred && var)) return rc;
   P2I_REQUIRE(T > 0 && T <= TS, "a site block is at most %d frames wide (got T = %d)", TS, T);
   P2I_REQUIRE(fcap > 0 && fcap <= MAX_NP, "bad frame row length %d", fcap);
-  if (int rc = krig_sys_check(s0, 1, 1, nsys, np, cap)) return rc;
-  P2I_LAUNCH(stkrig_loso_kernel, dim3(np, nsys), dim3(256), 0, (hipStream_t)stream, gram, sol, alpha, stz, stcounts, site_start, nsites,
-             back, status, cand, s0, T, fcap, cap, np, pred, var);
+  if (int rc = krig_sys_range(k, reads)) return rc;
+  P2I_REQUIRE(k->R == 1 && k->T == 1, "a space-time system is one sample: R = T = 1");
+  P2I_LAUNCH(stkrig_loso_kernel, dim3(k->np, k->nsys), dim3(256), 0, (hipStream_t)stream, gram, sol, alpha, k->z, k->counts, site_start,
+             nsites, back, (const int*)k->status, k->cand, k->f0, T, fcap, k->cap, k->np, pred, var);
   return launch_status();
 }

@@ -448,7 +448,7 @@ static int sn_launch(const SnBatch& b, int n, int maxO, int maxK, int training, 
 }  // namespace p2i
 using namespace p2i;
 
-extern "C" int p2i_abi_version(void) { return 2; }
+extern "C" int p2i_abi_version(void) { return 3; }
 extern "C" const char* p2i_last_error(void) { return p2i::g_err; }
 
 extern "C" int p2i_doconv_fold_fwd(const float* W, const float* D, const float* D_diag, int O, int I, int groups, int ksz,

@@ -25,6 +25,11 @@ class EvalInput(C.Structure):
     _fields_ = [("data", C.c_void_p)] + [(n, C.c_int) for n in ("dtype", "h", "w", "top", "left")]
 
 
+class KrigSystems(C.Structure):
+    """p2i_krig_systems: one chunk of nsys dense kriging systems, stated once for the nine stages that take it"""
+    _fields_ = [(n, C.c_void_p) for n in "pix z counts params cand status".split()] + [(n, C.c_int) for n in "model f0 R T nsys np cap".split()]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -32,6 +37,7 @@ _L = C.c_int64
 _F64 = C.c_double
 _D = C.POINTER(ConvDesc)
 _E = C.POINTER(EvalInput)
+_K = C.POINTER(KrigSystems)
 
 # name -> argtypes (every entry point returns int); must list EVERY symbol of include/p2i_hip.h
 SIGNATURES = {
@@ -138,26 +144,26 @@ SIGNATURES = {
     "p2i_krig_compact": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "p2i_krig_bins": [_P, _P, _P, _I, _I, _I, _I, _F64, _P, _P],
     "p2i_krig_fit": [_P, _I, _I, _I, _F64, _I, _P, _P, _P, _P, _P],
-    "p2i_krig_factor": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "p2i_krig_solve": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "p2i_krig_predict": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "p2i_krig_factor": [_K, _P, _P],
+    "p2i_krig_solve": [_K, _P, _P, _P, _P, _P],
+    "p2i_krig_predict": [_K, _P, _P, _I, _I, _P, _P],
     "p2i_idw_all": [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P],
     "p2i_krig_invert": [_P, _I, _I, _P, _P],
-    "p2i_krig_variance": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "p2i_krig_loo": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "p2i_krig_variance": [_K, _P, _P, _I, _I, _P, _P],
+    "p2i_krig_loo": [_K, _P, _P, _P, _P, _P, _P, _P],
     "p2i_krig_cs_spectrum": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "p2i_krig_cs_noise": [C.c_uint64, _L, _I, _I, _I, _I, _P, _P],
     "p2i_krig_cs_fields": [_P, _P, _P, _P, C.c_uint64, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "p2i_krig_cs_weights": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "p2i_krig_cs_predict": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "p2i_krig_cs_weights": [_K, _P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "p2i_krig_cs_predict": [_K, _P, _P, _I, _I, _I, _P, _P],
     "p2i_stkrig_gather": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "p2i_stkrig_bins": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F64, _P, _P],
     "p2i_stkrig_fit": [_P, _I, _I, _I, _I, _F64, _I, _P, _P, _P, _P, _P],
-    "p2i_stkrig_factor": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "p2i_stkrig_factor": [_K, _P, _P, _P, _P],
     "p2i_stkrig_predict": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "p2i_stkrig_gather_sites": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "p2i_stkrig_site_gram": [_P, _I, _I, _P, _P],
-    "p2i_stkrig_loso": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "p2i_stkrig_loso": [_K, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     "p2i_lagkrig_velocity": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F64, _F64, _P, _P],
     "p2i_lagkrig_pick": [_P, _I, _I, _I, _F64, _P, _P, _P, _P, _P, _P, _P],
     "p2i_lkrig_predict": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],

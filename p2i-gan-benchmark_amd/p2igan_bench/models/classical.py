@@ -98,9 +98,12 @@ def _sites_of_frames(res: LOOResult, masks) -> LOOResult:
 class _Systems:
     """The workspace of one call's nsys kriging systems of padded size np_, factored `per` at a time so that the factors (and, with
     inverse, their inverses: two workspaces per system) of one chunk stay under _FACTOR_BYTES; `limit` bounds the chunk further.
-    work / winv: the chunk's factors / inverses; status (nsys,), alpha (rows, cap) and mean (rows,) span the whole call."""
+    work / winv: the chunk's factors / inverses; status (nsys,), alpha (rows, cap) and mean (rows,) span the whole call.
+    pix, z, info, params, cand, model, r, t: the call's systems as ops.KrigSystems takes them (it checks them once, here)."""
 
-    def __init__(self, nsys, np_, rows, cap, dev, inverse=False, limit=None):
+    def __init__(self, pix, z, info, params, cand, model, r, t, np_, inverse=False, limit=None):
+        rows, cap = pix.shape
+        nsys, dev = rows // r, pix.device
         per = max(1, min(nsys, _FACTOR_BYTES // (np_ * np_ * 4 * (2 if inverse else 1))))
         if limit is not None:
             per = max(1, min(per, limit))
@@ -110,12 +113,12 @@ class _Systems:
         self.status = torch.zeros(nsys, device=dev, dtype=torch.int32)
         self.alpha = torch.empty(rows, cap, device=dev, dtype=torch.float32)
         self.mean = torch.empty(rows, device=dev, dtype=torch.float32)
+        self.sys = ops.KrigSystems(pix, z, info, params, cand, model, r, t, np_, self.status)
 
     def chunks(self):
-        """(first system, systems, their slice of status) of every chunk."""
+        """The descriptor (ops.KrigChunk: s0, ns, status) of every chunk."""
         for s0 in range(0, self.nsys, self.per):
-            ns = min(self.per, self.nsys - s0)
-            yield s0, ns, self.status[s0:s0 + ns]
+            yield self.sys.chunk(s0, min(self.per, self.nsys - s0))
 
     def finish(self, model, warning, each=1):
         """Leaves status in model.last_status and logs `warning` with the failed systems times `each` (a host read)."""
@@ -266,25 +269,25 @@ class KrigingGenerator(_ClassicalBase):
             self.last_ensemble = {"clip": clip, "embed": self.embed}
             ens = torch.empty(f, members, h * w, device=dev, dtype=torch.float32)
             ops.krig_cs_fields(amp, streams, seed, t, members, h, w, self.embed, ens)
-        sy = _Systems(nsys, np_, f, pix.shape[1], dev, inverse, limit)
+        sy = _Systems(pix, z, info, params, cand, self.variogram_model, r, t, np_, inverse, limit)
         work, winv, alpha, mean = sy.work, sy.winv, sy.alpha, sy.mean
         var = torch.empty(f, h * w, device=dev, dtype=torch.float32) if variance else None
         loo_pred, loo_var = (torch.empty_like(z), torch.empty_like(z)) if loo else (None, None)
-        for s0, ns, st in sy.chunks():
-            ops.krig_factor(pix, info, params, self.variogram_model, s0 * r, r, t, ns, np_, work, st)
-            sol = ops.krig_solve(work, z, info, st, cand, s0 * r, r, t, ns, np_, alpha, mean)
+        for ch in sy.chunks():
+            ops.krig_factor(ch, work)
+            sol = ops.krig_solve(ch, work, alpha, mean)
             if inverse:
-                ops.krig_invert(work, ns, np_, winv)
+                ops.krig_invert(work, ch.ns, np_, winv)
             if variance:
-                ops.krig_variance(winv, sol, pix, info, st, cand, params, self.variogram_model, s0 * r, r, t, ns, np_, h, w, var)
+                ops.krig_variance(ch, winv, sol, h, w, var)
             if loo:
-                ops.krig_loo(winv, sol, alpha, z, info, st, cand, s0 * r, r, t, ns, np_, loo_pred, loo_var)
+                ops.krig_loo(ch, winv, sol, alpha, loo_pred, loo_var)
             if ensemble is not None:
-                ca, cm = ops.krig_cs_weights(winv, sol, pix, z, info, st, cand, ens, s0 * r, r, t, ns, np_, members, h, w)
-                ops.krig_cs_predict(ca, cm, pix, z, info, st, cand, params, self.variogram_model, s0 * r, r, t, ns, np_, members, h, w, ens)
+                ca, cm = ops.krig_cs_weights(ch, winv, sol, ens, members, h, w)
+                ops.krig_cs_predict(ch, ca, cm, members, h, w, ens)
         out = {}
         if predict:
-            out["pred"] = ops.krig_predict(pix, alpha, mean, info, params, self.variogram_model, r, t, h, w).view(b, t, 1, h, w)
+            out["pred"] = ops.krig_predict(sy.sys.chunk(0, nsys), alpha, mean, h, w).view(b, t, 1, h, w)
         sy.finish(self, "kriging: %d frame(s) met a non-positive pivot and predict their gauge mean", r)
         if variance:
             out["var"] = var.view(b, t, 1, h, w)
@@ -398,13 +401,12 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
     def forward(self, masked_frames, masks):
         b, t, _, h, w = masked_frames.shape
         pix, z, info, np_ = self._points(masked_frames, masks)
-        dev = masked_frames.device
         stpix, stt, stz, stinfo = ops.stkrig_gather(pix, z, info, b, t, np_)
         cand, params = self._variogram(pix, z, info, b, t, h, w)
-        sy = _Systems(b, np_, b, np_, dev)
-        for s0, ns, st in sy.chunks():
-            ops.stkrig_factor(stpix, stt, stinfo, params, self.variogram_model, s0, ns, np_, sy.work, st, self._velf)
-            ops.krig_solve(sy.work, stz, stinfo, st, cand, s0, 1, 1, ns, np_, sy.alpha, sy.mean)      # the samples stand in for frames
+        sy = _Systems(stpix, stz, stinfo, params, cand, self.variogram_model, 1, 1, np_)     # the samples stand in for frames
+        for ch in sy.chunks():
+            ops.stkrig_factor(ch, stt, sy.work, self._velf)
+            ops.krig_solve(ch, sy.work, sy.alpha, sy.mean)
         out = ops.stkrig_predict(stpix, stt, sy.alpha, sy.mean, stinfo, params, self.variogram_model, t, h, w, self._velf)
         sy.finish(self, "space-time kriging: %d sample(s) met a non-positive pivot and predict their gauge mean")
         return out.view(b, t, 1, h, w)
@@ -419,17 +421,16 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         if t > ops.KRIG_TILE:
             raise ValueError(f"{type(self).__name__}: leave-one-site-out takes at most {ops.KRIG_TILE} frames per sample (got {t}): use "
                              f"shorter chunks (scripts/crossvalidate.py --stride)")
-        dev = masked_frames.device
         sites = ops.stkrig_gather_sites(pix, z, info, b, t, np_)
         cand, params = self._variogram(pix, z, info, b, t, h, w)
-        sy = _Systems(b, np_, b, np_, dev, inverse=True)
+        sy = _Systems(sites["stpix"], sites["stz"], sites["stinfo"], params, cand, self.variogram_model, 1, 1, np_, inverse=True)
         pred, var = torch.zeros_like(z), torch.zeros_like(z)
-        for s0, ns, st in sy.chunks():
-            ops.stkrig_factor(sites["stpix"], sites["stt"], sites["stinfo"], params, self.variogram_model, s0, ns, np_, sy.work, st, self._velf)
-            sol = ops.krig_solve(sy.work, sites["stz"], sites["stinfo"], st, cand, s0, 1, 1, ns, np_, sy.alpha, sy.mean)
-            ops.krig_invert(sy.work, ns, np_, sy.winv)
-            gram = ops.stkrig_site_gram(sy.winv, ns, np_)
-            ops.stkrig_loso(gram, sol, sy.alpha, sites, st, cand, s0, t, ns, np_, pred, var)
+        for ch in sy.chunks():
+            ops.stkrig_factor(ch, sites["stt"], sy.work, self._velf)
+            sol = ops.krig_solve(ch, sy.work, sy.alpha, sy.mean)
+            ops.krig_invert(sy.work, ch.ns, np_, sy.winv)
+            gram = ops.stkrig_site_gram(sy.winv, ch.ns, np_)
+            ops.stkrig_loso(ch, gram, sol, sy.alpha, sites, t, pred, var)
         sy.finish(self, "space-time kriging: %d sample(s) met a non-positive pivot and have no leave-one-site-out scores")
         return LOOResult(pix, z, pred, var, info[:b * t], sy.status, sites["fsite"])
 

@@ -1572,56 +1572,75 @@ def krig_variogram(pix, z, info, B, T, n_lags, lag_width, model):
     return bins, fit, cand, params
 
 
-def krig_factor(pix, info, params, model, f0, R, T, nsys, np_, L, status):
-    """Cholesky factors of the nsys covariance systems of frames f0, f0 + R, ... into L (>= nsys * np_ * np_ fp32); status (nsys,) int32
-    (zeroed by the caller) is set where a pivot was not positive."""
-    lib = _hip.load()
-    F, cap = pix.shape
-    _krig_t("krig_factor", pix, torch.int32)
-    _krig_t("krig_factor", info, torch.int32, (2 * F,))
-    _krig_t("krig_factor", params, torch.float32, (F // T, 4))
+class KrigSystems:
+    """The systems of one call, stated once for the nine dense stages (p2i_krig_systems of include/p2i_hip.h): pix, z (rows, cap) and
+    info (2 * rows,) as krig_compact packs them (or stkrig_gather's stpix, stz, stinfo: the samples stand in for frames, R = T = 1),
+    params (rows // T, 4), cand (rows // T,) int32 or None, status (rows // R,) int32 (zeroed by the caller): one entry per system,
+    system s being the gauge set of row s * R padded to np_.  Every tensor is checked here, once; chunk() only cuts a range."""
+
+    def __init__(self, pix, z, info, params, cand, model, R, T, np_, status):
+        who = "KrigSystems"
+        F, cap = _krig_t(who, pix, torch.int32, (pix.shape[0], pix.shape[-1])).shape
+        _krig_cap(who, cap)
+        _krig_sys(who, 0, R, T, F // max(R, 1), F, np_, cap)
+        _krig_t(who, z, torch.float32, (F, cap))
+        _krig_t(who, info, torch.int32, (2 * F,))
+        _krig_t(who, params, torch.float32, (F // T, 4))
+        if cand is not None:
+            _krig_t(who, cand, torch.int32, (F // T,))
+        _krig_t(who, status, torch.int32, (F // R,))
+        self.pix, self.z, self.info, self.params, self.cand, self.status = pix, z, info, params, cand, status
+        self.model, self.R, self.T, self.np_, self.F, self.cap = int(model), R, T, np_, F, cap
+
+    def chunk(self, s0, ns):
+        """The descriptor of systems s0 .. s0 + ns - 1: f0 = s0 * R and their slice of status."""
+        if s0 < 0 or ns < 1 or s0 + ns > self.status.numel():
+            raise RuntimeError(f"KrigSystems.chunk: systems {s0} + {ns} are not among the call's {self.status.numel()}")
+        return KrigChunk(self, s0, ns)
+
+
+class KrigChunk:
+    """Systems s0 .. s0 + ns - 1 of `of` (a KrigSystems): status is their slice, c the _hip.KrigSystems that the stages take."""
+
+    def __init__(self, of, s0, ns):
+        self.of, self.s0, self.ns, self.status = of, s0, ns, of.status[s0:s0 + ns]
+        self.c = _hip.KrigSystems(_ptr(of.pix), _ptr(of.z), _ptr(of.info), _ptr(of.params), _ptr(of.cand), _ptr(self.status), of.model,
+                                  s0 * of.R, of.R, of.T, ns, of.np_, of.cap)
+
+    def call(self, name, *args):
+        _hip.check(getattr(_hip.load(), name)(C.byref(self.c), *args, _stream()), name)
+
+
+def krig_factor(sys, L):
+    """Cholesky factors of the chunk's systems into L (>= nsys * np_ * np_ fp32); its status is set where a pivot was not positive."""
     _krig_t("krig_factor", L, torch.float32)
-    _krig_t("krig_factor", status, torch.int32, (nsys,))
-    _krig_sys("krig_factor", f0, R, T, nsys, F, np_, cap)
-    _krig_ws("krig_factor", L, nsys, np_)
-    _hip.check(lib.p2i_krig_factor(_ptr(pix), _ptr(info), _ptr(params), int(model), f0, R, T, nsys, np_, cap, _ptr(L), _ptr(status),
-                                   _stream()), "p2i_krig_factor")
+    _krig_ws("krig_factor", L, sys.ns, sys.of.np_)
+    sys.call("p2i_krig_factor", _ptr(L))
 
 
-def krig_solve(L, z, info, status, cand, f0, R, T, nsys, np_, alpha, mean):
-    """Dual coefficients alpha (F, cap) and mean (F,) of the frames of the nsys factored systems (written in place).  Returns the fp64
-    solutions sol (nsys, R + 1, np_): row 0 is u = K^-1 1, row 1 + t is K^-1 z of the system's frame t."""
-    lib = _hip.load()
-    F, cap = z.shape
+def krig_solve(sys, L, alpha, mean):
+    """Dual coefficients alpha (F, cap) and mean (F,) of the frames of the chunk's factored systems (written in place).  Returns the
+    fp64 solutions sol (nsys, R + 1, np_): row 0 is u = K^-1 1, row 1 + t is K^-1 z of the system's frame t."""
+    of = sys.of
     _krig_t("krig_solve", L, torch.float32)
-    _krig_t("krig_solve", z, torch.float32)
-    _krig_t("krig_solve", info, torch.int32, (2 * F,))
-    _krig_t("krig_solve", status, torch.int32, (nsys,))
-    if cand is not None:
-        _krig_t("krig_solve", cand, torch.int32, (F // T,))
-    _krig_t("krig_solve", alpha, torch.float32, (F, cap))
-    _krig_t("krig_solve", mean, torch.float32, (F,))
-    _krig_sys("krig_solve", f0, R, T, nsys, F, np_, cap)
-    _krig_ws("krig_solve", L, nsys, np_)
-    sol = torch.empty(nsys, R + 1, np_, device=z.device, dtype=torch.float64)
-    _hip.check(lib.p2i_krig_solve(_ptr(L), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), f0, R, T, nsys, np_, cap, _ptr(sol), _ptr(alpha),
-                                  _ptr(mean), _stream()), "p2i_krig_solve")
+    _krig_t("krig_solve", alpha, torch.float32, (of.F, of.cap))
+    _krig_t("krig_solve", mean, torch.float32, (of.F,))
+    _krig_ws("krig_solve", L, sys.ns, of.np_)
+    sol = torch.empty(sys.ns, of.R + 1, of.np_, device=of.z.device, dtype=torch.float64)
+    sys.call("p2i_krig_solve", _ptr(L), _ptr(sol), _ptr(alpha), _ptr(mean))
     return sol
 
 
-def krig_predict(pix, alpha, mean, info, params, model, R, T, H, W):
-    """out (F, H*W) = mean + sum_i alpha_i c0(p, x_i) for every frame; R = T: the frames of a sample share frame 0's gauges."""
-    lib = _hip.load()
-    F, cap = pix.shape
-    _krig_t("krig_predict", pix, torch.int32)
-    _krig_t("krig_predict", alpha, torch.float32, (F, cap))
-    _krig_t("krig_predict", mean, torch.float32, (F,))
-    _krig_t("krig_predict", info, torch.int32, (2 * F,))
-    _krig_t("krig_predict", params, torch.float32, (F // T, 4))
-    _krig_sys("krig_predict", 0, R, T, F // R, F, KRIG_TILE, cap)
-    out = torch.empty(F, H * W, device=pix.device, dtype=torch.float32)
-    _hip.check(lib.p2i_krig_predict(_ptr(pix), _ptr(alpha), _ptr(mean), _ptr(info), _ptr(params), int(model), 0, R, T, F // R, H, W, cap,
-                                    _ptr(out), _stream()), "p2i_krig_predict")
+def krig_predict(sys, alpha, mean, H, W, out=None):
+    """out (F, H*W) = mean + sum_i alpha_i c0(p, x_i) for the frames of the chunk's sets (a new tensor unless given; the other frames
+    are left as they are); R = T: the frames of a sample share frame 0's gauges."""
+    of = sys.of
+    _krig_t("krig_predict", alpha, torch.float32, (of.F, of.cap))
+    _krig_t("krig_predict", mean, torch.float32, (of.F,))
+    if out is None:
+        out = torch.empty(of.F, H * W, device=of.pix.device, dtype=torch.float32)
+    _krig_t("krig_predict", out, torch.float32, (of.F, H * W))
+    sys.call("p2i_krig_predict", _ptr(alpha), _ptr(mean), H, W, _ptr(out))
     return out
 
 
@@ -1697,24 +1716,17 @@ def stkrig_variogram(pix, z, info, B, T, n_lags, n_tlags, lag_width, model, vel=
     return bins, fit, cand, params
 
 
-def stkrig_factor(stpix, stt, stinfo, params, model, s0, nsys, np_, L, status, velf=None, who="stkrig_factor"):
-    """Cholesky factors of the space-time covariance systems of samples s0 .. s0 + nsys - 1 into L (>= nsys * np_ * np_ fp32); status
-    (nsys,) int32 (zeroed by the caller) is set where a pivot was not positive.  velf (B, 2) fp32 = (v_y, v_x) per sample: the
-    Lagrangian distance.  who: the name that errors report."""
-    lib = _hip.load()
-    B, cap = stpix.shape
-    _krig_t(who, stpix, torch.int32)
-    _krig_t(who, stt, torch.int32, (B, cap))
-    _krig_t(who, stinfo, torch.int32, (2 * B,))
-    _krig_t(who, params, torch.float32, (B, 4))
+def stkrig_factor(sys, stt, L, velf=None, who="stkrig_factor"):
+    """Cholesky factors of the space-time covariance systems of the chunk's samples (sys: stpix, stz, stinfo with R = T = 1) into L
+    (>= nsys * np_ * np_ fp32); the chunk's status is set where a pivot was not positive.  stt (B, cap): the points' frames; velf
+    (B, 2) fp32 = (v_y, v_x) per sample: the Lagrangian distance.  who: the name that errors report."""
+    of = sys.of
+    _krig_t(who, stt, torch.int32, (of.F, of.cap))
     _krig_t(who, L, torch.float32)
-    _krig_t(who, status, torch.int32, (nsys,))
-    _krig_sys(who, s0, 1, 1, nsys, B, np_, cap)
-    _krig_ws(who, L, nsys, np_)
+    _krig_ws(who, L, sys.ns, of.np_)
     if velf is not None:
-        _lag_vel(who, velf, torch.float32, B)
-    _hip.check(lib.p2i_stkrig_factor(_ptr(stpix), _ptr(stt), _ptr(stinfo), _ptr(params), _ptr(velf), int(model), s0, nsys, np_, cap,
-                                     _ptr(L), _ptr(status), _stream()), "p2i_stkrig_factor")
+        _lag_vel(who, velf, torch.float32, of.F)
+    sys.call("p2i_stkrig_factor", _ptr(stt), _ptr(velf), _ptr(L))
 
 
 def stkrig_predict(stpix, stt, alpha, mean, stinfo, params, model, T, H, W, velf=None, who="stkrig_predict"):
@@ -1777,34 +1789,26 @@ def stkrig_site_gram(Winv, nsys, np_):
     return gram
 
 
-def stkrig_loso(gram, sol, alpha, sites, status, cand, s0, T, nsys, np_, pred, var):
-    """Leave-one-site-out prediction and variance of every point of samples s0 .. s0 + nsys - 1 into pred, var (B*T, fcap), in place,
-    at the points only (the caller zeroes both).  sites: stkrig_gather_sites' dict; gram, sol, alpha, status as stkrig_site_gram,
-    krig_solve and stkrig_factor leave them for the same (s0, nsys, np_)."""
-    lib = _hip.load()
-    B, cap = sites["stz"].shape
+def stkrig_loso(sys, gram, sol, alpha, sites, T, pred, var):
+    """Leave-one-site-out prediction and variance of every point of the chunk's samples into pred, var (B*T, fcap), in place, at the
+    points only (the caller zeroes both).  sys: the systems of stkrig_gather_sites' dict `sites` (stpix, stz, stinfo, R = T = 1); gram,
+    sol, alpha as stkrig_site_gram and krig_solve leave them for the same chunk; T: frames per sample."""
+    of, ns = sys.of, sys.ns
+    B, cap = of.F, of.cap
     F, fcap = pred.shape
     if not 1 <= T <= KRIG_TILE or F != B * T:
         raise ValueError(f"stkrig_loso: a site block is at most {KRIG_TILE} frames wide (got T = {T}, {F} frames of {B} samples)")
-    _krig_t("stkrig_loso", gram, torch.float64, (nsys, np_ // KRIG_TILE, 2, KRIG_TILE, KRIG_TILE))
-    _krig_t("stkrig_loso", sol, torch.float64, (nsys, 2, np_))
+    _krig_t("stkrig_loso", gram, torch.float64, (ns, of.np_ // KRIG_TILE, 2, KRIG_TILE, KRIG_TILE))
+    _krig_t("stkrig_loso", sol, torch.float64, (ns, 2, of.np_))
     _krig_t("stkrig_loso", alpha, torch.float32, (B, cap))
-    _krig_t("stkrig_loso", sites["stz"], torch.float32)
-    _krig_t("stkrig_loso", sites["stinfo"], torch.int32, (2 * B,))
-    _krig_t("stkrig_loso", sites["site_start"], torch.int32, (B, cap + 1))
-    _krig_t("stkrig_loso", sites["nsites"], torch.int32, (B,))
-    _krig_t("stkrig_loso", sites["back"], torch.int32, (B, cap))
-    _krig_t("stkrig_loso", status, torch.int32, (nsys,))
-    if cand is not None:
-        _krig_t("stkrig_loso", cand, torch.int32, (B,))
+    for key, shape in (("site_start", (B, cap + 1)), ("nsites", (B,)), ("back", (B, cap))):
+        _krig_t("stkrig_loso", sites[key], torch.int32, shape)
     _krig_t("stkrig_loso", pred, torch.float32)
     _krig_t("stkrig_loso", var, torch.float32, (F, fcap))
-    _krig_sys("stkrig_loso", s0, 1, 1, nsys, B, np_, cap)
     if fcap > KRIG_MAX_CAP:
         raise RuntimeError(f"stkrig_loso: frame rows of {fcap} exceed {KRIG_MAX_CAP}")
-    _hip.check(lib.p2i_stkrig_loso(_ptr(gram), _ptr(sol), _ptr(alpha), _ptr(sites["stz"]), _ptr(sites["stinfo"]), _ptr(sites["site_start"]),
-                                   _ptr(sites["nsites"]), _ptr(sites["back"]), _ptr(status), _ptr(cand), s0, T, nsys, np_, fcap, cap,
-                                   _ptr(pred), _ptr(var), _stream()), "p2i_stkrig_loso")
+    sys.call("p2i_stkrig_loso", _ptr(gram), _ptr(sol), _ptr(alpha), _ptr(sites["site_start"]), _ptr(sites["nsites"]), _ptr(sites["back"]),
+             T, fcap, _ptr(pred), _ptr(var))
 
 
 # ---- Lagrangian space-time kriging (the velocity: csrc/lagkrig.hip; the rest: csrc/stkrig.hip with a velocity; DESIGN.md section 19)
@@ -1858,10 +1862,9 @@ def lagkrig_variogram(pix, z, info, vel, B, T, n_lags, n_tlags, lag_width, model
                             "lagkrig_variogram")
 
 
-def lagkrig_factor(stpix, stt, stinfo, params, velf, model, s0, nsys, np_, L, status):
+def lagkrig_factor(sys, stt, velf, L):
     """stkrig_factor with a velocity that must be there: velf (B, 2) fp32 = (v_y, v_x) per sample."""
-    return stkrig_factor(stpix, stt, stinfo, params, model, s0, nsys, np_, L, status,
-                         _lag_vel("lagkrig_factor", velf, torch.float32, stpix.shape[0]), "lagkrig_factor")
+    return stkrig_factor(sys, stt, L, _lag_vel("lagkrig_factor", velf, torch.float32, sys.of.F), "lagkrig_factor")
 
 
 def lagkrig_predict(stpix, stt, alpha, mean, stinfo, params, velf, model, T, H, W):
@@ -1948,45 +1951,27 @@ def krig_invert(L, nsys, np_, Winv):
     _hip.check(lib.p2i_krig_invert(_ptr(L), nsys, np_, _ptr(Winv), _stream()), "p2i_krig_invert")
 
 
-def krig_variance(Winv, sol, pix, info, status, cand, params, model, f0, R, T, nsys, np_, H, W, var):
-    """Kriging variance of the R frames of each of the nsys systems into var (F, H*W), in place: c00 - |Winv k(p)|^2 +
+def krig_variance(sys, Winv, sol, H, W, var):
+    """Kriging variance of the R frames of each of the chunk's systems into var (F, H*W), in place: c00 - |Winv k(p)|^2 +
     (1 - u^T k(p))^2 / s clamped at 0, exactly 0 on a gauge pixel, NaN for a system without a model."""
-    lib = _hip.load()
-    F, cap = pix.shape
+    of = sys.of
     _krig_t("krig_variance", Winv, torch.float32)
-    _krig_t("krig_variance", sol, torch.float64, (nsys, R + 1, np_))
-    _krig_t("krig_variance", pix, torch.int32)
-    _krig_t("krig_variance", info, torch.int32, (2 * F,))
-    _krig_t("krig_variance", status, torch.int32, (nsys,))
-    if cand is not None:
-        _krig_t("krig_variance", cand, torch.int32, (F // T,))
-    _krig_t("krig_variance", params, torch.float32, (F // T, 4))
-    _krig_t("krig_variance", var, torch.float32, (F, H * W))
-    _krig_sys("krig_variance", f0, R, T, nsys, F, np_, cap)
-    _krig_ws("krig_variance", Winv, nsys, np_, "inverse")
-    _hip.check(lib.p2i_krig_variance(_ptr(Winv), _ptr(sol), _ptr(pix), _ptr(info), _ptr(status), _ptr(cand), _ptr(params), int(model), f0,
-                                     R, T, nsys, np_, H, W, cap, _ptr(var), _stream()), "p2i_krig_variance")
+    _krig_t("krig_variance", sol, torch.float64, (sys.ns, of.R + 1, of.np_))
+    _krig_t("krig_variance", var, torch.float32, (of.F, H * W))
+    _krig_ws("krig_variance", Winv, sys.ns, of.np_, "inverse")
+    sys.call("p2i_krig_variance", _ptr(Winv), _ptr(sol), H, W, _ptr(var))
 
 
-def krig_loo(Winv, sol, alpha, z, info, status, cand, f0, R, T, nsys, np_, pred, var):
-    """Leave-one-out prediction and variance of every gauge of the nsys systems' frames into pred, var (F, cap), in place."""
-    lib = _hip.load()
-    F, cap = z.shape
+def krig_loo(sys, Winv, sol, alpha, pred, var):
+    """Leave-one-out prediction and variance of every gauge of the chunk's systems' frames into pred, var (F, cap), in place."""
+    of = sys.of
     _krig_t("krig_loo", Winv, torch.float32)
-    _krig_t("krig_loo", sol, torch.float64, (nsys, R + 1, np_))
-    _krig_t("krig_loo", alpha, torch.float32, (F, cap))
-    _krig_t("krig_loo", z, torch.float32)
-    _krig_t("krig_loo", info, torch.int32, (2 * F,))
-    _krig_t("krig_loo", status, torch.int32, (nsys,))
-    if cand is not None:
-        _krig_t("krig_loo", cand, torch.int32, (F // T,))
-    _krig_t("krig_loo", pred, torch.float32, (F, cap))
-    _krig_t("krig_loo", var, torch.float32, (F, cap))
-    _krig_sys("krig_loo", f0, R, T, nsys, F, np_, cap)
-    _krig_ws("krig_loo", Winv, nsys, np_, "inverse")
-    colsq = torch.empty(nsys, np_, device=z.device, dtype=torch.float64)
-    _hip.check(lib.p2i_krig_loo(_ptr(Winv), _ptr(sol), _ptr(alpha), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), f0, R, T, nsys, np_, cap,
-                                _ptr(colsq), _ptr(pred), _ptr(var), _stream()), "p2i_krig_loo")
+    _krig_t("krig_loo", sol, torch.float64, (sys.ns, of.R + 1, of.np_))
+    for t in (alpha, pred, var):
+        _krig_t("krig_loo", t, torch.float32, (of.F, of.cap))
+    _krig_ws("krig_loo", Winv, sys.ns, of.np_, "inverse")
+    colsq = torch.empty(sys.ns, of.np_, device=of.z.device, dtype=torch.float64)
+    sys.call("p2i_krig_loo", _ptr(Winv), _ptr(sol), _ptr(alpha), _ptr(colsq), _ptr(pred), _ptr(var))
 
 
 # ---- conditional simulation of ordinary kriging (csrc/krig_cs.hip, DESIGN.md section 24)
@@ -2082,45 +2067,30 @@ def krig_cs_fields(amp, streams, seed, T, M, H, W, embed, ens):
                                           min(per, F - f0), T, M, H, W, Sy, Sx, _ptr(P), _ptr(ens), _stream()), "p2i_krig_cs_fields")
 
 
-def _krig_cs_sys(who, Winv_or_alpha, pix, z, info, status, cand, ens, f0, R, T, nsys, np_, M, H, W):
-    F, cap = pix.shape
-    _krig_cs_members(who, M)
-    _krig_t(who, pix, torch.int32)
-    _krig_t(who, z, torch.float32, (F, cap))
-    _krig_t(who, info, torch.int32, (2 * F,))
-    _krig_t(who, status, torch.int32, (nsys,))
-    if cand is not None:
-        _krig_t(who, cand, torch.int32, (F // T,))
-    _krig_t(who, ens, torch.float32, (F, M, H * W))
-    _krig_t(who, Winv_or_alpha, torch.float32)
-    _krig_sys(who, f0, R, T, nsys, F, np_, cap)
-    return cap
-
-
-def krig_cs_weights(Winv, sol, pix, z, info, status, cand, ens, f0, R, T, nsys, np_, M, H, W):
-    """(alpha (nsys, R*M, cap), mu (nsys, R*M)): the kriging of the residuals z - U(gauges) of every member of the systems' frames,
-    ens holding U; column t*M + m of a system is member m of its frame t."""
-    lib = _hip.load()
-    cap = _krig_cs_sys("krig_cs_weights", Winv, pix, z, info, status, cand, ens, f0, R, T, nsys, np_, M, H, W)
-    _krig_t("krig_cs_weights", sol, torch.float64, (nsys, R + 1, np_))
-    _krig_ws("krig_cs_weights", Winv, nsys, np_, "inverse")
-    alpha = torch.empty(nsys, R * M, cap, device=z.device, dtype=torch.float32)
-    mu = torch.empty(nsys, R * M, device=z.device, dtype=torch.float32)
-    _hip.check(lib.p2i_krig_cs_weights(_ptr(Winv), _ptr(sol), _ptr(pix), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), _ptr(ens), f0, R, T,
-                                       nsys, np_, M, H, W, cap, _ptr(alpha), _ptr(mu), _stream()), "p2i_krig_cs_weights")
+def krig_cs_weights(sys, Winv, sol, ens, M, H, W):
+    """(alpha (nsys, R*M, cap), mu (nsys, R*M)): the kriging of the residuals z - U(gauges) of every member of the chunk's systems'
+    frames, ens (F, M, H*W) holding U; column t*M + m of a system is member m of its frame t."""
+    of, ns = sys.of, sys.ns
+    _krig_cs_members("krig_cs_weights", M)
+    _krig_t("krig_cs_weights", ens, torch.float32, (of.F, M, H * W))
+    _krig_t("krig_cs_weights", Winv, torch.float32)
+    _krig_t("krig_cs_weights", sol, torch.float64, (ns, of.R + 1, of.np_))
+    _krig_ws("krig_cs_weights", Winv, ns, of.np_, "inverse")
+    alpha = torch.empty(ns, of.R * M, of.cap, device=of.z.device, dtype=torch.float32)
+    mu = torch.empty(ns, of.R * M, device=of.z.device, dtype=torch.float32)
+    sys.call("p2i_krig_cs_weights", _ptr(Winv), _ptr(sol), _ptr(ens), M, H, W, _ptr(alpha), _ptr(mu))
     return alpha, mu
 
 
-def krig_cs_predict(alpha, mu, pix, z, info, status, cand, params, model, f0, R, T, nsys, np_, M, H, W, ens):
-    """ens[f][m] = U + mu + sum_i alpha_i c0(p, x_i) for the members of the systems' frames, in place; z on a gauge pixel; NaN for a
-    system without a model."""
-    lib = _hip.load()
-    cap = _krig_cs_sys("krig_cs_predict", alpha, pix, z, info, status, cand, ens, f0, R, T, nsys, np_, M, H, W)
-    _krig_t("krig_cs_predict", alpha, torch.float32, (nsys, R * M, cap))
-    _krig_t("krig_cs_predict", mu, torch.float32, (nsys, R * M))
-    _krig_t("krig_cs_predict", params, torch.float32, (pix.shape[0] // T, 4))
-    _hip.check(lib.p2i_krig_cs_predict(_ptr(alpha), _ptr(mu), _ptr(pix), _ptr(z), _ptr(info), _ptr(status), _ptr(cand), _ptr(params),
-                                       int(model), f0, R, T, nsys, np_, M, H, W, cap, _ptr(ens), _stream()), "p2i_krig_cs_predict")
+def krig_cs_predict(sys, alpha, mu, M, H, W, ens):
+    """ens[f][m] = U + mu + sum_i alpha_i c0(p, x_i) for the members of the chunk's systems' frames, in place; z on a gauge pixel; NaN
+    for a system without a model."""
+    of, ns = sys.of, sys.ns
+    _krig_cs_members("krig_cs_predict", M)
+    _krig_t("krig_cs_predict", ens, torch.float32, (of.F, M, H * W))
+    _krig_t("krig_cs_predict", alpha, torch.float32, (ns, of.R * M, of.cap))
+    _krig_t("krig_cs_predict", mu, torch.float32, (ns, of.R * M))
+    sys.call("p2i_krig_cs_predict", _ptr(alpha), _ptr(mu), M, H, W, _ptr(ens))
 
 
 def idw_loo(pix, z, info, power=2.0):

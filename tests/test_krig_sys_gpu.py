@@ -8,6 +8,7 @@ section 24b).
   C  a system whose factorisation meets a non-positive pivot falls back (gauge mean, alpha = 0, NaN variance / LOO / members / LOSO)
      without leaking anything non-finite into its neighbours
   D  krig_predict_kernel's second and third group of 8 frames of a shared set
+  E  the fields of the systems descriptor that a stage does not read may be NULL: the same bits
 
 Error bound of every comparison with a restatement, the rule of the classical baselines: device error <= max(32 e32, 1e-6) max|ref|,
 with e32 the fp32 restatement's own error against fp64 relative to max|ref|, computed in the same test."""
@@ -128,16 +129,18 @@ def _krig_stages(dev, x, m, model, params, shared, s0, ns, np_, cap, members, st
     o["ens"][f0:f0 + nf] = fields[f0:f0 + nf]
     work = torch.empty(ns * np_ * np_, device=dev, dtype=torch.float32)
     winv = torch.empty_like(work)
-    status = torch.zeros(ns, device=dev, dtype=torch.int32)
-    ops.krig_factor(pix, info, params, code, f0, R, T, ns, np_, work, status)
-    sol = ops.krig_solve(work, z, info, status, cand, f0, R, T, ns, np_, o["alpha"], o["mean"])
+    call = ops.KrigSystems(pix, z, info, params, cand, code, R, T, np_, torch.zeros(F // R, device=dev, dtype=torch.int32))
+    sys = call.chunk(s0, ns)
+    ops.krig_factor(sys, work)
+    sol = ops.krig_solve(sys, work, o["alpha"], o["mean"])
     ops.krig_invert(work, ns, np_, winv)
-    ops.krig_variance(winv, sol, pix, info, status, cand, params, code, f0, R, T, ns, np_, H, W, o["var"])
-    ops.krig_loo(winv, sol, o["alpha"], z, info, status, cand, f0, R, T, ns, np_, o["loo_pred"], o["loo_var"])
-    ca, cm = ops.krig_cs_weights(winv, sol, pix, z, info, status, cand, o["ens"], f0, R, T, ns, np_, members, H, W)
-    ops.krig_cs_predict(ca, cm, pix, z, info, status, cand, params, code, f0, R, T, ns, np_, members, H, W, o["ens"])
-    o["pred"] = ops.krig_predict(pix, o["alpha"], o["mean"], info, params, code, R, T, H, W)       # every frame; outside: of the sentinel
-    o.update(status=status, sol=sol, counts=info[:F].cpu().numpy(), f0=f0, nf=nf, R=R)
+    ops.krig_variance(sys, winv, sol, H, W, o["var"])
+    ops.krig_loo(sys, winv, sol, o["alpha"], o["loo_pred"], o["loo_var"])
+    ca, cm = ops.krig_cs_weights(sys, winv, sol, o["ens"], members, H, W)
+    ops.krig_cs_predict(sys, ca, cm, members, H, W, o["ens"])
+    o["pred"] = ops.krig_predict(call.chunk(0, F // R), o["alpha"], o["mean"], H, W)       # every frame; outside: of the sentinel
+    assert not call.status[:s0].any() and not call.status[s0 + ns:].any()
+    o.update(status=sys.status, sol=sol, counts=info[:F].cpu().numpy(), f0=f0, nf=nf, R=R)
     return o
 
 
@@ -188,11 +191,12 @@ def test_space_time_stages_of_a_sub_range(dev):
     pred, var = _sentinel((B * T, fcap), dev), _sentinel((B * T, fcap), dev)
     work = torch.empty(ns * np_ * np_, device=dev, dtype=torch.float32)
     winv = torch.empty_like(work)
-    status = torch.zeros(ns, device=dev, dtype=torch.int32)
-    ops.stkrig_factor(sites["stpix"], sites["stt"], sites["stinfo"], pt, ops.KRIG_MODELS[model], s0, ns, np_, work, status)
-    sol = ops.krig_solve(work, sites["stz"], sites["stinfo"], status, None, s0, 1, 1, ns, np_, alpha, mean)
+    status = torch.zeros(B, device=dev, dtype=torch.int32)
+    sys = ops.KrigSystems(sites["stpix"], sites["stz"], sites["stinfo"], pt, None, ops.KRIG_MODELS[model], 1, 1, np_, status).chunk(s0, ns)
+    ops.stkrig_factor(sys, sites["stt"], work)
+    sol = ops.krig_solve(sys, work, alpha, mean)
     ops.krig_invert(work, ns, np_, winv)
-    ops.stkrig_loso(ops.stkrig_site_gram(winv, ns, np_), sol, alpha, sites, status, None, s0, T, ns, np_, pred, var)
+    ops.stkrig_loso(sys, ops.stkrig_site_gram(winv, ns, np_), sol, alpha, sites, T, pred, var)
     assert not status.any()
     for t in (alpha, mean):
         assert _is_sentinel(t[:s0]) and _is_sentinel(t[s0 + ns:]) and bool(torch.isfinite(t[s0:s0 + ns]).all())
@@ -208,6 +212,81 @@ def test_space_time_stages_of_a_sub_range(dev):
     _within("st LOSO variance", got_v[inside], v64[inside], v32[inside])
     n = int(kc.st_sample_counts(kc.inputs(name)[1])[s0])
     assert not sol.cpu().numpy()[0, :, n:].any() and not alpha[s0, n:].any()
+
+
+# ---- the descriptor's fields that a stage does not read (include/p2i_hip.h, p2i_krig_systems) may be NULL on the device too
+UNREAD = {"krig_factor": ("z", "cand"), "krig_solve": ("pix", "params"), "krig_predict": ("z", "status", "cand"), "krig_variance": ("z",),
+          "krig_loo": ("pix", "params"), "krig_cs_weights": ("params",), "krig_cs_predict": (), "stkrig_factor": ("z", "cand"),
+          "stkrig_loso": ("pix", "params")}
+
+
+def _nine_stages(dev, x, m, null):
+    """Every stage for systems 1 and 2 of the four per-frame systems (space-time: of four one-frame samples); null: each stage's
+    descriptor with its unread pointer fields NULL (and np = 0 for krig_predict, which does not read it)."""
+    from p2igan_bench import ops
+    B, T, _, H, W = x.shape
+    F, HW, M, np_, cap, s0, ns = B * T, H * W, 2, 64, 64, 1, 2
+    params = torch.tensor([[0.002, 0.05, 6.0, 1.0]] * F, dtype=torch.float32, device=dev)
+    cand = torch.zeros(F, dtype=torch.int32, device=dev)
+    zeros = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)      # noqa: E731
+    o = {}
+
+    def stage(call, name):
+        ch = call.chunk(s0, ns)
+        if null:
+            for field in UNREAD[name]:
+                setattr(ch.c, field, None)
+            if name == "krig_predict":
+                ch.c.np = 0
+        return ch
+
+    def run(call, tag, factor):
+        work, winv = torch.empty(ns * np_ * np_, device=dev), torch.empty(ns * np_ * np_, device=dev)
+        alpha, mean = zeros(call.F, cap), zeros(call.F)
+        factor(stage(call, tag + "krig_factor"), work)
+        sol = ops.krig_solve(stage(call, "krig_solve"), work, alpha, mean)
+        ops.krig_invert(work, ns, np_, winv)
+        o.update({tag + "L": work.view(ns, np_, np_).tril(), tag + "sol": sol, tag + "alpha": alpha, tag + "mean": mean})
+        return winv, sol, alpha, mean
+
+    pix, z, info = ops.krig_compact(x.reshape(F, 1, H, W).contiguous(), m.reshape(F, 1, H, W).contiguous(), cap)
+    # the dense stages: one system per frame of the (B, T) call
+    call = ops.KrigSystems(pix, z, info, params[:B], cand[:B], 0, 1, T, np_, torch.zeros(F, dtype=torch.int32, device=dev))
+    winv, sol, alpha, mean = run(call, "", ops.krig_factor)
+    o["pred"] = ops.krig_predict(stage(call, "krig_predict"), alpha, mean, H, W, zeros(F, HW))
+    o["var"], o["loo_pred"], o["loo_var"], o["ens"] = zeros(F, HW), zeros(F, cap), zeros(F, cap), zeros(F, M, HW)
+    ops.krig_variance(stage(call, "krig_variance"), winv, sol, H, W, o["var"])
+    ops.krig_loo(stage(call, "krig_loo"), winv, sol, alpha, o["loo_pred"], o["loo_var"])
+    amp, _ = ops.krig_cs_spectrum(params[:B], None, 0, H, W, kc.EMBED)
+    ops.krig_cs_fields(amp, torch.from_numpy(kc.streams_of(B, T)).reshape(F).to(dev), kc.SEED, T, M, H, W, kc.EMBED, o["ens"])
+    o["cs_alpha"], o["cs_mu"] = ops.krig_cs_weights(stage(call, "krig_cs_weights"), winv, sol, o["ens"], M, H, W)
+    ops.krig_cs_predict(stage(call, "krig_cs_predict"), o["cs_alpha"], o["cs_mu"], M, H, W, o["ens"])
+    # the space-time stages: every frame as a sample of its own
+    sites = ops.stkrig_gather_sites(pix, z, info, F, 1, np_)
+    st = ops.KrigSystems(sites["stpix"], sites["stz"], sites["stinfo"], params, cand, 0, 1, 1, np_, torch.zeros(F, dtype=torch.int32, device=dev))
+    winv, sol, alpha, _ = run(st, "st", lambda ch, L: ops.stkrig_factor(ch, sites["stt"], L))
+    o["loso_pred"], o["loso_var"] = zeros(F, cap), zeros(F, cap)
+    ops.stkrig_loso(stage(st, "stkrig_loso"), ops.stkrig_site_gram(winv, ns, np_), sol, alpha, sites, 1, o["loso_pred"], o["loso_var"])
+    o["status"], o["ststatus"] = call.status, st.status
+    return o
+
+
+def test_unread_descriptor_fields_may_be_null(dev):
+    """B = 2, T = 2, 8 x 8, 33 gauges per frame (np = 64: two tiles), fixed exponential parameters, 2 members: each of the nine stages
+    with a full descriptor and with the fields it does not read set to NULL gives the same bits."""
+    rng = np.random.RandomState(24)
+    masks = np.zeros((2, 2, 1, 8, 8), np.float32)
+    for f in range(4):
+        masks.reshape(4, 64)[f, rng.permutation(64)[:33]] = 1.0
+    masked = (rng.rand(2, 2, 1, 8, 8).astype(np.float32) + 0.1) * masks
+    x, m = torch.from_numpy(masked).to(dev), torch.from_numpy(masks).to(dev)
+    full, null = _nine_stages(dev, x, m, False), _nine_stages(dev, x, m, True)
+    assert not full["status"].any() and not full["ststatus"].any()
+    assert bool(full["pred"][1:3].any()) and bool(torch.isfinite(full["ens"][1:3]).all()) and bool(torch.isfinite(full["loso_pred"][1:3]).all())
+    assert not full["pred"][0].any() and not full["pred"][3].any() and not full["stalpha"][0].any()      # systems 1 and 2 only
+    assert sorted(full) == sorted(null)
+    for k in full:
+        assert _same(full[k], null[k]), (k, "differs once the fields the stage does not read are NULL")
 
 
 # ---- C: the failed factorisation

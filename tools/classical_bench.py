@@ -89,9 +89,10 @@ def main():
             nsys = f // r
             work = torch.empty(nsys * np_ * np_, device=dev)
             status = torch.zeros(nsys, device=dev, dtype=torch.int32)
-            out[f"factor_{label}_ms"] = timed(lambda: ops.krig_factor(pix, info, params, 0, 0, r, t, nsys, np_, work, status))
-            out[f"solve_{label}_ms"] = timed(lambda: ops.krig_solve(work, z, info, status, cand, 0, r, t, nsys, np_, alpha, mean))
-            out[f"predict_{label}_ms"] = timed(lambda: ops.krig_predict(pix, alpha, mean, info, params, 0, r, t, h, w))
+            ch = ops.KrigSystems(pix, z, info, params, cand, 0, r, t, np_, status).chunk(0, nsys)
+            out[f"factor_{label}_ms"] = timed(lambda: ops.krig_factor(ch, work))
+            out[f"solve_{label}_ms"] = timed(lambda: ops.krig_solve(ch, work, alpha, mean))
+            out[f"predict_{label}_ms"] = timed(lambda: ops.krig_predict(ch, alpha, mean, h, w))
             assert int(status.sum()) == 0
             del work
         out["idw_all_ms"] = timed(lambda: ops.idw_all(pix, z, info, h, w, 2.0))

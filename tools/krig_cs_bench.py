@@ -88,16 +88,17 @@ def main():
             winv = torch.empty_like(work)
             status = torch.zeros(nsys, device=dev, dtype=torch.int32)
             alpha, mean = torch.empty(f, 1024, device=dev), torch.empty(f, device=dev)
-            ops.krig_factor(pix, info, params, 0, 0, r, t, nsys, np_, work, status)
-            sol = ops.krig_solve(work, z, info, status, None, 0, r, t, nsys, np_, alpha, mean)
+            ch = ops.KrigSystems(pix, z, info, params, None, 0, r, t, np_, status).chunk(0, nsys)
+            ops.krig_factor(ch, work)
+            sol = ops.krig_solve(ch, work, alpha, mean)
             ops.krig_invert(work, nsys, np_, winv)
             assert int(status.sum()) == 0
             ops.krig_cs_fields(amp, streams, 1, t, M, h, w, EMBED, ens)
-            ca, cm = ops.krig_cs_weights(winv, sol, pix, z, info, status, None, ens, 0, r, t, nsys, np_, M, h, w)
+            ca, cm = ops.krig_cs_weights(ch, winv, sol, ens, M, h, w)
             o = {"systems": nsys}
-            o["weights_us"] = round(1e3 * timed(lambda: ops.krig_cs_weights(winv, sol, pix, z, info, status, None, ens, 0, r, t, nsys, np_, M, h, w)), 1)
+            o["weights_us"] = round(1e3 * timed(lambda: ops.krig_cs_weights(ch, winv, sol, ens, M, h, w)), 1)
             # in place: every timed call adds the conditioning once more to the same buffer, which costs what the first call costs
-            o["predict_us"] = round(1e3 * timed(lambda: ops.krig_cs_predict(ca, cm, pix, z, info, status, None, params, 0, 0, r, t, nsys, np_, M, h, w, ens)), 1)
+            o["predict_us"] = round(1e3 * timed(lambda: ops.krig_cs_predict(ch, ca, cm, M, h, w, ens)), 1)
             o["predict_fraction_of_f32_mfma_peak"] = round(2.0 * n * h * w * M * f / (o["predict_us"] * 1e-6) / PEAK_F32_MFMA, 4)
             out[path] = o
             if path == "shared" and not a.no_torch:

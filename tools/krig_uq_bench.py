@@ -59,13 +59,14 @@ def main():
         alpha, mean = torch.empty(f, 1024, device=dev), torch.empty(f, device=dev)
         var = torch.empty(f, h * w, device=dev)
         pred, lvar = torch.empty_like(z), torch.empty_like(z)
-        ops.krig_factor(pix, info, params, 0, 0, t, t, b, np_, work, status)
-        sol = ops.krig_solve(work, z, info, status, None, 0, t, t, b, np_, alpha, mean)
+        ch = ops.KrigSystems(pix, z, info, params, None, 0, t, t, np_, status).chunk(0, b)
+        ops.krig_factor(ch, work)
+        sol = ops.krig_solve(ch, work, alpha, mean)
         assert int(status.sum()) == 0
         out = {"gauges_per_frame": n, "padded_system": np_, "systems": b}
         out["invert_us"] = round(1e3 * timed(lambda: ops.krig_invert(work, b, np_, winv)), 1)
-        out["variance_us"] = round(1e3 * timed(lambda: ops.krig_variance(winv, sol, pix, info, status, None, params, 0, 0, t, t, b, np_, h, w, var)), 1)
-        out["loo_us"] = round(1e3 * timed(lambda: ops.krig_loo(winv, sol, alpha, z, info, status, None, 0, t, t, b, np_, pred, lvar)), 1)
+        out["variance_us"] = round(1e3 * timed(lambda: ops.krig_variance(ch, winv, sol, h, w, var)), 1)
+        out["loo_us"] = round(1e3 * timed(lambda: ops.krig_loo(ch, winv, sol, alpha, pred, lvar)), 1)
         out["variance_fraction_of_f32_mfma_peak"] = round(float(n) * n * h * w * b / (out["variance_us"] * 1e-6) / PEAK_F32_MFMA, 4)
         if not a.no_torch:
             print(json.dumps({f"block{block}": out}), file=sys.stderr, flush=True)   # the kernels' figures, should the restatement fail

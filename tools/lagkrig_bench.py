@@ -59,13 +59,15 @@ def main():
     status = torch.zeros(b, device=dev, dtype=torch.int32)
     alpha = torch.empty(b, np_, device=dev)
     mean = torch.empty(b, device=dev)
-    out["stkriging_factor_ms"] = timed(lambda: ops.stkrig_factor(stpix, stt, stinfo, sparams, 0, 0, b, np_, work, status))
-    ops.krig_solve(work, stz, stinfo, status, scand, 0, 1, 1, b, np_, alpha, mean)
+    sch = ops.KrigSystems(stpix, stz, stinfo, sparams, scand, 0, 1, 1, np_, status).chunk(0, b)
+    ch = ops.KrigSystems(stpix, stz, stinfo, params, cand, 0, 1, 1, np_, status).chunk(0, b)
+    out["stkriging_factor_ms"] = timed(lambda: ops.stkrig_factor(sch, stt, work))
+    ops.krig_solve(sch, work, alpha, mean)
     out["stkriging_predict_ms"] = timed(lambda: ops.stkrig_predict(stpix, stt, alpha, mean, stinfo, sparams, 0, t, h, w))
     out["stkriging_failed_pivots"] = int(status.sum())
     status.zero_()
-    out["factor_ms"] = timed(lambda: ops.lagkrig_factor(stpix, stt, stinfo, params, velf, 0, 0, b, np_, work, status))
-    out["solve_ms"] = timed(lambda: ops.krig_solve(work, stz, stinfo, status, cand, 0, 1, 1, b, np_, alpha, mean))
+    out["factor_ms"] = timed(lambda: ops.lagkrig_factor(ch, stt, velf, work))
+    out["solve_ms"] = timed(lambda: ops.krig_solve(ch, work, alpha, mean))
     out["predict_ms"] = timed(lambda: ops.lagkrig_predict(stpix, stt, alpha, mean, stinfo, params, velf, 0, t, h, w))
     out["failed_pivots"] = int(status.sum())
     del work

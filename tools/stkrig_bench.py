@@ -54,8 +54,9 @@ def main():
         status = torch.zeros(b, device=dev, dtype=torch.int32)
         alpha = torch.empty(b, np_, device=dev)
         mean = torch.empty(b, device=dev)
-        out["factor_ms"] = timed(lambda: ops.stkrig_factor(stpix, stt, stinfo, params, 0, 0, b, np_, work, status))
-        out["solve_ms"] = timed(lambda: ops.krig_solve(work, stz, stinfo, status, cand, 0, 1, 1, b, np_, alpha, mean))
+        ch = ops.KrigSystems(stpix, stz, stinfo, params, cand, 0, 1, 1, np_, status).chunk(0, b)
+        out["factor_ms"] = timed(lambda: ops.stkrig_factor(ch, stt, work))
+        out["solve_ms"] = timed(lambda: ops.krig_solve(ch, work, alpha, mean))
         out["predict_ms"] = timed(lambda: ops.stkrig_predict(stpix, stt, alpha, mean, stinfo, params, 0, t, h, w))
         out["failed_pivots"] = int(status.sum())
         del work

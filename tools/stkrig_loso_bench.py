@@ -52,13 +52,14 @@ def main():
         alpha = torch.empty(b, np_, device=dev)
         mean = torch.empty(b, device=dev)
         pred, var = torch.zeros_like(z), torch.zeros_like(z)
-        out["factor_ms"] = timed(lambda: ops.stkrig_factor(sites["stpix"], sites["stt"], sites["stinfo"], params, 0, 0, b, np_, work, status))
-        out["solve_ms"] = timed(lambda: ops.krig_solve(work, sites["stz"], sites["stinfo"], status, cand, 0, 1, 1, b, np_, alpha, mean))
-        sol = ops.krig_solve(work, sites["stz"], sites["stinfo"], status, cand, 0, 1, 1, b, np_, alpha, mean)
+        ch = ops.KrigSystems(sites["stpix"], sites["stz"], sites["stinfo"], params, cand, 0, 1, 1, np_, status).chunk(0, b)
+        out["factor_ms"] = timed(lambda: ops.stkrig_factor(ch, sites["stt"], work))
+        out["solve_ms"] = timed(lambda: ops.krig_solve(ch, work, alpha, mean))
+        sol = ops.krig_solve(ch, work, alpha, mean)
         out["invert_ms"] = timed(lambda: ops.krig_invert(work, b, np_, winv))
         out["site_gram_ms"] = timed(lambda: ops.stkrig_site_gram(winv, b, np_))
         gram = ops.stkrig_site_gram(winv, b, np_)
-        out["site_solve_ms"] = timed(lambda: ops.stkrig_loso(gram, sol, alpha, sites, status, cand, 0, t, b, np_, pred, var))
+        out["site_solve_ms"] = timed(lambda: ops.stkrig_loso(ch, gram, sol, alpha, sites, t, pred, var))
         out["failed_pivots"] = int(status.sum())
         out["points_without_a_prediction"] = int(torch.isnan(pred).sum())
         del work, winv, gram
