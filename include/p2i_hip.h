@@ -12,8 +12,8 @@
  *    (PyTorch) owns all memory including workspaces; the library never allocates or frees;
  *  - every call only ENQUEUES work on `stream` (a hipStream_t passed as void*), never syncs;
  *  - state kept by the library: none that a result depends on.  Per calling THREAD it remembers the tile plan of the last
- *    conv / wgrad launch (p2i_conv_last_plan / p2i_wgrad_last_plan, diagnostics) and the scratch pointers of a running
- *    p2i_conv_*_x6 / p2i_conv_wgrad_ws call.  Tuning switches (P2I_* environment variables): the engine on/off switches
+ *    conv / wgrad launch (p2i_conv_last_plan / p2i_wgrad_last_plan, diagnostics), nothing that a later call reads: what a
+ *    convolution call computes stands in its argument list.  Tuning switches (P2I_* environment variables): the engine on/off switches
  *    (P2I_CONV_X6C, P2I_CONV_X6C_FUSED, P2I_X6C_KSPLIT, P2I_CONV_V4, P2I_CONV_CK16, P2I_CONV_KG27, P2I_DGRAD_FUSED, P2I_DGRAD_PAIR,
  *    P2I_C1_FAST, P2I_O1_FWD, P2I_WGRAD_X4, P2I_WGRAD_WINDOW) are read ONCE per process; the per-launch choices that the parity
  *    tests flip inside one process (P2I_X6C_MIN_WG, P2I_X6C_MIN_WG_LOW, P2I_X6C_TILE, P2I_X6C_TPS, P2I_X6C_PC, P2I_X6P_NPW, P2I_X6P_TN1,
@@ -59,8 +59,8 @@ const char* p2i_last_error(void);
  *                 mask_y (dx-shaped or NULL): dx is finally multiplied by mask_act'(mask_y), the
  *                 derivative of the activation that produced this layer's INPUT, so the next
  *                 dgrad/wgrad up the chain consume a ready gradient and need no prologue)
- * p2i_conv_wgrad: dWp[tap][cin][cout_pad] += sum_pixels x * (dy * act'(y))   (atomic fp32 adds;
- *                 caller zeroes dWp), db[cout] += sum dy*act'(y) when db != NULL.
+ * p2i_conv_wgrad: dWp[tap][cin][cout_pad] += sum_pixels x * (dy * act'(y))   (atomic fp32 adds, or slices
+ *                 summed in order with a scratch `ws`; caller zeroes dWp), db[cout] += sum dy*act'(y) when db != NULL.
  * dims: x (B,Cin,Ti,Hi,Wi), y (B,Cout,To,Ho,Wo); kernel (kt,kh,kw); stride (st,sh,sw);
  * padding (pt,ph,pw).  bias / residual / y_act may be NULL.
  * Limits (refused with P2I_EINVAL / P2I_ELDS and a p2i_last_error message, never answered wrongly): kt*kh*kw <= 27;
@@ -77,27 +77,10 @@ typedef struct {
   int pt, ph, pw;
 } p2i_conv_desc;
 
-int p2i_conv_fwd(const p2i_conv_desc* d, const float* x, const float* wp, const float* bias,
-                 const float* residual, float* y, int act, void* stream);
-int p2i_conv_dgrad(const p2i_conv_desc* d, const float* dy, const float* y_act, int act,
-                   const float* wp_d, const float* dx_add, const float* mask_y, int mask_act,
-                   float* dx, void* stream);
-int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const float* dy, const float* y_act,
-                   int act, float* dwp, float* dbias, void* stream);
-/* p2i_conv_wgrad with a caller-owned scratch `ws` of ws_floats floats: when it holds every workgroup's partial tile
- * (<= 256 * kh*kw * Cin * pad32(Cout) floats, 37.7 MB for the generator's 3x3 C->C layers) the partial tiles are stored
- * and summed by a second kernel instead of being added with float atomics: faster, and bit-reproducible.  ws == NULL or
- * too small: the atomic path of p2i_conv_wgrad.
- * With a sufficient scratch, 3x3 pad-1 2-D layers and 3x3x3 pad-1 layers with t stride <= 2 (three t slices), spatial stride 1,
- * whose Cin and Cout are multiples of 64, Ho % 4 == 0, Wo % 16 == 0, called without act'(y) prologue (the generator's DO-Conv stack,
- * the discriminators' 256 -> 256 and 128 -> 128 layers) are computed on the bf16 matrix pipe with fp32 accuracy (wgrad_x6.hip: x
- * and dy split exactly into three bf16 terms each, six MFMA products per fp32 product, transposed LDS reads), dbias included
- * (summed from the staged dy tiles, added atomically); same result contract, same slices + reduce.  P2I_WGRAD_X6=0 (read per
- * call) keeps the fp32-MFMA kernel. */
-int p2i_conv_wgrad_ws(const p2i_conv_desc* d, const float* x, const float* dy, const float* y_act, int act, float* dwp,
-                      float* dbias, float* ws, int64_t ws_floats, void* stream);
-/* Same contracts as p2i_conv_fwd / p2i_conv_dgrad (without the act'(y) prologue).  With a contraction width K % 16 == 0 and
- * enough output tiles to fill the chip, these layers are computed on the bf16 matrix pipe with fp32 accuracy (conv_x6c.hip):
+/* What the bf16-split pipe of a forward / data-gradient call may use.  `sp` == NULL, or a descriptor whose three pointers are all
+ * NULL, keeps the call on the fp32-MFMA kernels (and the single-channel kernels of conv_c1.hip).  Otherwise, with a contraction
+ * width K % 16 == 0 (K = Cin for fwd, Cout for dgrad; M the other one) and enough output tiles to fill the chip, these layers are
+ * computed on the bf16 matrix pipe with fp32 accuracy (conv_x6c.hip):
  *   - 3x3 stride-1 pad-1 2-D layers, forward and data gradient;
  *   - 3x3x3 pad-1 layers with spatial stride 1 and t stride 1 or 2 (the 27 taps as three t slices of nine), forward and data
  *     gradient (one launch per t-parity class);
@@ -105,34 +88,53 @@ int p2i_conv_wgrad_ws(const p2i_conv_desc* d, const float* x, const float* dy, c
  *     of the destination fused in one workgroup (patch_gemm_x6c_kernel<8,1,true,.>).
  * Every fp32 operand is split exactly into three bf16 terms and six v_mfma_f32_32x32x16_bf16 products are accumulated in fp32
  * (the dropped products are <= 2^-23 |a b| each, below the rounding of an fp32 fma chain).  Every other layer runs on the
- * fp32-MFMA kernels, exactly as p2i_conv_fwd / p2i_conv_dgrad would; the choice is the library's.
- * `wsplit`: caller-owned scratch of 3*ntaps*K*pad32(M) uint16 (K = contraction channels: Cin for fwd, Cout for dgrad; M the
- * other one), overwritten by the call; wsplit == NULL forces the fp32-MFMA kernels.  P2I_X6C_MIN_WG (read per call) overrides
- * the tile-count thresholds (default: 200 workgroups for a tile variant to be preferred, 64 for the smallest tile as the last resort). */
-int p2i_conv_fwd_x6(const p2i_conv_desc* d, const float* x, const float* wp, uint16_t* wsplit, const float* bias,
-                    const float* residual, float* y, int act, void* stream);
-int p2i_conv_dgrad_x6(const p2i_conv_desc* d, const float* dy, const float* wp_d, uint16_t* wsplit, const float* dx_add,
-                      const float* mask_y, int mask_act, float* dx, void* stream);
-/* Pre-split variant: split a weight tensor -- or a whole stack of same-shape packed tensors [n][ntaps][K][pad32(M)], passed as
- * ntaps = n * taps -- ONCE per weight update (p2i_x6_split; wb: 3 * ntaps * K * Mpad uint16, image Wb[plane][ntaps][K/8][Mpad][8]),
- * then call p2i_conv_fwd_x6s / p2i_conv_dgrad_x6s any number of times with wb_layer = wb + layer * taps * K * Mpad (uint16 elements:
- * plane 0 of that layer) and ntaps_w = the stack's total tap count.  p2i_x6c_would_take tells (1 / 0) whether a call with this
- * geometry (and, for a forward call, this epilogue activation) would use the split at all, so that callers can skip splitting
- * stacks no layer needs.  Layers with too few output tiles for 256 CUs whose epilogue is linear (no activation) run with the channel
- * chunks split over two workgroups per tile that add their partial sums into the zeroed destination (P2I_X6C_KSPLIT=0 disables).
- * The split is exact -- hi + mid + lo == w, each term w's remainder truncated to its upper 16 bits -- for +-0 and every normal
- * float32 whose remainders stay normal (pinned bit for bit for binary exponents -60 .. 60 by tests/test_weightprep_gpu.py); a
- * subnormal w loses its last bits (1e-40: the remainder's significant bits fall in the lower half-word). */
+ * fp32-MFMA kernels exactly as with sp == NULL, and launches no split; the choice is the library's (p2i_x6c_would_take tells it,
+ * 1 / 0, for a geometry and, for a forward call, an epilogue activation, so that callers can skip splitting stacks no layer needs).
+ * The weights' split comes from ONE of two places, w_split first when both are set:
+ *   - w_split: split a weight tensor -- or a whole stack of same-shape packed tensors [n][ntaps][K][pad32(M)], passed as ntaps =
+ *     n * taps -- ONCE per weight update (p2i_x6_split / p2i_x6_split_batched; wb: 3 * ntaps * K * Mpad uint16, image
+ *     Wb[plane][ntaps][K/8][Mpad][8]); w_split = wb + layer * taps * K * Mpad (uint16 elements: plane 0 of that layer) and
+ *     w_split_taps = the image's total tap count (refused when smaller than the layer's);
+ *   - w_scratch: 3*ntaps*K*pad32(M) uint16 of caller-owned scratch that the call overwrites with the split of its `wp`.
+ * src_planes: the call's source (x / dy) as the pre-split bf16 planes of p2i_x6_split_planes; read instead of the fp32 tensor by
+ * the 32-channel tiles with whole-chunk stages, ignored by every other tile and engine (an experiment, measured and not adopted:
+ * tools/presplit_probe.py).  A p2i_conv_dgrad call with the act'(y) prologue (y_act != NULL) ignores `sp`.
+ * Layers with too few output tiles for 256 CUs whose epilogue is linear (no activation) run with the channel chunks split over two
+ * workgroups per tile that add their partial sums into the zeroed destination (P2I_X6C_KSPLIT=0 disables).  P2I_X6C_MIN_WG (read
+ * per call) overrides the tile-count thresholds (default: 200 workgroups for a tile variant to be preferred, 64 for the smallest
+ * tile as the last resort). */
+typedef struct p2i_conv_split {
+  const uint16_t* w_split;    /* plane 0 of THIS layer inside a pre-split image (p2i_x6_split / _batched), or NULL */
+  uint16_t*       w_scratch;  /* else: 3*ntaps*K*pad32(M) uint16 the call may overwrite with the split, or NULL */
+  const void*     src_planes; /* pre-split source of p2i_x6_split_planes, or NULL; read only by the tiles that can */
+  int             w_split_taps; /* total taps of the image w_split lies in; read only with w_split */
+} p2i_conv_split;
+
+int p2i_conv_fwd(const p2i_conv_desc* d, const float* x, const float* wp, const p2i_conv_split* sp, const float* bias,
+                 const float* residual, float* y, int act, void* stream);
+int p2i_conv_dgrad(const p2i_conv_desc* d, const float* dy, const float* y_act, int act, const float* wp_d,
+                   const p2i_conv_split* sp, const float* dx_add, const float* mask_y, int mask_act, float* dx, void* stream);
+/* `ws`: caller-owned scratch of ws_floats floats, or NULL.  When it holds every workgroup's partial tile (<= 256 * kh*kw * Cin *
+ * pad32(Cout) floats, 37.7 MB for the generator's 3x3 C->C layers) the partial tiles are stored and summed by a second kernel
+ * instead of being added with float atomics: faster, and bit-reproducible.  ws == NULL or too small: the atomic path.
+ * With a sufficient scratch, 3x3 pad-1 2-D layers and 3x3x3 pad-1 layers with t stride <= 2 (three t slices), spatial stride 1,
+ * whose Cin and Cout are multiples of 64, Ho % 4 == 0, Wo % 16 == 0, called without act'(y) prologue (the generator's DO-Conv stack,
+ * the discriminators' 256 -> 256 and 128 -> 128 layers) are computed on the bf16 matrix pipe with fp32 accuracy (wgrad_x6.hip: x
+ * and dy split exactly into three bf16 terms each, six MFMA products per fp32 product, transposed LDS reads), dbias included
+ * (summed from the staged dy tiles, added atomically); same result contract, same slices + reduce.  P2I_WGRAD_X6=0 (read per
+ * call) keeps the fp32-MFMA kernel. */
+int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const float* dy, const float* y_act, int act, float* dwp,
+                   float* dbias, float* ws, int64_t ws_floats, void* stream);
+/* The weight split behind p2i_conv_split.w_split.  It is exact -- hi + mid + lo == w, each term w's remainder truncated to its
+ * upper 16 bits -- for +-0 and every normal float32 whose remainders stay normal (pinned bit for bit for binary exponents
+ * -60 .. 60 by tests/test_weightprep_gpu.py); a subnormal w loses its last bits (1e-40: the remainder's significant bits fall in
+ * the lower half-word). */
 int p2i_x6_split(const float* wp, uint16_t* wb, int ntaps, int K, int Mpad, void* stream);
 /* the same for n <= 24 packed tensors of different shapes in one launch (wb[i]: 3 * ntaps[i] * K[i] * Mpad[i] uint16 each): the
  * discriminators' layers after p2i_weight_pack_batched */
 int p2i_x6_split_batched(const float* const* wp, uint16_t* const* wb, const int* ntaps, const int* K, const int* Mpad, int n,
                          void* stream);
 int p2i_x6c_would_take(const p2i_conv_desc* d, int dgrad, int act);
-int p2i_conv_fwd_x6s(const p2i_conv_desc* d, const float* x, const float* wp, const uint16_t* wb_layer, int ntaps_w,
-                     const float* bias, const float* residual, float* y, int act, void* stream);
-int p2i_conv_dgrad_x6s(const p2i_conv_desc* d, const float* dy, const float* wp_d, const uint16_t* wb_layer, int ntaps_w,
-                       const float* dx_add, const float* mask_y, int mask_act, float* dx, void* stream);
 /* tile plan {MB, NPIX, WAVES_M, CK, NT, KG} of the calling thread's most recent fwd/dgrad launch: names the
  * patch_gemm_dma_kernel<MB,NPIX,WAVES_M,CK,NT,KG> instance (NT = -1: the prologue kernel
  * patch_gemm_kernel<MB,NPIX,WAVES_M,CK>; KG = 7: patch_gemm_x6c_kernel<8, MB/32, false, TPS>, fields {MB = 32 or 64, 256, ksplit,
@@ -191,18 +193,14 @@ int p2i_weight_unpack_grad(const float* dwp_f, int O, int I, int ntaps, const fl
                            float* dw, void* stream);
 
 /* p2i_weight_pack / p2i_weight_unpack_grad for n <= 16 layers of different shapes in one launch each (arrays of n HOST
- * entries).  The caller zeroes padded pack outputs (pad32(O) != O or pad32(I) != I); `dots`: n floats of device scratch. */
+ * entries).  The caller zeroes padded pack outputs (pad32(O) != O or pad32(I) != I); `dots`: n floats of device scratch.
+ * accumulate != 0: dw += ... (the discriminator's second backward pass of a D step adds to the first one's gradient:
+ * train.py:264-283 calls D twice before loss_d.backward()); 0: dw = ... */
 int p2i_weight_pack_batched(const float* const* w, const int* O, const int* I, const int* ntaps, const float* const* inv_div,
                             float* const* wp_f, float* const* wp_d, int n, void* stream);
 int p2i_weight_unpack_grad_batched(const float* const* dwp_f, const int* O, const int* I, const int* ntaps,
                                    const float* const* w_orig, const float* const* sigma, const float* const* u,
-                                   const float* const* v, float* dots, float* const* dw, int n, void* stream);
-
-/* p2i_weight_unpack_grad_batched with accumulate != 0: dw += ... (the discriminator's second backward pass of a D step adds to
- * the first one's gradient: train.py:264-283 calls D twice before loss_d.backward()) */
-int p2i_weight_unpack_grad_batched_acc(const float* const* dwp_f, const int* O, const int* I, const int* ntaps,
-                                       const float* const* w_orig, const float* const* sigma, const float* const* u,
-                                       const float* const* v, float* dots, float* const* dw, int n, int accumulate, void* stream);
+                                   const float* const* v, float* dots, float* const* dw, int n, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------ spectral norm
  * One power iteration of torch.nn.utils.spectral_norm (call sites layer.py:402-407,
@@ -241,12 +239,9 @@ int p2i_attn_bwd(const float* x, const float* w0, const float* b0, const float* 
  * raises, layer.py:282).  The library is enqueue-only and cannot raise without a device sync: it writes ZEROS for that sample
  * (out, sel_idx, sel_w; p2i_idw_bwd then gives a zero gradient), other samples of the batch are unaffected, and pt_count[b]
  * holds the count for a caller that wants the reference's error (the Python wrapper: P2I_IDW_STRICT=1, one host sync).
- * Pinned by tests/test_ops_gpu.py::test_idw_fewer_than_four_points_gives_zeros_or_raises. */
-int p2i_idw_fwd(const float* vals_src, const float* mask, const float* grid_x, const float* grid_y,
-                const float* grid_z, float* out, int32_t* pt_pos, int32_t* pt_count, int32_t* frame_count,
-                int32_t* row_start, float* pt_xyzn, int32_t* sel_idx, float* sel_w, int B, int T, int H, int W, float tau,
-                void* stream);
-/* The same result from a two-pass search (round 3).  The reference's scan order matters only where the 4th and 5th smallest
+ * Pinned by tests/test_ops_gpu.py::test_idw_fewer_than_four_points_gives_zeros_or_raises.
+ * amb == NULL: one kernel scans the points of every voxel in index order, as the reference does.  With the work buffer `amb` the
+ * same result comes from a two-pass search (round 3; what ops.idw_fwd calls).  The reference's scan order matters only where the 4th and 5th smallest
  * computed distances of a voxel are EQUAL (which tied point is kept depends on the heap's history); everywhere else the set of
  * selected points is the four nearest, whatever the order.  Pass 1 searches outwards from the voxel (own frame and rows first:
  * ~10 % of the distance evaluations of the index-order scan) and lists the voxels it finds tied; pass 2 replays the reference's
@@ -262,10 +257,10 @@ int p2i_idw_fwd(const float* vals_src, const float* mask, const float* grid_x, c
  * 0.558 / 0.189.  The replay's grid covers Q / 8 voxels per sample and loops beyond that.
  *   amb int32 [B*(2Q+2+ceil(Q/256))]: per sample the number of listed voxels, the lists of pass 1's workgroups (256 slots each) and
  *       their lengths / prefix sums; behind the B samples' blocks the second list, per sample [count, voxels ...] (work buffer). */
-int p2i_idw_fwd_ws(const float* vals_src, const float* mask, const float* grid_x, const float* grid_y,
-                   const float* grid_z, float* out, int32_t* pt_pos, int32_t* pt_count, int32_t* frame_count,
-                   int32_t* row_start, float* pt_xyzn, int32_t* sel_idx, float* sel_w, int32_t* amb, int B, int T, int H, int W,
-                   float tau, void* stream);
+int p2i_idw_fwd(const float* vals_src, const float* mask, const float* grid_x, const float* grid_y,
+                const float* grid_z, float* out, int32_t* pt_pos, int32_t* pt_count, int32_t* frame_count,
+                int32_t* row_start, float* pt_xyzn, int32_t* sel_idx, float* sel_w, int32_t* amb, int B, int T, int H, int W,
+                float tau, void* stream);
 /* Backward: dvals_src[pt_pos[j]] = sum over the voxels that selected point j of dout * sel_w, every other entry 0 (values enter the
  * output linearly; the weights are data).  Float atomics by default; with a scratch registered through p2i_det_workspace the same
  * scatter in 64-bit fixed point, scaled from the largest FINITE |dout| of the call: bit-equal from run to run and exact up to the
@@ -280,13 +275,12 @@ int p2i_idw_bwd(const float* dout, const int32_t* pt_pos, const int32_t* pt_coun
 int p2i_pooldup_fwd(const float* x, float* y, int B, int C, int H, int W, void* stream);
 int p2i_pooldup_bwd(const float* x, const float* dy, float* dx, int B, int C, int H, int W, void* stream);
 
-/* UPPos front half (layer.py:392-396): u = bilinear_x2(x, align_corners=True) * 2*sigmoid(pos). */
-int p2i_upmod_fwd(const float* x, const float* pos, float* u, int B, int C, int S, int S2w /*in W*/, void* stream);
-/* The same with the rest of UPPos behind it: u = act(bilinear_x2(v) * 2*sigmoid(pos) + bias[c]).  The modulation is ONE factor per
+/* UPPos front half (layer.py:392-396): u = bilinear_x2(x, align_corners=True) * 2*sigmoid(pos); bias == NULL: no epilogue, `act`
+ * is not read.  With a bias, the rest of UPPos behind it: u = act(bilinear_x2(v) * 2*sigmoid(pos) + bias[c]).  The modulation is ONE factor per
  * pixel for all channels and the upsampling acts on every channel alike, so the 1x1 projection (layer.py:390,397) commutes with
  * both: relu(W (up(h) * s) + b) == relu(up(W h) * s + b).  The build projects at the LOW resolution (a quarter of the positions,
  * v = W h through p2i_conv_fwd) and finishes here; equal to the reference's order up to fp32 rounding of the reordered sums. */
-int p2i_upmod_fwd_ba(const float* v, const float* pos, const float* bias, int act, float* u, int B, int C, int S, int S2w, void* stream);
+int p2i_upmod_fwd(const float* x, const float* pos, const float* bias, int act, float* u, int B, int C, int S, int S2w /*in W*/, void* stream);
 int p2i_upmod_bwd(const float* x, const float* pos, const float* du, float* dx, float* dpos,
                   int B, int C, int S, int S2w, void* stream);
 
@@ -427,12 +421,11 @@ int p2i_act_bwd_bias(const float* dy, const float* y, int act, float* out, float
  *     device). */
 /* ---- Pre-split source planes (round 4, EXPERIMENT: measured, not used by the engine -- DESIGN.md section 7).  p2i_x6_split_planes:
  * fp32 activations (B, C, P) (P = frames x pixels, C % 8 == 0) -> their exact 3-way bf16 split as planes [plane][b][C/8][P][8]
- * (3 * B * C * P bf16, caller-owned).  p2i_x6_next_source_planes: the next split-pipe forward / data-gradient call of the calling
- * thread (p2i_conv_fwd_x6s / _dgrad_x6s ...) reads its source from these planes instead of splitting the fp32 tensor in the kernel
- * (32-channel tiles with whole-chunk stages; any other tile ignores them); the same deconv_pytorch.py:103-109 convolution, bit-equal
- * results (tests/test_ops_gpu.py::test_presplit_source_planes_are_bit_equal). */
+ * (3 * B * C * P bf16, caller-owned).  A forward / data-gradient call given them as p2i_conv_split.src_planes reads its source from
+ * these planes instead of splitting the fp32 tensor in the kernel (32-channel tiles with whole-chunk stages; any other tile ignores
+ * them); the same deconv_pytorch.py:103-109 convolution, bit-equal results
+ * (tests/test_ops_gpu.py::test_presplit_source_planes_are_bit_equal). */
 int p2i_x6_split_planes(const float* x, void* planes, int B, int C, int64_t P, void* stream);
-int p2i_x6_next_source_planes(const void* planes);
 
 /* ---- Run-to-run reproducibility (round 4).  The step's small cross-workgroup sums (bias / position / attention-weight / alpha
  * gradients, spectral-norm dot products, the 1 -> 32 layer's weight gradient, the IDW backward scatter) are float atomics by

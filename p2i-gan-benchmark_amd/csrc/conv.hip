@@ -206,18 +206,18 @@ static int dispatch_patch(const TileCfg& c, const PatchGeom& g, dim3 grid, size_
 
 static thread_local int g_last_plan[6] = {0, 0, 0, 0, 0, 0};
 
-static int run_patch_gemm(PatchGeom g, const ClassSpec& cs, hipStream_t s);
+static int run_patch_gemm(PatchGeom g, const ClassSpec& cs, const X6Split& x6, hipStream_t s);
 
 // One launch for `ncls` classes sharing source/dest tensors and multipliers (strided dgrad: blockIdx.z = class).
 // Returns 1 if the merged DMA launch is not possible (caller falls back to one launch per class).
-static int run_patch_gemm_classes(PatchGeom g, const ClassSpec* css, int ncls, hipStream_t s) {
+static int run_patch_gemm_classes(PatchGeom g, const ClassSpec* css, int ncls, const X6Split& x6, hipStream_t s) {
   if (g.src_y != nullptr || ncls > MAX_CLASSES) return 1;
-  if (const X6Ctx& xc = x6_ctx(); xc.wb != nullptr) {        // inside a p2i_conv_*_x6 call: bf16-split kernel first, one launch per class
+  if (x6.wb != nullptr) {                                   // the call brought a weight split: bf16-split kernel first, one launch per class
     bool all = true;                                        // (all classes or none)
-    for (int q = 0; q < ncls && all; ++q) all = run_patch_gemm_x6c(g, css[q], xc.wb, xc.ntaps_w, nullptr, s, true) == 0;
+    for (int q = 0; q < ncls && all; ++q) all = run_patch_gemm_x6c(g, css[q], x6, nullptr, s, true) == 0;
     if (all) {
       for (int q = 0; q < ncls; ++q)
-        if (const int rc = run_patch_gemm_x6c(g, css[q], xc.wb, xc.ntaps_w, g_last_plan, s)) return rc == 1 ? P2I_EINVAL : rc;
+        if (const int rc = run_patch_gemm_x6c(g, css[q], x6, g_last_plan, s)) return rc == 1 ? P2I_EINVAL : rc;
       return P2I_OK;
     }
   }
@@ -357,11 +357,11 @@ static int run_patch_gemm_classes(PatchGeom g, const ClassSpec* css, int ncls, h
   return dispatch_patch_dma(c, KG, bg, best_grid, best_lds, s);
 }
 
-static int run_patch_gemm(PatchGeom g, const ClassSpec& cs, hipStream_t s) {
+static int run_patch_gemm(PatchGeom g, const ClassSpec& cs, const X6Split& x6, hipStream_t s) {
   if (cs.nT <= 0 || cs.nH <= 0 || cs.nW <= 0) return P2I_OK;
   // ---- DMA-pipelined path (no act'(y) prologue)
   {
-    const int rc = run_patch_gemm_classes(g, &cs, 1, s);
+    const int rc = run_patch_gemm_classes(g, &cs, 1, x6, s);
     if (rc != 1) return rc;
   }
   g.nT = cs.nT; g.nH = cs.nH; g.nW = cs.nW;
@@ -456,11 +456,33 @@ extern "C" int p2i_fast_div_magic(int d, uint32_t* magic) {
   return P2I_OK;
 }
 
-extern "C" int p2i_conv_fwd(const p2i_conv_desc* d, const float* x, const float* wp, const float* bias,
+// What the split pipe of ONE forward / data-gradient call uses, from the caller's p2i_conv_split (p2i_hip.h): nothing (x6->wb stays
+// null: fp32-MFMA engines, no split launched) without a weight split in the descriptor or for a layer the bf16-split kernels do not
+// take (x6c_would_take); else the pre-split image, or the scratch after splitting `wp` into it.
+static int resolve_split(const p2i_conv_desc* d, bool dgrad, int act, const float* wp, const p2i_conv_split* sp, hipStream_t s, X6Split* x6) {
+  *x6 = X6Split{nullptr, 0, nullptr};
+  if (sp == nullptr || (sp->w_split == nullptr && sp->w_scratch == nullptr)) return P2I_OK;
+  const int K = dgrad ? d->Cout : d->Cin, M = dgrad ? d->Cin : d->Cout;
+  if ((K & 15) != 0 || (dgrad && d->Cin == 1) || !x6c_would_take(d, dgrad, dgrad ? P2I_ACT_NONE : act)) return P2I_OK;
+  const int nt = d->kt * d->kh * d->kw;
+  if (sp->w_split != nullptr) {
+    P2I_REQUIRE(sp->w_split_taps >= nt, "ntaps_w smaller than the layer's tap count");
+    *x6 = X6Split{sp->w_split, sp->w_split_taps, sp->src_planes};
+    return P2I_OK;
+  }
+  P2I_REQUIRE(wp != nullptr, "null pointer");
+  if (int e = x6_split_weights(wp, sp->w_scratch, nt, K, (M + 31) / 32 * 32, s)) return e;
+  *x6 = X6Split{sp->w_scratch, nt, sp->src_planes};
+  return P2I_OK;
+}
+
+extern "C" int p2i_conv_fwd(const p2i_conv_desc* d, const float* x, const float* wp, const p2i_conv_split* sp, const float* bias,
                             const float* residual, float* y, int act, void* stream) {
   if (int e = check_desc(d)) return e;
+  X6Split x6;
+  if (int e = resolve_split(d, false, act, wp, sp, (hipStream_t)stream, &x6)) return e;
   P2I_REQUIRE(x && wp && y, "null pointer");
-  if (d->Cin == 1 && residual == nullptr && x6_ctx().wb == nullptr) {         // single-channel input: dedicated kernel (conv_c1.hip)
+  if (d->Cin == 1 && residual == nullptr && x6.wb == nullptr) {         // single-channel input: dedicated kernel (conv_c1.hip)
     const int rc = c1_fwd(d, x, wp, bias, y, act, (hipStream_t)stream);
     if (rc != 1) { g_last_plan[0] = 32; g_last_plan[1] = 64; g_last_plan[2] = 1; g_last_plan[3] = 2; g_last_plan[4] = 27; g_last_plan[5] = 1; return rc; }
   }
@@ -484,13 +506,14 @@ extern "C" int p2i_conv_fwd(const p2i_conv_desc* d, const float* x, const float*
         cs.tw[n] = (short)n; cs.dt[n] = a - d->pt; cs.dh[n] = b - d->ph; cs.dw[n] = c - d->pw; ++n;
       }
   cs.ntaps = n;
-  return run_patch_gemm(g, cs, (hipStream_t)stream);
+  return run_patch_gemm(g, cs, x6, (hipStream_t)stream);
 }
 
-extern "C" int p2i_conv_dgrad(const p2i_conv_desc* d, const float* dy, const float* y_act, int act,
-                              const float* wp_d, const float* dx_add, const float* mask_y, int mask_act,
-                              float* dx, void* stream) {
+extern "C" int p2i_conv_dgrad(const p2i_conv_desc* d, const float* dy, const float* y_act, int act, const float* wp_d,
+                              const p2i_conv_split* sp, const float* dx_add, const float* mask_y, int mask_act, float* dx, void* stream) {
   if (int e = check_desc(d)) return e;
+  X6Split x6;                                               // (the bf16-split kernels have no act'(y) prologue)
+  if (int e = resolve_split(d, true, P2I_ACT_NONE, wp_d, y_act ? nullptr : sp, (hipStream_t)stream, &x6)) return e;
   P2I_REQUIRE(dy && wp_d && dx, "null pointer");
   PatchGeom g{};
   g.src = dy; g.src_y = y_act; g.wp = wp_d; g.bias = nullptr; g.res = dx_add; g.dst = dx; g.act_epi = P2I_ACT_NONE; g.act_pro = y_act ? act : P2I_ACT_NONE;
@@ -532,59 +555,26 @@ extern "C" int p2i_conv_dgrad(const p2i_conv_desc* d, const float* dy, const flo
         }
         cs.ntaps = n;
         if (mergeable) css[ncls++] = cs;
-        else if (int e = run_patch_gemm(g, cs, (hipStream_t)stream)) return e;
+        else if (int e = run_patch_gemm(g, cs, x6, (hipStream_t)stream)) return e;
       }
   if (mergeable) {
     int rc = 1;
-    if (const X6Ctx& xc = x6_ctx(); xc.wb != nullptr && ncls == 4)      // bf16-split kernel with the four parity classes fused
-      rc = run_patch_gemm_x6c_fused(g, css, ncls, xc.wb, xc.ntaps_w, g_last_plan, (hipStream_t)stream);
-    if (rc == 1) rc = (ncls > 1 && x6_ctx().wb == nullptr) ? run_patch_gemm_fused(g, css, ncls, g_last_plan, (hipStream_t)stream) : 1;
-    if (rc == 1) rc = ncls > 1 ? run_patch_gemm_classes(g, css, ncls, (hipStream_t)stream) : 1;
+    if (x6.wb != nullptr && ncls == 4)                      // bf16-split kernel with the four parity classes fused
+      rc = run_patch_gemm_x6c_fused(g, css, ncls, x6, g_last_plan, (hipStream_t)stream);
+    if (rc == 1) rc = (ncls > 1 && x6.wb == nullptr) ? run_patch_gemm_fused(g, css, ncls, g_last_plan, (hipStream_t)stream) : 1;
+    if (rc == 1) rc = ncls > 1 ? run_patch_gemm_classes(g, css, ncls, x6, (hipStream_t)stream) : 1;
     if (rc == 1) {
       for (int q = 0; q < ncls; ++q)
-        if (int e = run_patch_gemm(g, css[q], (hipStream_t)stream)) return e;
+        if (int e = run_patch_gemm(g, css[q], x6, (hipStream_t)stream)) return e;
     } else if (rc != P2I_OK) return rc;
   }
   return P2I_OK;
 }
 
 
-// ---- exact-fp32 convolution on the bf16 matrix pipe (conv_x6c.hip).  `wsplit` is caller-owned scratch of
-// 3 * ntaps * K * pad32(M) bf16 (K = contraction channels, M = destination channels of the call) that receives the
-// 3-plane split of `wp`; layers the bf16-split kernel does not take (x6c_would_take) run on the fp32-MFMA kernels above.
-namespace p2i { int x6_split_weights(const float* wp, uint16_t* wb, int ntaps, int Ck, int CmPad, hipStream_t s); }
-
-
-extern "C" int p2i_conv_fwd_x6(const p2i_conv_desc* d, const float* x, const float* wp, uint16_t* wsplit, const float* bias,
-                               const float* residual, float* y, int act, void* stream) {
-  if (int e = check_desc(d)) return e;
-  if (wsplit == nullptr || (d->Cin & 15) != 0 || !x6c_would_take(d, false, act))
-    return p2i_conv_fwd(d, x, wp, bias, residual, y, act, stream);
-  P2I_REQUIRE(wp != nullptr, "null pointer");
-  const int nt = d->kt * d->kh * d->kw;
-  if (int e = x6_split_weights(wp, wsplit, nt, d->Cin, (d->Cout + 31) / 32 * 32, (hipStream_t)stream)) return e;
-  x6_ctx() = X6Ctx{wsplit, nt};
-  const int rc = p2i_conv_fwd(d, x, wp, bias, residual, y, act, stream);
-  x6_ctx() = X6Ctx{nullptr, 0};
-  return rc;
-}
-
-extern "C" int p2i_conv_dgrad_x6(const p2i_conv_desc* d, const float* dy, const float* wp_d, uint16_t* wsplit, const float* dx_add,
-                                 const float* mask_y, int mask_act, float* dx, void* stream) {
-  if (int e = check_desc(d)) return e;
-  if (wsplit == nullptr || (d->Cout & 15) != 0 || d->Cin == 1 || !x6c_would_take(d, true, P2I_ACT_NONE))
-    return p2i_conv_dgrad(d, dy, nullptr, P2I_ACT_NONE, wp_d, dx_add, mask_y, mask_act, dx, stream);
-  P2I_REQUIRE(wp_d != nullptr, "null pointer");
-  const int nt = d->kt * d->kh * d->kw;
-  if (int e = x6_split_weights(wp_d, wsplit, nt, d->Cout, (d->Cin + 31) / 32 * 32, (hipStream_t)stream)) return e;
-  x6_ctx() = X6Ctx{wsplit, nt};
-  const int rc = p2i_conv_dgrad(d, dy, nullptr, P2I_ACT_NONE, wp_d, dx_add, mask_y, mask_act, dx, stream);
-  x6_ctx() = X6Ctx{nullptr, 0};
-  return rc;
-}
-
 // ---- pre-split weights: split once per weight update (a whole stack of same-shape packed tensors in one launch), then any number
-// of conv calls.  `wb_layer` points at plane 0 of THIS layer inside the stack's split image Wb[plane][ntaps_w][K/8][pad32(M)][8].
+// of conv calls whose p2i_conv_split.w_split points at plane 0 of THEIR layer inside the stack's split image
+// Wb[plane][ntaps_w][K/8][pad32(M)][8].
 extern "C" int p2i_x6_split(const float* wp, uint16_t* wb, int ntaps, int K, int Mpad, void* stream) {
   P2I_REQUIRE(wp && wb && ntaps > 0 && K > 0 && (K & 7) == 0 && Mpad > 0 && (Mpad & 31) == 0, "p2i_x6_split: bad arguments");
   return x6_split_weights(wp, wb, ntaps, K, Mpad, (hipStream_t)stream);
@@ -594,27 +584,4 @@ extern "C" int p2i_x6c_would_take(const p2i_conv_desc* d, int dgrad, int act) {
   if (check_desc(d)) return 0;
   if (dgrad ? ((d->Cout & 15) != 0 || d->Cin == 1) : (d->Cin & 15) != 0) return 0;
   return x6c_would_take(d, dgrad != 0, dgrad ? P2I_ACT_NONE : act) ? 1 : 0;
-}
-
-extern "C" int p2i_conv_fwd_x6s(const p2i_conv_desc* d, const float* x, const float* wp, const uint16_t* wb_layer, int ntaps_w,
-                                const float* bias, const float* residual, float* y, int act, void* stream) {
-  if (int e = check_desc(d)) return e;
-  if (wb_layer == nullptr || (d->Cin & 15) != 0 || !x6c_would_take(d, false, act)) return p2i_conv_fwd(d, x, wp, bias, residual, y, act, stream);
-  P2I_REQUIRE(ntaps_w >= d->kt * d->kh * d->kw, "ntaps_w smaller than the layer's tap count");
-  x6_ctx() = X6Ctx{wb_layer, ntaps_w};
-  const int rc = p2i_conv_fwd(d, x, wp, bias, residual, y, act, stream);
-  x6_ctx() = X6Ctx{nullptr, 0};
-  return rc;
-}
-
-extern "C" int p2i_conv_dgrad_x6s(const p2i_conv_desc* d, const float* dy, const float* wp_d, const uint16_t* wb_layer, int ntaps_w,
-                                  const float* dx_add, const float* mask_y, int mask_act, float* dx, void* stream) {
-  if (int e = check_desc(d)) return e;
-  if (wb_layer == nullptr || (d->Cout & 15) != 0 || d->Cin == 1 || !x6c_would_take(d, true, P2I_ACT_NONE))
-    return p2i_conv_dgrad(d, dy, nullptr, P2I_ACT_NONE, wp_d, dx_add, mask_y, mask_act, dx, stream);
-  P2I_REQUIRE(ntaps_w >= d->kt * d->kh * d->kw, "ntaps_w smaller than the layer's tap count");
-  x6_ctx() = X6Ctx{wb_layer, ntaps_w};
-  const int rc = p2i_conv_dgrad(d, dy, nullptr, P2I_ACT_NONE, wp_d, dx_add, mask_y, mask_act, dx, stream);
-  x6_ctx() = X6Ctx{nullptr, 0};
-  return rc;
 }

@@ -422,16 +422,21 @@ struct ClassSpec {
   int dt[MAX_TAPS], dh[MAX_TAPS], dw[MAX_TAPS];
 };
 
-// exact-fp32 convolution on the bf16 matrix pipe (conv_x6c.hip): set for the duration of a p2i_conv_*_x6 call,
-// points at the 3-plane bf16 split of the packed weights the call is about to use (nullptr: fp32 MFMA path)
-struct X6Ctx { const uint16_t* wb; int ntaps_w; };
-X6Ctx& x6_ctx();
+static_assert(sizeof(p2i_conv_split) == 32 && offsetof(p2i_conv_split, w_split) == 0 && offsetof(p2i_conv_split, w_scratch) == 8 &&
+                  offsetof(p2i_conv_split, src_planes) == 16 && offsetof(p2i_conv_split, w_split_taps) == 24,
+              "p2i_conv_split is mirrored field by field by the ctypes binding");
+
+// exact-fp32 convolution on the bf16 matrix pipe (conv_x6c.hip): the p2i_conv_split of a forward / data-gradient call as resolved
+// by its entry point (conv.hip, resolve_split) and handed down the planners.  wb: the 3-plane bf16 split of the packed weights the
+// call uses inside an image of ntaps_w taps (nullptr: fp32-MFMA engines only); src_planes: the call's pre-split source or nullptr.
+struct X6Split { const uint16_t* wb; int ntaps_w; const void* src_planes; };
 
 // 3x3 stride-1 2-D layers on the bf16 matrix pipe, chunk/tap-row pipeline (conv_x6c.hip); returns 1 when it does not apply
-int run_patch_gemm_x6c(const PatchGeom& g, const ClassSpec& cs, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry = false);
+int run_patch_gemm_x6c(const PatchGeom& g, const ClassSpec& cs, const X6Split& x6, int* plan6, hipStream_t s, bool dry = false);
 // data gradient of a 3x3(x3) stride-(1,2,2) pad-1 convolution: the four input-parity classes in one workgroup, bf16 matrix pipe
-int run_patch_gemm_x6c_fused(const PatchGeom& g, const ClassSpec* css, int ncls, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry = false);
+int run_patch_gemm_x6c_fused(const PatchGeom& g, const ClassSpec* css, int ncls, const X6Split& x6, int* plan6, hipStream_t s, bool dry = false);
 bool x6c_would_take(const p2i_conv_desc* d, bool dgrad, int act_epi);
+int x6_split_weights(const float* wp, uint16_t* wb, int ntaps, int Ck, int CmPad, hipStream_t s);
 
 // strided dgrad with the parity classes fused in one workgroup (conv_fused.hip); returns 1 when it does not apply
 int run_patch_gemm_fused(PatchGeom g, const ClassSpec* css, int ncls, int* plan6, hipStream_t s);

@@ -101,11 +101,6 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
   }
 }
 
-X6Ctx& x6_ctx() {
-  static thread_local X6Ctx c{nullptr, 0};
-  return c;
-}
-
 int x6_split_weights(const float* wp, uint16_t* wb, int ntaps, int Ck, int CmPad, hipStream_t s) {
   const int total = ntaps * (Ck >> 3) * CmPad;
   const int blocks = total > 0 ? (total + 255) / 256 : 1;
@@ -1155,9 +1150,6 @@ __global__ __launch_bounds__(256) void x6c_post_act_kernel(float* __restrict__ y
   }
 }
 
-// experiment (round 4): the source planes of the NEXT split-pipe launch of this thread (tools/presplit_probe.py); consumed by it
-static thread_local const void* g_next_splanes = nullptr;
-
 static size_t x6c_lds_bytes(int csl, int tm, int tps) {
   const int ring = tps == 9 ? 3 : (tm == 2 ? 4 : 6);
   return sizeof(float) * (size_t)((csl + 3) & ~3) + 16 * (size_t)(ring * 6 * tps * 32 * tm + 2 * 6 * csl);
@@ -1166,15 +1158,15 @@ static size_t x6c_lds_bytes(int csl, int tm, int tps) {
 // What both runners fill alike: pointers, extents, the picked tile with a patch of (jh + halo) x (jw + halo) pixels, the weight
 // stack's bounds, the time-axis fields of class css[0] and the per-call switches.  The runners add their tap tables, slice offsets
 // and what only one of them has (bH / bW, fused_atomic, vec4_epi, splanes).
-static X6cGeom x6c_geom(const PatchGeom& g, const ClassSpec* css, int ncls, const X6cPick& pk, int halo, int ns, const uint16_t* wb, int ntaps_w) {
+static X6cGeom x6c_geom(const PatchGeom& g, const ClassSpec* css, int ncls, const X6cPick& pk, int halo, int ns, const X6Split& x6) {
   const ClassSpec& c0 = css[0];
   X6cGeom k{};
-  k.src = g.src; k.dst = g.dst; k.wb = wb; k.bias = g.bias; k.res = g.res; k.mask_y = g.mask_y;
+  k.src = g.src; k.dst = g.dst; k.wb = x6.wb; k.bias = g.bias; k.res = g.res; k.mask_y = g.mask_y;
   // planes 0..2 of this layer inside a stack of ntaps_w taps; the layer's own taps reach up to max(tw) + 1
   int tw_max = 0;
   for (int q = 0; q < ncls; ++q)
     for (int i = 0; i < css[q].ntaps; ++i) tw_max = css[q].tw[i] > tw_max ? css[q].tw[i] : tw_max;
-  k.wb_bytes = (2u * (unsigned)ntaps_w + (unsigned)tw_max + 1u) * (unsigned)g.Ck * (unsigned)g.CmPad * 2u;
+  k.wb_bytes = (2u * (unsigned)x6.ntaps_w + (unsigned)tw_max + 1u) * (unsigned)g.Ck * (unsigned)g.CmPad * 2u;
   k.act_epi = g.act_epi; k.mask_act = g.mask_act;
   k.B = g.B; k.Ck = g.Ck; k.Cm = g.Cm; k.CmPad = g.CmPad;
   k.sH = g.sH; k.sW = g.sW; k.dT = g.dT; k.dH = g.dH; k.dW = g.dW; k.nH = c0.nH; k.nW = c0.nW;
@@ -1182,7 +1174,7 @@ static X6cGeom x6c_geom(const PatchGeom& g, const ClassSpec* css, int ncls, cons
   k.eH = pk.jh + halo; k.eW = pk.jw + halo; k.CSl = pk.csl;
   k.nth = ceil_div(c0.nH, pk.jh); k.ntw = ceil_div(c0.nW, pk.jw);
   k.mg_ew = magic_u16(k.eW); k.mg_eh = magic_u16(k.eH);      // (3 .. 34 by construction: jh, jw in 1 .. 32, halo 1 or 2)
-  k.ntaps_w = ntaps_w; k.ksplit = pk.ksplit;
+  k.ntaps_w = x6.ntaps_w; k.ksplit = pk.ksplit;
   k.sT = g.sT; k.nT = c0.nT; k.mT = c0.mT; k.oT = c0.oT; k.pT = c0.pT; k.ns = ns;
   k.stagger = x6c_stagger(); k.cons_prio = x6p_prio();
   return k;
@@ -1228,8 +1220,8 @@ static void x6c_dispatch(const X6cGeom& k, const X6cVariant& tv, int tps, bool f
 }
 
 // returns 1 when the layer is not an x6c case (caller continues with the other engines)
-int run_patch_gemm_x6c(const PatchGeom& g, const ClassSpec& cs, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry) {
-  if (!x6c_on() || (!dry && wb == nullptr) || g.src_y != nullptr || (g.Ck & 15) != 0 || g.Ck < 16) return 1;
+int run_patch_gemm_x6c(const PatchGeom& g, const ClassSpec& cs, const X6Split& x6, int* plan6, hipStream_t s, bool dry) {
+  if (!x6c_on() || (!dry && x6.wb == nullptr) || g.src_y != nullptr || (g.Ck & 15) != 0 || g.Ck < 16) return 1;
   // spatially a 3x3 stride-1 layer; along t: any source multiplier / destination stride / offset, taps in 1..3 slices of 9
   if (cs.mH != 1 || cs.mW != 1 || cs.oH != 1 || cs.oW != 1 || cs.pH || cs.pW) return 1;
   if (cs.ntaps != 9 && cs.ntaps != 18 && cs.ntaps != 27) return 1;
@@ -1262,7 +1254,7 @@ int run_patch_gemm_x6c(const PatchGeom& g, const ClassSpec& cs, const uint16_t* 
   if (sbytes >= 0x7FFFFFF0ull || 4ull * (unsigned long long)n_dst >= 0x7FFFFFF0ull) return 1;
   if (dry) return 0;
   const X6cVariant& tv = kX6cVariants[pk.v];
-  X6cGeom k = x6c_geom(g, &cs, 1, pk, 2, ns, wb, ntaps_w);
+  X6cGeom k = x6c_geom(g, &cs, 1, pk, 2, ns, x6);
   k.bH = lo[1]; k.bW = lo[2];
   for (int i = 0; i < 9; ++i) {
     k.tap_w[i] = cs.tw[i];
@@ -1278,12 +1270,10 @@ int run_patch_gemm_x6c(const PatchGeom& g, const ClassSpec& cs, const uint16_t* 
     if (p2i::memset_async(g.dst, 0, sizeof(float) * (size_t)n_dst, s) != hipSuccess) return P2I_EINVAL;
     if (post_act != P2I_ACT_NONE) { k.res = nullptr; k.act_epi = P2I_ACT_NONE; }   // act(sum + bias) + res: second pass
   }
-  if (g_next_splanes != nullptr) {                        // pre-split source (32-channel tiles with whole-chunk stages only)
-    if (x6c_pc() && g.Ck >= 32 && tv.TM == 1 && tps == 9 && pk.ksplit == 1) {
-      k.splanes = static_cast<const u32x4c*>(g_next_splanes);
-      k.plane_units = (unsigned)((long long)g.B * (g.Ck >> 3) * g.sT * g.sH * g.sW);
-    }
-    g_next_splanes = nullptr;
+  // pre-split source (round 4 experiment, tools/presplit_probe.py): 32-channel tiles with whole-chunk stages only
+  if (x6.src_planes != nullptr && x6c_pc() && g.Ck >= 32 && tv.TM == 1 && tps == 9 && pk.ksplit == 1) {
+    k.splanes = static_cast<const u32x4c*>(x6.src_planes);
+    k.plane_units = (unsigned)((long long)g.B * (g.Ck >> 3) * g.sT * g.sH * g.sW);
   }
   {
     const int v4_on = P2I_ENV_ONCE("P2I_X6C_EPI4", 1);
@@ -1305,8 +1295,8 @@ int run_patch_gemm_x6c(const PatchGeom& g, const ClassSpec& cs, const uint16_t* 
 // ---- fused strided data gradient (stride (1,2,2), 3x3 or 3x3x3 taps, pad 1 in h and w; t stride 1): classes q = 2 pH + pW in the
 // order p2i_conv_dgrad builds them; class q must hold ns * {1, 2, 2, 4}[q] taps (slice-major), every class the same extents.
 // Returns 1 when the layer is not such a case.
-int run_patch_gemm_x6c_fused(const PatchGeom& g, const ClassSpec* css, int ncls, const uint16_t* wb, int ntaps_w, int* plan6, hipStream_t s, bool dry) {
-  if (!x6c_fused_on() || ncls != 4 || (!dry && wb == nullptr) || g.src_y != nullptr || (g.Ck & 15) != 0 || g.Ck < 16) return 1;
+int run_patch_gemm_x6c_fused(const PatchGeom& g, const ClassSpec* css, int ncls, const X6Split& x6, int* plan6, hipStream_t s, bool dry) {
+  if (!x6c_fused_on() || ncls != 4 || (!dry && x6.wb == nullptr) || g.src_y != nullptr || (g.Ck & 15) != 0 || g.Ck < 16) return 1;
   static const int per[4] = {1, 2, 2, 4};
   const int ns = css[0].ntaps;                            // class (0,0) has one tap per t slice
   if (ns < 1 || ns > 3) return 1;
@@ -1339,7 +1329,7 @@ int run_patch_gemm_x6c_fused(const PatchGeom& g, const ClassSpec* css, int ncls,
   const unsigned long long sbytes = 4ull * g.B * g.Ck * g.sT * g.sH * g.sW;
   if (sbytes >= 0x7FFFFFF0ull || 4ull * (unsigned long long)n_dst >= 0x7FFFFFF0ull) return 1;
   if (dry) return 0;
-  X6cGeom k = x6c_geom(g, css, 4, pk, 1, ns, wb, ntaps_w);
+  X6cGeom k = x6c_geom(g, css, 4, pk, 1, ns, x6);
   k.bias = nullptr; k.act_epi = P2I_ACT_NONE;
   k.fused_atomic = pk.ksplit > 1 ? 1 : 0;
   k.sdt0 = sdt[0]; k.sdt1 = sdt[1]; k.sdt2 = sdt[2]; k.swt0 = swt[0]; k.swt1 = swt[1]; k.swt2 = swt[2];
@@ -1373,8 +1363,8 @@ extern "C" int p2i_x6_split_batched(const float* const* wp, uint16_t* const* wb,
 }
 
 // ---- pre-split source planes (round 4 experiment; tools/presplit_probe.py).  p2i_x6_split_planes: fp32 (B, C, frames x pixels) ->
-// planes; p2i_x6_next_source_planes: the next split-pipe forward / data-gradient call of this thread reads its source from them
-// (32-channel tiles with whole-chunk stages; any other tile ignores them).
+// planes; a forward / data-gradient call reads its source from them when they come as p2i_conv_split.src_planes (32-channel tiles
+// with whole-chunk stages; any other tile ignores them).
 extern "C" int p2i_x6_split_planes(const float* x, void* planes, int B, int C, int64_t P, void* stream) {
   P2I_REQUIRE(x && planes && B > 0 && C > 0 && (C & 7) == 0 && P > 0, "split planes: C % 8 == 0");
   const long long total = (long long)B * (C >> 3) * P;
@@ -1382,8 +1372,4 @@ extern "C" int p2i_x6_split_planes(const float* x, void* planes, int B, int C, i
   P2I_LAUNCH(p2i::split_planes_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, (hipStream_t)stream, x,
              static_cast<p2i::u32x4c*>(planes), B, C >> 3, (long long)P);
   return p2i::launch_status();
-}
-extern "C" int p2i_x6_next_source_planes(const void* planes) {
-  p2i::g_next_splanes = planes;
-  return P2I_OK;
 }

@@ -595,24 +595,13 @@ extern "C" int p2i_pooldup_bwd(const float* x, const float* dy, float* dx, int B
   P2I_LAUNCH(pooldup_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, B * C, H, W);
   return launch_status();
 }
-extern "C" int p2i_upmod_fwd(const float* x, const float* pos, float* u, int B, int C, int S, int S2w, void* stream) {
+extern "C" int p2i_upmod_fwd(const float* x, const float* pos, const float* bias, int act, float* u, int B, int C, int S, int S2w, void* stream) {
   P2I_REQUIRE(x && pos && u, "null pointer");
-  {
-    const int BC = B * C, npix = 4 * S * S2w;
-    int chunk = BC;                                  // enough (pixel tile, channel chunk) blocks to fill the chip ~8 times
-    while (chunk > 8 && (long long)ceil_div(npix, 256) * ceil_div(BC, chunk) < 2048) chunk = (chunk + 1) / 2;
-    P2I_LAUNCH(upmod_fwd_kernel, dim3(ceil_div(npix, 256), ceil_div(BC, chunk)), dim3(256), 0, (hipStream_t)stream, x, pos, u, BC, S, S2w, chunk,
-                       (const float*)nullptr, P2I_ACT_NONE, C);
-  }
-  return launch_status();
-}
-extern "C" int p2i_upmod_fwd_ba(const float* x, const float* pos, const float* bias, int act, float* u, int B, int C, int S, int S2w, void* stream) {
-  P2I_REQUIRE(x && pos && bias && u, "null pointer");
   const int BC = B * C, npix = 4 * S * S2w;
-  int chunk = BC;
+  int chunk = BC;                                  // enough (pixel tile, channel chunk) blocks to fill the chip ~8 times
   while (chunk > 8 && (long long)ceil_div(npix, 256) * ceil_div(BC, chunk) < 2048) chunk = (chunk + 1) / 2;
   P2I_LAUNCH(upmod_fwd_kernel, dim3(ceil_div(npix, 256), ceil_div(BC, chunk)), dim3(256), 0, (hipStream_t)stream, x, pos, u, BC, S, S2w, chunk,
-                     bias, act, C);
+                     bias, bias ? act : P2I_ACT_NONE, C);       // (no bias: no epilogue at all)
   return launch_status();
 }
 extern "C" int p2i_upmod_bwd(const float* x, const float* pos, const float* du, float* dx, float* dpos, int B, int C, int S,

@@ -757,10 +757,10 @@ __global__ __launch_bounds__(256) void idw_bwd_fix_finish_kernel(const unsigned 
 }  // namespace p2i
 using namespace p2i;
 
-static int idw_fwd_impl(const float* vals_src, const float* mask, const float* grid_x, const float* grid_y,
-                        const float* grid_z, float* out, int32_t* pt_pos, int32_t* pt_count, int32_t* frame_count,
-                        int32_t* row_start, float* pt_xyzn, int32_t* sel_idx, float* sel_w, int32_t* amb, int B, int T, int H, int W, float tau,
-                        void* stream) {
+extern "C" int p2i_idw_fwd(const float* vals_src, const float* mask, const float* grid_x, const float* grid_y,
+                           const float* grid_z, float* out, int32_t* pt_pos, int32_t* pt_count, int32_t* frame_count,
+                           int32_t* row_start, float* pt_xyzn, int32_t* sel_idx, float* sel_w, int32_t* amb, int B, int T, int H, int W, float tau,
+                           void* stream) {
   P2I_REQUIRE(vals_src && mask && grid_x && grid_y && grid_z && out && pt_pos && pt_count && frame_count && row_start && pt_xyzn,
               "null pointer");
   P2I_REQUIRE((sel_idx == nullptr) == (sel_w == nullptr), "sel_idx and sel_w go together");
@@ -803,22 +803,6 @@ static int idw_fwd_impl(const float* vals_src, const float* mask, const float* g
                        sel_idx, sel_w, (int32_t*)nullptr, nblk1, T, H, W, tau, 0);
   }
   return launch_status();
-}
-
-extern "C" int p2i_idw_fwd(const float* vals_src, const float* mask, const float* grid_x, const float* grid_y,
-                           const float* grid_z, float* out, int32_t* pt_pos, int32_t* pt_count, int32_t* frame_count,
-                           int32_t* row_start, float* pt_xyzn, int32_t* sel_idx, float* sel_w, int B, int T, int H, int W, float tau, void* stream) {
-  return idw_fwd_impl(vals_src, mask, grid_x, grid_y, grid_z, out, pt_pos, pt_count, frame_count, row_start, pt_xyzn, sel_idx, sel_w, nullptr,
-                      B, T, H, W, tau, stream);
-}
-
-extern "C" int p2i_idw_fwd_ws(const float* vals_src, const float* mask, const float* grid_x, const float* grid_y,
-                              const float* grid_z, float* out, int32_t* pt_pos, int32_t* pt_count, int32_t* frame_count,
-                              int32_t* row_start, float* pt_xyzn, int32_t* sel_idx, float* sel_w, int32_t* amb, int B, int T, int H, int W,
-                              float tau, void* stream) {
-  P2I_REQUIRE(amb, "null workspace");
-  return idw_fwd_impl(vals_src, mask, grid_x, grid_y, grid_z, out, pt_pos, pt_count, frame_count, row_start, pt_xyzn, sel_idx, sel_w, amb,
-                      B, T, H, W, tau, stream);
 }
 
 extern "C" int p2i_idw_bwd(const float* dout, const int32_t* pt_pos, const int32_t* pt_count, const int32_t* sel_idx,

@@ -448,7 +448,7 @@ static int sn_launch(const SnBatch& b, int n, int maxO, int maxK, int training, 
 }  // namespace p2i
 using namespace p2i;
 
-extern "C" int p2i_abi_version(void) { return 3; }
+extern "C" int p2i_abi_version(void) { return 4; }
 extern "C" const char* p2i_last_error(void) { return p2i::g_err; }
 
 extern "C" int p2i_doconv_fold_fwd(const float* W, const float* D, const float* D_diag, int O, int I, int groups, int ksz,
@@ -578,10 +578,10 @@ extern "C" int p2i_weight_pack_batched(const float* const* w, const int* O, cons
   return pack_launch(b, n, maxn, (hipStream_t)stream);
 }
 
-extern "C" int p2i_weight_unpack_grad_batched_acc(const float* const* dwp_f, const int* O, const int* I, const int* ntaps,
-                                                  const float* const* w_orig, const float* const* sigma, const float* const* u,
-                                                  const float* const* v, float* dots, float* const* dw, int n, int accumulate,
-                                                  void* stream) {
+extern "C" int p2i_weight_unpack_grad_batched(const float* const* dwp_f, const int* O, const int* I, const int* ntaps,
+                                              const float* const* w_orig, const float* const* sigma, const float* const* u,
+                                              const float* const* v, float* dots, float* const* dw, int n, int accumulate,
+                                              void* stream) {
   P2I_REQUIRE(dwp_f && O && I && ntaps && dw && dots && n >= 1 && n <= PACK_MAX_LAYERS, "1..%d layers", PACK_MAX_LAYERS);
   PackBatch b{};
   b.accumulate = accumulate;
@@ -596,10 +596,4 @@ extern "C" int p2i_weight_unpack_grad_batched_acc(const float* const* dwp_f, con
     if (O[i] * I[i] * ntaps[i] > maxn) maxn = O[i] * I[i] * ntaps[i];
   }
   return unpack_launch(b, n, maxn, dots, (hipStream_t)stream);
-}
-
-extern "C" int p2i_weight_unpack_grad_batched(const float* const* dwp_f, const int* O, const int* I, const int* ntaps,
-                                              const float* const* w_orig, const float* const* sigma, const float* const* u,
-                                              const float* const* v, float* dots, float* const* dw, int n, void* stream) {
-  return p2i_weight_unpack_grad_batched_acc(dwp_f, O, I, ntaps, w_orig, sigma, u, v, dots, dw, n, 0, stream);
 }

@@ -693,22 +693,19 @@ int run_wgrad_x6(const p2i_conv_desc* d, const float* x, const float* dy, float*
                  int* ns_out, long long* slice_out, hipStream_t s);
 }
 
-static thread_local float* g_wgrad_ws = nullptr;          // caller-owned slice scratch of the running p2i_conv_wgrad_ws call
-static thread_local long long g_wgrad_ws_floats = 0;
+// the caller-owned slice scratch of one p2i_conv_wgrad call (p == nullptr: none, float atomics)
+struct WgradWs {
+  float* p; long long floats;
+  // slice mode: ns >= 2 partial tiles of `slice` floats per output element, `stride` floats apart, and a scratch that holds all ns
+  bool sliced(int ns, long long slice, long long stride) const { return ns >= 2 && p != nullptr && stride * ns <= floats && slice < (1ll << 31); }
+};
 
-extern "C" int p2i_conv_wgrad_ws(const p2i_conv_desc* d, const float* x, const float* dy, const float* y_act, int act, float* dwp,
-                                 float* dbias, float* ws, int64_t ws_floats, void* stream) {
-  g_wgrad_ws = ws; g_wgrad_ws_floats = ws ? (long long)ws_floats : 0;
-  const int rc = p2i_conv_wgrad(d, x, dy, y_act, act, dwp, dbias, stream);
-  g_wgrad_ws = nullptr; g_wgrad_ws_floats = 0;
-  return rc;
-}
-
-extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const float* dy, const float* y_act,
-                              int act, float* dwp, float* dbias, void* stream) {
+extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const float* dy, const float* y_act, int act, float* dwp,
+                              float* dbias, float* ws_ptr, int64_t ws_floats, void* stream) {
   if (int e = check_desc(d)) return e;
   P2I_REQUIRE(x && dy && dwp, "null pointer");
   hipStream_t s = (hipStream_t)stream;
+  const WgradWs ws{ws_ptr, ws_ptr ? (long long)ws_floats : 0};
   if (d->Cin == 1 && d->Cout <= 32 && d->kt * d->kh * d->kw <= 32 && !y_act) {
     g_wgrad_plan[0] = 2; g_wgrad_plan[1] = d->kt * d->kh * d->kw; g_wgrad_plan[2] = 0; g_wgrad_plan[3] = 1;
     return c1_wgrad(d, x, dy, dwp, dbias, s);
@@ -716,11 +713,11 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
   if (y_act == nullptr) {                                   // bf16-split kernel where it applies (spatial stride 1, 64-multiple channels)
     int ns6 = 0;
     long long slice6 = 0;
-    const int rc = run_wgrad_x6(d, x, dy, dwp, dbias, g_wgrad_ws, g_wgrad_ws_floats, &ns6, &slice6, s);
+    const int rc = run_wgrad_x6(d, x, dy, dwp, dbias, ws.p, ws.floats, &ns6, &slice6, s);
     if (rc != 1) {
       if (rc) return rc;
       g_wgrad_plan[0] = 3; g_wgrad_plan[1] = 9 * d->kt; g_wgrad_plan[2] = 1; g_wgrad_plan[3] = 64;
-      if (ns6 >= 2) return launch_wgrad_reduce(g_wgrad_ws, ns6, slice6, d->Cout, (d->Cout + 31) / 32 * 32, dwp, s, dbias,
+      if (ns6 >= 2) return launch_wgrad_reduce(ws.p, ns6, slice6, d->Cout, (d->Cout + 31) / 32 * 32, dwp, s, dbias,
                                                slice6 + (dbias ? (d->Cout + 31) / 32 * 32 : 0));
       return P2I_OK;
     }
@@ -853,17 +850,16 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
         if (g.x4) ga.bW = g.bW - g.x4sh;
         ga.dbias = (dbias != nullptr && y4 && a == 0) ? dbias : nullptr;   // one kt slice sums dy (every slice sees all of it)
         if (ga.dbias) bias_fused = true;
-        // slice mode: ns >= 2 partial tiles per output element and a scratch that holds all ns slices of this launch
         const long long slice = (long long)g.tpg * d->Cin * g.CoPad;
         const long long pstr = slice + (ga.dbias ? g.CoPad : 0);          // (+ the slice's bias row)
-        const bool sliced = ns >= 2 && g_wgrad_ws != nullptr && pstr * ns <= g_wgrad_ws_floats && slice < (1ll << 31);
-        ga.partial = sliced ? g_wgrad_ws : nullptr;
+        const bool sliced = ws.sliced(ns, slice, pstr);
+        ga.partial = sliced ? ws.p : nullptr;
         ga.pstride = pstr;
         ga.bias_off = slice;
         P2I_LAUNCH(kern, dim3(ns, ncb, nco), dim3(512), lds2, s, ga);
         if (int e = launch_status()) return e;
         if (sliced)
-          if (int e = launch_wgrad_reduce(g_wgrad_ws, ns, slice, d->Cout, g.CoPad, ga.dwp, s, ga.dbias, pstr)) return e;
+          if (int e = launch_wgrad_reduce(ws.p, ns, slice, d->Cout, g.CoPad, ga.dwp, s, ga.dbias, pstr)) return e;
       }
     }
   }
@@ -871,11 +867,11 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
     // slice mode here too (round 4: maps narrower than 8 columns -- the deep levels of small crops -- took nsplit-way float atomics):
     // as many pixel splits as the scratch holds slices for, each storing its tile, summed in split order
     const long long slice = (long long)g.tpg * d->Cin * g.CoPad;
-    if (g_wgrad_ws != nullptr && nsplit >= 2 && slice < (1ll << 31)) {
-      const long long fit = g_wgrad_ws_floats / slice;
+    if (ws.p != nullptr && nsplit >= 2 && slice < (1ll << 31)) {
+      const long long fit = ws.floats / slice;
       if (fit < nsplit) nsplit = fit >= 2 ? (int)fit : 1;
     }
-    const bool sliced = nsplit >= 2 && g_wgrad_ws != nullptr && slice * nsplit <= g_wgrad_ws_floats && slice < (1ll << 31);
+    const bool sliced = ws.sliced(nsplit, slice, slice);
     for (int a = 0; a < d->kt; ++a) {   // one launch per kt slice (the patch's t origin differs per slice)
       WgradGeom ga = g;
       ga.nsplit = nsplit;
@@ -883,13 +879,13 @@ extern "C" int p2i_conv_wgrad(const p2i_conv_desc* d, const float* x, const floa
       ga.ntaps = g.tpg;
       ga.tpg = g.tpg;
       ga.dwp = dwp + (size_t)a * g.tpg * d->Cin * g.CoPad;
-      ga.partial = sliced ? g_wgrad_ws : nullptr;
+      ga.partial = sliced ? ws.p : nullptr;
       ga.pstride = slice;
       for (int i = 0; i < g.tpg; ++i) ga.tap_off[i] = g.tap_off[a * g.tpg + i];
       P2I_LAUNCH(plain, dim3(nsplit, ncx, nco), dim3(256), lds, s, ga);
       if (int e = launch_status()) return e;
       if (sliced)
-        if (int e = launch_wgrad_reduce(g_wgrad_ws, nsplit, slice, d->Cout, g.CoPad, ga.dwp, s)) return e;
+        if (int e = launch_wgrad_reduce(ws.p, nsplit, slice, d->Cout, g.CoPad, ga.dwp, s)) return e;
     }
   }
   if (dbias && !bias_fused) return p2i_bias_grad(dy, y_act, act, dbias, d->B, d->Cout, (int64_t)d->To * d->Ho * d->Wo, stream);

@@ -20,6 +20,12 @@ class ConvDesc(C.Structure):
                  "st", "sh", "sw", "pt", "ph", "pw")]
 
 
+class ConvSplit(C.Structure):
+    """p2i_conv_split: what the bf16-split pipe of one forward / data-gradient call may use (pre-split weights, or a scratch to split
+    them into; pre-split source planes)"""
+    _fields_ = [("w_split", C.c_void_p), ("w_scratch", C.c_void_p), ("src_planes", C.c_void_p), ("w_split_taps", C.c_int)]
+
+
 class EvalInput(C.Structure):
     """p2i_eval_input: one evaluation input [T][h][w] of dtype code ``dtype`` and the origin (top, left) of the crop read from it"""
     _fields_ = [("data", C.c_void_p)] + [(n, C.c_int) for n in ("dtype", "h", "w", "top", "left")]
@@ -36,22 +42,18 @@ _F = C.c_float
 _L = C.c_int64
 _F64 = C.c_double
 _D = C.POINTER(ConvDesc)
+_S = C.POINTER(ConvSplit)
 _E = C.POINTER(EvalInput)
 _K = C.POINTER(KrigSystems)
 
 # name -> argtypes (every entry point returns int); must list EVERY symbol of include/p2i_hip.h
 SIGNATURES = {
-    "p2i_conv_fwd": [_D, _P, _P, _P, _P, _P, _I, _P],
-    "p2i_conv_dgrad": [_D, _P, _P, _I, _P, _P, _P, _I, _P, _P],
-    "p2i_conv_wgrad": [_D, _P, _P, _P, _I, _P, _P, _P],
-    "p2i_conv_wgrad_ws": [_D, _P, _P, _P, _I, _P, _P, _P, _L, _P],
-    "p2i_conv_fwd_x6": [_D, _P, _P, _P, _P, _P, _P, _I, _P],
-    "p2i_conv_dgrad_x6": [_D, _P, _P, _P, _P, _P, _I, _P, _P],
+    "p2i_conv_fwd": [_D, _P, _P, _S, _P, _P, _P, _I, _P],
+    "p2i_conv_dgrad": [_D, _P, _P, _I, _P, _S, _P, _P, _I, _P, _P],
+    "p2i_conv_wgrad": [_D, _P, _P, _P, _I, _P, _P, _P, _L, _P],
     "p2i_x6_split": [_P, _P, _I, _I, _I, _P],
     "p2i_x6_split_batched": [_P, _P, _P, _P, _P, _I, _P],
     "p2i_x6c_would_take": [_D, _I, _I],
-    "p2i_conv_fwd_x6s": [_D, _P, _P, _P, _I, _P, _P, _P, _I, _P],
-    "p2i_conv_dgrad_x6s": [_D, _P, _P, _P, _I, _P, _P, _I, _P, _P],
     "p2i_conv_last_plan": [C.POINTER(C.c_int)],
     "p2i_wgrad_last_plan": [C.POINTER(C.c_int)],
     "p2i_fast_div_magic": [_I, C.POINTER(C.c_uint32)],
@@ -61,22 +63,19 @@ SIGNATURES = {
     "p2i_doconv_fold_bwd_batched": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "p2i_weight_pack": [_P, _I, _I, _I, _P, _P, _P, _P],
     "p2i_weight_pack_batched": [_P, _P, _P, _P, _P, _P, _P, _I, _P],
-    "p2i_weight_unpack_grad_batched": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
-    "p2i_weight_unpack_grad_batched_acc": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "p2i_weight_unpack_grad_batched": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "p2i_weight_unpack_grad": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "p2i_spectral_norm": [_P, _I, _I, _P, _P, _I, _P, _P, _P],
     "p2i_spectral_norm_batched": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P],
     "p2i_attn_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "p2i_attn_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "p2i_idw_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "p2i_idw_fwd_ws": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "p2i_idw_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "p2i_idw_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "p2i_pooldup_fwd": [_P, _P, _I, _I, _I, _I, _P],
     "p2i_pooldup_bwd": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "p2i_upmod_fwd": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "p2i_upmod_fwd": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P],
     "p2i_window_gather": [_P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P],
     "p2i_window_mean": [_P, _P, _I, _L, _I, _I, _I, _F, _P],
-    "p2i_upmod_fwd_ba": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P],
     "p2i_upmod_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "p2i_dtail_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "p2i_dtail_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -112,7 +111,6 @@ SIGNATURES = {
     "p2i_act_bwd_bias": [_P, _P, _I, _P, _P, _I, _I, _L, _P],
     "p2i_det_workspace": [_P, _L, _P, _I],
     "p2i_x6_split_planes": [_P, _P, _I, _I, _L, _P],
-    "p2i_x6_next_source_planes": [_P],
     "p2i_event_record": [_I, _P],
     "p2i_event_wait": [_I, _P],
     "p2i_tape_begin": [_P],

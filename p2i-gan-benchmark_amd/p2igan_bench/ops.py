@@ -135,13 +135,15 @@ _X6_SCRATCH = {}
 
 def _x6_scratch(numel: int, device):
     """uint16 scratch for the split weights of ONE conv call, reused by every call on the same stream (the split
-    kernel and its consumer are stream-ordered, so the next call may overwrite it)."""
+    kernel and its consumer are stream-ordered, so the next call may overwrite it).  Its `_split` is the p2i_conv_split that
+    offers it to a call: built with the buffer, so that a conv call constructs no ctypes structure."""
     if CONV_ENGINE not in ("auto", "x6"):
         return None
     key = (device.index, _stream())
     buf = _X6_SCRATCH.get(key)
     if buf is None or buf.numel() < numel:
         buf = torch.empty(max(numel, 1 << 22), device=device, dtype=torch.int16)
+        buf._split = _hip.ConvSplit(None, buf.data_ptr(), None, 0)
         _X6_SCRATCH[key] = buf
     return buf
 
@@ -155,12 +157,19 @@ class X6Stack:
         self.w = wstack
         self.wb = None
         self.n, self.taps, self.k, self.mpad = wstack.shape
+        self.splits = {}                    # layer -> its p2i_conv_split, built at the layer's first call
 
     def layer_ptr(self, i):
         if self.wb is None:                 # first layer that the bf16-split kernel takes: split the whole stack in one launch
             self.wb = torch.empty(3 * self.w.numel(), device=self.w.device, dtype=torch.int16)
             _hip.check(_hip.load().p2i_x6_split(_ptr(self.w), _ptr(self.wb), self.n * self.taps, self.k, self.mpad, _stream()), "p2i_x6_split")
         return self.wb.data_ptr() + 2 * i * self.taps * self.k * self.mpad
+
+    def split(self, i):
+        sp = self.splits.get(i)
+        if sp is None:
+            sp = self.splits[i] = _hip.ConvSplit(self.layer_ptr(i), None, None, self.n * self.taps)
+        return sp
 
     @staticmethod
     def attach(wstack, views):
@@ -176,9 +185,15 @@ class _X6One:
 
     def __init__(self, ptr, taps):
         self.ptr, self.n, self.taps = ptr, 1, taps
+        self.sp = None
 
     def layer_ptr(self, i):
         return self.ptr
+
+    def split(self, i):
+        if self.sp is None:
+            self.sp = _hip.ConvSplit(self.ptr, None, None, self.taps)
+        return self.sp
 
 
 def x6_presplit(tensors, wants, buf=None):
@@ -211,12 +226,25 @@ def x6_presplit(tensors, wants, buf=None):
 
 
 def _x6s_of(wp, d, dgrad, act=ACT_NONE):
-    """(layer pointer, total taps) of a pre-split stack when this call would run on the bf16-split kernel, else None."""
+    """The p2i_conv_split of this layer inside a pre-split stack when the call would run on the bf16-split kernel, else None."""
     h = getattr(wp, "_x6s", None)
     if h is None or CONV_ENGINE not in ("auto", "x6") or not _hip.load().p2i_x6c_would_take(d, 1 if dgrad else 0, act):
         return None
     st, i = h
-    return st.layer_ptr(i), st.n * st.taps
+    return st.split(i)
+
+
+def _conv_split(wp, d, dgrad, act, scratch_ok, device, src_planes):
+    """What the split pipe of one conv call may use: the layer's pre-split image, else (scratch_ok: a channel count the pipe can
+    take at all) the per-stream scratch, else None = fp32-MFMA kernels only.  src_planes (a tensor of p2i_x6_split_planes,
+    experiments only) is the one case that builds a descriptor on the fly."""
+    sp = _x6s_of(wp, d, dgrad, act)
+    if sp is None and scratch_ok:
+        ws = _x6_scratch(3 * wp.numel(), device)
+        sp = ws._split if ws is not None else None
+    if sp is not None and src_planes is not None:
+        sp = _hip.ConvSplit(sp.w_split, sp.w_scratch, src_planes.data_ptr(), sp.w_split_taps)
+    return sp
 
 
 # Weight-gradient partial tiles: stored to a per-stream scratch and summed by a second kernel (deterministic, and faster than
@@ -390,7 +418,7 @@ def _dims5(x: torch.Tensor):
     return b, c, t, h, w
 
 
-def conv_fwd(spec: ConvSpec, x, wp_f, bias=None, residual=None, act=ACT_NONE, out=None):
+def conv_fwd(spec: ConvSpec, x, wp_f, bias=None, residual=None, act=ACT_NONE, out=None, src_planes=None):
     lib = _hip.load()
     b, c, t, h, w = _dims5(x)
     if c != spec.cin or tuple(wp_f.shape) != spec.wp_f_shape():
@@ -405,22 +433,14 @@ def conv_fwd(spec: ConvSpec, x, wp_f, bias=None, residual=None, act=ACT_NONE, ou
     _chk(x, wp_f, bias, residual, y)
     d = spec.desc(b, t, h, w)
     e0 = _prof_begin()
-    pre = _x6s_of(wp_f, d, False, act)
-    ws = _x6_scratch(3 * wp_f.numel(), x.device) if (pre is None and spec.cin % 16 == 0) else None
-    if pre is not None:
-        _hip.check(lib.p2i_conv_fwd_x6s(d, _ptr(x), _ptr(wp_f), pre[0], pre[1], _ptr(bias), _ptr(residual), _ptr(y), act, _stream()),
-                   "p2i_conv_fwd_x6s")
-    elif ws is not None:
-        _hip.check(lib.p2i_conv_fwd_x6(d, _ptr(x), _ptr(wp_f), _ptr(ws), _ptr(bias), _ptr(residual), _ptr(y), act, _stream()),
-                   "p2i_conv_fwd_x6")
-    else:
-        _hip.check(lib.p2i_conv_fwd(d, _ptr(x), _ptr(wp_f), _ptr(bias), _ptr(residual), _ptr(y), act, _stream()), "p2i_conv_fwd")
+    sp = _conv_split(wp_f, d, False, act, spec.cin % 16 == 0, x.device, src_planes)
+    _hip.check(lib.p2i_conv_fwd(d, _ptr(x), _ptr(wp_f), sp, _ptr(bias), _ptr(residual), _ptr(y), act, _stream()), "p2i_conv_fwd")
     _prof_end(e0, "fwd", spec, d, True)
     return y
 
 
-def conv_dgrad(spec: ConvSpec, dy, wp_d, in_shape, y_act=None, act=ACT_NONE, add=None, mask_y=None, mask_act=ACT_NONE):
-    """dx for input of shape in_shape; if y_act is given dy is first multiplied by act'(y_act)."""
+def conv_dgrad(spec: ConvSpec, dy, wp_d, in_shape, y_act=None, act=ACT_NONE, add=None, mask_y=None, mask_act=ACT_NONE, src_planes=None):
+    """dx for input of shape in_shape; if y_act is given dy is first multiplied by act'(y_act) (fp32-MFMA kernels only)."""
     lib = _hip.load()
     if len(in_shape) == 4:
         b, c, h, w = in_shape
@@ -441,17 +461,9 @@ def conv_dgrad(spec: ConvSpec, dy, wp_d, in_shape, y_act=None, act=ACT_NONE, add
     _chk(dy, wp_d, y_act, dx, add, mask_y)
     d = spec.desc(b, t, h, w)
     e0 = _prof_begin()
-    pre = _x6s_of(wp_d, d, True) if y_act is None else None
-    ws = _x6_scratch(3 * wp_d.numel(), dy.device) if (pre is None and y_act is None and spec.cout % 16 == 0 and spec.cin > 1) else None
-    if pre is not None:
-        _hip.check(lib.p2i_conv_dgrad_x6s(d, _ptr(dy), _ptr(wp_d), pre[0], pre[1], _ptr(add), _ptr(mask_y), mask_act, _ptr(dx), _stream()),
-                   "p2i_conv_dgrad_x6s")
-    elif ws is not None:
-        _hip.check(lib.p2i_conv_dgrad_x6(d, _ptr(dy), _ptr(wp_d), _ptr(ws), _ptr(add), _ptr(mask_y), mask_act, _ptr(dx), _stream()),
-                   "p2i_conv_dgrad_x6")
-    else:
-        _hip.check(lib.p2i_conv_dgrad(d, _ptr(dy), _ptr(y_act), act, _ptr(wp_d), _ptr(add), _ptr(mask_y), mask_act, _ptr(dx), _stream()),
-                   "p2i_conv_dgrad")
+    sp = _conv_split(wp_d, d, True, ACT_NONE, spec.cout % 16 == 0 and spec.cin > 1, dy.device, src_planes) if y_act is None else None
+    _hip.check(lib.p2i_conv_dgrad(d, _ptr(dy), _ptr(y_act), act, _ptr(wp_d), sp, _ptr(add), _ptr(mask_y), mask_act, _ptr(dx), _stream()),
+               "p2i_conv_dgrad")
     _prof_end(e0, "dgrad", spec, d, spec.stride == (1, 1, 1))
     return dx
 
@@ -510,11 +522,8 @@ def conv_wgrad(spec: ConvSpec, x, dy, y_act=None, act=ACT_NONE, want_bias=False,
     d = spec.desc(b, t, h, w)
     e0 = _prof_begin()
     ws = _wgrad_scratch(x.device)
-    if ws is not None:
-        _hip.check(lib.p2i_conv_wgrad_ws(d, _ptr(x), _ptr(dy), _ptr(y_act), act, _ptr(dwp), _ptr(db), _ptr(ws), ws.numel(), _stream()),
-                   "p2i_conv_wgrad_ws")
-    else:
-        _hip.check(lib.p2i_conv_wgrad(d, _ptr(x), _ptr(dy), _ptr(y_act), act, _ptr(dwp), _ptr(db), _stream()), "p2i_conv_wgrad")
+    _hip.check(lib.p2i_conv_wgrad(d, _ptr(x), _ptr(dy), _ptr(y_act), act, _ptr(dwp), _ptr(db), _ptr(ws), ws.numel() if ws is not None else 0,
+                                  _stream()), "p2i_conv_wgrad")
     _prof_end(e0, "wgrad", spec, d, True)
     return dwp, db
 
@@ -684,10 +693,10 @@ def weight_unpack_grad_batched(dwps, likes, w_origs=None, sigmas=None, us=None, 
     dots = torch.empty(n, device=dwps[0].device, dtype=torch.float32)
     arr_i = ctypes.c_int * n
     none = [None] * n
-    _hip.check(lib.p2i_weight_unpack_grad_batched_acc(_ptr_array(dwps), arr_i(*Os), arr_i(*Is), arr_i(*NTs), _ptr_array(w_origs or none),
-                                                      _ptr_array(sigmas or none), _ptr_array(us or none), _ptr_array(vs or none),
-                                                      _ptr(dots), _ptr_array(dws), n, int(accumulate), _stream()),
-               "p2i_weight_unpack_grad_batched_acc")
+    _hip.check(lib.p2i_weight_unpack_grad_batched(_ptr_array(dwps), arr_i(*Os), arr_i(*Is), arr_i(*NTs), _ptr_array(w_origs or none),
+                                                  _ptr_array(sigmas or none), _ptr_array(us or none), _ptr_array(vs or none),
+                                                  _ptr(dots), _ptr_array(dws), n, int(accumulate), _stream()),
+               "p2i_weight_unpack_grad_batched")
     return dws
 
 
@@ -851,18 +860,14 @@ def idw_fwd(vals_src, mask, tau=0.05, save=True, _amb_out=None):
     sel_idx = torch.empty(B * Q * 4, device=dev, dtype=torch.int32) if save else None
     sel_w = torch.empty(B * Q * 4, device=dev, dtype=torch.float32) if save else None
     _chk(vals_src, mask)
-    if _os.environ.get("P2I_IDW_FAST", "1") != "0":     # two-pass search (p2i_hip.h); "0": the reference's scan for every voxel (A/B, tests)
+    amb = None                                          # no work buffer: the reference's scan for every voxel (P2I_IDW_FAST=0: A/B, tests)
+    if _os.environ.get("P2I_IDW_FAST", "1") != "0":     # two-pass search (p2i_hip.h)
         amb = torch.empty(B * (2 * Q + 2 + (Q + 255) // 256), device=dev, dtype=torch.int32)
-        _hip.check(lib.p2i_idw_fwd_ws(_ptr(vals_src), _ptr(mask), _ptr(gx), _ptr(gy), _ptr(gz), _ptr(out), _ptr(pt_pos), _ptr(pt_count),
-                                      _ptr(frame_count), _ptr(row_start), _ptr(pt_xyzn), _ptr(sel_idx), _ptr(sel_w), _ptr(amb), B, T, H, W,
-                                      float(tau), _stream()), "p2i_idw_fwd_ws")
-        if _amb_out is not None:                       # tests: the per-sample count of voxels left to the replay pass
+        if _amb_out is not None:                        # tests: the per-sample count of voxels left to the replay pass
             _amb_out.append(amb)
-        _idw_strict(pt_count)
-        return out, (pt_pos, pt_count, sel_idx, sel_w)
     _hip.check(lib.p2i_idw_fwd(_ptr(vals_src), _ptr(mask), _ptr(gx), _ptr(gy), _ptr(gz), _ptr(out), _ptr(pt_pos), _ptr(pt_count),
-                               _ptr(frame_count), _ptr(row_start), _ptr(pt_xyzn), _ptr(sel_idx), _ptr(sel_w), B, T, H, W, float(tau), _stream()),
-               "p2i_idw_fwd")
+                               _ptr(frame_count), _ptr(row_start), _ptr(pt_xyzn), _ptr(sel_idx), _ptr(sel_w), _ptr(amb), B, T, H, W,
+                               float(tau), _stream()), "p2i_idw_fwd")
     _idw_strict(pt_count)
     return out, (pt_pos, pt_count, sel_idx, sel_w)
 
@@ -901,19 +906,16 @@ def pooldup_bwd(x, dy):
 
 def upmod_fwd(x, pos, bias=None, act=ACT_NONE):
     """bilinear x2 (align_corners) * 2 sigmoid(pos); with `bias`: act(that + bias[c]) -- UPPos's tail when the 1x1 projection has
-    already been applied at the low resolution (p2i_upmod_fwd_ba in p2i_hip.h has the algebra)."""
+    already been applied at the low resolution (p2i_upmod_fwd in p2i_hip.h has the algebra)."""
     lib = _hip.load()
     B, Cc, Sh, Sw = x.shape
     if pos.numel() != 4 * Sh * Sw:
         raise RuntimeError(f"upmod_fwd: pos has {pos.numel()} elements, expected {4 * Sh * Sw}")
     u = torch.empty((B, Cc, 2 * Sh, 2 * Sw), device=x.device, dtype=torch.float32)
     _chk(x, pos, bias)
-    if bias is not None:
-        if bias.numel() != Cc:
-            raise RuntimeError("upmod_fwd: bias size mismatch")
-        _hip.check(lib.p2i_upmod_fwd_ba(_ptr(x), _ptr(pos), _ptr(bias), act, _ptr(u), B, Cc, Sh, Sw, _stream()), "p2i_upmod_fwd_ba")
-    else:
-        _hip.check(lib.p2i_upmod_fwd(_ptr(x), _ptr(pos), _ptr(u), B, Cc, Sh, Sw, _stream()), "p2i_upmod_fwd")
+    if bias is not None and bias.numel() != Cc:
+        raise RuntimeError("upmod_fwd: bias size mismatch")
+    _hip.check(lib.p2i_upmod_fwd(_ptr(x), _ptr(pos), _ptr(bias), act, _ptr(u), B, Cc, Sh, Sw, _stream()), "p2i_upmod_fwd")
     return u
 
 

@@ -24,7 +24,7 @@ def test_header_symbols_exported():
     missing = [n for n in names if n not in _hip.SIGNATURES and n not in ("p2i_abi_version", "p2i_last_error")]
     assert not missing, f"no ctypes signature for {missing}"
     lib.p2i_abi_version.restype = ctypes.c_int
-    assert lib.p2i_abi_version() == 3
+    assert lib.p2i_abi_version() == 4
 
 
 def test_product_path_refuses_cpu_tensors():

@@ -137,4 +137,4 @@ def test_lagrangian_twins_are_gone():
         proto = re.search(rf"\bint {name}\s*\(([^;]*)\);", header)
         assert proto and vel in [" ".join(a.split()) for a in proto.group(1).split(",")] and hasattr(lib, name)
         assert len(proto.group(1).split(",")) == len(_hip.SIGNATURES[name])
-    assert len(set(re.findall(r"\b(p2i_[a-z0-9_]+)\s*\(", header))) == 145 and len(_hip.SIGNATURES) == 143
+    assert len(set(re.findall(r"\b(p2i_[a-z0-9_]+)\s*\(", header))) == 136 and len(_hip.SIGNATURES) == 134

@@ -72,7 +72,7 @@ def test_layout_and_parameter_counts():
         proto = re.search(rf"\bint {name}\s*\(([^;]*)\);", header)
         assert proto and proto.group(1).split(",")[0].strip() == "const p2i_krig_systems* sys", name
         assert len(proto.group(1).split(",")) == len(_hip.SIGNATURES[name]) == len(args) + 2, name
-    assert _hip.load().p2i_abi_version() == 3
+    assert _hip.load().p2i_abi_version() == 4
 
 
 @pytest.mark.parametrize("name", CALLS)

@@ -159,7 +159,7 @@ def test_x6c_split_k_matches_f32_engine(ops, monkeypatch):
 
 
 def test_x6c_presplit_stack_matches_per_call_split(ops, monkeypatch):
-    """Weights split ONCE per stack (ops.X6Stack, p2i_x6_split + p2i_conv_*_x6s) give bit-identical results to the per-call split,
+    """Weights split ONCE per stack (ops.X6Stack, p2i_x6_split + p2i_conv_split.w_split) give bit-identical results to the per-call split,
     for every layer of the stack, forward and data gradient."""
     monkeypatch.setenv("P2I_X6C_MIN_WG", "1")
     old = ops.CONV_ENGINE
@@ -368,7 +368,7 @@ def test_idw_matches_oracle_and_golden(ops, kind, golden):
 @pytest.mark.parametrize("kind,shape", [("gauge", (2, 16, 64, 64)), ("gauge", (1, 16, 40, 96)), ("block", (2, 16, 64, 64)), ("pergauge", (2, 8, 48, 48)),
                                         ("gauge", (1, 8, 12, 20)), ("one_empty", (3, 16, 32, 32))])
 def test_idw_two_pass_search_equals_index_order_scan(ops, monkeypatch, kind, shape):
-    """ops.idw_fwd's default (outward search + replay of the tied voxels, p2i_idw_fwd_ws) against the single-kernel replay of the
+    """ops.idw_fwd's default (outward search + replay of the tied voxels, p2i_idw_fwd with its work buffer) against the single-kernel replay of the
     reference's scan (P2I_IDW_FAST=0, the kernel the oracle / golden tests pinned in rounds 1-2): the same four points for every voxel
     -- compared as sets: ties among the four may come out in another order -- and outputs equal to summation order."""
     from p2igan_bench.utils import seeded
@@ -666,7 +666,7 @@ def test_metric_suite_matches_reference_golden(ops, golden):
 
 
 def test_wgrad_slices_are_bit_reproducible_and_match_atomics(ops):
-    """p2i_conv_wgrad_ws: partial tiles stored and summed by wgrad_reduce_kernel -> the same bits on every run (the
+    """p2i_conv_wgrad with a scratch: partial tiles stored and summed by wgrad_reduce_kernel -> the same bits on every run (the
     atomic path only agrees to summation-order noise), for a split-heavy layer (64 channels: 256 slices) and a deep one."""
     for (B, C, S) in [(4, 64, 64), (2, 256, 16)]:
         spec = ops.ConvSpec(C, C, (1, 3, 3), (1, 1, 1), (0, 1, 1))
@@ -851,7 +851,7 @@ def test_wgrad_x6_producer_consumer_variant_matches_symmetric_kernel(ops, monkey
 
 @pytest.mark.parametrize("C,S", [(256, 32), (512, 16)], ids=["L2_256@32", "L3_512@16"])
 def test_presplit_source_planes_are_bit_equal(ops, monkeypatch, C, S):
-    """Round-4 experiment (p2i_x6_split_planes / p2i_x6_next_source_planes): a split-pipe convolution that reads its source as
+    """Round-4 experiment (p2i_x6_split_planes, p2i_conv_split.src_planes): a split-pipe convolution that reads its source as
     pre-split bf16 planes runs the same three planes through the same MFMAs as the in-kernel split: forward and data gradient are
     bit-equal on the 32-channel tiles it applies to (32 x 256 at 256 channels, 32 x 128 at 512)."""
     B = 8
@@ -865,12 +865,139 @@ def test_presplit_source_planes_are_bit_equal(ops, monkeypatch, C, S):
     res = _rand(B, C, S, S, seed=3).cuda()
     y0 = ops.conv_fwd(spec, x, wp_f, residual=res, act=ops.ACT_RELU)
     assert _last_plan(ops)[5] == 7 and _last_plan(ops)[0] == 32, _last_plan(ops)
-    lib.p2i_x6_next_source_planes(planes.data_ptr())
-    y1 = ops.conv_fwd(spec, x, wp_f, residual=res, act=ops.ACT_RELU)
+    y1 = ops.conv_fwd(spec, x, wp_f, residual=res, act=ops.ACT_RELU, src_planes=planes)
     assert torch.equal(y0, y1)
     d0 = ops.conv_dgrad(spec, x, wp_d, tuple(x.shape), add=res, mask_y=res, mask_act=ops.ACT_RELU)
-    lib.p2i_x6_next_source_planes(planes.data_ptr())
-    d1 = ops.conv_dgrad(spec, x, wp_d, tuple(x.shape), add=res, mask_y=res, mask_act=ops.ACT_RELU)
+    d1 = ops.conv_dgrad(spec, x, wp_d, tuple(x.shape), add=res, mask_y=res, mask_act=ops.ACT_RELU, src_planes=planes)
     assert torch.equal(d0, d1)
-    y2 = ops.conv_fwd(spec, x, wp_f, residual=res, act=ops.ACT_RELU)          # the planes were consumed: back to the in-kernel split
+    y2 = ops.conv_fwd(spec, x, wp_f, residual=res, act=ops.ACT_RELU)          # a call without the argument: the in-kernel split
     assert torch.equal(y0, y2)
+
+
+# ---- ABI v4: what the split pipe may use is an argument (p2i_conv_split), the weight gradient's scratch too; through the raw entry points
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _raw_fwd(ops, spec, x, wp, sp, res, act):
+    y = torch.empty_like(res)
+    d = spec.desc(*ops._dims5(x)[:1], *ops._dims5(x)[2:])
+    ops._hip.check(ops._hip.load().p2i_conv_fwd(d, x.data_ptr(), wp.data_ptr(), sp, None, res.data_ptr(), y.data_ptr(), act, _stream()), "p2i_conv_fwd")
+    return y, _last_plan(ops)
+
+
+def _raw_dgrad(ops, spec, dy, wp_d, sp, add, mask_y, mask_act):
+    dx = torch.empty_like(add)
+    d = spec.desc(*ops._dims5(add)[:1], *ops._dims5(add)[2:])
+    ops._hip.check(ops._hip.load().p2i_conv_dgrad(d, dy.data_ptr(), None, ops.ACT_NONE, wp_d.data_ptr(), sp, add.data_ptr(), mask_y.data_ptr(), mask_act,
+                                                  dx.data_ptr(), _stream()), "p2i_conv_dgrad")
+    return dx, _last_plan(ops)
+
+
+NAN_BF16 = 0x7fc0
+
+
+@pytest.fixture(scope="module")
+def split_layer(ops):
+    """One small layer the split pipe takes once the tile threshold is lowered (32 -> 32 channels, 3x3, B = 2, 16 x 16: two 32 x 256
+    tiles), its operands, and its forward (residual, ReLU) and data gradient (add, leaky mask) with a per-call weight-split scratch:
+    computed once for the tests below."""
+    spec = ops.ConvSpec(32, 32, (1, 3, 3), (1, 1, 1), (0, 1, 1))
+    wp_f, wp_d = ops.weight_pack(_rand(32, 32, 9, seed=41, scale=0.05).cuda())
+    x, res, mk = _rand(2, 32, 16, 16, seed=42).cuda(), _rand(2, 32, 16, 16, seed=43).cuda(), _rand(2, 32, 16, 16, seed=44).cuda()
+    scratch = torch.empty(3 * wp_f.numel(), device="cuda", dtype=torch.int16)
+    L = dict(spec=spec, wp_f=wp_f, wp_d=wp_d, x=x, res=res, mk=mk, scratch=scratch, sp=ops._hip.ConvSplit(None, scratch.data_ptr(), None, 0))
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("P2I_X6C_MIN_WG", "1")
+        L["y"], plan_f = _raw_fwd(ops, spec, x, wp_f, L["sp"], res, ops.ACT_RELU)
+        L["dx"], plan_d = _raw_dgrad(ops, spec, x, wp_d, L["sp"], res, mk, ops.ACT_LEAKY)
+    torch.cuda.synchronize()
+    assert plan_f[5] == 7 and plan_d[5] == 7, (plan_f, plan_d)          # the split pipe took both
+    return L
+
+
+def test_conv_split_spellings_agree_bit_for_bit(ops, monkeypatch, split_layer):
+    """The weights' split from a per-call scratch, from a pre-split image, and with both in the descriptor (the image wins and the
+    scratch is left alone) is the same split: forward and data gradient are bit-equal.  No descriptor is the fp32-MFMA engine."""
+    monkeypatch.setenv("P2I_X6C_MIN_WG", "1")
+    L, lib = split_layer, ops._hip.load()
+    spec, x, res, mk = L["spec"], L["x"], L["res"], L["mk"]
+    for wp, ref, run in ((L["wp_f"], L["y"], lambda sp: _raw_fwd(ops, spec, x, L["wp_f"], sp, res, ops.ACT_RELU)),
+                         (L["wp_d"], L["dx"], lambda sp: _raw_dgrad(ops, spec, x, L["wp_d"], sp, res, mk, ops.ACT_LEAKY))):
+        wb = torch.empty(3 * wp.numel(), device="cuda", dtype=torch.int16)
+        ops._hip.check(lib.p2i_x6_split(wp.data_ptr(), wb.data_ptr(), 9, 32, 32, _stream()), "p2i_x6_split")
+        untouched = torch.full((3 * wp.numel(),), NAN_BF16, device="cuda", dtype=torch.int16)
+        for sp in (ops._hip.ConvSplit(wb.data_ptr(), None, None, 9), ops._hip.ConvSplit(wb.data_ptr(), untouched.data_ptr(), None, 9)):
+            out, plan = run(sp)
+            assert plan[5] == 7, plan
+            assert torch.equal(out, ref)
+        assert bool((untouched == NAN_BF16).all())
+        for sp in (None, ops._hip.ConvSplit(None, None, None, 0)):
+            out32, plan = run(sp)
+            assert plan[5] != 7, plan
+            old = ops.CONV_ENGINE
+            try:
+                ops.CONV_ENGINE = "f32"
+                if wp is L["wp_f"]:
+                    want = ops.conv_fwd(spec, x, wp, residual=res, act=ops.ACT_RELU)
+                else:
+                    want = ops.conv_dgrad(spec, x, wp, tuple(x.shape), add=res, mask_y=mk, mask_act=ops.ACT_LEAKY)
+            finally:
+                ops.CONV_ENGINE = old
+            assert torch.equal(out32, want)
+            assert rel_err(ref.cpu().numpy(), out32.cpu().numpy()) < 5e-6      # (the two engines agree to fp32 rounding)
+
+
+def test_conv_call_leaves_nothing_behind(ops, monkeypatch, split_layer):
+    """Source planes given to a call that cannot use them (24 channels: the split pipe declines the layer) are ignored by it and
+    reach no later call: the layer above, run next without planes, gives its own result.  The planes hold bf16 NaNs."""
+    monkeypatch.setenv("P2I_X6C_MIN_WG", "1")
+    L = split_layer
+    spec24 = ops.ConvSpec(24, 24, (1, 3, 3), (1, 1, 1), (0, 1, 1))
+    wp24, _ = ops.weight_pack(_rand(24, 24, 9, seed=45, scale=0.05).cuda())
+    x24, res24 = _rand(2, 24, 8, 8, seed=46).cuda(), _rand(2, 24, 8, 8, seed=47).cuda()
+    planes = torch.full((3 * L["x"].numel(),), NAN_BF16, device="cuda", dtype=torch.int16)       # (large enough for either layer)
+    scratch = L["scratch"].data_ptr()
+    y_plain, _ = _raw_fwd(ops, spec24, x24, wp24, ops._hip.ConvSplit(None, scratch, None, 0), res24, ops.ACT_RELU)
+    y_planes, plan = _raw_fwd(ops, spec24, x24, wp24, ops._hip.ConvSplit(None, scratch, planes.data_ptr(), 0), res24, ops.ACT_RELU)
+    assert plan[5] != 7, plan
+    y, plan = _raw_fwd(ops, L["spec"], L["x"], L["wp_f"], L["sp"], L["res"], ops.ACT_RELU)
+    assert plan[5] == 7, plan
+    assert torch.equal(y_planes, y_plain)
+    assert torch.equal(y, L["y"]) and bool(torch.isfinite(y).all())
+
+
+def test_wgrad_without_or_with_short_scratch_takes_the_atomic_path(ops):
+    """p2i_conv_wgrad with ws = NULL, and with a scratch one float short of two slices (9 * 64 * 64 floats each): float atomics, equal
+    to the sliced sum up to summation order; the sliced sum itself is the same bits on every run."""
+    spec = ops.ConvSpec(64, 64, (1, 3, 3), (1, 1, 1), (0, 1, 1))
+    x, dy = _rand(2, 64, 16, 16, seed=48).cuda(), _rand(2, 64, 16, 16, seed=49).cuda()
+    lib, d = ops._hip.load(), spec.desc(2, 1, 16, 16)
+    ops.det_ready(x.device)
+    ws = torch.empty(16 * 9 * 64 * 64, device="cuda", dtype=torch.float32)     # (8 tiles: at most 8 slices)
+
+    def run(ws_ptr, ws_floats):
+        dwp = torch.zeros(spec.wp_f_shape(), device="cuda")
+        ops._hip.check(lib.p2i_conv_wgrad(d, x.data_ptr(), dy.data_ptr(), None, ops.ACT_NONE, dwp.data_ptr(), None, ws_ptr, ws_floats, _stream()),
+                       "p2i_conv_wgrad")
+        return dwp
+
+    sliced = run(ws.data_ptr(), ws.numel())
+    assert torch.equal(sliced, run(ws.data_ptr(), ws.numel()))
+    for ws_ptr, ws_floats in ((None, 0), (None, ws.numel()), (ws.data_ptr(), 2 * 9 * 64 * 64 - 1)):
+        got = run(ws_ptr, ws_floats)
+        print("wgrad atomic vs sliced rel_err", ws_floats, rel_err(got.cpu().numpy(), sliced.cpu().numpy()))
+        assert rel_err(got.cpu().numpy(), sliced.cpu().numpy()) < 1e-5
+
+
+def test_upmod_without_bias_has_no_epilogue(ops):
+    """p2i_upmod_fwd with bias = NULL at C = 3, S = 5 x 7: upsample and modulation only -- `act` is not read -- as torch computes it."""
+    x, pos = _rand(2, 3, 5, 7, seed=50), _rand(1, 1, 10, 14, seed=51, scale=0.5)
+    u = F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True)
+    u = u + u * (2 * torch.sigmoid(pos) - 1)
+    xg, pg = x.cuda(), pos.cuda()
+    got = torch.empty((2, 3, 10, 14), device="cuda")
+    ops._hip.check(ops._hip.load().p2i_upmod_fwd(xg.data_ptr(), pg.data_ptr(), None, ops.ACT_RELU, got.data_ptr(), 2, 3, 5, 7, _stream()), "p2i_upmod_fwd")
+    assert bool((got < 0).any())
+    assert torch.equal(got, ops.upmod_fwd(xg, pg))
+    assert rel_err(got.cpu().numpy(), u.numpy()) < TOL_OP

@@ -43,10 +43,7 @@ for name, spec, (c, t, h, w) in LAYERS:
     stream = lambda: torch.cuda.current_stream().cuda_stream
     split = lambda: _hip.check(lib.p2i_x6_split_planes(x.data_ptr(), planes.data_ptr(), B, c, P, stream()), "split")
     plain = lambda: ops.conv_fwd(spec, x, wp_f, residual=res, act=ops.ACT_NONE)
-
-    def pre():
-        lib.p2i_x6_next_source_planes(planes.data_ptr())
-        return ops.conv_fwd(spec, x, wp_f, residual=res, act=ops.ACT_NONE)
+    pre = lambda: ops.conv_fwd(spec, x, wp_f, residual=res, act=ops.ACT_NONE, src_planes=planes)
 
     split()
     y0, y1 = plain(), pre()
