@@ -185,6 +185,16 @@ SIGNATURES = {
     "p2i_objects_fill": [_P, _I, _P, _I, _I, _I, _P, _L, _P, _P],
 }
 
+# the ensemble-verification unit's entry points (include/p2i_ens.h, versioned by p2i_ens_abi_version): a table of their own, because
+# the table above mirrors p2i_hip.h name for name; must list EVERY symbol of include/p2i_ens.h
+ENS_SIGNATURES = {
+    "p2i_ens_abi_version": [],
+    "p2i_ens_record": [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "p2i_ens_points": [_E, _I, _L, _E, _L, _I, _I, _I, _P, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, _P, _L, _P],
+    "p2i_ens_energy": [_E, _I, _L, _E, _L, _I, _I, _P, _P, _P],
+    "p2i_ens_variogram": [_E, _I, _L, _E, _L, _I, _I, _P, C.POINTER(C.c_int), _I, _P, _P],
+}
+
 
 def lib_path() -> str:
     return _LIB_PATH
@@ -201,10 +211,11 @@ def load():
             "or `make -C p2i-gan-benchmark_amd/csrc`.  There is no CPU fallback for the product path.")
     # P2I_HIP_LIB: another build of the SAME library (kernel A/B experiments, tools/); never a different backend
     lib = C.CDLL(os.environ.get("P2I_HIP_LIB") or _LIB_PATH)
-    for name, args in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = C.c_int
+    for table in (SIGNATURES, ENS_SIGNATURES):
+        for name, args in table.items():
+            fn = getattr(lib, name)
+            fn.argtypes = args
+            fn.restype = C.c_int
     lib.p2i_abi_version.restype = C.c_int
     lib.p2i_last_error.restype = C.c_char_p
     _lib = lib

@@ -32,6 +32,10 @@ objects (``objects.py``, section 23; no counterpart in the reference): ``run_obj
 frame at the absolute thresholds and at one relative level and returns per method and level SAL (structure, amplitude, location)
 against the truth and the object population of both sides.  ``ObjectEvaluator`` is the streaming form (one host read per launch).
 
+ensemble (``ensemble.py``, section 25; no counterpart in the reference): ``run_ensemble`` scores M-member ensembles (a deterministic
+field is a one-member one) against the truth: CRPS and fair CRPS, rank histograms, spread against skill and exceedance reliability of
+pixels and of box means, and per frame the energy score and the variogram score.  ``EnsembleEvaluator`` is the streaming form.
+
 ``_common.py`` holds what the units share: the input and event-dict rules and ``Streaming``, the base of the exp1, scale, prob and
 objects evaluators (section 10a)."""
 from ._common import crop_mask, crop_origin, ensure_thw_shape, selection, transform_mmhr, truth_lut  # noqa: F401
@@ -48,5 +52,7 @@ from .scale import (DEFAULT_SCALES, ScaleEvaluator, check_overflow, fss_value, r
 from .prob import (DEFAULT_LEVELS, DEFAULT_PIT_BINS, DEFAULT_REL_BINS, DEFAULT_SIGMA_EDGES, ProbEvaluator, half_width,  # noqa: F401
                    pixel_threshold, prob_arrays, prob_lines, prob_scores, roc_area, run_prob, run_prob_points, unpack_record,
                    write_prob_figure, write_prob_outputs)
+from .ensemble import (DEFAULT_BOX_SIZES, DEFAULT_OFFSETS, EnsembleEvaluator, energy_scores, ens_arrays, ens_lines, ens_scores,  # noqa: F401
+                       run_ensemble, variogram_scores, write_ens_figure, write_ens_outputs)
 from .objects import (DEFAULT_SAL_FACTOR, DEFAULT_SAL_FLOOR, ObjectEvaluator, level_keys, objects_lines, run_objects, sal_frames,  # noqa: F401
                       sal_summary, write_objects_figure, write_objects_outputs)

@@ -2497,3 +2497,78 @@ def prob_merge(part, nf, ni, acc):
         raise RuntimeError("prob_merge: bad buffer")
     _eval_bufs("prob_merge", (part, torch.float64, part.numel()), (acc, torch.float64, nf + ni))
     _hip.check(_hip.load().p2i_prob_merge(_ptr(part), part.numel() // (nf + ni), nf, ni, _ptr(acc), _stream()), "p2i_prob_merge")
+
+
+# ---- ensemble verification (csrc/eval_ens.hip, include/p2i_ens.h; p2igan_bench/evaluation/ensemble.py drives these) ----
+ENS_MAX_MEMBERS = 64
+ENS_MAX_OFFSETS = 16
+ENS_WG_PIXELS = 256
+
+
+def ens_abi_version() -> int:
+    return int(_hip.load().p2i_ens_abi_version())
+
+
+def ens_record(M: int, nthr: int, nedges: int):
+    """(nf, ni): the fp64 and int64 word counts of a per-point record for M members (layout: include/p2i_ens.h)."""
+    nf, ni = C.c_int(0), C.c_int(0)
+    _hip.check(_hip.load().p2i_ens_record(M, nthr, nedges, C.byref(nf), C.byref(ni)), "p2i_ens_record")
+    return int(nf.value), int(ni.value)
+
+
+def _ens_inputs(what, members, origins, frame_stride, truth, gtl):
+    """The member descriptors as one ctypes array, M, the stride and the truth's descriptor.  ``members`` are [T, h, w] views whose
+    frames lie ``frame_stride`` elements apart (0: each member's own h * w, which needs contiguous members)."""
+    M, T = len(members), truth.shape[0]
+    if not 1 <= M <= ENS_MAX_MEMBERS or len(origins) != M:
+        raise RuntimeError(f"{what}: 1 to {ENS_MAX_MEMBERS} members, one crop origin each")
+    descs = (_hip.EvalInput * M)()
+    for m, (x, tl) in enumerate(zip(members, origins)):
+        if x.dim() != 3 or x.shape[0] != T or not x.is_cuda or x.dtype not in _EVAL_DTYPES:
+            raise RuntimeError(f"{what}: member {m} is not a device [T, h, w] (uint8 / f32 / f64) of the truth's {T} frames")
+        want = int(frame_stride) if frame_stride else x.shape[1] * x.shape[2]
+        if x.stride(2) != 1 or x.stride(1) != x.shape[2] or (T > 1 and x.stride(0) != want):
+            raise RuntimeError(f"{what}: member {m} has strides {tuple(x.stride())}, frame stride {want} expected")
+        descs[m] = _hip.EvalInput(_ptr(x), _EVAL_DTYPES[x.dtype], x.shape[1], x.shape[2], int(tl[0]), int(tl[1]))
+    return descs, M, int(frame_stride), _eval_input(truth, gtl)
+
+
+def ens_points(members, origins, frame_stride, truth, gtl, rows, cols, box, rank, xq, edges, part):
+    """One piece of T frames at one box size: writes ceil(T * (rows // box) * (cols // box) / ENS_WG_PIXELS) records to part (fp64
+    words; the int64 sections travel as their bits)."""
+    descs, M, fs, gin = _ens_inputs("ens_points", members, origins, frame_stride, truth, gtl)
+    nf, ni = ens_record(M, len(xq), len(edges))
+    nwg = -(-truth.shape[0] * (rows // box) * (cols // box) // ENS_WG_PIXELS)
+    bufs = [(part, torch.float64, nwg * (nf + ni))]
+    if rank is not None:
+        bufs.append((rank, torch.int32, rows * cols))
+    _eval_bufs("ens_points", *bufs)
+    _hip.check(_hip.load().p2i_ens_points(descs, M, fs, gin, truth.shape[0], rows, cols, box, _ptr(rank) if rank is not None else None,
+                                          _f64s(xq), len(xq), _f64s(edges), len(edges), _ptr(part), part.numel(), _stream()),
+               "p2i_ens_points")
+
+
+def ens_energy(members, origins, frame_stride, truth, gtl, rows, cols, rank, out):
+    """out [T, 4] f64: per frame (d, ES, ES_fair, the mean distance to the truth) over the valid pixels."""
+    descs, M, fs, gin = _ens_inputs("ens_energy", members, origins, frame_stride, truth, gtl)
+    bufs = [(out, torch.float64, truth.shape[0] * 4)]
+    if rank is not None:
+        bufs.append((rank, torch.int32, rows * cols))
+    _eval_bufs("ens_energy", *bufs)
+    _hip.check(_hip.load().p2i_ens_energy(descs, M, fs, gin, truth.shape[0], rows, cols, _ptr(rank) if rank is not None else None,
+                                          _ptr(out), _stream()), "p2i_ens_energy")
+
+
+def ens_variogram(members, origins, frame_stride, truth, gtl, rows, cols, rank, offsets, out):
+    """out [T, len(offsets), 2] f64: per frame and offset (dy, dx) the pair (V_o, n_o)."""
+    descs, M, fs, gin = _ens_inputs("ens_variogram", members, origins, frame_stride, truth, gtl)
+    flat = [int(v) for o in offsets for v in o]
+    if len(flat) != 2 * len(offsets):
+        raise RuntimeError("ens_variogram: offsets are (dy, dx) pairs")
+    bufs = [(out, torch.float64, truth.shape[0] * len(offsets) * 2)]
+    if rank is not None:
+        bufs.append((rank, torch.int32, rows * cols))
+    _eval_bufs("ens_variogram", *bufs)
+    _hip.check(_hip.load().p2i_ens_variogram(descs, M, fs, gin, truth.shape[0], rows, cols, _ptr(rank) if rank is not None else None,
+                                             (C.c_int * max(1, len(flat)))(*flat), len(offsets), _ptr(out), _stream()),
+               "p2i_ens_variogram")

@@ -34,6 +34,14 @@ With ``--objects DIRO [--connectivity {4,8}] [--sal-factor F] [--sal-floor Q]`` 
 on the whole crop and writes DIRO/metrics.json, DIRO/metrics.txt (``SAL_<name>_<level>: S=.. A=.. L=..`` and ``OBJ_<name>_<level>:
 pred=.. truth=..`` lines), DIRO/objects_data.npz and DIRO/objects_panels.pdf.  It needs ``--mode radar``; the other outputs do not
 depend on it.
+
+With ``--ens DIRE --ensemble NAME=MEMBERDIR [--ensemble ...] [--box-sizes S ...]`` it also runs the ensemble verification
+(run_ensemble) on the mode's pixels: MEMBERDIR holds the ``member_%03d.zarr`` groups that ``scripts/infer.py --ensemble-output``
+writes, every one with all of the truth's events.  Per ensemble and box size (box means on the 0-255 scale, not areal rain rates):
+CRPS and fair CRPS, the rank histogram, spread against skill and the exceedance reliability; per ensemble the energy and variogram
+scores.  Writes DIRE/metrics.json, DIRE/metrics.txt (``CRPSFAIR_<name>_box<s>: value``, ``ES_<name>``, ``VS_<name>`` ... lines),
+DIRE/ens_data.npz and DIRE/ens_panels.pdf.  ``--ensemble`` without ``--ens`` is an argument error; the other outputs do not depend
+on it.
 """
 from __future__ import annotations
 
@@ -51,6 +59,7 @@ from p2igan_bench.data import zarr_lite  # noqa: E402
 from p2igan_bench.evaluation import (DEFAULT_SCALES, DEFAULT_THRESHOLDS, crop_mask, run_exp1, run_exp2, run_exp2_paper_zarr,  # noqa: E402
                                      run_exp3, run_scale, write_scale_outputs)
 from p2igan_bench.evaluation.objects import (DEFAULT_SAL_FACTOR, DEFAULT_SAL_FLOOR, run_objects, write_objects_outputs)  # noqa: E402
+from p2igan_bench.evaluation.ensemble import DEFAULT_BOX_SIZES, run_ensemble, write_ens_outputs  # noqa: E402
 from p2igan_bench.evaluation.prob import DEFAULT_LEVELS, half_width, pixel_threshold, run_prob, write_prob_outputs  # noqa: E402
 
 
@@ -96,6 +105,13 @@ def parse_args(argv=None):
     p.add_argument("--levels", type=float, nargs="+", default=list(DEFAULT_LEVELS), metavar="L", help="nominal levels of the central "
                    "intervals (at most 8, each in (0, 1))")
     p.add_argument("--no-censor", action="store_true", help="score the plain Gaussian instead of the one left-censored at 0")
+    p.add_argument("--ens", default=None, metavar="DIR", help="also run the ensemble verification (fair CRPS, rank histograms, "
+                   "spread-skill and exceedance reliability of pixels and box means, energy and variogram scores) of every --ensemble into DIR")
+    p.add_argument("--ensemble", type=_method, action="append", default=[], metavar="NAME=MEMBERDIR",
+                   help="the directory of ensemble NAME's member_%%03d.zarr files, as infer.py --ensemble-output writes them "
+                        "(repeatable; needs --ens)")
+    p.add_argument("--box-sizes", type=int, nargs="+", default=list(DEFAULT_BOX_SIZES), metavar="S",
+                   help="box sizes in pixels of the ensemble scores' points (1: pixels; means on the 0-255 scale)")
     p.add_argument("--objects", default=None, metavar="DIR", help="also run the object-based verification (connected rain objects, "
                    "their population, SAL) and write its outputs into DIR")
     p.add_argument("--connectivity", type=int, choices=(4, 8), default=8, help="pixel connectivity of the objects")
@@ -112,6 +128,22 @@ def parse_args(argv=None):
         p.error("--sal-factor lies in (0, 1] and --sal-floor is >= 0")
     if args.variance and not args.prob:
         p.error("--variance needs --prob")
+    if args.ensemble and not args.ens:
+        p.error("--ensemble needs --ens")
+    if args.ens:
+        if not args.ensemble:
+            p.error("--ens needs at least one --ensemble")
+        if len({n for n, _ in args.ensemble}) != len(args.ensemble):
+            p.error("--ensemble names repeat")
+        if not 0 < len(args.thresholds) <= 8:
+            p.error("--thresholds takes 1 to 8 thresholds")
+        if len(set(args.box_sizes)) != len(args.box_sizes) or any(not 1 <= s <= args.crop_size for s in args.box_sizes):
+            p.error("--box-sizes takes distinct sizes in 1 .. the crop size")
+        try:
+            for q in args.thresholds:
+                pixel_threshold(q, True)
+        except ValueError as e:
+            p.error(str(e))
     if args.prob:
         unknown = [n for n, _ in args.variance if n not in [m for m, _ in args.method]]
         if unknown:
@@ -156,6 +188,23 @@ def check_events(truth_keys: List[str], method: str, keys) -> None:
     missing = [k for k in truth_keys if k not in keys]
     if missing:
         raise ValueError(f"method {method!r} lacks truth event {missing[0]!r}" + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+
+
+def load_members(path: str, truth_keys: List[str]) -> Dict[str, List[np.ndarray]]:
+    """{event: [member 0's array, member 1's, ...]} of the member_%03d.zarr groups under ``path`` (infer.py --ensemble-output)."""
+    names = sorted(n for n in os.listdir(path) if n.startswith("member_") and n.endswith(".zarr"))
+    if not names or names != [f"member_{k:03d}.zarr" for k in range(len(names))]:
+        raise SystemExit(f"{path}: expected member_000.zarr .. member_<M-1>.zarr, found {names[:4]}")
+    events = {k: [] for k in truth_keys}
+    for n in names:
+        g = zarr_lite.Group(os.path.join(path, n), "r")
+        try:
+            check_events(truth_keys, n, set(g.array_keys()))
+        except ValueError as e:
+            raise SystemExit(f"{os.path.join(path, n)}: {e}")
+        for k in truth_keys:
+            events[k].append(np.asarray(g[k][:]))
+    return events
 
 
 def check_output_scale(name: str, pred_attrs, var_attrs) -> None:
@@ -250,6 +299,11 @@ def main(argv=None):
                       levels=tuple(args.levels), censor=not args.no_censor, divide_by_3=True, device=args.device)
         write_prob_outputs(args.prob, mp)
         print(f"wrote {os.path.join(args.prob, 'metrics.json')} and the probability figure")
+    if args.ens:
+        me = run_ensemble({name: load_members(path, list(truth)) for name, path in args.ensemble}, truth, mask, args.mode, args.crop_size,
+                          box_sizes=tuple(args.box_sizes), thresholds=tuple(args.thresholds), divide_by_3=True, device=args.device)
+        write_ens_outputs(args.ens, me)
+        print(f"wrote {os.path.join(args.ens, 'metrics.json')} and the ensemble figure")
     if args.exp2:
         run_exp2(paths, args.truth, args.observation, mask, args.exp2, args.crop_size, None, 0.0, 0.0, args.gif_fps, divide_by_3=True,
                  mode=args.mode, device=args.device, zoom=args.exp2_zoom)
