@@ -1,4 +1,4 @@
-// What the kriging files (classical.hip, krig_uq.hip, krig_cs.hip, stkrig.hip, stkrig_loso.hip, lagkrig.hip, lkrig.hip) share: the tile
+// What the kriging files (classical.hip, krig_uq.hip, krig_cs.hip, stkrig_cs.hip, stkrig.hip, stkrig_loso.hip, lagkrig.hip, lkrig.hip) share: the tile
 // and size limits, the covariance function and the space-time distances, the fixed-tree fp64 block sum, the "no model" rule, the
 // variogram's bin image and fit candidate, the covariance tile writer and the host-side checks.  krig_mfma.h adds the c0 slab core.
 #pragma once

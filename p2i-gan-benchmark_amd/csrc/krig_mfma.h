@@ -1,8 +1,8 @@
 // The c0 slab core of the kernels that multiply a matrix with k(p) = [c0(p, i)]_i on v_mfma_f32_32x32x2_f32 (krig_uq.hip's variance
-// map, krig_cs.hip's members predictor): D = A c0 with A = a 32 x 32 operand tile (m = row), B = c0 (n = pixel), K = gauge.  A
-// workgroup of 256 threads owns PT pixels, wave w the pixels 32 w .. 32 w + 31.  Per 32-gauge slab all threads evaluate c0 [32][PT]
-// into LDS (k(p) never touches HBM) next to the staged operand tiles, and the waves feed both to the MFMAs.  The kernels keep their
-// own loops over slabs and tiles; the layout, the fill, the stage and the product are here once.
+// map, krig_cs.hip's and stkrig_cs.hip's members predictors): D = A c0 with A = a 32 x 32 operand tile (m = row), B = c0 (n = pixel),
+// K = gauge.  A workgroup of 256 threads owns PT pixels, wave w the pixels 32 w .. 32 w + 31.  Per 32-gauge slab all threads evaluate
+// c0 [32][PT] into LDS (k(p) never touches HBM) next to the staged operand tiles, and the waves feed both to the MFMAs.  The kernels
+// keep their own loops over slabs and tiles; the layout, the fill, the stage and the product are here once.
 #pragma once
 #include "krig_common.h"
 
@@ -35,6 +35,28 @@ __device__ __forceinline__ void slab_fill(float (*slab)[SLAB_LD], const int* __r
       const int d2 = dy * dy + dx * dx;
       c0 = cov_f(sqrtf((float)d2), psill, a, model) + (d2 == 0 ? nug : 0.f);
       visit(i, c0, d2 == 0);
+    }
+    slab[g][bp] = c0;
+  }
+}
+
+// ---- the space-time slab: the workgroup's pixels in frame t against the points 32 sb .. 32 sb + 31 of a sample's point set (gp the
+// pixels, gt the frames), c0 = cov_f(st_dist(d2, dt, k2)) + nugget [(d2 | dt) = 0], the space-time predictor's expression.
+// visit(i, c0, at) as above, at: the point is the pixel in this frame.
+template <class Visit>
+__device__ __forceinline__ void slab_fill(float (*slab)[SLAB_LD], const int* __restrict__ gp, const int* __restrict__ gt, int n, int sb,
+                                          int py, int px, int t, float nug, float psill, float a, float k2, int model, Visit visit) {
+  const int bp = threadIdx.x & (PT - 1), bg = threadIdx.x >> 7;
+#pragma unroll 1
+  for (int j = 0; j < TS / 2; ++j) {
+    const int g = bg * (TS / 2) + j, i = sb * TS + g;
+    float c0 = 0.f;
+    if (i < n) {
+      const int gq = gp[i];
+      const int dy = py - (gq >> 16), dx = px - (gq & 0xffff), dt = t - gt[i];
+      const int d2 = dy * dy + dx * dx;
+      c0 = cov_f(st_dist(d2, dt, k2), psill, a, model) + ((d2 | dt) == 0 ? nug : 0.f);
+      visit(i, c0, (d2 | dt) == 0);
     }
     slab[g][bp] = c0;
   }

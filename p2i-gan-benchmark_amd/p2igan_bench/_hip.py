@@ -195,6 +195,17 @@ ENS_SIGNATURES = {
     "p2i_ens_variogram": [_E, _I, _L, _E, _L, _I, _I, _P, C.POINTER(C.c_int), _I, _P, _P],
 }
 
+# the space-time conditional simulation's entry points (include/p2i_stcs.h, versioned by p2i_stcs_abi_version), a table of their own
+# for the same reason; must list EVERY symbol of include/p2i_stcs.h
+STCS_SIGNATURES = {
+    "p2i_stcs_abi_version": [],
+    "p2i_stcs_spectrum": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "p2i_stcs_noise": [C.c_uint64, _L, _I, _I, _I, _I, _I, _P, _P],
+    "p2i_stcs_fields": [_P, _P, _P, _P, _P, C.c_uint64, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "p2i_stcs_weights": [_K, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "p2i_stcs_predict": [_K, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+}
+
 
 def lib_path() -> str:
     return _LIB_PATH
@@ -211,7 +222,7 @@ def load():
             "or `make -C p2i-gan-benchmark_amd/csrc`.  There is no CPU fallback for the product path.")
     # P2I_HIP_LIB: another build of the SAME library (kernel A/B experiments, tools/); never a different backend
     lib = C.CDLL(os.environ.get("P2I_HIP_LIB") or _LIB_PATH)
-    for table in (SIGNATURES, ENS_SIGNATURES):
+    for table in (SIGNATURES, ENS_SIGNATURES, STCS_SIGNATURES):
         for name, args in table.items():
             fn = getattr(lib, name)
             fn.argtypes = args

@@ -66,16 +66,27 @@ def infer_event_variance(generator, masked: torch.Tensor, masks: torch.Tensor, s
 def infer_event_ensemble(generator, masked: torch.Tensor, masks: torch.Tensor, members: int, seed: int = 0, event_index: int = 0,
                          stride: int = 16, output_scale: float = 255.0) -> torch.Tensor:
     """The conditional-simulation members of infer_event_chunks' predictions, chunk by chunk (the same chunks, so the same fits):
-    (L, members, H, W) float32 = member x output_scale, unclipped (NaN over a frame without a model).  The stream id of frame l of the
-    event is (event_index << 32) | l, so the chunk length changes the fit but not the noise.  generator.last_ensemble["clip"] holds the
-    clip shares of all the event's chunks afterwards."""
+    (L, members, H, W) float32 = member x output_scale, unclipped (NaN where there is no model).  generator.last_ensemble["clip"] holds
+    the clip shares of all the event's chunks afterwards.
+    'kriging' (forward_ensemble): the noise is per frame; the stream id of frame l of the event is (event_index << 32) | l, so the chunk
+    length changes the fit but not the noise.
+    'stkriging' (forward_simulation): the noise is one space-time field per chunk; the stream id of a chunk is (event_index << 32) | its
+    first frame.  Members are coherent within a chunk and independent across chunk borders."""
     L = masked.shape[1]
+    per_frame = hasattr(generator, "forward_ensemble")
+    if not per_frame and not hasattr(generator, "forward_simulation"):
+        raise RuntimeError(f"{type(generator).__name__} has no conditional simulation: 'kriging' (forward_ensemble) and 'stkriging' "
+                           f"(forward_simulation) have")
     parts, clips = [], []
     for s in range(0, L, stride):
         n = min(stride, L - s)
-        streams = (int(event_index) << 32) + torch.arange(s, s + n, dtype=torch.int64).view(1, n)
-        parts.append(generator.forward_ensemble(masked[:, s:s + stride].contiguous(), masks[:, s:s + stride].contiguous(), members,
-                                                seed=seed, streams=streams)[1][0])
+        x, m = masked[:, s:s + stride].contiguous(), masks[:, s:s + stride].contiguous()
+        if per_frame:
+            streams = (int(event_index) << 32) + torch.arange(s, s + n, dtype=torch.int64).view(1, n)
+            parts.append(generator.forward_ensemble(x, m, members, seed=seed, streams=streams)[1][0])
+        else:
+            streams = torch.tensor([(int(event_index) << 32) + s], dtype=torch.int64)
+            parts.append(generator.forward_simulation(x, m, members, seed=seed, streams=streams)[1][0])
         clips.append(generator.last_ensemble["clip"])
     generator.last_ensemble = dict(generator.last_ensemble, clip=torch.cat(clips))
     return torch.cat(parts, dim=0) * float(output_scale)

@@ -17,6 +17,10 @@ from all gauges of all frames of that sample, one system per sample, with a metr
 leave-one-site-out (csrc/stkrig_loso.hip): cross_validate_sites of all models predicts every point of a
 site (a gauge pixel in all the sample's frames) with the whole site left out.
 
+Space-time conditional simulation (csrc/stkrig_cs.hip): SpaceTimeKrigingGenerator.forward_simulation adds
+ensemble members that are one Gaussian field over the whole sample: they equal the gauge values in every frame and their noise is
+correlated from frame to frame as the space-time covariance says.
+
 Lagrangian space-time kriging (csrc/lagkrig.hip for the velocity, csrc/stkrig.hip's kernels with it):
 LagrangianKrigingGenerator measures the space-time distance in the frame that moves with the rain, with an advection velocity per
 sample that it estimates from the gauges.
@@ -354,12 +358,27 @@ def _advection_config(self, mc):
             raise ValueError(f"model.advection: vy and vx must be finite (got {self.fixed_v})")
 
 
+def _simulation_config(mc):
+    """(embed, embed_time) of model.ensemble for the space-time conditional simulation, each an integer in 2..4, default 2."""
+    ens = mc.get("ensemble")
+    if ens is not None and not isinstance(ens, dict):
+        raise ValueError(f"model.ensemble must be a mapping such as {{\"embed\": 2, \"embed_time\": 2}} (got {ens!r})")
+    out = []
+    for key in ("embed", "embed_time"):
+        v = (ens or {}).get(key, 2)
+        if isinstance(v, bool) or not isinstance(v, int) or v not in ops.KRIG_CS_EMBEDS:
+            raise ValueError(f"model.ensemble.{key} must be an integer in {list(ops.KRIG_CS_EMBEDS)} (got {v!r})")
+        out.append(v)
+    return tuple(out)
+
+
 class SpaceTimeKrigingGenerator(_ClassicalBase):
     """Ordinary kriging of every pixel of every frame of a sample from ALL gauges of ALL frames of that sample: one system per sample,
     global in space and time, with the distance sqrt(dy^2 + dx^2 + kappa^2 dt^2) (kappa in pixels per frame) inside the covariance.
     model.variogram = {"model", "fit": true, "n_lags": 16, "n_tlags": 3} fits (nugget, psill, range, kappa) per sample on the device;
     {"model", "fit": false, "nugget", "psill", "range", "time_scale"} takes them as given (time_scale is kappa).  model.max_points
-    (default 4096) bounds the points of one sample.
+    (default 4096) bounds the points of one sample.  model.ensemble = {"embed": 2, "embed_time": 2} (each 2 to 4) sets the sides of
+    forward_simulation's embedding torus in frame sides and in sample lengths.
 
     There is no forward_uq and no cross_validate: leaving out one (site, frame) observation while the same site's neighbouring
     frames stay in would flatter the method; the honest score is leave-one-site-out, cross_validate_sites."""
@@ -372,6 +391,8 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
         self.last_fit = None         # {"bins", "fit", "cand", "q", "c"} device tensors of the last call (fit=true)
         self.last_status = None      # per-sample int32 of the last call: 1 where the factorisation met a non-positive pivot
         self._velf = None            # (B, 2) fp32 of the last call's velocities where _variogram fits them (LagrangianKrigingGenerator)
+        self.embed, self.embed_time = _simulation_config(config.get("model", {}))     # forward_simulation's torus, in sample sides
+        self.last_ensemble = None    # {"clip": (B,) fp64 clip share of each sample's spectrum, "embed", "embed_time"} of the last one
 
     def cross_validate(self, masked_frames, masks):
         raise RuntimeError(ST_NO_LOO)
@@ -399,17 +420,64 @@ class SpaceTimeKrigingGenerator(_ClassicalBase):
 
     @torch.no_grad()
     def forward(self, masked_frames, masks):
+        return self._krige(masked_frames, masks)["pred"]
+
+    @torch.no_grad()
+    def forward_simulation(self, masked_frames, masks, members, seed=0, streams=None):
+        """(prediction (B, T, 1, H, W), ensemble (B, T, members, H, W)) by conditional simulation in space and time (DESIGN.md section
+        26).  The prediction is forward()'s.  A member is one Gaussian field over the whole sample with the space-time covariance of the
+        model, conditioned on all the sample's points: it equals the gauge values at the gauge pixels of every frame and its noise is
+        correlated from frame to frame, so the spread of a member's accumulation over the sample is the model's.  Member m of a sample
+        is a function of (seed, the sample's stream id, m, the variogram, the points) only; streams (B,) int64 defaults to b.  Members
+        are raw Gaussian (they can be negative) and NaN over a sample without points, with a degenerate fit or with a failed
+        factorisation; a frame without gauges inside a sample that has points is simulated like any other.  1 <= members <= 64."""
+        if isinstance(members, bool) or not isinstance(members, int) or not 1 <= members <= ops.KRIG_CS_MAX_MEMBERS:
+            raise ValueError(f"forward_simulation: members must be an integer in [1, {ops.KRIG_CS_MAX_MEMBERS}] (got {members!r})")
+        if masked_frames.dim() != 5:
+            raise RuntimeError(f"{type(self).__name__}.forward_simulation takes (B, T, 1, H, W) frames")
+        b, t, _, h, w = masked_frames.shape
+        ops.stcs_torus(t, h, w, self.embed, self.embed_time)     # ValueError before any launch
+        if not (masked_frames.is_cuda and masks.is_cuda):
+            raise RuntimeError(f"{type(self).__name__}.forward_simulation runs on the HIP path only (CUDA tensors)")
+        if streams is None:
+            streams = torch.arange(b, dtype=torch.int64)
+        else:
+            streams = torch.as_tensor(streams)
+            if streams.dtype != torch.int64 or tuple(streams.shape) != (b,):
+                raise ValueError(f"forward_simulation: streams must be an int64 ({b},) tensor")
+        streams = streams.contiguous().to(masked_frames.device)
+        out = self._krige(masked_frames, masks, simulation=(members, int(seed), streams))
+        return out["pred"], out["ens"]
+
+    def _krige(self, masked_frames, masks, simulation=None):
         b, t, _, h, w = masked_frames.shape
         pix, z, info, np_ = self._points(masked_frames, masks)
         stpix, stt, stz, stinfo = ops.stkrig_gather(pix, z, info, b, t, np_)
         cand, params = self._variogram(pix, z, info, b, t, h, w)
-        sy = _Systems(stpix, stz, stinfo, params, cand, self.variogram_model, 1, 1, np_)     # the samples stand in for frames
+        limit = None
+        if simulation is not None:           # the members' dual coefficients of one chunk of samples stay under the factors' bound
+            members, seed, streams = simulation
+            limit = _FACTOR_BYTES // (members * np_ * 4)
+            amp, clip = ops.stcs_spectrum(params, cand, self.variogram_model, t, h, w, self.embed, self.embed_time)
+            self.last_ensemble = {"clip": clip, "embed": self.embed, "embed_time": self.embed_time}
+            ens = torch.empty(b, t, members, h * w, device=masked_frames.device, dtype=torch.float32)
+            ops.stcs_fields(amp, streams, seed, members, t, h, w, self.embed, self.embed_time, ens)
+            del amp
+        # the samples stand in for frames
+        sy = _Systems(stpix, stz, stinfo, params, cand, self.variogram_model, 1, 1, np_, simulation is not None, limit)
         for ch in sy.chunks():
             ops.stkrig_factor(ch, stt, sy.work, self._velf)
-            ops.krig_solve(ch, sy.work, sy.alpha, sy.mean)
-        out = ops.stkrig_predict(stpix, stt, sy.alpha, sy.mean, stinfo, params, self.variogram_model, t, h, w, self._velf)
+            sol = ops.krig_solve(ch, sy.work, sy.alpha, sy.mean)
+            if simulation is not None:
+                ops.krig_invert(sy.work, ch.ns, np_, sy.winv)
+                ca, cm = ops.stcs_weights(ch, stt, sy.winv, sol, ens, members, t, h, w)
+                ops.stcs_predict(ch, stt, ca, cm, members, t, h, w, ens)
+        pred = ops.stkrig_predict(stpix, stt, sy.alpha, sy.mean, stinfo, params, self.variogram_model, t, h, w, self._velf)
         sy.finish(self, "space-time kriging: %d sample(s) met a non-positive pivot and predict their gauge mean")
-        return out.view(b, t, 1, h, w)
+        out = {"pred": pred.view(b, t, 1, h, w)}
+        if simulation is not None:
+            out["ens"] = ens.view(b, t, members, h, w)
+        return out
 
     @torch.no_grad()
     def cross_validate_sites(self, masked_frames, masks) -> LOOResult:
@@ -451,6 +519,9 @@ class LagrangianKrigingGenerator(SpaceTimeKrigingGenerator):
 
     def cross_validate(self, masked_frames, masks):
         raise RuntimeError(LAG_NO_LOO)
+
+    def forward_simulation(self, masked_frames, masks, members, seed=0, streams=None):
+        raise RuntimeError(LAG_NO_SIMULATION)
 
     def _variogram(self, pix, z, info, b, t, h, w):
         """(cand or None, params): the velocity first (kept in _velf for the factor and the predictor), then the variogram on the
@@ -574,6 +645,10 @@ ST_NO_LOO = ("space-time kriging ('stkriging') has no leave-one-out cross-valida
               "cross_validate_sites, evaluation.run_loso, scripts/crossvalidate.py --by-site")
 
 LAG_NO_LOO = ST_NO_LOO.replace("space-time kriging ('stkriging')", "Lagrangian space-time kriging ('lagkriging')")
+
+LAG_NO_SIMULATION = ("Lagrangian space-time kriging ('lagkriging') has no conditional simulation: its covariance is stationary in the frame "
+                     "that moves with the rain, which on the pixel grid is a sheared torus that the circulant embedding of 'stkriging' "
+                     "(forward_simulation) does not draw")
 
 LOCAL_NO_LOO = ST_NO_LOO.replace("space-time kriging ('stkriging')", "moving-neighbourhood space-time kriging ('localkriging')")
 

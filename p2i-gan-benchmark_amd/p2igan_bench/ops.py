@@ -2000,20 +2000,22 @@ def _krig_cs_members(who, M):
         raise ValueError(f"{who}: members must be an integer in [1, {KRIG_CS_MAX_MEMBERS}] (got {M!r})")
 
 
+def _cs_twiddles(S, n, device):
+    """(2, S, n) fp32 = cos, sin of 2 pi (a b mod S) / S, a < S, b < n, rounded from fp64 of the reduced argument."""
+    ang = (torch.arange(S, dtype=torch.int64)[:, None] * torch.arange(n, dtype=torch.int64)[None, :]) % S
+    ang = ang.double() * (2.0 * math.pi / S)
+    return torch.stack([torch.cos(ang), torch.sin(ang)]).float().contiguous().to(device)
+
+
 def krig_cs_tables(H, W, embed, device):
     """The host-built fp64 twiddles of one (H, W, embed), on `device` (kept): tw (Sy + Sx,) fp64 = cos(2 pi m / Sy), cos(2 pi m / Sx)
     for the spectrum; tx (2, Sx, W) and ty (2, Sy, H) fp32 = cos, sin of 2 pi k w / Sx and 2 pi j h / Sy for the fields."""
     key = (H, W, embed, str(device))
     if key not in _KRIG_CS_TABLES:
         Sy, Sx = krig_cs_torus(H, W, embed)
-
-        def pair(S, n):
-            ang = (torch.arange(S, dtype=torch.int64)[:, None] * torch.arange(n, dtype=torch.int64)[None, :]) % S
-            ang = ang.double() * (2.0 * math.pi / S)
-            return torch.stack([torch.cos(ang), torch.sin(ang)]).float().contiguous().to(device)
-
         tw = torch.cat([torch.cos(torch.arange(S, dtype=torch.float64) * (2.0 * math.pi / S)) for S in (Sy, Sx)])
-        _KRIG_CS_TABLES[key] = {"Sy": Sy, "Sx": Sx, "tw": tw.contiguous().to(device), "tx": pair(Sx, W), "ty": pair(Sy, H)}
+        _KRIG_CS_TABLES[key] = {"Sy": Sy, "Sx": Sx, "tw": tw.contiguous().to(device), "tx": _cs_twiddles(Sx, W, device),
+                                "ty": _cs_twiddles(Sy, H, device)}
     return _KRIG_CS_TABLES[key]
 
 
@@ -2093,6 +2095,140 @@ def krig_cs_predict(sys, alpha, mu, M, H, W, ens):
     _krig_t("krig_cs_predict", alpha, torch.float32, (ns, of.R * M, of.cap))
     _krig_t("krig_cs_predict", mu, torch.float32, (ns, of.R * M))
     sys.call("p2i_krig_cs_predict", _ptr(alpha), _ptr(mu), M, H, W, _ptr(ens))
+
+
+# ---- conditional simulation of space-time kriging (csrc/stkrig_cs.hip, include/p2i_stcs.h)
+STCS_MAX_ST = 128            # temporal side of the embedding torus
+_STCS_WORK_BYTES = 1 << 28   # the spectrum's fp64 workspace and each of the fields' workspaces of one call stay under this, except that a
+                             # chunk is never less than one sample: 16 St Sy Sx bytes, above the bound past 16 Mi cells (512 MiB at most)
+_STCS_TABLES = {}
+STCS_STAGES_ALL = 7          # the three transforms of p2i_stcs_fields: along k, along j, along l
+
+
+def stcs_abi_version() -> int:
+    return int(_hip.load().p2i_stcs_abi_version())
+
+
+def stcs_torus(T, H, W, embed, embed_time):
+    """(St, Sy, Sx) = (embed_time T, embed H, embed W) of the space-time embedding torus; ValueError for an embed outside 2..4, a
+    spatial side past 512 or more than 128 temporal cells."""
+    if isinstance(embed_time, bool) or not isinstance(embed_time, int) or embed_time not in KRIG_CS_EMBEDS:
+        raise ValueError(f"model.ensemble.embed_time must be an integer in {list(KRIG_CS_EMBEDS)} (got {embed_time!r})")
+    Sy, Sx = krig_cs_torus(H, W, embed)
+    St = embed_time * T
+    if St > STCS_MAX_ST:
+        raise ValueError(f"conditional simulation: the embedding torus has {St} temporal cells (embed_time {embed_time} of {T} frames), "
+                         f"more than {STCS_MAX_ST}: use shorter chunks (scripts/infer.py --stride)")
+    return St, Sy, Sx
+
+
+def stcs_tables(T, H, W, embed, embed_time, device):
+    """The host-built fp64 twiddles of one (T, H, W, embed, embed_time), on `device` (kept): tw (St + Sy + Sx,) fp64 = cos(2 pi m / S) of
+    the three sides for the spectrum; tx (2, Sx, W), ty (2, Sy, H) and tt (2, St, T) fp32 = cos, sin of 2 pi (a b mod S) / S."""
+    key = (T, H, W, embed, embed_time, str(device))
+    if key not in _STCS_TABLES:
+        St, Sy, Sx = stcs_torus(T, H, W, embed, embed_time)
+        tw = torch.cat([torch.cos(torch.arange(S, dtype=torch.float64) * (2.0 * math.pi / S)) for S in (St, Sy, Sx)])
+        _STCS_TABLES[key] = {"St": St, "Sy": Sy, "Sx": Sx, "tw": tw.contiguous().to(device), "tx": _cs_twiddles(Sx, W, device),
+                             "ty": _cs_twiddles(Sy, H, device), "tt": _cs_twiddles(St, T, device)}
+    return _STCS_TABLES[key]
+
+
+def stcs_spectrum(params, cand, model, T, H, W, embed, embed_time):
+    """amp (B, St, Sy, Sx) fp32, the amplitude of the circulant embedding of every sample's space-time covariance (params (B, 4) =
+    nugget, psill, range, kappa), and clip (B,) fp64, the share of the spectrum that was negative and clipped (0 where the embedding
+    is exact; NaN for a degenerate sample).  The samples go through the fp64 workspace a chunk at a time (at least one sample: 16 bytes
+    per torus cell); amp is held whole, 4 bytes per cell and sample, because the fields of every sample read it."""
+    lib = _hip.load()
+    _krig_t("stcs_spectrum", params, torch.float32)
+    B = params.shape[0]
+    if tuple(params.shape) != (B, 4):
+        raise RuntimeError("stcs_spectrum: params (B, 4) expected")
+    if cand is not None:
+        _krig_t("stcs_spectrum", cand, torch.int32, (B,))
+    tab = stcs_tables(T, H, W, embed, embed_time, params.device)
+    St, Sy, Sx = tab["St"], tab["Sy"], tab["Sx"]
+    cells = St * Sy * Sx
+    per = max(1, min(B, _STCS_WORK_BYTES // (2 * cells * 8), 65535 // St))
+    work = torch.empty(2, per, cells, device=params.device, dtype=torch.float64)
+    amp = torch.empty(B, St, Sy, Sx, device=params.device, dtype=torch.float32)
+    clip = torch.empty(B, device=params.device, dtype=torch.float64)
+    for b0 in range(0, B, per):
+        nb = min(per, B - b0)
+        _hip.check(lib.p2i_stcs_spectrum(_ptr(params[b0:]), _ptr(cand[b0:]) if cand is not None else None, int(model), nb, St, Sy, Sx,
+                                         _ptr(tab["tw"]), _ptr(work), _ptr(amp[b0:]), _ptr(clip[b0:]), _stream()), "p2i_stcs_spectrum")
+    return amp, clip
+
+
+def stcs_noise(seed, stream_id, q0, npairs, St, Sy, Sx, device):
+    """xi (npairs, St, Sy, Sx, 2) fp32: the complex standard normal of the member pairs q0 .. q0 + npairs - 1 of sample id stream_id."""
+    lib = _hip.load()
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("stcs_noise runs on the HIP path only (a CUDA device)")
+    if not (1 <= St <= STCS_MAX_ST and 1 <= Sy <= KRIG_CS_MAX_SIDE and 1 <= Sx <= KRIG_CS_MAX_SIDE) or q0 < 0 or npairs < 1:
+        raise ValueError(f"stcs_noise: bad torus {St} x {Sy} x {Sx} or pairs {q0} + {npairs}")
+    xi = torch.empty(npairs, St, Sy, Sx, 2, device=device, dtype=torch.float32)
+    _hip.check(lib.p2i_stcs_noise(int(seed) & (2 ** 64 - 1), int(stream_id), int(q0), int(npairs), St, Sy, Sx, _ptr(xi), _stream()),
+               "p2i_stcs_noise")
+    return xi
+
+
+def stcs_fields(amp, streams, seed, M, T, H, W, embed, embed_time, ens, stages=STCS_STAGES_ALL):
+    """The unconditional members U of every sample into ens (B, T, M, H*W), in place: pair q of sample b is DFT3(amp[b] xi)[:T, :H, :W]
+    with xi of (seed, streams[b], q); member 2q is its real part, member 2q + 1 its imaginary part.  The (sample, pair) units go
+    through the two workspaces a chunk at a time.  stages: a subset of the three transforms (bit 0 along k, bit 1 along j, bit 2 along
+    l), meaningful on its own only where all units fit one chunk: the bench tool times a stage with it."""
+    lib = _hip.load()
+    _krig_cs_members("stcs_fields", M)
+    tab = stcs_tables(T, H, W, embed, embed_time, ens.device)
+    St, Sy, Sx = tab["St"], tab["Sy"], tab["Sx"]
+    B = ens.shape[0]
+    _krig_t("stcs_fields", ens, torch.float32, (B, T, M, H * W))
+    _krig_t("stcs_fields", amp, torch.float32, (B, St, Sy, Sx))
+    _krig_t("stcs_fields", streams, torch.int64, (B,))
+    units = B * ((M + 1) // 2)
+    per = max(1, min(units, _STCS_WORK_BYTES // (2 * St * Sy * W * 4), 65535))
+    P = torch.empty(per * 2 * St * Sy * W, device=ens.device, dtype=torch.float32)
+    P2 = torch.empty(per * 2 * St * H * W, device=ens.device, dtype=torch.float32)
+    for u0 in range(0, units, per):
+        _hip.check(lib.p2i_stcs_fields(_ptr(amp), _ptr(streams), _ptr(tab["tx"]), _ptr(tab["ty"]), _ptr(tab["tt"]),
+                                       int(seed) & (2 ** 64 - 1), u0, min(per, units - u0), M, T, H, W, St, Sy, Sx, int(stages), _ptr(P), _ptr(P2),
+                                       _ptr(ens), _stream()), "p2i_stcs_fields")
+
+
+def _stcs_sys(who, sys, stt, ens, M, T, H, W):
+    of = sys.of
+    _krig_cs_members(who, M)
+    if of.R != 1 or of.T != 1:
+        raise RuntimeError(f"{who}: a space-time system is one sample (R = T = 1)")
+    if not 1 <= T <= STCS_MAX_ST:
+        raise ValueError(f"{who}: frames per sample must be in [1, {STCS_MAX_ST}] (got {T})")
+    _krig_t(who, stt, torch.int32, (of.F, of.cap))
+    _krig_t(who, ens, torch.float32, (of.F, T, M, H * W))
+
+
+def stcs_weights(sys, stt, Winv, sol, ens, M, T, H, W):
+    """(alpha (nsys, M, cap), mu (nsys, M)): the space-time kriging of the residuals z_i - U_m(stt_i, stpix_i) of every member of the
+    chunk's samples (sys: stpix, stz, stinfo with R = T = 1), ens (B, T, M, H*W) holding U."""
+    of, ns = sys.of, sys.ns
+    _stcs_sys("stcs_weights", sys, stt, ens, M, T, H, W)
+    _krig_t("stcs_weights", Winv, torch.float32)
+    _krig_t("stcs_weights", sol, torch.float64, (ns, 2, of.np_))
+    _krig_ws("stcs_weights", Winv, ns, of.np_, "inverse")
+    alpha = torch.empty(ns, M, of.cap, device=of.z.device, dtype=torch.float32)
+    mu = torch.empty(ns, M, device=of.z.device, dtype=torch.float32)
+    sys.call("p2i_stcs_weights", _ptr(stt), _ptr(Winv), _ptr(sol), _ptr(ens), M, T, H, W, _ptr(alpha), _ptr(mu))
+    return alpha, mu
+
+
+def stcs_predict(sys, stt, alpha, mu, M, T, H, W, ens):
+    """ens[b][t][m] = U + mu + sum_i alpha_i c0((t, p), i) for the members of the chunk's samples, in place; z at a point's own frame
+    and pixel; NaN for a sample without a model."""
+    of, ns = sys.of, sys.ns
+    _stcs_sys("stcs_predict", sys, stt, ens, M, T, H, W)
+    _krig_t("stcs_predict", alpha, torch.float32, (ns, M, of.cap))
+    _krig_t("stcs_predict", mu, torch.float32, (ns, M))
+    sys.call("p2i_stcs_predict", _ptr(stt), _ptr(alpha), _ptr(mu), M, T, H, W, _ptr(ens))
 
 
 def idw_loo(pix, z, info, power=2.0):

@@ -24,6 +24,7 @@ from p2igan_bench.models import CLASSICAL, build_generator  # noqa: E402
 from p2igan_bench.models.classical import LOCAL  # noqa: E402
 
 VARIANCE_MODELS = ("kriging",) + LOCAL          # the models with a forward_uq
+ENSEMBLE_MODELS = ("kriging", "stkriging")      # the models with a conditional simulation (forward_ensemble, forward_simulation)
 
 
 def parse_args(argv=None):
@@ -43,7 +44,8 @@ def parse_args(argv=None):
     p.add_argument("--variance-output", type=Path, default=None,
                    help="kriging, localkriging and locallagkriging only: a second zarr with the kriging variance x output-scale^2 under the same event keys")
     p.add_argument("--ensemble-output", type=Path, default=None,
-                   help="kriging only: a directory of member_%%03d.zarr, the conditional-simulation members laid out as --output is")
+                   help="kriging and stkriging only: a directory of member_%%03d.zarr, the conditional-simulation members laid out as "
+                        "--output is (stkriging: coherent in time within a chunk of --stride frames)")
     p.add_argument("--members", type=int, default=None, help="ensemble members per frame (1..64), with --ensemble-output")
     p.add_argument("--ensemble-seed", type=int, default=0)
     p.add_argument("--log-level", type=str, default="INFO")
@@ -73,8 +75,9 @@ def main(argv=None):
         cfg = json.load(f)
     if args.ensemble_output is not None:         # refused before the device, the data or a checkpoint is touched
         asked = cfg.get("model", {}).get("name", "model")
-        if str(asked).lower() != "kriging":
-            raise RuntimeError(f"--ensemble-output needs model.name 'kriging', the model with a forward_ensemble (got '{asked}')")
+        if str(asked).lower() not in ENSEMBLE_MODELS:
+            raise RuntimeError(f"--ensemble-output needs model.name 'kriging' or 'stkriging', the models with a conditional simulation "
+                               f"(got '{asked}')")
         if args.members is None or not 1 <= args.members <= 64:
             raise ValueError(f"--ensemble-output needs --members in 1..64 (got {args.members})")
     elif args.members is not None:
@@ -149,8 +152,9 @@ def main(argv=None):
     if args.ensemble_output is not None:
         for m in range(args.members):
             mgroup = zarr_lite.Group(str(args.ensemble_output / f"member_{m:03d}.zarr"), "w")
+            extra = {"embed_time": int(G.embed_time)} if hasattr(G, "embed_time") else {}      # stkriging: the torus' temporal side
             mgroup.attrs.update(dict(group.attrs, member=m, members=int(args.members), seed=int(args.ensemble_seed), embed=int(G.embed),
-                                     clip_share_max=clip_max))
+                                     clip_share_max=clip_max, **extra))
             for key, ens in ensembles.items():
                 comp = np.ascontiguousarray(ens[:, m:m + 1])
                 mgroup.create_dataset(key, comp.astype(np.float32), chunks=comp.shape)
